@@ -7,8 +7,12 @@ UNet forward on a 16-image batch + fresh Gaussian noise + the ancestral update, 
 resident in HBM.  N GPUs run N independent 16-image batches (sampling shards by image, no collective on the data
 path) => weak scaling; `value` counts batch-steps of all ranks per second, `image_steps_per_s` = 16x that.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--impl direct|mfma_f32|mfma_bf16x3|mfma_f16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--impl direct|mfma_f32|mfma_bf16x3|mfma_f16] [--dump-outputs DIR]
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU, RCCL).
+
+--dump-outputs DIR writes what the timed path computed in its last timed step as DIR/<name>.npy (rank 0; float32, at
+most 64 MB).  Inputs are seeded (weights, images and the device noise generator), so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -39,6 +43,28 @@ HBM_PEAK_GBS = 8000.0
 # one rank per GPU, backend "nccl" = RCCL over xGMI.  The JSON line records the backend in config.process_group.
 _BACKEND = os.environ.get("DRS_BENCH_BACKEND", "nccl")
 _SHARE_DEVICE = os.environ.get("DRS_BENCH_SHARE_DEVICE", "") not in ("", "0")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def seed_rngs(rank):
+    """The torch generators (CPU and device: the sampling noise, the training step's timesteps and noise) seeded per rank
+    before the first step, so that the same arguments give the same inputs from run to run."""
+    torch.manual_seed(1000 + rank)
+
+
+def dump_outputs(dirname, arrays):
+    """{name: tensor} -> dirname/<name>.npy: float64 stays float64, everything else is written as float32."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def _host_model():
@@ -111,7 +137,8 @@ def psnr_vs_reference(model, dev, impl):
 
 
 def _build_workload(wl, impl, dev, rank, multi):
-    """(step, unit, batch, gflop per step, description, dtype) of a non-headline BASELINE.json config: `train` = configs[2]
+    """(step, unit, batch, gflop per step, description, dtype, module, outputs) of a non-headline BASELINE.json config
+    (`outputs(r)`: the arrays a caller receives from a step that returned r): `train` = configs[2]
     (per-rank batch 16 of 256x256, train-mode forward + backward + flat RCCL all-reduce + FusedAdam), `sar` = configs[3]
     (SAR->NDVI sampling step, B=32 128x128), `generation` = configs[4] (class-conditional sampling step with CFG scale 3,
     B=64 64x64, 10 classes)."""
@@ -130,11 +157,15 @@ def _build_workload(wl, impl, dev, rank, multi):
         opt = FusedAdam(m.parameters(), lr=1e-4)
         loss_fn = torch.nn.MSELoss()
         step = lambda: d.train_step(m, opt, loss_fn, lr, hr)  # noqa: E731
+
+        def outputs(loss):  # the loss and the model after the update: parameters and BatchNorm running statistics
+            return {"loss": loss.reshape(1), "params": torch.cat([p.detach().flatten() for p in m.parameters()]),
+                    "bn_stats": torch.cat([b.flatten() for b in m.buffers() if b.is_floating_point()])}
         timpl = os.environ.get("DRS_TRAIN_IMPL", "mfma_f32")
         return (step, "train_steps/s (16 images per rank)", 16, 3 * 454.39,
                 f"BASELINE configs[2] per-rank shape: superres 256x256 train step, batch 16 per GPU, MSE, Adam, train_impl={timpl}",
                 ("forward f32 (v_mfma_f32_16x16x4_f32); backward: data gradients split bf16 x3 (SP-format dZ), weight gradients "
-                 "bf16 MFMA on split operands, fp32 accumulate") if timpl == "mfma_f32" else DTYPE.get(timpl, timpl), m)
+                 "bf16 MFMA on split operands, fp32 accumulate") if timpl == "mfma_f32" else DTYPE.get(timpl, timpl), m, outputs)
     if wl == "sar":
         from diffusionremotesensing_amd.train_diffusion_SAR_TO_NDVI import Diffusion
         from diffusionremotesensing_amd.UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
@@ -154,8 +185,10 @@ def _build_workload(wl, impl, dev, rank, multi):
             hip_ops.sampler_step_(x, eps, torch.randn_like(x), i, d.alpha, d.alpha_hat, d.beta)
             state["i"] -= 1
             state["first"] = False
+            return eps
         return (step, "batch32_steps/s", 32, 32 * 7.088,
-                "BASELINE configs[3]: SAR->NDVI UNet 128x128, 1-ch out / 2-ch SAR, batch 32 per GPU, sampling step", DTYPE[impl], m)
+                "BASELINE configs[3]: SAR->NDVI UNet 128x128, 1-ch out / 2-ch SAR, batch 32 per GPU, sampling step", DTYPE[impl], m,
+                lambda eps: {"x": x, "eps": eps})
     from diffusionremotesensing_amd.generate_new_imgs.train_diffusion_generation import Diffusion
     from diffusionremotesensing_amd.generate_new_imgs.UNet_model_generation import Residual_Attention_UNet_generation
     m = Residual_Attention_UNet_generation(3, 3, 10, dev)
@@ -176,24 +209,29 @@ def _build_workload(wl, impl, dev, rank, multi):
         hip_ops.sampler_step_cfg_(x, eps2[:64], eps2[64:], 3.0, torch.randn_like(x), i, d.alpha, d.alpha_hat, d.beta)
         state["i"] -= 1
         state["first"] = False
+        return eps2
     return (step, "batch64_cfg_steps/s", 64, 2 * 64 * 1.771,
             "BASELINE configs[4]: class-conditional generation UNet 64x64, 10 classes, batch 64 per GPU, one CFG "
-            "sampling step = conditional + unconditional forward (one 128-row batch) + guided update", DTYPE[impl], m)
+            "sampling step = conditional + unconditional forward (one 128-row batch) + guided update", DTYPE[impl], m,
+            lambda eps2: {"x": x, "eps_cond": eps2[:64], "eps_uncond": eps2[64:]})
 
 
-def _time_workload(wl, impl, dev, rank, steps, warmup, sync):
-    step, unit, batch, gflop, desc, dtype, m = _build_workload(wl, impl, dev, rank, torch.distributed.is_initialized())
+def _time_workload(wl, impl, dev, rank, steps, warmup, sync, dump_dir=None):
+    step, unit, batch, gflop, desc, dtype, m, outputs = _build_workload(wl, impl, dev, rank, torch.distributed.is_initialized())
+    seed_rngs(rank)
     ctx = torch.enable_grad() if wl == "train" else torch.no_grad()
     with ctx:
         for _ in range(max(warmup, 1)):
-            step()
+            last = step()
         sync()
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            last = step()
         sync()
         elapsed = time.perf_counter() - t0
     m.hip_engine().check_faults()  # (outside the timed region) a forward whose wave-specialised kernels gave up on a counter is not a measurement
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, outputs(last))
     return elapsed, unit, batch, gflop, desc, dtype
 
 
@@ -222,7 +260,8 @@ def other_workload(args):
         if dist.is_initialized():
             torch.distributed.barrier()
         torch.cuda.synchronize()
-    elapsed, unit, batch, gflop, desc, dtype = _time_workload(wl, args.impl, dev, rank, args.steps, args.warmup, sync)
+    elapsed, unit, batch, gflop, desc, dtype = _time_workload(wl, args.impl, dev, rank, args.steps, args.warmup, sync,
+                                                              args.dump_outputs)
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if dist.is_initialized():
         torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
@@ -278,6 +317,8 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the PSNR chain and the exact-fp32 line")
     ap.add_argument("--workload", default="superres", choices=["superres", "train", "sar", "generation"],
                     help="superres = the headline (BASELINE configs[1]); the others are the remaining configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0, float32, <= 64 MB)")
     args = ap.parse_args()
     if args.workload != "superres":
         return other_workload(args)
@@ -320,12 +361,15 @@ def main():
         eps = engine.forward(x, t_rows[i], lr, MAG, reuse_cond=not first, check_weights=first)
         noise = torch.randn_like(x) if i > 1 else None
         hip_ops.sampler_step_(x, eps, noise, i, diffusion.alpha, diffusion.alpha_hat, diffusion.beta)
+        return eps
 
     def sync():
         if dist.is_initialized():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    seed_rngs(rank)
+    eps = None
     with torch.no_grad():
         i = T_STEPS - 1
         for w in range(args.warmup):
@@ -336,11 +380,13 @@ def main():
         sync()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step(max(i, 1), False)
+            eps = step(max(i, 1), False)
             i -= 1
         sync()
         elapsed = time.perf_counter() - t0
     engine.check_faults()  # (outside the timed region) a forward whose wave-specialised kernels gave up on a counter is not a measurement
+    if args.dump_outputs and rank == 0:  # before the profiling below overwrites x: the sampler state and the UNet's prediction
+        dump_outputs(args.dump_outputs, {"x": x} if eps is None else {"x": x, "eps": eps})
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if dist.is_initialized():
         torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
