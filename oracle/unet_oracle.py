@@ -23,7 +23,9 @@ BN_MOMENTUM = 0.1
 
 
 def pos_encoding(t, channels):
-    """UNet_model_superres.py:328-335.  t: (B,1) float32."""
+    """UNet_model_superres.py:328-335.  t: (B,1) float32.  Always fp32 like the reference: the forwards cast the encoding
+    to the dtype of their inputs (a no-op in fp32; the float64 gradient oracle of tests/grad_check.py runs the rest in
+    float64)."""
     inv_freq = 1.0 / (10000 ** (torch.arange(0, channels, 2).float() / channels))
     a = torch.sin(t.repeat(1, channels // 2) * inv_freq)
     b = torch.cos(t.repeat(1, channels // 2) * inv_freq)
@@ -148,7 +150,7 @@ def _trunk(sd, x, t, skip_name, training, stats, taps):
 def unet_forward(sd, x, timestep, lr_img, magnification_factor, training=False, stats=None, taps=None):
     """Residual_Attention_UNet_superres.forward, :337-379.  `taps`, when a dict, receives the named
     intermediate activations (names match drs_unet_tensor_name)."""
-    t = pos_encoding(timestep.unsqueeze(-1).type(torch.float), TIME_EMB_DIM)
+    t = pos_encoding(timestep.unsqueeze(-1).type(torch.float), TIME_EMB_DIM).to(x.dtype)
     x = _conv(sd, "conv0", x, padding=1)
     lr = rrdb(sd, "LR_encoder", lr_img)
     up = F.interpolate(lr, scale_factor=magnification_factor, mode="bicubic")
@@ -161,7 +163,7 @@ def unet_forward(sd, x, timestep, lr_img, magnification_factor, training=False, 
 
 def unet_forward_sar(sd, ndvi_img, timestep, sar_img, training=False, stats=None, taps=None):
     """Residual_Attention_UNet_SAR_TO_NDVI.forward, UNet_model_SAR_TO_NDVI.py:332-370."""
-    t = pos_encoding(timestep.unsqueeze(-1).type(torch.float), TIME_EMB_DIM)
+    t = pos_encoding(timestep.unsqueeze(-1).type(torch.float), TIME_EMB_DIM).to(ndvi_img.dtype)
     x = _conv(sd, "conv0", ndvi_img, padding=1)
     sar = rrdb(sd, "SAR_encoder", sar_img)
     if taps is not None:
@@ -172,7 +174,7 @@ def unet_forward_sar(sd, ndvi_img, timestep, sar_img, training=False, stats=None
 
 def unet_forward_generation(sd, x, timestep, y=None, training=False, stats=None, taps=None):
     """Residual_Attention_UNet_generation.forward, generate_new_imgs/UNet_model_generation.py:296-329."""
-    t = pos_encoding(timestep.unsqueeze(-1).type(torch.float), TIME_EMB_DIM)
+    t = pos_encoding(timestep.unsqueeze(-1).type(torch.float), TIME_EMB_DIM).to(x.dtype)
     if y is not None:
         t = t + F.embedding(y, sd["label_emb.weight"])  # `t += self.label_emb(y)`, :300-301
     x = _conv(sd, "conv0", x, padding=1)
