@@ -795,6 +795,37 @@ __global__ void fl_range_kernel(unsigned* __restrict__ flag, const unsigned* __r
   if (__uint_as_float(*wmax_bits) < 0.0009765625f) atomicOr(flag, 1u);
 }
 
+// Rows and columns far below the layer.  The fp6 cross terms carry one power-of-two scale per (row, tap, 32-channel block) of the
+// weights and per (pixel, 32-channel block) of the activations: a weight or activation far below its block's largest keeps only
+// its fp16 main, and a row far below the layer sits in fp16's subnormal range.  A network that moves a channel scale alpha out of
+// one layer and 1 / alpha into the next one's input columns keeps its function and produces exactly that: a row of the producer
+// and a column of the reader 1 / alpha away from the rest, its activations alpha away (tests/test_gpu_rescale.py: outputs up to
+// 1.1e-3 off).  One thread per output row (threads 0 .. Cout-1) and per input column (Cout .. Cout+Cin-1) over the fp16 mains:
+// a non-zero row or column whose largest weight is under 2^-10 of the layer's largest leaves the layer on split bf16.  (The
+// fixtures' BatchNorm folding keeps every row within 7.5e-3 and every column within 0.23 of its layer's largest.)
+__global__ void fl_rowcol_kernel(const char* __restrict__ dst, int Cout, int Cin, int nchunks, int taps, unsigned* __restrict__ flag,
+                                 const unsigned* __restrict__ wmax_bits) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Cout + Cin) return;
+  float m = 0.f;
+  if (i < Cout) {
+    for (int c = 0; c < nchunks; ++c)
+      for (int tap = 0; tap < taps; ++tap)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f16x8 v = *reinterpret_cast<const f16x8*>(dst + ((((size_t)c * taps + tap) * 4 + q) * Cout + i) * 16);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf((float)v[j]));
+        }
+  } else {
+    const int ci = i - Cout, c = ci >> 5, q = (ci & 31) >> 3, j = ci & 7;
+    for (int tap = 0; tap < taps; ++tap)
+      for (int co = 0; co < Cout; ++co)
+        m = fmaxf(m, fabsf((float)*reinterpret_cast<const _Float16*>(dst + ((((size_t)c * taps + tap) * 4 + q) * Cout + co) * 16 + j * 2)));
+  }
+  if (m > 0.f && m < __uint_as_float(*wmax_bits) * 0.0009765625f) atomicOr(flag, 1u);
+}
+
 }  // namespace
 
 size_t drs_fl_image_bytes(int Cout, int Cin, int taps) {  // = the two split-bf16 images of the layer
@@ -812,6 +843,8 @@ int drs_launch_fl_repack(const void* sp_images, void* dst, int Cout, int Cin, in
   // flag[0]: the layer's range flag, flag[1]: scratch for the largest |weight| (both zeroed by the caller)
   DRS_LAUNCH(fl_repack_kernel, dim3(blocks), dim3(128), 0, s, (const char*)sp_images, image, (char*)dst, Cout, nchunks, taps, flag, flag + 1);
   DRS_LAUNCH(fl_range_kernel, dim3(1), dim3(1), 0, s, flag, (const unsigned*)(flag + 1));
+  DRS_LAUNCH(fl_rowcol_kernel, dim3((unsigned)((Cout + Cin + 127) / 128)), dim3(128), 0, s, (const char*)dst, Cout, Cin, nchunks, taps, flag,
+             (const unsigned*)(flag + 1));
   DRS_CHECK_HIP(hipGetLastError());
   return DRS_OK;
 }
