@@ -69,6 +69,16 @@ SIGNATURES = {
     "drs_unet_profile_read": (_I, [_P, _I, C.c_char_p, _I, C.POINTER(_F), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "drs_unet_profile_num_launches": (_I, [_P]),
     "drs_unet_profile_launch": (_I, [_P, _I, C.c_char_p, _I, C.c_char_p, _I]),
+    "drs_vgg_plan_create": (_I, [C.POINTER(_P), _I, _I, _I, _I]),
+    "drs_vgg_plan_destroy": (None, [_P]),
+    "drs_vgg_packed_bytes": (_Z, [_P]),
+    "drs_vgg_workspace_bytes": (_Z, [_P]),
+    "drs_vgg_pack_weights": (_I, [_P, C.POINTER(_P), _P, _Z, _P]),
+    "drs_vgg_forward": (_I, [_P, _P, _P, _P, _P, _I, _P, _Z, _P]),
+    "drs_vgg_backward": (_I, [_P, _P, _P, _P, _P, _Z, _P]),
+    "drs_vgg_profile_enable": (_I, [_P, _I]),
+    "drs_vgg_profile_num_ops": (_I, [_P]),
+    "drs_vgg_profile_read": (_I, [_P, _I, C.c_char_p, _I, C.POINTER(_F), C.POINTER(C.c_double)]),
 }
 
 _lib = None

@@ -302,6 +302,36 @@ DRS_API int drs_unet_profile_read(drs_plan* plan, int i, char* name, int name_le
 DRS_API int drs_unet_profile_num_launches(const drs_plan* plan);
 DRS_API int drs_unet_profile_launch(const drs_plan* plan, int i, char* op, int op_len, char* kernel, int kernel_len);
 
+/* ---- VGG19 perceptual loss (the MSE+Perceptual_noise training loss; csrc/vgg_loss.hip) ----------------------------------
+ * Replaces VGGPerceptualLoss.forward (reference train_diffusion_superres.py:63-68, train_diffusion_SAR_TO_NDVI.py:64-69,
+ * generate_new_imgs/train_diffusion_generation.py:66-71) and its autograd backward w.r.t. the prediction:
+ *   loss = mean((F(P(pred)) - F(P(target)))^2),  P = bicubic resize to 224 x 224 when width != 224 (:46-50) + ImageNet
+ *   normalise (:42-44),  F = torchvision vgg19().features (:28).
+ * pred / target: (batch, 3, height, width) NCHW fp32.  Prediction and target run as one batched forward of 2 x batch images.
+ * Every convolution runs on the MFMA kernels (impl DRS_IMPL_MFMA_F32 or DRS_IMPL_MFMA_BF16X3); a shape any layer of which
+ * they do not take fails plan creation with DRS_ERR_SHAPE. */
+typedef struct drs_vgg_plan drs_vgg_plan;
+DRS_API int drs_vgg_plan_create(drs_vgg_plan** plan, int batch, int height, int width, int impl);
+DRS_API void drs_vgg_plan_destroy(drs_vgg_plan* plan);
+DRS_API size_t drs_vgg_packed_bytes(const drs_vgg_plan* plan);
+DRS_API size_t drs_vgg_workspace_bytes(const drs_vgg_plan* plan);
+/* params[2 l], params[2 l + 1] = device pointers of features.{k}.weight / .bias of the l-th convolution (k = 0, 2, 5, 7, 10, 12,
+ * 14, 16, 19, 21, 23, 25, 28, 30, 32, 34: torchvision's key layout), fp32.  Packs forward and data-gradient images once. */
+DRS_API int drs_vgg_pack_weights(drs_vgg_plan* plan, const void* const* params, void* packed, size_t packed_bytes,
+                         drs_stream_t stream);
+/* *loss (device scalar) = the loss.  save = 1 keeps the prediction half's activations in the workspace for drs_vgg_backward;
+ * save = 0 (validation under torch.no_grad) keeps nothing.  No host synchronisation. */
+DRS_API int drs_vgg_forward(drs_vgg_plan* plan, const void* packed, const float* pred, const float* target, float* loss,
+                    int save, void* workspace, size_t workspace_bytes, drs_stream_t stream);
+/* dpred = d(loss)/d(pred) * (*grad_loss) (device scalar: autograd's upstream gradient); needs the workspace as the last
+ * drs_vgg_forward with save = 1 left it.  Deterministic: no atomics. */
+DRS_API int drs_vgg_backward(drs_vgg_plan* plan, const void* packed, const float* grad_loss, float* dpred, void* workspace,
+                     size_t workspace_bytes, drs_stream_t stream);
+/* Per-op timing of the last forward / backward (HIP events on its stream): name, milliseconds, algorithmic FLOPs. */
+DRS_API int drs_vgg_profile_enable(drs_vgg_plan* plan, int on);
+DRS_API int drs_vgg_profile_num_ops(const drs_vgg_plan* plan);
+DRS_API int drs_vgg_profile_read(drs_vgg_plan* plan, int i, char* name, int name_len, float* ms, double* flops);
+
 #ifdef __cplusplus
 }
 #endif
