@@ -1162,6 +1162,7 @@ struct FwdCtx {
 };
 }  // namespace
 
+// A step of the forward or backward (train_bwd.inc) schedule returns its first non-zero status
 #define RUN(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
 // A profiled op that is not a layer's TapConv (plan_conv brackets those itself)
 template <class Launch>
@@ -1674,7 +1675,6 @@ extern "C" int drs_unet_forward_labels(drs_plan* plan, const void* packed, const
   }
   return DRS_OK;
 }
-#undef RUN
 
 // Synchronises `stream` and reports whether a wave of the wave-specialised kernels ran into its bounded poll since the
 // weights were last packed into `packed` (a protocol bug: the forward's output is then incomplete).
@@ -1756,3 +1756,4 @@ extern "C" int drs_unet_profile_launch(const drs_plan* plan, int i, char* op, in
 }
 
 #include "train_bwd.inc"
+#undef RUN
