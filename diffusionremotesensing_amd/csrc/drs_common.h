@@ -125,6 +125,8 @@ static inline int drs_cdiv(int a, int b) { return (a + b - 1) / b; }
 // fmaxf (v_max_f32) returns the other operand: a NaN accumulator would leave a ReLU as 0 and the divergence it signals
 // would be gone from the output (tests/test_gpu_parity.py: test_nan_reaches_the_output).
 __device__ __forceinline__ float drs_maxf(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+// most image / conditioning bands of a network (include/drs_hip.h: drs_unet_config): the few-channel kernels' LDS and partial rows
+constexpr int kMaxBands = 16;
 #define DRS_RED_BLOCKS 512  // most blocks a partial-sum reduction of the training kernels uses (size of the partials buffer)
 
 // Every kernel of the library is launched through DRS_LAUNCH (same arguments as hipLaunchKernelGGL).  While a plan runs a
@@ -384,13 +386,13 @@ struct DrsMlpBwdTable { DrsMlpBwd m[8]; int n; };
 int drs_launch_time_mlp_bwd(const long long* t, const float* inv_freq, const DrsMlpBwdTable& tab, int stride, int B,
                             const float* label_emb, const long long* labels, int label_batch, int num_classes, float* dlabel,
                             hipStream_t s);
-// weight + bias gradient of a 3x3 stem convolution (CI <= 4 -> 16 channels); partials: >= 512 x (144 CI + 16) floats, stream-ordered
+// weight + bias gradient of a 3x3 stem convolution (CI <= kMaxBands -> 16 channels); partials: >= 512 x (144 CI + 16) floats, stream-ordered
 int drs_launch_stem_wgrad(const float* g, int g_cs, const float* x, int N, int CI, int H, int W, float* partials,
                           size_t partial_bytes, float* dW, float* db, hipStream_t s);
 int drs_launch_stem_dgrad(const float* g, int g_cs, const float* w, float* dx, int N, int H, int W, int C, hipStream_t s);
 int drs_launch_bicubic_bwd(const float* dy, float* dx, int N, int C, int H, int W, int scale, hipStream_t s);
-// whole backward of one few-channel 3x3 layer (CC -> CC, CC <= 4): dW / db accumulate, gin (+)= conv^T(gout) [* (mask_y > 0)];
-// partials: >= 1024 x (9 CC^2 + CC) floats of stream-ordered scratch
+// whole backward of one few-channel 3x3 layer (CC -> CC, CC <= kMaxBands): dW / db accumulate, gin (+)= conv^T(gout)
+// [* (mask_y > 0)]; partials: >= 1024 x (9 CC^2 + CC) floats of stream-ordered scratch (partial_bytes)
 int drs_launch_small_conv_bwd(const float* in, const float* gout, const float* w, float* gin, int accumulate,
-                              const float* mask_y, int N, int CC, int H, int W, float* partials, float* dW, float* db,
-                              hipStream_t s);
+                              const float* mask_y, int N, int CC, int H, int W, float* partials, size_t partial_bytes,
+                              float* dW, float* db, hipStream_t s);

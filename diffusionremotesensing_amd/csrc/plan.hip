@@ -464,7 +464,8 @@ struct drs_plan {
   // stream (BatchNorm statistics, BatchNorm backward, bias-gradient column sums: kRedBlocks x 2 x 1024 doubles).  Partials +
   // a small finishing kernel replaced per-block atomics onto the same 2 x Cout addresses: 512 blocks x 90 ns per serialised
   // atomic = a 46 us floor under every one of those launches, whatever the tensor size (round 3: 63 of them per step).
-  size_t o_bn_sums = 0, bn_sums_bytes = 0, o_red = 0;
+  // (also the partial rows of the few-channel LR / SAR encoder backward: 1024 x (9 CC^2 + CC) floats, train_kernels.hip)
+  size_t o_bn_sums = 0, bn_sums_bytes = 0, o_red = 0, red_bytes = 0;
   // FL arithmetic (conv_mfma_fl.hip) for the layers the wave-specialised SP kernel takes at 64 channels per item; per-layer range
   // flags (device words, one per FL image: bit 0 = a folded weight outside what fp16 holds) are read back at pack time
   bool fl = false;
@@ -558,8 +559,9 @@ extern "C" int drs_unet_plan_create(drs_plan** out, const drs_unet_config* cfg) 
   DRS_REQUIRE(out && cfg, DRS_ERR_ARG, "plan_create: null pointer");
   DRS_REQUIRE(cfg->batch >= 1 && (cfg->lr_batch == cfg->batch || cfg->lr_batch == 1), DRS_ERR_SHAPE,
               "plan_create: batch=%d lr_batch=%d (lr batch must equal batch or be 1)", cfg->batch, cfg->lr_batch);
-  DRS_REQUIRE(cfg->image_channels >= 1 && cfg->image_channels <= 4 && cfg->out_dim >= 1, DRS_ERR_SHAPE,
-              "plan_create: image_channels=%d out_dim=%d", cfg->image_channels, cfg->out_dim);
+  DRS_REQUIRE(cfg->image_channels >= 1 && cfg->image_channels <= kMaxBands && cfg->out_dim >= 1 && cfg->out_dim <= kMaxBands,
+              DRS_ERR_SHAPE, "plan_create: image_channels=%d out_dim=%d (each 1..%d)", cfg->image_channels, cfg->out_dim,
+              kMaxBands);
   DRS_REQUIRE(cfg->magnification >= 1 && cfg->height > 0 && cfg->width > 0 && cfg->height % 8 == 0 &&
                   cfg->width % 8 == 0 && cfg->height % cfg->magnification == 0 && cfg->width % cfg->magnification == 0,
               DRS_ERR_SHAPE, "plan_create: H=%d W=%d must be divisible by 8 and by magnification=%d", cfg->height,
@@ -576,8 +578,8 @@ extern "C" int drs_unet_plan_create(drs_plan** out, const drs_unet_config* cfg) 
   if (p->cfg.variant == DRS_VARIANT_SUPERRES && p->cfg.cond_channels == 0) p->cfg.cond_channels = C;
   if (p->cfg.variant == DRS_VARIANT_GENERATION) p->cfg.cond_channels = 0;
   const int CC = p->cfg.cond_channels;  // conditioning image channels
-  if (p->cfg.variant != DRS_VARIANT_GENERATION && (CC < 1 || CC > 4)) {
-    DrsErr::set("plan_create: cond_channels=%d", CC);
+  if (p->cfg.variant != DRS_VARIANT_GENERATION && (CC < 1 || CC > kMaxBands)) {
+    DrsErr::set("plan_create: cond_channels=%d (1..%d)", CC, kMaxBands);
     delete p;
     return DRS_ERR_SHAPE;
   }
@@ -860,7 +862,8 @@ extern "C" int drs_unet_plan_create(drs_plan** out, const drs_unet_config* cfg) 
     }
     p->bn_sums_bytes = align_up(sums_cur);
     p->o_bn_sums = ws; ws += 2 * p->bn_sums_bytes;  // [forward | backward]
-    p->o_red = ws; ws += align_up((size_t)kRedBlocks * 2 * 1024 * sizeof(double));
+    p->red_bytes = std::max((size_t)kRedBlocks * 2 * 1024 * sizeof(double), (size_t)1024 * (9 * CCw * CCw + CCw) * 4);
+    p->o_red = ws; ws += align_up(p->red_bytes);
   }
   if (cfg->flags & DRS_PLAN_TRAIN) {
     p->o_dtemb = ws; ws += align_up((size_t)B * p->temb_total * 4);

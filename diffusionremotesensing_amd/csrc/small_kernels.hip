@@ -165,16 +165,19 @@ int drs_launch_nhwc_to_nchw(const float* src, float* dst, int N, int C, int H, i
 
 // ---------------------------------------------------------------------------------------------
 // Planar 3x3 s1 p1 convolution for the few-channel LR encoder (RRDB, reference :230-260):
-// out = [relu](conv(in) + b) [+ res].  Cin, Cout <= 4.  Weights are torch layout (Cout,Cin,3,3).
-// HBM-bound: one lane per pixel, coalesced along x; neighbours come from L1.
+// out = [relu](conv(in) + b) [+ res].  Cin, Cout <= kMaxBands.  Weights are torch layout (Cout,Cin,3,3).
+// HBM-bound: one lane per pixel, coalesced along x; neighbours come from L1.  The output channels go in chunks of 4
+// (4 accumulators per lane, the input re-read from L1 per chunk); within a chunk every output sums bias, then ci, ky, kx
+// in that order, so a layer of at most 4 outputs is one chunk with the arithmetic it always had.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void conv3x3_planar_kernel(const float* __restrict__ in, const float* __restrict__ w,
                                                              const float* __restrict__ b,
                                                              const float* __restrict__ res, float* __restrict__ out,
                                                              int N, int Cin, int Cout, int H, int W, int relu) {
-  __shared__ float sw[4 * 4 * 9 + 4];
+  constexpr int kW = kMaxBands * kMaxBands * 9;
+  __shared__ float sw[kW + kMaxBands];
   for (int i = threadIdx.x; i < Cout * Cin * 9; i += blockDim.x) sw[i] = w[i];
-  if (threadIdx.x < Cout) sw[4 * 4 * 9 + threadIdx.x] = b ? b[threadIdx.x] : 0.f;
+  if (threadIdx.x < Cout) sw[kW + threadIdx.x] = b ? b[threadIdx.x] : 0.f;
   __syncthreads();
   const int64_t hw = (int64_t)H * W;
   const int64_t total = (int64_t)N * hw;
@@ -182,41 +185,46 @@ __global__ __launch_bounds__(256) void conv3x3_planar_kernel(const float* __rest
     const int x = (int)(p % W);
     const int y = (int)((p / W) % H);
     const int n = (int)(p / hw);
-    float acc[4];
+#pragma unroll 1
+    for (int c0 = 0; c0 < Cout; c0 += 4) {
+      const int nc = min(4, Cout - c0);  // outputs of this chunk
+      const float* swc = sw + c0 * Cin * 9;
+      float acc[4];
 #pragma unroll
-    for (int co = 0; co < 4; ++co) acc[co] = co < Cout ? sw[4 * 4 * 9 + co] : 0.f;
-    for (int ci = 0; ci < Cin; ++ci) {
-      const float* ip = in + ((int64_t)n * Cin + ci) * hw;
+      for (int co = 0; co < 4; ++co) acc[co] = co < nc ? sw[kW + c0 + co] : 0.f;
+      for (int ci = 0; ci < Cin; ++ci) {
+        const float* ip = in + ((int64_t)n * Cin + ci) * hw;
 #pragma unroll
-      for (int ky = 0; ky < 3; ++ky) {
-        const int iy = y + ky - 1;
-        if (iy < 0 || iy >= H) continue;
+        for (int ky = 0; ky < 3; ++ky) {
+          const int iy = y + ky - 1;
+          if (iy < 0 || iy >= H) continue;
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          const int ix = x + kx - 1;
-          if (ix < 0 || ix >= W) continue;
-          const float a = ip[(int64_t)iy * W + ix];
+          for (int kx = 0; kx < 3; ++kx) {
+            const int ix = x + kx - 1;
+            if (ix < 0 || ix >= W) continue;
+            const float a = ip[(int64_t)iy * W + ix];
 #pragma unroll
-          for (int co = 0; co < 4; ++co)
-            if (co < Cout) acc[co] = fmaf(a, sw[(co * Cin + ci) * 9 + ky * 3 + kx], acc[co]);
+            for (int co = 0; co < 4; ++co)
+              if (co < nc) acc[co] = fmaf(a, swc[(co * Cin + ci) * 9 + ky * 3 + kx], acc[co]);
+          }
         }
       }
-    }
 #pragma unroll
-    for (int co = 0; co < 4; ++co) {
-      if (co >= Cout) break;
-      float v = acc[co];
-      if (relu) v = drs_maxf(v, 0.f);
-      const int64_t o = ((int64_t)n * Cout + co) * hw + (int64_t)y * W + x;
-      if (res) v += res[o];
-      out[o] = v;
+      for (int co = 0; co < 4; ++co) {
+        if (co >= nc) break;
+        float v = acc[co];
+        if (relu) v = drs_maxf(v, 0.f);
+        const int64_t o = ((int64_t)n * Cout + c0 + co) * hw + (int64_t)y * W + x;
+        if (res) v += res[o];
+        out[o] = v;
+      }
     }
   }
 }
 int drs_launch_conv3x3_planar(const float* in, const float* w, const float* b, const float* res, float* out, int N,
                               int Cin, int Cout, int H, int W, int relu, hipStream_t s) {
-  DRS_REQUIRE(Cin >= 1 && Cin <= 4 && Cout >= 1 && Cout <= 4, DRS_ERR_SHAPE, "planar conv: Cin=%d Cout=%d (max 4)", Cin,
-              Cout);
+  DRS_REQUIRE(Cin >= 1 && Cin <= kMaxBands && Cout >= 1 && Cout <= kMaxBands, DRS_ERR_SHAPE,
+              "planar conv: Cin=%d Cout=%d (max %d)", Cin, Cout, kMaxBands);
   DRS_LAUNCH(conv3x3_planar_kernel, dim3(ew_blocks((int64_t)N * H * W)), dim3(256), 0, s, in, w, b, res, out,
                      N, Cin, Cout, H, W, relu);
   DRS_CHECK_HIP(hipGetLastError());
@@ -224,7 +232,7 @@ int drs_launch_conv3x3_planar(const float* in, const float* w, const float* b, c
 }
 
 // ---------------------------------------------------------------------------------------------
-// Stem: 3x3 s1 p1 convolution from a planar few-channel image to channels-last Cout (=16) with an
+// Stem: 3x3 s1 p1 convolution from a planar image of 1 .. kMaxBands channels to channels-last Cout (=16) with an
 // optional channels-last residual (the cached LR-conditioning term, broadcast over the batch when it
 // has batch 1).  conv0 and conv_upsampled_lr_img of the reference (:342,:353-355).
 // ---------------------------------------------------------------------------------------------
@@ -247,13 +255,14 @@ __global__ __launch_bounds__(256, DRS_STEM_BPC) void stem_kernel(const float* __
                                                    int W, int out_sp) {
   static_assert(COUT == 16, "a pixel is 64 bytes in both output formats");
   constexpr int R = kStemRows;
-  __shared__ __attribute__((aligned(16))) float sw[COUT * 4 * 9 + COUT];  // [tap][ci][co] + bias
+  constexpr int kB = COUT * kMaxBands * 9;                                     // bias offset
+  __shared__ __attribute__((aligned(16))) float sw[kB + COUT];                // [tap][ci][co] + bias
   __shared__ __attribute__((aligned(16))) char sT[4][64 * 64];            // per wave: 64 pixels x 64 bytes
   for (int i = threadIdx.x; i < COUT * Cin * 9; i += blockDim.x) {
     const int co = i / (Cin * 9), r = i % (Cin * 9), ci = r / 9, tap = r % 9;
     sw[(tap * Cin + ci) * COUT + co] = w[i];
   }
-  if (threadIdx.x < COUT) sw[COUT * 4 * 9 + threadIdx.x] = b[threadIdx.x];
+  if (threadIdx.x < COUT) sw[kB + threadIdx.x] = b[threadIdx.x];
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   char* tb = sT[wave];
@@ -276,7 +285,7 @@ __global__ __launch_bounds__(256, DRS_STEM_BPC) void stem_kernel(const float* __
 #pragma unroll
     for (int o = 0; o < R; ++o)
 #pragma unroll
-      for (int co = 0; co < COUT; ++co) acc[o][co] = sw[COUT * 4 * 9 + co];
+      for (int co = 0; co < COUT; ++co) acc[o][co] = sw[kB + co];
     // residual rows: 4 x 1 KB of consecutive bytes per row, lanes past the segment read the zero word
     u32x4 rnext[4] = {};
     auto load_res = [&](int o) __attribute__((always_inline)) {
@@ -366,7 +375,8 @@ __global__ __launch_bounds__(256, DRS_STEM_BPC) void stem_kernel(const float* __
 }
 int drs_launch_stem(const float* in_nchw, const float* w, const float* b, const float* res_nhwc, int res_batch,
                     float* out_nhwc, int N, int Cin, int Cout, int H, int W, hipStream_t s, int out_sp) {
-  DRS_REQUIRE(Cout == 16 && Cin >= 1 && Cin <= 4, DRS_ERR_SHAPE, "stem: Cin=%d Cout=%d unsupported", Cin, Cout);
+  DRS_REQUIRE(Cout == 16 && Cin >= 1 && Cin <= kMaxBands, DRS_ERR_SHAPE, "stem: Cin=%d Cout=%d unsupported (Cin max %d)", Cin,
+              Cout, kMaxBands);
   const int64_t units = (int64_t)N * ((H + kStemRows - 1) / kStemRows) * ((W + 63) / 64);  // a wave per kStemRows rows x 64 columns
   if (units == 0) return DRS_OK;
   DRS_REQUIRE(units < (1LL << 31), DRS_ERR_SHAPE, "stem: %lld row segments", (long long)units);

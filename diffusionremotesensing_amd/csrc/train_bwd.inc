@@ -260,7 +260,7 @@ static int wgrad(BwdCtx& c, const ConvLayer& L, const WgradDesc& d) { return wgr
 // like every weight gradient (operands x.nhwc / upsampled_lr_img.nhwc / grad.x0 are not rewritten below; the partial
 // rows share the side stream's slice workspace, whose users are stream-ordered).  Direct (VALU) plans keep wgrad_kernel.
 static int stem_wgrad(BwdCtx& c, const PlanarConv& L, const WgradDesc& d) {
-  if (c.wgrad_mfma && d.Cb == 16 && d.Ca <= 4)
+  if (c.wgrad_mfma && d.Cb == 16 && d.Ca <= kMaxBands)
     return drs_launch_stem_wgrad(d.B, d.b_cs, d.A, d.N, d.Ca, d.AH, d.AW, (float*)((char*)c.ws + c.plan->o_wgrad),
                                  kWgradPartialBytes, c.G(L.w), c.G(L.b), wgrad_stream(c));
   return wgrad(c, d, c.G(L.w), c.G(L.b));
@@ -269,7 +269,7 @@ static int stem_wgrad(BwdCtx& c, const PlanarConv& L, const WgradDesc& d) {
 static int small_bwd(BwdCtx& c, const PlanarConv& L, const float* in_nhwc, const float* gout, float* gin, bool accumulate,
                      const float* mask_y) {
   return drs_launch_small_conv_bwd(in_nhwc, gout, c.PARAM(L.w), gin, accumulate ? 1 : 0, mask_y, c.B, c.cfg.cond_channels,
-                                   c.h, c.w, c.red, c.G(L.w), c.G(L.b), c.s);
+                                   c.h, c.w, c.red, c.plan->red_bytes, c.G(L.w), c.G(L.b), c.s);
 }
 
 // zero every requested gradient and the per-image embedding gradients
@@ -415,7 +415,7 @@ static int bwd_stem(BwdCtx& c, const float* x) {
 }
 
 // ---- LR branch: cond = conv_upsampled_lr_img(bicubic(RRDB(lr))) (:342-355) ----
-// d(up) = conv^T(gx0), adjoint bicubic, RRDB backward (all 3-channel tensors, channels-last copies)
+// d(up) = conv^T(gx0), adjoint bicubic, RRDB backward (all CC-channel tensors, channels-last copies)
 static int bwd_lr_branch(BwdCtx& c) {
   const drs_plan* plan = c.plan;
   const int B = c.B, H = c.H, W = c.W, CC = c.cfg.cond_channels;
@@ -424,7 +424,7 @@ static int bwd_lr_branch(BwdCtx& c) {
   RUN(drs_launch_nchw_to_nhwc(c.TP(plan->t_up), upn, B, CC, H, W, CC, 0, c.s));
   RUN(stem_wgrad(c, plan->stemc, wgrad_conv(upn, CC, 0, CC, H, W, gx0, kGx0Stride, 0, kDown[0], H, W, B, 3, 1, 1)));
   float* gup = c.TP(plan->g_upn);
-  // dgrad of the 3 -> 16 conditioning convolution (its own LDS-tiled kernel: train_kernels.hip)
+  // dgrad of the CC -> 16 conditioning convolution (its own LDS-tiled kernel: train_kernels.hip)
   RUN(drs_launch_stem_dgrad(gx0, kGx0Stride, c.PARAM(plan->stemc.w), gup, B, H, W, CC, c.s));
   float* genc = c.TP(plan->g_lr[3]);  // gradient w.r.t. the LR encoding (h x w)
   RUN(drs_launch_bicubic_bwd(gup, genc, B, CC, c.h, c.w, c.cfg.magnification, c.s));  // (gather form: writes every element)

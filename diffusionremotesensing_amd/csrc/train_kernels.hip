@@ -742,14 +742,18 @@ int drs_launch_bicubic_bwd(const float* dy, float* dx, int N, int C, int H, int 
 
 // ---------------------------------------------------------------------------------------------------------------
 // Whole backward of ONE few-channel 3x3 layer of the LR / SAR encoder (reference ResidualBlock / RRDB,
-// UNet_model_superres.py:237-260: CC -> CC channels, stride 1, pad 1, CC <= 4; channels-last tensors, pixel stride CC):
+// UNet_model_superres.py:237-260: CC -> CC channels, stride 1, pad 1, CC <= kMaxBands; channels-last tensors, pixel stride CC):
 //   dW[co][ci][ky][kx] += sum_p gout[p][co] * in[p + (ky-1, kx-1)][ci]          db[co] += sum_p gout[p][co]
 //   gin[p][ci] (+)= sum_{co,ky,kx} W[co][ci][ky][kx] * gout[p - (ky-1, kx-1)][co], then * (mask_y[p][ci] > 0) if mask_y
-// (zero outside the image).  One thread per pixel, the CC*CC*9 + CC sums in registers -> wave shuffles -> LDS -> this
-// block's row of `partials`; stem_wgrad_finish_kernel adds the rows in a fixed order into dW / db.  (A first version let the
-// last block to arrive add the rows itself: one block summing 256 rows was a 40 us tail on a 25 us kernel.)  Replaces, per layer, a weight-gradient launch of the MFMA kernel on the side stream (35 us + a 50 us reduce
-// for 81 sums) that the main stream had to wait for, a weight re-pack, a direct tap convolution and a mask pass: the seven
-// layers were 0.9 ms of a 16.5 ms training step spent almost idle.
+// (zero outside the image).  The channels go in chunks of KC = min(CC, 4): block row blockIdx.y = (output chunk k, input chunk
+// j) owns the KC x KC x 9 (+ KC bias) weight-gradient sums of that pair, one thread per pixel, in registers -> wave shuffles
+// -> LDS -> its columns of this block's row of `partials`; stem_wgrad_finish_kernel adds the rows in a fixed order into dW /
+// db.  The k = 0 blocks also form input chunk j of gin, over every output channel in the order co, ky, kx.  With CC <= 4 there
+// is one chunk pair and that is the arithmetic of the single-chunk kernel this generalises.  (A first version let the last
+// block to arrive add the rows itself: one block summing 256 rows was a 40 us tail on a 25 us kernel.)  Replaces, per layer, a
+// weight-gradient launch of the MFMA kernel on the side stream (35 us + a 50 us reduce for 81 sums) that the main stream had
+// to wait for, a weight re-pack, a direct tap convolution and a mask pass: the seven layers were 0.9 ms of a 16.5 ms training
+// step spent almost idle.
 // ---------------------------------------------------------------------------------------------------------------
 template <int CC>
 __global__ __launch_bounds__(256) void small_conv_bwd_kernel(const float* __restrict__ in, const float* __restrict__ gout,
@@ -757,52 +761,77 @@ __global__ __launch_bounds__(256) void small_conv_bwd_kernel(const float* __rest
                                                              int accumulate, const float* __restrict__ mask_y, int N, int H,
                                                              int W, float* __restrict__ partials, const float* dW,
                                                              const float* db) {
-  constexpr int NW = CC * CC * 9, NACC = NW + CC;
+  constexpr int KC = CC < 4 ? CC : 4, NCH = (CC + KC - 1) / KC;  // chunk width, chunks per side
+  constexpr int NW = KC * KC * 9, NACC = NW + KC, NCOL = CC * CC * 9 + CC;
   __shared__ float red[4][NACC];
+  const int k = blockIdx.y / NCH, j = blockIdx.y % NCH;  // output chunk, input chunk (block-uniform)
+  const int co0 = k * KC, ci0 = j * KC;
   const long long npix = (long long)N * H * W;
   float acc[NACC];
 #pragma unroll
   for (int i = 0; i < NACC; ++i) acc[i] = 0.f;
-  float wr[NW];  // launch-uniform: scalar loads
-#pragma unroll
-  for (int i = 0; i < NW; ++i) wr[i] = w[i];
   for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long long)gridDim.x * 256) {
     const int x = (int)(p % W), y = (int)((p / W) % H);
-    float go[3][3][CC], xi[3][3][CC];
+    float go[3][3][KC], xi[3][3][KC];  // gout: output chunk kk of the gin loop below; in: input chunk j
+    auto load_go = [&](int c0) __attribute__((always_inline)) {
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const int yy = y + ky - 1, xx = x + kx - 1;
+          const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
+          const long long q = (p + (long long)(ky - 1) * W + (kx - 1)) * CC + c0;
+#pragma unroll
+          for (int c = 0; c < KC; ++c) go[ky][kx][c] = ok && c0 + c < CC ? gout[q + c] : 0.f;
+        }
+    };
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
         const int yy = y + ky - 1, xx = x + kx - 1;
         const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
-        const long long q = (p + (long long)(ky - 1) * W + (kx - 1)) * CC;
+        const long long q = (p + (long long)(ky - 1) * W + (kx - 1)) * CC + ci0;
 #pragma unroll
-        for (int c = 0; c < CC; ++c) {
-          go[ky][kx][c] = ok ? gout[q + c] : 0.f;
-          xi[ky][kx][c] = ok ? in[q + c] : 0.f;
-        }
+        for (int c = 0; c < KC; ++c) xi[ky][kx][c] = ok && ci0 + c < CC ? in[q + c] : 0.f;
       }
-    float o[CC];
+    load_go(co0);
 #pragma unroll
-    for (int ci = 0; ci < CC; ++ci) o[ci] = accumulate ? gin[p * CC + ci] : 0.f;
-#pragma unroll
-    for (int co = 0; co < CC; ++co) {
+    for (int co = 0; co < KC; ++co) {
       acc[NW + co] += go[1][1][co];
 #pragma unroll
-      for (int ci = 0; ci < CC; ++ci)
+      for (int ci = 0; ci < KC; ++ci)
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-          for (int kx = 0; kx < 3; ++kx) {
-            const int wi = ((co * CC + ci) * 3 + ky) * 3 + kx;
-            acc[wi] += go[1][1][co] * xi[ky][kx][ci];
-            o[ci] += wr[wi] * go[2 - ky][2 - kx][co];
-          }
+          for (int kx = 0; kx < 3; ++kx) acc[((co * KC + ci) * 3 + ky) * 3 + kx] += go[1][1][co] * xi[ky][kx][ci];
+    }
+    if (k != 0) continue;  // (block-uniform)
+    float o[KC];
+#pragma unroll
+    for (int ci = 0; ci < KC; ++ci) o[ci] = accumulate && ci0 + ci < CC ? gin[p * CC + ci0 + ci] : 0.f;
+#pragma unroll 1
+    for (int kk = 0; kk < NCH; ++kk) {  // (a loop: the weights of one output chunk at a time, not all of W, stay in registers)
+      if (kk > 0) load_go(kk * KC);
+#pragma unroll
+      for (int co = 0; co < KC; ++co) {
+        if (kk * KC + co >= CC) break;
+#pragma unroll
+        for (int ci = 0; ci < KC; ++ci) {
+          if (ci0 + ci >= CC) break;
+#pragma unroll
+          for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx)
+              o[ci] += w[(((kk * KC + co) * CC + ci0 + ci) * 3 + ky) * 3 + kx] * go[2 - ky][2 - kx][co];  // (launch-uniform: scalar loads)
+        }
+      }
     }
 #pragma unroll
-    for (int ci = 0; ci < CC; ++ci) {
-      if (mask_y && !(mask_y[p * CC + ci] > 0.f)) o[ci] = 0.f;
-      gin[p * CC + ci] = o[ci];
+    for (int ci = 0; ci < KC; ++ci) {
+      if (ci0 + ci >= CC) break;
+      if (mask_y && !(mask_y[p * CC + ci0 + ci] > 0.f)) o[ci] = 0.f;
+      gin[p * CC + ci0 + ci] = o[ci];
     }
   }
   if (!dW && !db) return;
@@ -815,51 +844,68 @@ __global__ __launch_bounds__(256) void small_conv_bwd_kernel(const float* __rest
     if (lane == 0) red[wave][i] = v;
   }
   __syncthreads();
-  if (threadIdx.x < NACC)
-    partials[(size_t)blockIdx.x * NACC + threadIdx.x] =
-        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  const int i = threadIdx.x;
+  if (i >= NACC) return;
+  int col;
+  if (i < NW) {  // ((co0 + co) * CC + ci0 + ci) * 9 + t
+    const int co = i / (KC * 9), ci = (i / 9) % KC, t = i % 9;
+    if (co0 + co >= CC || ci0 + ci >= CC) return;
+    col = ((co0 + co) * CC + ci0 + ci) * 9 + t;
+  } else {  // bias sums: written by the j = 0 blocks
+    if (j != 0 || co0 + i - NW >= CC) return;
+    col = CC * CC * 9 + co0 + i - NW;
+  }
+  partials[(size_t)blockIdx.x * NCOL + col] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
 }
 __global__ __launch_bounds__(1024) void stem_wgrad_finish_kernel(const float* __restrict__ partials, int nrows, int ncol, int nW,
                                                                 float* __restrict__ dW, float* __restrict__ db);  // (below: adds partial rows into dW | db)
+// one instantiation per band count (1 .. kMaxBands) of a few-channel template kernel
+#define DRS_BANDS_SWITCH(n, X)                                                                                              \
+  switch (n) {                                                                                                              \
+    case 1: X(1); break; case 2: X(2); break; case 3: X(3); break; case 4: X(4); break; case 5: X(5); break;               \
+    case 6: X(6); break; case 7: X(7); break; case 8: X(8); break; case 9: X(9); break; case 10: X(10); break;             \
+    case 11: X(11); break; case 12: X(12); break; case 13: X(13); break; case 14: X(14); break; case 15: X(15); break;      \
+    default: X(16); break;                                                                                                  \
+  }
+static_assert(kMaxBands == 16, "DRS_BANDS_SWITCH instantiates 1 .. 16");
 int drs_launch_small_conv_bwd(const float* in, const float* gout, const float* w, float* gin, int accumulate,
-                              const float* mask_y, int N, int CC, int H, int W, float* partials, float* dW, float* db,
-                              hipStream_t s) {
-  DRS_REQUIRE(CC >= 1 && CC <= 4, DRS_ERR_SHAPE, "small_conv_bwd: CC=%d (1..4)", CC);
+                              const float* mask_y, int N, int CC, int H, int W, float* partials, size_t partial_bytes,
+                              float* dW, float* db, hipStream_t s) {
+  DRS_REQUIRE(CC >= 1 && CC <= kMaxBands, DRS_ERR_SHAPE, "small_conv_bwd: CC=%d (1..%d)", CC, kMaxBands);
   const long long npix = (long long)N * H * W;
   if (npix == 0) return DRS_OK;
-  const unsigned blocks = grid1d(npix, 256, 1024);  // <= 1024 partial rows of <= 148 floats
-#define DRS_SCB(K) DRS_LAUNCH(small_conv_bwd_kernel<K>, dim3(blocks), dim3(256), 0, s, in, gout, w, gin, accumulate, mask_y, N, H, \
-                              W, partials, dW, db)
-  switch (CC) {
-    case 1: DRS_SCB(1); break;
-    case 2: DRS_SCB(2); break;
-    case 3: DRS_SCB(3); break;
-    default: DRS_SCB(4); break;
-  }
+  const unsigned blocks = grid1d(npix, 256, 1024);  // <= 1024 partial rows of 9 CC^2 + CC floats
+  const int ncol = 9 * CC * CC + CC, nch = (CC + 3) / 4;
+  DRS_REQUIRE(!(dW || db) || partial_bytes >= (size_t)blocks * ncol * 4, DRS_ERR_WORKSPACE,
+              "small_conv_bwd: partial workspace too small");
+#define DRS_SCB(K) DRS_LAUNCH(small_conv_bwd_kernel<K>, dim3(blocks, nch * nch), dim3(256), 0, s, in, gout, w, gin, accumulate, \
+                              mask_y, N, H, W, partials, dW, db)
+  DRS_BANDS_SWITCH(CC, DRS_SCB)
 #undef DRS_SCB
-  if (dW || db) {
-    const int ncol = 9 * CC * CC + CC;
+  if (dW || db)
     DRS_LAUNCH(stem_wgrad_finish_kernel, dim3((ncol + 63) / 64), dim3(1024), 0, s, partials, (int)blocks, ncol, 9 * CC * CC, dW, db);
-  }
   DRS_CHECK_HIP(hipGetLastError());
   return DRS_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Weight + bias gradient of a stem convolution (3x3, pad 1, CI <= 4 image-like channels -> 16; reference conv0 /
+// Weight + bias gradient of a stem convolution (3x3, pad 1, CI <= kMaxBands image-like channels -> 16; reference conv0 /
 // conv_upsampled_lr_img, UNet_model_superres.py:281,287):
 //   dW[co][ci][ky][kx] += sum_p g[p][co] * x[p + (ky-1, kx-1)][ci]      db[co] += sum_p g[p][co]
-// g: channels-last, pixel stride g_cs (16 used); x: channels-last, CI channels.  Wave w of a block owns output channels
-// 4w .. 4w+3 for 64 pixels per pass: 36 CI + 4 sums per lane in registers over the block's pixels, one shuffle reduction at
-// the end, lane 0 writes the wave's columns of the block's partial row (column = flat dW index, then the 16 bias sums);
-// stem_wgrad_finish_kernel adds the rows in a fixed order.  The MFMA weight-gradient kernel spent 230 us + a 35 - 90 us slice
-// reduction per layer on these 432 sums (scalar staging of a 3-channel operand into 16-wide tiles).
+// g: channels-last, pixel stride g_cs (16 used); x: channels-last, CI channels.  Block row blockIdx.y = input chunk j of
+// KC = min(CI, 4) channels; wave w of a block owns output channels 4w .. 4w+3 for 64 pixels per pass: 36 KC + 4 sums per lane
+// in registers over the block's pixels, one shuffle reduction at the end, lane 0 writes the wave's columns of the block's
+// partial row (column = flat dW index, then the 16 bias sums, those from the j = 0 blocks); stem_wgrad_finish_kernel adds the
+// rows in a fixed order.  The MFMA weight-gradient kernel spent 230 us + a 35 - 90 us slice reduction per layer on these 432
+// sums (scalar staging of a 3-channel operand into 16-wide tiles).
 // ---------------------------------------------------------------------------------------------------------------
 template <int CI>
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict__ g, int g_cs, const float* __restrict__ x,
                                                          int N, int H, int W, float* __restrict__ partials) {
-  constexpr int NW = 4 * CI * 9, NACC = NW + 4, NCOL = 16 * CI * 9 + 16;
+  constexpr int KC = CI < 4 ? CI : 4;
+  constexpr int NW = 4 * KC * 9, NACC = NW + 4, NCOL = 16 * CI * 9 + 16;
   const int lane = threadIdx.x & 63, cg = threadIdx.x >> 6;
+  const int ci0 = blockIdx.y * KC;
   const long long npix = (long long)N * H * W;
   float acc[NACC];
 #pragma unroll
@@ -868,24 +914,24 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
     const int xx = (int)(p % W), yy = (int)((p / W) % H);
     const float4 gv4 = *reinterpret_cast<const float4*>(g + p * g_cs + cg * 4);
     const float gv[4] = {gv4.x, gv4.y, gv4.z, gv4.w};
-    float xi[9][CI];
+    float xi[9][KC];
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
         const int y2 = yy + ky - 1, x2 = xx + kx - 1;
         const bool ok = y2 >= 0 && y2 < H && x2 >= 0 && x2 < W;
-        const long long q = (p + (long long)(ky - 1) * W + (kx - 1)) * CI;
+        const long long q = (p + (long long)(ky - 1) * W + (kx - 1)) * CI + ci0;
 #pragma unroll
-        for (int c = 0; c < CI; ++c) xi[ky * 3 + kx][c] = ok ? x[q + c] : 0.f;
+        for (int c = 0; c < KC; ++c) xi[ky * 3 + kx][c] = ok && ci0 + c < CI ? x[q + c] : 0.f;
       }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       acc[NW + j] += gv[j];
 #pragma unroll
-      for (int c = 0; c < CI; ++c)
+      for (int c = 0; c < KC; ++c)
 #pragma unroll
-        for (int t = 0; t < 9; ++t) acc[(j * CI + c) * 9 + t] += gv[j] * xi[t][c];
+        for (int t = 0; t < 9; ++t) acc[(j * KC + c) * 9 + t] += gv[j] * xi[t][c];
     }
   }
   float* row = partials + (size_t)blockIdx.x * NCOL;
@@ -895,8 +941,12 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
     if (lane == 0) {
-      if (i < NW) row[cg * NW + i] = v;              // ((4 cg + j) * CI + c) * 9 + t
-      else row[16 * CI * 9 + cg * 4 + (i - NW)] = v;
+      if (i < NW) {  // ((4 cg + j) * CI + ci0 + c) * 9 + t
+        const int j = i / (KC * 9), c = (i / 9) % KC, t = i % 9;
+        if (ci0 + c < CI) row[((4 * cg + j) * CI + ci0 + c) * 9 + t] = v;
+      } else if (blockIdx.y == 0) {
+        row[16 * CI * 9 + cg * 4 + (i - NW)] = v;
+      }
     }
   }
 }
@@ -919,19 +969,14 @@ __global__ __launch_bounds__(1024) void stem_wgrad_finish_kernel(const float* __
 }
 int drs_launch_stem_wgrad(const float* g, int g_cs, const float* x, int N, int CI, int H, int W, float* partials,
                           size_t partial_bytes, float* dW, float* db, hipStream_t s) {
-  DRS_REQUIRE(CI >= 1 && CI <= 4 && (g_cs & 3) == 0, DRS_ERR_SHAPE, "stem_wgrad: CI=%d g_cs=%d", CI, g_cs);
+  DRS_REQUIRE(CI >= 1 && CI <= kMaxBands && (g_cs & 3) == 0, DRS_ERR_SHAPE, "stem_wgrad: CI=%d g_cs=%d", CI, g_cs);
   const long long npix = (long long)N * H * W;
   if (npix == 0 || (!dW && !db)) return DRS_OK;
   const int ncol = 16 * CI * 9 + 16;
   const unsigned blocks = grid1d(npix, 64, 512);
   DRS_REQUIRE(partial_bytes >= (size_t)blocks * ncol * 4, DRS_ERR_WORKSPACE, "stem_wgrad: partial workspace too small");
-#define DRS_SWG(K) DRS_LAUNCH(stem_wgrad_kernel<K>, dim3(blocks), dim3(256), 0, s, g, g_cs, x, N, H, W, partials)
-  switch (CI) {
-    case 1: DRS_SWG(1); break;
-    case 2: DRS_SWG(2); break;
-    case 3: DRS_SWG(3); break;
-    default: DRS_SWG(4); break;
-  }
+#define DRS_SWG(K) DRS_LAUNCH(stem_wgrad_kernel<K>, dim3(blocks, (K + 3) / 4), dim3(256), 0, s, g, g_cs, x, N, H, W, partials)
+  DRS_BANDS_SWITCH(CI, DRS_SWG)
 #undef DRS_SWG
   DRS_LAUNCH(stem_wgrad_finish_kernel, dim3((ncol + 63) / 64), dim3(1024), 0, s, partials, (int)blocks, ncol, 16 * CI * 9, dW, db);
   DRS_CHECK_HIP(hipGetLastError());
@@ -939,20 +984,23 @@ int drs_launch_stem_wgrad(const float* g, int g_cs, const float* x, int N, int C
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Data gradient of a stem convolution (3x3, pad 1, C <= 4 image-like channels -> 16; reference conv_upsampled_lr_img /
+// Data gradient of a stem convolution (3x3, pad 1, C <= kMaxBands image-like channels -> 16; reference conv_upsampled_lr_img /
 // conv0, UNet_model_superres.py:281,287):  dx[n][y][x][c] = sum_{ky,kx,o} g[n][y+1-ky][x+1-kx][o] * w[o][c][ky][kx], zero
 // outside the image.  Block = 16 x 16 pixels; the 18 x 18 x 16 tile of g goes through LDS once (the direct tap kernel this
 // replaces re-read every pixel's 16 channels for each of the 9 taps from L1 / L2: 610 us per configs[2] step for a
-// 3-channel result).  g: channels-last with pixel stride g_cs (16 used); w: the layer's own (16, C, 3, 3) parameter.
+// 3-channel result).  Up to kMaxBands accumulators, the 4-wide groups past C skipped; each sums in the order ky, kx, o.
+// g: channels-last with pixel stride g_cs (16 used); w: the layer's own (16, C, 3, 3) parameter.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void stem_dgrad_kernel(const float* __restrict__ g, int g_cs, const float* __restrict__ w,
                                                          float* __restrict__ dx, int H, int W, int C) {
-  __shared__ float sg[18 * 18][17];  // (+1: a lane's 16-float rows start in different banks)
-  __shared__ float sw[16 * 4 * 9];   // [o][c (padded to 4)][tap]
+  constexpr int kC = kMaxBands;
+  __shared__ float sg[18 * 18][17];   // (+1: a lane's 16-float rows start in different banks)
+  __shared__ float sw[16 * kC * 9];   // [o][c (padded to kC)][tap]
   const int n = blockIdx.z, y0 = blockIdx.y * 16, x0 = blockIdx.x * 16;
-  for (int i = threadIdx.x; i < 16 * 4 * 9; i += 256) {
-    const int tap = i % 9, c = (i / 9) & 3, o = i / 36;
-    sw[i] = c < C ? w[(o * C + c) * 9 + tap] : 0.f;
+  const int cpad = (C + 3) & ~3;      // channels rounded up to the 4-wide chunks (the padding weights are zero)
+  for (int i = threadIdx.x; i < 16 * cpad * 9; i += 256) {
+    const int tap = i % 9, c = (i / 9) % cpad, o = i / (9 * cpad);
+    sw[(o * kC + c) * 9 + tap] = c < C ? w[(o * C + c) * 9 + tap] : 0.f;
   }
   for (int i = threadIdx.x; i < 18 * 18 * 4; i += 256) {  // one float4 (4 of the 16 channels) per step
     const int q = i & 3, pix = i >> 2;
@@ -967,7 +1015,9 @@ __global__ __launch_bounds__(256) void stem_dgrad_kernel(const float* __restrict
   const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
   const int y = y0 + ty, x = x0 + tx;
   if (y >= H || x >= W) return;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  float acc[kC];
+#pragma unroll
+  for (int c = 0; c < kC; ++c) acc[c] = 0.f;
 #pragma unroll
   for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
@@ -977,14 +1027,20 @@ __global__ __launch_bounds__(256) void stem_dgrad_kernel(const float* __restrict
       for (int o = 0; o < 16; ++o) {
         const float gv = gp[o];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) acc[c] = fmaf(gv, sw[(o * 4 + c) * 9 + ky * 3 + kx], acc[c]);
+        for (int c0 = 0; c0 < kC; c0 += 4) {
+          if (c0 >= cpad) break;  // (launch-uniform)
+#pragma unroll
+          for (int c = c0; c < c0 + 4; ++c) acc[c] = fmaf(gv, sw[(o * kC + c) * 9 + ky * 3 + kx], acc[c]);
+        }
       }
     }
   float* out = dx + (((long long)n * H + y) * W + x) * C;
-  for (int c = 0; c < C; ++c) out[c] = acc[c];
+#pragma unroll
+  for (int c = 0; c < kC; ++c)
+    if (c < C) out[c] = acc[c];
 }
 int drs_launch_stem_dgrad(const float* g, int g_cs, const float* w, float* dx, int N, int H, int W, int C, hipStream_t s) {
-  DRS_REQUIRE(C >= 1 && C <= 4 && (g_cs & 3) == 0 && g_cs >= 16, DRS_ERR_SHAPE, "stem_dgrad: C=%d g_cs=%d", C, g_cs);
+  DRS_REQUIRE(C >= 1 && C <= kMaxBands && (g_cs & 3) == 0 && g_cs >= 16, DRS_ERR_SHAPE, "stem_dgrad: C=%d g_cs=%d", C, g_cs);
   if ((long long)N * H * W == 0) return DRS_OK;
   DRS_LAUNCH(stem_dgrad_kernel, dim3((W + 15) / 16, (H + 15) / 16, N), dim3(256), 0, s, g, g_cs, w, dx, H, W, C);
   DRS_CHECK_HIP(hipGetLastError());

@@ -152,6 +152,30 @@ class NoisePrefetcher:
         self._t.join(timeout=5)
 
 
+MAX_BANDS = 16  # most image bands a network takes (include/drs_hip.h: drs_unet_config)
+
+
+def load_npy_u8(path, image_size=None):
+    """One multispectral image of a dataset folder as a (C, S, S) uint8 array: the (H, W, C) float array of a `.npy` file
+    in [0, 1] turned into bytes as the reference's numpy data format does (`(y * 255).astype(np.uint8)`, utils.py:131-133),
+    then each band resized to image_size x image_size as a Pillow mode-L image with BILINEAR when its size differs.  For
+    C = 3 that is the bytes Pillow's RGB resize gives (Pillow resamples the bands of an RGB image independently, with the
+    same arithmetic); a (H, W) array is one band."""
+    from PIL import Image
+    y = np.load(path, allow_pickle=False)
+    if y.ndim == 2:
+        y = y[:, :, None]
+    if y.ndim != 3 or not 1 <= y.shape[2] <= MAX_BANDS or not np.issubdtype(y.dtype, np.floating):
+        raise ValueError(f"{path}: expected one (H, W, C) float array with 1 <= C <= {MAX_BANDS} bands, got "
+                         f"{y.dtype} {tuple(y.shape)}")
+    u8 = (y * 255).astype(np.uint8)
+    h, w, c = u8.shape
+    if image_size is None or (w, h) == (image_size, image_size):
+        return np.ascontiguousarray(np.moveaxis(u8, -1, 0))
+    return np.stack([np.asarray(Image.fromarray(np.ascontiguousarray(u8[:, :, b])).resize(
+        (image_size, image_size), Image.BILINEAR), dtype=np.uint8) for b in range(c)])
+
+
 def load_image_folder_u8(root_dir, image_size=None, rank=0, world_size=1, limit=None):
     """Decode side of the reference's `get_data_superres` (utils.py:93-138) + the `transforms.Resize((image_size,
     image_size))` its `launch` hands it as `transform` (train_diffusion_superres.py:594-605): the images of `root_dir` in
@@ -166,7 +190,11 @@ def load_image_folder_u8(root_dir, image_size=None, rank=0, world_size=1, limit=
     is printed; DistributedSampler pads with repeats instead).  `limit`: only the first `limit` files of the (unsharded) list -
     the reference's `train_dataset[0..4]` of the final sampling.  Entries that are not files are skipped like any directory
     listing tool would; a file Pillow cannot read raises with its name.  8-bit modes L / RGB / RGBA (what ToTensor turns into
-    1 / 3 / 4 channels of uint8 / 255); other modes raise."""
+    1 / 3 / 4 channels of uint8 / 255); other modes raise.
+
+    Multispectral images: a `.npy` file holds one (H, W, C) float array in [0, 1] with C <= MAX_BANDS bands (the reference's
+    `data_format='numpy'`, utils.py:131-133: `(y * 255).astype(np.uint8)`); resizing treats every band as a Pillow mode-L image
+    (load_npy_u8).  A folder whose images differ in band count raises."""
     import os
 
     from PIL import Image, UnidentifiedImageError
@@ -182,6 +210,9 @@ def load_image_folder_u8(root_dir, image_size=None, rank=0, world_size=1, limit=
         names = names[rank::world_size][:per_rank]
     planes = []
     for name in names:
+        if name.endswith(".npy"):
+            planes.append(load_npy_u8(os.path.join(root_dir, name), image_size))
+            continue
         try:
             img = Image.open(os.path.join(root_dir, name))
         except (UnidentifiedImageError, OSError) as e:
@@ -195,6 +226,9 @@ def load_image_folder_u8(root_dir, image_size=None, rank=0, world_size=1, limit=
                 y = y.resize((image_size, image_size), Image.BILINEAR)
             a = np.asarray(y, dtype=np.uint8)
         planes.append(a[None] if a.ndim == 2 else np.moveaxis(a, -1, 0))
+    bands = {p.shape[0] for p in planes}
+    if len(bands) > 1:
+        raise ValueError(f"images of {root_dir} differ in band count {sorted(bands)}")
     shapes = {p.shape for p in planes}
     if len(shapes) != 1:
         raise ValueError(f"images of {root_dir} differ in shape {sorted(shapes)}: pass image_size, as the reference's launch does")

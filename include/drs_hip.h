@@ -198,15 +198,15 @@ DRS_API int drs_time_mlp(const int64_t* t, const float* inv_freq, const float* W
 typedef struct drs_unet_config {
   int batch;          /* n images in x */
   int lr_batch;       /* batch of lr_img: == batch, or 1 (broadcast, Diffusion.sample :224) */
-  int image_channels; /* reference ctor arg (3) */
-  int out_dim;        /* reference ctor arg (3) */
+  int image_channels; /* reference ctor arg (3); 1..16 bands */
+  int out_dim;        /* reference ctor arg (3); 1..16 (above 4 the output projection is not folded into up_convs.2) */
   int height, width;  /* of x; divisible by 8 and by magnification */
   int magnification;  /* lr_img is (height/mag, width/mag) */
   int impl;           /* DRS_IMPL_* used for the wide convolutions */
   float bn_eps;       /* 1e-5 */
   int flags;          /* DRS_PLAN_* */
   int variant;        /* DRS_VARIANT_* : which of the reference's three near-identical UNets */
-  int cond_channels;  /* channels of the conditioning image (superres: = image_channels; SAR: 2; generation: 0) */
+  int cond_channels;  /* channels of the conditioning image, 1..16 (superres: = image_channels; SAR: 2; generation: 0) */
   int num_classes;    /* generation: rows of label_emb (0 = no label embedding) */
 } drs_unet_config;
 /* Variants (same kernels, different wiring and state_dict key names):
