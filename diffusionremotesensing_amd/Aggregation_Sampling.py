@@ -73,9 +73,9 @@ class split_aggregation_sampling:
         weights = torch.tensor(np.outer(y_probs, x_probs)).to(torch.float32).to(self.device)
         return torch.tile(weights, (nbatches, 3, 1, 1))
 
-    def sample_tiles(self, noise_source=None):
+    def sample_tiles(self, noise_source=None, sampling_steps=None, eta=0.0):
         """Super-resolve every tile: (n_tiles, C, S, S) on this rank's device.  One batched chain (sharded over the
-        ranks of an initialised process group)."""
+        ranks of an initialised process group); `sampling_steps` / `eta` select a DDIM chain (`Diffusion.sample`)."""
         d = self.diffusion_model
         lr = torch.cat([p[:1] for p in self.patches_lr], dim=0).to(self.device).contiguous()  # (n, C, ps, ps)
         n = lr.shape[0]
@@ -88,6 +88,8 @@ class split_aggregation_sampling:
         # 2048 x 2048 scene at stride 32 has ~4000 tiles: as a single batch its workspace would not fit any device).
         # The last chunk is padded with repeats of its last tile so that it runs on the same plan.
         chunk = max(1, int(getattr(self, "tile_batch", 0) or TILE_BATCH))
+        # the DDIM arguments are passed only when set: the default call is the reference's, whatever sampler `d` is
+        ddim = {"sampling_steps": sampling_steps, "eta": eta} if sampling_steps is not None or eta != 0.0 else {}
         outs = []
         for c0 in range(lo, hi, chunk):
             c1 = min(c0 + chunk, hi)
@@ -103,18 +105,19 @@ class split_aggregation_sampling:
                     if shape[0] > take:
                         real = torch.cat([real, real[-1:].expand(shape[0] - take, -1, -1, -1)], dim=0)
                     return real
-            out_c = d.sample(size, self.model, lr_c, input_channels=lr.shape[1], generate_video=False, noise_source=csrc)
+            out_c = d.sample(size, self.model, lr_c, input_channels=lr.shape[1], generate_video=False, noise_source=csrc,
+                             **ddim)
             outs.append(out_c[:take])
         mine = torch.cat(outs, dim=0) if outs else lr.new_zeros((0, lr.shape[1], d.image_size, d.image_size))
         if drs_dist.world_size() > 1:
             mine = drs_dist.gather_shards(mine, n)
         return mine
 
-    def aggregation_sampling(self, noise_source=None):
-        """Reference :76-116."""
+    def aggregation_sampling(self, noise_source=None, sampling_steps=None, eta=0.0):
+        """Reference :76-116 (`sampling_steps` / `eta`: every tile runs a DDIM chain)."""
         batch_size, channels, height, width = self.img_lr.shape
         m = self.magnification_factor
-        tiles = self.sample_tiles(noise_source)
+        tiles = self.sample_tiles(noise_source, sampling_steps=sampling_steps, eta=eta)
         origins = [(info[0], info[2]) for info in self.patches_sr_infos]
         out = hip_ops.aggregate_tiles(tiles, origins, self.weight[0, 0].contiguous(), height * m, width * m)
         # the reference broadcasts the single chain of each tile over the batch dimension of img_lr
@@ -147,13 +150,16 @@ def launch(args):
                           image_size=args.model_input_size, model_name=args.model_name,
                           Degradation_type=args.Degradation_type, multiple_gpus=False, ema_smoothing=False)
     tiler = split_aggregation_sampling(img_lr, args.patch_size, args.stride, args.magnification_factor, diffusion, device)
-    final_pred = tiler.aggregation_sampling()
+    final_pred = tiler.aggregation_sampling(sampling_steps=getattr(args, "sampling_steps", None),
+                                            eta=getattr(args, "eta", 0.0))
     torch.save(final_pred.squeeze(0).cpu(), args.destination_path)
 
 
 def build_arg_parser():
-    """The reference's flags, verbatim (:217-231)."""
+    """The reference's flags, verbatim (:217-231), and the DDIM flags."""
     import argparse
+
+    from .train_diffusion_superres import add_sampling_args
     p = argparse.ArgumentParser(description=" ")
     p.add_argument("--noise_schedule", type=str, default="cosine")
     p.add_argument("--snapshot_name", type=str, default="snapshot.pt")
@@ -169,6 +175,7 @@ def build_arg_parser():
     p.add_argument("--stride", type=int, default=32)
     p.add_argument("--destination_path", type=str)
     p.add_argument("--img_lr_path", type=str)
+    add_sampling_args(p)
     return p
 
 

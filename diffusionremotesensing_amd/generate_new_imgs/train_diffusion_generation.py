@@ -13,7 +13,8 @@ import torch.nn as nn
 
 from .. import dist as drs_dist
 from .. import hip_ops
-from ..train_diffusion_superres import Diffusion as _SuperresDiffusion, run_reverse_chain
+from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, add_sampling_args, check_sampling_args,
+                                        ddim_chain_noise, ddim_timesteps, run_reverse_chain)
 from .UNet_model_generation import Residual_Attention_UNet_generation
 
 
@@ -39,8 +40,9 @@ class Diffusion(_SuperresDiffusion):
         return net(x_t, t, cond)
 
     def sample(self, n, model, target_class=None, cfg_scale=3, input_channels=3, generate_video=False,
-               noise_source=None):
-        """Reference :206-259."""
+               noise_source=None, sampling_steps=None, eta=0.0):
+        """Reference :206-259.  `sampling_steps` / `eta`: a DDIM chain, as in the super-resolution sampler."""
+        check_sampling_args(self.noise_steps, sampling_steps, eta)
         frames = []
         net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
         model.eval()
@@ -63,24 +65,36 @@ class Diffusion(_SuperresDiffusion):
                                                                                    device=x.device)]).contiguous()
             t_rows = hip_ops.timestep_table(self.noise_steps, 2 * n, x.device)  # (row i: step i; the unguided forward takes n of the 2n)
             state = {"first": True}
+            taus = ddim_timesteps(self.noise_steps, sampling_steps) if sampling_steps is not None else None
+            prev = dict(zip(taus, taus[1:] + [0])) if taus is not None else None
 
             def step(i):
-                if i > 1:
+                if taus is not None:
+                    noise = ddim_chain_noise(eta, i, prev[i], shape, x, noise_source)
+                elif i > 1:
                     noise = noise_source(i, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
                 else:
                     noise = None
                 if guided:
                     eps2 = engine.forward(x.repeat(2, 1, 1, 1), t_rows[i], None, 1, labels=labels2, check_weights=state["first"])
-                    hip_ops.sampler_step_cfg_(x, eps2[:n], eps2[n:], cfg_scale, noise, i, self.alpha, self.alpha_hat,
-                                              self.beta)
+                    if taus is not None:
+                        hip_ops.ddim_step_(x, eps2[:n], noise, i, prev[i], eta, self.alpha_hat, eps_uncond=eps2[n:],
+                                           cfg_scale=cfg_scale)
+                    else:
+                        hip_ops.sampler_step_cfg_(x, eps2[:n], eps2[n:], cfg_scale, noise, i, self.alpha, self.alpha_hat,
+                                                  self.beta)
                 else:
                     # cfg_scale > 0 without a class: lerp(u, u, w) == u, one forward is enough
                     predicted_noise = engine.forward(x, t_rows[i, :n], None, 1, labels=target_class, check_weights=state["first"])
-                    hip_ops.sampler_step_(x, predicted_noise, noise, i, self.alpha, self.alpha_hat, self.beta)
+                    if taus is not None:
+                        hip_ops.ddim_step_(x, predicted_noise, noise, i, prev[i], eta, self.alpha_hat)
+                    else:
+                        hip_ops.sampler_step_(x, predicted_noise, noise, i, self.alpha, self.alpha_hat, self.beta)
                 state["first"] = False
                 if generate_video:
                     frames.append(x.clone())
-            run_reverse_chain(engine, x, self.noise_steps, step, frames if generate_video else None)  # (reads the kernels' fault word)
+            run_reverse_chain(engine, x, self.noise_steps, step, frames if generate_video else None,
+                              timesteps=taus)  # (reads the kernels' fault word)
         if generate_video:
             from ..video import video_maker
             video_maker(frames, os.path.join(os.getcwd(), "models_run", self.model_name, "results",
@@ -155,13 +169,14 @@ def launch(args):
     if args.multiple_gpus:
         drs_dist.destroy_process_group()
     outs = [diffusion.sample(n=5, model=model, target_class=torch.full((5,), i, dtype=torch.int64), cfg_scale=3,
-                             input_channels=ch, generate_video=False) for i in range(min(num_classes, 3))]
+                             input_channels=ch, generate_video=False, sampling_steps=getattr(args, "sampling_steps", None),
+                             eta=getattr(args, "eta", 0.0)) for i in range(min(num_classes, 3))]
     torch.save(torch.cat(outs).cpu(), os.path.join(os.getcwd(), "models_run", args.model_name, "results",
                                                   "generation_results.pt"))
 
 
 def build_arg_parser():
-    """The reference's flags, verbatim (:649-665)."""
+    """The reference's flags, verbatim (:649-665), and the DDIM flags."""
     import argparse
 
     def str2bool(v):
@@ -185,6 +200,7 @@ def build_arg_parser():
     p.add_argument("--UNet_type", type=str, default="Residual Attention UNet")
     p.add_argument("--multiple_gpus", type=str2bool, nargs="?", const=True, default=False)
     p.add_argument("--ema_smoothing", type=str2bool, nargs="?", const=True, default=False)
+    add_sampling_args(p)
     return p
 
 

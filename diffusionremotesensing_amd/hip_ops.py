@@ -176,6 +176,26 @@ def sampler_step_cfg_(x, eps_cond, eps_uncond, cfg_scale, noise, t, alpha, alpha
     return x
 
 
+def ddim_step_(x, eps_cond, noise, t, t_prev, eta, alpha_hat, eps_uncond=None, cfg_scale=0.0):
+    """In-place DDIM update of x from timestep t to t_prev (include/drs_hip.h: drs_ddim_step); with `eps_uncond` the
+    prediction is torch.lerp(eps_uncond, eps_cond, cfg_scale).  `noise` may be None when eta == 0 or t_prev == 0."""
+    lib = _lib.load()
+    if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
+        raise RuntimeError("ddim_step_: x must be a contiguous fp32 ROCm tensor (no CPU fallback)")
+    eps_cond = _req(eps_cond, "eps_cond")
+    eps_uncond = _req(eps_uncond, "eps_uncond") if eps_uncond is not None else None
+    noise = _req(noise, "noise") if noise is not None else None
+    alpha_hat = _req(alpha_hat, "alpha_hat")
+    for name, t_ in (("eps_cond", eps_cond), ("eps_uncond", eps_uncond), ("noise", noise)):
+        if t_ is not None and t_.numel() != x.numel():
+            raise RuntimeError(f"ddim_step_: {name} has {t_.numel()} elements, x has {x.numel()}")
+    with torch.cuda.device(x.device):
+        st = lib.drs_ddim_step(_ptr(x), _ptr(eps_cond), _ptr(eps_uncond), float(cfg_scale), _ptr(noise), int(t),
+                               int(t_prev), float(eta), _ptr(alpha_hat), alpha_hat.numel(), x.numel(), _stream(x.device))
+    _lib.check(st, "drs_ddim_step")
+    return x
+
+
 def aggregate_tiles(tiles, origins, weight, height, width):
     """Gaussian-weighted blend of (n,C,S,S) tiles placed at `origins` [(y0, x0), ...] into a (C,height,width) image,
     normalised by the summed weights and clamped to [0,1] (reference Aggregation_Sampling.py:90-116).

@@ -12,7 +12,8 @@ import torch.nn as nn
 
 from . import dist as drs_dist
 from . import hip_ops
-from .train_diffusion_superres import Diffusion as _SuperresDiffusion, run_reverse_chain
+from .train_diffusion_superres import (Diffusion as _SuperresDiffusion, add_sampling_args, check_sampling_args,
+                                       ddim_chain_noise, ddim_timesteps, run_reverse_chain)
 from .UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
 
 
@@ -29,9 +30,12 @@ class Diffusion(_SuperresDiffusion):
     def _predict(self, net, x_t, t, cond):
         return net(x_t, t, cond)
 
-    def sample(self, n, model, SAR_img, NDVI_channels=1, generate_video=False, noise_source=None):
+    def sample(self, n, model, SAR_img, NDVI_channels=1, generate_video=False, noise_source=None, sampling_steps=None,
+               eta=0.0):
         """Reference :204-249.  One (SAR_channels, S, S) image conditions all n chains; its encoder branch is computed
-        once per chain instead of once per step.  `noise_source(i, shape)` as in the super-resolution sampler."""
+        once per chain instead of once per step.  `noise_source(i, shape)`, `sampling_steps` and `eta` as in the
+        super-resolution sampler."""
+        check_sampling_args(self.noise_steps, sampling_steps, eta)
         SAR_img = SAR_img.to(self.device).unsqueeze(0).contiguous()
         frames = []
         net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
@@ -43,18 +47,25 @@ class Diffusion(_SuperresDiffusion):
             x = x.contiguous()
             t_rows = hip_ops.timestep_table(self.noise_steps, n, x.device)
             state = {"first": True}
+            taus = ddim_timesteps(self.noise_steps, sampling_steps) if sampling_steps is not None else None
+            prev = dict(zip(taus, taus[1:] + [0])) if taus is not None else None
 
             def step(i):
                 predicted_noise = engine.forward(x, t_rows[i], SAR_img, 1, reuse_cond=not state["first"], check_weights=state["first"])
                 state["first"] = False
-                if i > 1:
-                    noise = noise_source(i, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
+                if taus is not None:
+                    noise = ddim_chain_noise(eta, i, prev[i], shape, x, noise_source)
+                    hip_ops.ddim_step_(x, predicted_noise, noise, i, prev[i], eta, self.alpha_hat)
                 else:
-                    noise = None
-                hip_ops.sampler_step_(x, predicted_noise, noise, i, self.alpha, self.alpha_hat, self.beta)
+                    if i > 1:
+                        noise = noise_source(i, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
+                    else:
+                        noise = None
+                    hip_ops.sampler_step_(x, predicted_noise, noise, i, self.alpha, self.alpha_hat, self.beta)
                 if generate_video:
                     frames.append(x.clone())
-            run_reverse_chain(engine, x, self.noise_steps, step, frames if generate_video else None)  # (reads the kernels' fault word)
+            run_reverse_chain(engine, x, self.noise_steps, step, frames if generate_video else None,
+                              timesteps=taus)  # (reads the kernels' fault word)
         if generate_video:
             from .video import video_maker
             video_maker(frames, os.path.join(os.getcwd(), "models_run", self.model_name, "results",
@@ -124,13 +135,14 @@ def launch(args):
     if args.multiple_gpus:
         drs_dist.destroy_process_group()
     outs = [diffusion.sample(n=1, model=model, SAR_img=train_dataset[i][0], NDVI_channels=args.NDVI_channels,
-                             generate_video=args.generate_video) for i in range(min(5, len(train_dataset)))]
+                             generate_video=args.generate_video, sampling_steps=getattr(args, "sampling_steps", None),
+                             eta=getattr(args, "eta", 0.0)) for i in range(min(5, len(train_dataset)))]
     torch.save(torch.cat(outs).cpu(), os.path.join(os.getcwd(), "models_run", args.model_name, "results",
                                                   "SAR_TO_NDVI_results.pt"))
 
 
 def build_arg_parser():
-    """The reference's flags, verbatim (:646-663)."""
+    """The reference's flags, verbatim (:646-663), and the DDIM flags."""
     import argparse
 
     def str2bool(v):
@@ -155,6 +167,7 @@ def build_arg_parser():
     p.add_argument("--UNet_type", type=str, default="Residual Attention UNet")
     p.add_argument("--multiple_gpus", type=str2bool, nargs="?", const=True, default=False)
     p.add_argument("--ema_smoothing", type=str2bool, nargs="?", const=True, default=False)
+    add_sampling_args(p)
     return p
 
 

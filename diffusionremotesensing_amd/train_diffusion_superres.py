@@ -13,6 +13,7 @@ Deliberately different (documented in DESIGN.md):
     DistributedDataParallel(find_unused_parameters=True) (:658).
 """
 import copy
+import math
 import os
 import sys
 
@@ -31,31 +32,67 @@ _DEGRADATIONS = ("downblur", "bsrgan", "downblurnoise")
 CHAIN_CHECK_EVERY = 128  # reverse steps between two reads of the kernels' fault word inside a sampling chain
 
 
-def run_reverse_chain(engine, x, noise_steps, step, frames=None, every=CHAIN_CHECK_EVERY):
+def ddim_timesteps(noise_steps, sampling_steps):
+    """The S timesteps a DDIM chain visits, descending: [1 + (k * (T - 2)) // (S - 1) for k in range(S)] reversed, or
+    [T - 1] for S = 1 (integer arithmetic only).  S = T - 1 visits the ancestral chain's T - 1 .. 1; the step after the
+    last entry goes to timestep 0."""
+    T, S = int(noise_steps), int(sampling_steps)
+    if not 1 <= S <= T - 1:
+        raise ValueError(f"sampling_steps={sampling_steps} outside [1, noise_steps - 1 = {T - 1}]")
+    if S == 1:
+        return [T - 1]
+    return [1 + (k * (T - 2)) // (S - 1) for k in reversed(range(S))]
+
+
+def check_sampling_args(noise_steps, sampling_steps, eta):
+    """ValueError for a DDIM request `Diffusion.sample` cannot run (checked before the engine is touched)."""
+    if sampling_steps is not None:
+        if isinstance(sampling_steps, bool) or int(sampling_steps) != sampling_steps:
+            raise ValueError(f"sampling_steps must be an integer, got {sampling_steps!r}")
+        if not 1 <= sampling_steps <= noise_steps - 1:
+            raise ValueError(f"sampling_steps={sampling_steps} outside [1, noise_steps - 1 = {noise_steps - 1}]")
+    if not (math.isfinite(eta) and eta >= 0):
+        raise ValueError(f"eta={eta} must be finite and >= 0")
+
+
+def ddim_chain_noise(eta, t, t_prev, shape, x, noise_source):
+    """Noise of the DDIM move t -> t_prev: drawn only when sigma > 0 (eta > 0 and t_prev > 0), from `noise_source(t, shape)`
+    or torch.randn_like(x); None otherwise, so an eta = 0 chain draws x_T and nothing else."""
+    if eta > 0 and t_prev > 0:
+        return noise_source(t, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
+    return None
+
+
+CHAIN_CHECK_EVERY = 128  # reverse steps between two reads of the kernels' fault word inside a sampling chain
+
+
+def run_reverse_chain(engine, x, noise_steps, step, frames=None, every=CHAIN_CHECK_EVERY, timesteps=None):
     """The reverse loop of `Diffusion.sample` (reference :234-251): `step(i)` performs reverse step i in place on x, for i =
-    noise_steps - 1 .. 1.  Every `every` steps (and at the end) the fault word of the wave-specialised kernels is read (one
-    4-byte copy + a stream synchronisation: ~0.1 ms per 128 steps of ~1.2 ms each).  A protocol fault raises.  DRS_ERR_RANGE - an
-    activation left the range of the FL arithmetic's fp16 main operand (csrc/conv_mfma_fl.hip; chains of UNTRAINED weights do
-    that, their amplitude grows without bound) - has already switched the plan to the split-bf16 kernels: the chain goes back
-    to its last checkpoint (x as of the last clean check) and continues from there."""
-    i = noise_steps - 1
-    ckpt_i, ckpt_x, ckpt_frames, since = i, x.clone(), 0, 0
-    while i >= 1:
-        step(i)
-        i -= 1
+    noise_steps - 1 .. 1, or for every entry of the descending list `timesteps` (a DDIM chain).  Every `every` steps (and at
+    the end) the fault word of the wave-specialised kernels is read (one 4-byte copy + a stream synchronisation: ~0.1 ms per
+    128 steps of ~1.2 ms each).  A protocol fault raises.  DRS_ERR_RANGE - an activation left the range of the FL arithmetic's
+    fp16 main operand (csrc/conv_mfma_fl.hip; chains of UNTRAINED weights do that, their amplitude grows without bound) - has
+    already switched the plan to the split-bf16 kernels: the chain goes back to its last checkpoint (x as of the last clean
+    check, a position in the step list) and continues from there."""
+    seq = range(noise_steps - 1, 0, -1) if timesteps is None else list(timesteps)
+    k = 0
+    ckpt_k, ckpt_x, ckpt_frames, since = k, x.clone(), 0, 0
+    while k < len(seq):
+        step(seq[k])
+        k += 1
         since += 1
-        if since >= every or i == 0:
+        if since >= every or k == len(seq):
             since = 0
             try:
                 engine.check_faults()
             except _lib.RangeFault as e:
-                print(f"[drs] {e}\n[drs] resuming the chain at step {ckpt_i} on the split-bf16 kernels", file=sys.stderr)
+                print(f"[drs] {e}\n[drs] resuming the chain at step {seq[ckpt_k]} on the split-bf16 kernels", file=sys.stderr)
                 x.copy_(ckpt_x)
-                i = ckpt_i
+                k = ckpt_k
                 if frames is not None:
                     del frames[ckpt_frames:]
                 continue
-            ckpt_i = i
+            ckpt_k = k
             ckpt_x.copy_(x)
             ckpt_frames = len(frames) if frames is not None else 0
     return x
@@ -118,9 +155,13 @@ class Diffusion:
         return torch.randint(low=1, high=self.noise_steps, size=(n,))
 
     # -- reverse process (reference :207-255) ---------------------------------------------------
-    def sample(self, n, model, lr_img, input_channels=3, generate_video=False, noise_source=None):
+    def sample(self, n, model, lr_img, input_channels=3, generate_video=False, noise_source=None, sampling_steps=None,
+               eta=0.0):
         """`noise_source(i, shape)`, when given, supplies x_T (i == noise_steps) and the per-step noise z_i
-        instead of torch.randn — used to drive this sampler and the oracle with identical noise."""
+        instead of torch.randn — used to drive this sampler and the oracle with identical noise.
+        `sampling_steps=S` runs a DDIM chain over the S timesteps of `ddim_timesteps` instead of the reference's ancestral
+        chain (None); `eta` moves it from deterministic (0) to DDPM-like (1) sampling."""
+        check_sampling_args(self.noise_steps, sampling_steps, eta)
         if self.Degradation_type.lower() not in _DEGRADATIONS:
             raise ValueError("The degradation type must be either BSRGAN or DownBlur")
         if lr_img.dim() == 4:
@@ -145,20 +186,27 @@ class Diffusion:
             t_rows = hip_ops.timestep_table(self.noise_steps, n, x.device)
             state = {"first": True}
 
+            taus = ddim_timesteps(self.noise_steps, sampling_steps) if sampling_steps is not None else None
+            prev = dict(zip(taus, taus[1:] + [0])) if taus is not None else None
+
             def step(i):
                 predicted_noise = engine.forward(x, t_rows[i], lr_img, self.magnification_factor, reuse_cond=not state["first"],
                                                  check_weights=state["first"])
                 state["first"] = False
-                if i > 1:
-                    noise = noise_source(i, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
+                if taus is not None:
+                    noise = ddim_chain_noise(eta, i, prev[i], shape, x, noise_source)
+                    hip_ops.ddim_step_(x, predicted_noise, noise, i, prev[i], eta, self.alpha_hat)
                 else:
-                    noise = None  # reference adds zeros at the last step (:248)
-                hip_ops.sampler_step_(x, predicted_noise, noise, i, self.alpha, self.alpha_hat, self.beta)
+                    if i > 1:
+                        noise = noise_source(i, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
+                    else:
+                        noise = None  # reference adds zeros at the last step (:248)
+                    hip_ops.sampler_step_(x, predicted_noise, noise, i, self.alpha, self.alpha_hat, self.beta)
                 if generate_video:
                     frames.append(x.clone())
             # (the fault word of the wave-specialised kernels - a protocol fault reports itself through it instead of a trap,
             #  csrc/sp_sync.h - is read inside the loop, every CHAIN_CHECK_EVERY steps and at the end)
-            run_reverse_chain(engine, x, self.noise_steps, step, frames if generate_video else None)
+            run_reverse_chain(engine, x, self.noise_steps, step, frames if generate_video else None, timesteps=taus)
         if generate_video:
             from .video import video_maker  # optional dependency (cv2), same call as reference :253
             video_maker(frames, os.path.join(os.getcwd(), "models_run", self.model_name, "results",
@@ -436,14 +484,15 @@ def launch(args):
         drs_dist.destroy_process_group()
     if r != 0:
         return  # one rank samples and writes models_run/<name>/results/superres_results.pt (every rank holds the same weights)
-    outs = [diffusion.sample(n=1, model=model, lr_img=lr_i, input_channels=ch, generate_video=args.generate_video)
+    outs = [diffusion.sample(n=1, model=model, lr_img=lr_i, input_channels=ch, generate_video=args.generate_video,
+                             sampling_steps=getattr(args, "sampling_steps", None), eta=getattr(args, "eta", 0.0))
             for lr_i in final_lr]
     torch.save(torch.cat(outs).cpu(), os.path.join(os.getcwd(), "models_run", args.model_name, "results",
                                                   "superres_results.pt"))
 
 
 def build_arg_parser():
-    """The reference's flags, verbatim (:703-724)."""
+    """The reference's flags, verbatim (:703-724), and the DDIM flags (`add_sampling_args`)."""
     import argparse
 
     def str2bool(v):
@@ -471,7 +520,15 @@ def build_arg_parser():
     p.add_argument("--multiple_gpus", type=str2bool, nargs="?", const=True, default=False)
     p.add_argument("--ema_smoothing", type=str2bool, nargs="?", const=True, default=False)
     p.add_argument("--Blur_radius", type=str, default="random")
+    add_sampling_args(p)
     return p
+
+
+def add_sampling_args(p):
+    """The DDIM flags of the final sampling (not in the reference): none = the reference's ancestral chain."""
+    p.add_argument("--sampling_steps", type=int, default=None,
+                   help="sample with DDIM over this many timesteps (1 .. noise_steps - 1); default: the full ancestral chain")
+    p.add_argument("--eta", type=float, default=0.0, help="DDIM eta: 0 deterministic, 1 DDPM-like (with --sampling_steps)")
 
 
 def main(argv=None):

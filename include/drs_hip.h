@@ -88,6 +88,20 @@ DRS_API int drs_sampler_step_cfg(float* x, const float* eps_cond, const float* e
                          int t, const float* alpha, const float* alpha_hat, const float* beta, int noise_steps,
                          int64_t numel, drs_stream_t stream);
 
+/* One DDIM update (Song et al., "Denoising Diffusion Implicit Models"), in place on x, from timestep t to t_prev:
+ *   eps   = eps_uncond ? lerp(eps_uncond, eps_cond, cfg_scale) : eps_cond   (torch.lerp, as drs_sampler_step_cfg)
+ *   sigma = t_prev == 0 ? 0 : eta * sqrt((1 - ah_p) / (1 - ah_t)) * sqrt(1 - ah_t / ah_p)
+ *   x     = sqrt(ah_p / ah_t) * x + (sqrt(max(1 - ah_p - sigma^2, 0)) - sqrt(ah_p) * sqrt(1 - ah_t) / sqrt(ah_t)) * eps
+ *           + sigma * noise
+ * with ah_t = alpha_hat[t], ah_p = alpha_hat[t_prev] read on the device.  The three coefficients are formed in fp64 and
+ * rounded to fp32 once (near t = T - 1 of the cosine schedule ah_t is ~1e-6 and they reach ~+-900 on a long jump); the
+ * per-element update is fp32.  The step to t_prev = 0 is deterministic whatever eta is (the reference adds zeros at its
+ * last step).  `eps_uncond` and `noise` may be NULL; `noise` must be given when eta > 0 and t_prev > 0.
+ * Requires 0 <= t_prev < t < noise_steps and a finite eta >= 0 (DRS_ERR_ARG otherwise). */
+DRS_API int drs_ddim_step(float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale, const float* noise,
+                          int t, int t_prev, float eta, const float* alpha_hat, int noise_steps, int64_t numel,
+                          drs_stream_t stream);
+
 /* One Adam step over many tensors in ONE launch (torch.optim.Adam defaults: no weight decay, no amsgrad):
  *   m = lerp(m, g, 1-beta1); v = v*beta2 + (1-beta2)*g*g; p -= lr/(1-beta1^step) * m / (sqrt(v)/sqrt(1-beta2^step) + eps)
  * `table` (device): ntensors x drs_adam_tensor {p, g, m, v, n, step}; entries with g == NULL are skipped (parameters
