@@ -700,9 +700,8 @@ int drs_pack_queue_flush(hipStream_t s) {
 
 int drs_launch_pack_conv_mfma(const float* w, const float* b, const float* gamma, const float* beta, const float* rmean,
                               const float* rvar, float eps, void* dst_w, float* dst_b, int Cout, int Cin, int taps,
-                              int transposed, int impl, hipStream_t s, int cout_src, int flip_taps, int co_off, int partial,
-                              int perm, int cin_total, int cin_off) {
-  if (cout_src <= 0) cout_src = Cout;
+                              int transposed, int impl, hipStream_t s, PackMfmaOpts opt) {
+  const int cout_src = opt.cout_src > 0 ? opt.cout_src : Cout;
   const int KC = 4 * slot_ch(impl);
   const int nchunks = drs_cdiv(Cin, KC);
   const size_t image = (size_t)nchunks * taps * 4 * Cout * 16;
@@ -711,7 +710,7 @@ int drs_launch_pack_conv_mfma(const float* w, const float* b, const float* gamma
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   const PackJob job{w, b, gamma, beta, rmean, rvar, (char*)dst_w, dst_b, image, eps, Cout, Cin, taps, transposed, nchunks,
-                    cout_src, flip_taps, co_off, partial, perm, cin_total, cin_off};
+                    cout_src, opt.flip_taps, opt.co_off, opt.partial, opt.perm, opt.cin_total, opt.cin_off};
   const int pol = impl == DRS_IMPL_MFMA_F32 ? 0 : (impl == DRS_IMPL_MFMA_F16 ? 1 : 2);
   PackQueue& q = g_pack_queue;
   if (q.open) {

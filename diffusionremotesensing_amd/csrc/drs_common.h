@@ -190,10 +190,14 @@ struct DrsPackQueueScope {  // opens the queue; an early return abandons it, the
   ~DrsPackQueueScope() { drs_pack_queue_abandon(); }
   int flush(hipStream_t s) { return drs_pack_queue_flush(s); }
 };
+// Options of drs_launch_pack_conv_mfma, all 0 by default.  The source fills output channels [co_off, co_off + cout_src) of
+// the image (cout_src 0: Cout); the other channels get zero weights, or are left alone with `partial` (a second layer packed
+// into the same image).  flip_taps: taps in reverse order (data gradients); perm: the SP output-row permutation; cin_total > 0:
+// the source has cin_total input channels, of which [cin_off, cin_off + Cin) are packed.
+struct PackMfmaOpts { int cout_src = 0, flip_taps = 0, co_off = 0, partial = 0, perm = 0, cin_total = 0, cin_off = 0; };
 int drs_launch_pack_conv_mfma(const float* w, const float* b, const float* gamma, const float* beta, const float* rmean,
                               const float* rvar, float eps, void* dst_w, float* dst_b, int Cout, int Cin, int taps,
-                              int transposed, int impl, hipStream_t s, int cout_src = 0, int flip_taps = 0, int co_off = 0,
-                              int partial = 0, int perm = 0, int cin_total = 0, int cin_off = 0);
+                              int transposed, int impl, hipStream_t s, PackMfmaOpts opt = {});
 
 // FL operand images (conv_mfma_fl.hip) of a layer from its packed split-bf16 images (hi image, then lo image); `flag`: device
 // word, bit 0 is set when a folded weight lies outside what fp16 holds (|w| > 60000, or a layer whose largest weight is under 2^-10)

@@ -7,6 +7,7 @@
 #include <cxxabi.h>
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -28,6 +29,10 @@ extern "C" const char* drs_last_error(void) { return g_err; }
 extern "C" int drs_abi_version(void) { return 7; }
 
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+static inline char* aligned_base(const void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
+
+// A step of the weight packing or of the forward / backward (train_bwd.inc) schedule returns its first non-zero status
+#define RUN(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
 
 int drs_kernel_prepare(const void* kernel, int max_dynamic_lds, int* num_cu) {
   static std::mutex mu;
@@ -129,10 +134,9 @@ static int run_conv(const TapConv& d, int impl, hipStream_t s) {
 static double conv_flops(const TapConv& d) {
   return 2.0 * d.N * d.TH * d.TW * (double)d.Cout * ((double)d.Cin * d.ntaps + (d.in2 ? d.Cin2 : 0));
 }
-static double conv_bytes(const TapConv& d, bool count_out_once = true) {
+static double conv_bytes(const TapConv& d) {
   const double in = (double)d.N * d.H * d.W * d.Cin;
   const double out = (double)d.N * d.TH * d.TW * d.Cout * (d.mode == DRS_TAPMODE_CONVT ? 4 : 1);
-  (void)count_out_once;
   const double in2 = d.in2 ? (double)d.N * d.H2 * d.W2 * d.Cin2 + (double)d.Cin2 * d.Cout : 0.0;
   return 4.0 * (in + in2 + out + (double)d.ntaps * d.Cin * d.Cout);
 }
@@ -183,11 +187,10 @@ extern "C" int drs_conv2d_nchw(const float* x, const float* w, const float* b, f
   DRS_REQUIRE(impl >= DRS_IMPL_DIRECT && impl <= DRS_IMPL_MFMA_F16, DRS_ERR_ARG, "conv2d: impl=%d", impl);
   DRS_REQUIRE(workspace_bytes >= drs_conv2d_workspace_bytes(N, Cin, H, W, Cout, KH, KW, stride, pad, transposed, out_pad),
               DRS_ERR_WORKSPACE, "conv2d: workspace too small");
-  if (N == 0) return DRS_OK;
   int OH, OW;
   conv_out_hw(H, W, KH, KW, stride, pad, transposed, out_pad, &OH, &OW);
   DRS_REQUIRE(OH > 0 && OW > 0, DRS_ERR_SHAPE, "conv2d: empty output");
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* base = aligned_base(workspace);
   float* xin = (float*)base; base += align_up((size_t)N * H * W * Cin * 4);
   float* yout = (float*)base; base += align_up((size_t)N * OH * OW * Cout * 4);
   float* pw = (float*)base;
@@ -229,34 +232,74 @@ extern "C" int drs_conv2d_nchw(const float* x, const float* w, const float* b, f
 // ------------------------------------------------------------------------------------------------
 // operator-level fused up-sampling stage (NCHW boundary): y = conv3x3(cat[conv_transpose(h), att])
 // ------------------------------------------------------------------------------------------------
-static size_t upfused_sizes(int N, int Cc, int Ch, int LH, int LW, size_t* o) {
-  // o[0] h (SP), o[1] att (SP), o[2] att-half partial sums, o[3] result (SP), o[4] composite image, o[5] aux, o[6] att-half
-  // weights, o[7] att-half bias, o[8] eh, o[9] ev, o[10] zero line + fault word, o[11] edge operand image, o[12..14] fold scratch
+// Where the weights of one fused up-sampling stage go (upfuse_sp.hip: ups.i.transform composed with the x-half of up_convs.i,
+// and the att-half of up_convs.i as its own Ch -> Ch 3x3 convolution).  The optional ones select the folded forms of the top
+// stage (DecStage::ah_proj: ah_tmp, gate_psi: ah_tmp2 / ah_tab, uf_proj: uf_tmpw / uf_tmpb / ufp_w).
+struct UpfuseDst {
+  void* w; float* aux; void* edge;  // composite operand image, edge / bias weights, edge operand image
+  void* ah_w; float* ah_b;          // att-half operand image, zero bias
+  float *ah_tmp = nullptr, *ah_tmp2 = nullptr, *ah_tab = nullptr, *uf_tmpw = nullptr, *uf_tmpb = nullptr;
+  void* ufp_w = nullptr;
+};
+// t_w / t_b: ups.i.transform, v_w / v_b: up_convs.i, out_w / out_b / out_dim: the `output` projection (folded forms), res: the
+// weight, bias and BatchNorm gamma, beta, mean, var of attention_blocks.2.result (ah_tmp2), perm: SP output rows of the att-half
+static int pack_upfuse_stage_images(const UpfuseDst& d, const float* t_w, const float* t_b, const float* v_w, const float* v_b,
+                                    const float* out_w, const float* out_b, int out_dim, const float* const* res, float eps,
+                                    int Cc, int Ch, int impl, int perm, hipStream_t s) {
+  const float *uv_w = v_w, *uv_b = v_b;
+  if (d.uf_tmpw) {  // `output` folded into up_convs.2: the composite, its edge weights and its bias are built from the folded layer
+    RUN(drs_launch_upfuse_fold_proj(v_w, v_b, out_w, out_b, out_dim, Cc, Ch, d.uf_tmpw, d.uf_tmpb, s));
+    uv_w = d.uf_tmpw; uv_b = d.uf_tmpb;
+    RUN(drs_launch_upfuse_proj_pack(uv_w, t_w, Cc, Ch, out_dim, d.ufp_w, s));
+  }
+  RUN(drs_launch_upfuse_pack(uv_w, uv_b, t_w, t_b, Cc, Ch, d.w, d.aux, d.edge, s));
+  // att-half: input channels [Cc, Cc + Ch) of up_convs.i, zero bias (it is in the composite's) - or, folded: output o
+  // up_convs.2[att half] is ONE 3x3 convolution Ch -> out_dim (reference :377,:379: no activation or normalisation between
+  // the two), half the MFMAs of the 32-channel form
+  if (!d.ah_tmp)
+    return drs_launch_pack_conv_mfma(v_w, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, d.ah_w, d.ah_b, Ch, Ch, 9, 0, impl, s,
+                                     {.perm = perm, .cin_total = Cc + Ch, .cin_off = Cc});
+  const float* tmp = d.ah_tmp;
+  RUN(drs_launch_fold_proj(v_w, Cc + Ch, Cc, Ch, Ch, out_w, out_dim, d.ah_tmp, s));
+  if (d.ah_tmp2) {  // ... o attention_blocks.2.result (1x1 + BatchNorm, linear): the convolution then reads psi * x_res
+    RUN(drs_launch_fold_result(d.ah_tmp, Ch, res[0], res[1], res[2], res[3], res[4], res[5], eps, d.ah_tmp2, d.ah_tab, s));
+    tmp = d.ah_tmp2;
+  }
+  return drs_launch_pack_conv_mfma(tmp, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, d.ah_w, d.ah_b, 16, Ch, 3, 0, impl, s);
+}
+
+// Workspace of drs_upconv_fused_nchw: byte offsets from its 256-aligned base
+struct UpfusedWs {
+  size_t h, att, part, res;          // SP copies of h and att, att-half partial sums, result (SP)
+  size_t w, aux, ah_w, ah_b;         // composite image, edge / bias weights, att-half image and bias
+  size_t eh, ev, zero, edge;         // edge vectors, zero line + fault word, edge operand image
+  size_t ah_tmp, uf_tmpw, uf_tmpb, ufp_w;  // folded output projection (fuse_w, shapes the direct kernel takes)
+  size_t bytes;
+};
+static UpfusedWs upfused_layout(int N, int Cc, int Ch, int LH, int LW) {
   const size_t hi = (size_t)N * 4 * LH * LW;
+  UpfusedWs o;
   size_t b = 0;
-  o[0] = b; b += align_up((size_t)N * LH * LW * Cc * 4);
-  o[1] = b; b += align_up(hi * Ch * 4);
-  o[2] = b; b += align_up(hi * Ch * 4);
-  o[3] = b; b += align_up(hi * Ch * 4);
-  o[4] = b; b += align_up(drs_upfuse_weight_bytes(Cc, Ch));
-  o[5] = b; b += align_up(drs_upfuse_aux_floats(Cc, Ch) * 4);
-  o[6] = b; b += align_up(drs_pack_conv_mfma_bytes(Ch, Ch, 9, DRS_IMPL_MFMA_BF16X3));
-  o[7] = b; b += align_up((size_t)Ch * 4);
-  o[8] = b; b += align_up((size_t)N * 2 * 2 * LW * Ch * 4);
-  o[9] = b; b += align_up((size_t)N * 2 * 2 * LH * Ch * 4);
-  o[10] = b; b += 512;
-  o[11] = b; b += align_up(drs_upfuse_edge_image_bytes(Cc, Ch));
-  // folded output projection (fuse_w given, shapes the direct kernel takes): the two fp32 contractions the images are packed from
-  o[12] = b; b += align_up((size_t)16 * Ch * 9 * 4);
-  o[13] = b; b += align_up((size_t)32 * (Cc + Ch) * 9 * 4);
-  o[14] = b; b += align_up((size_t)32 * 4);
-  o[15] = b; b += align_up(drs_upfuse_proj_weight_bytes(Cc > 64 ? 64 : Cc));
-  return b + 256;
+  o.h = b; b += align_up((size_t)N * LH * LW * Cc * 4);
+  o.att = b; b += align_up(hi * Ch * 4);
+  o.part = b; b += align_up(hi * Ch * 4);
+  o.res = b; b += align_up(hi * Ch * 4);
+  o.w = b; b += align_up(drs_upfuse_weight_bytes(Cc, Ch));
+  o.aux = b; b += align_up(drs_upfuse_aux_floats(Cc, Ch) * 4);
+  o.ah_w = b; b += align_up(drs_pack_conv_mfma_bytes(Ch, Ch, 9, DRS_IMPL_MFMA_BF16X3));
+  o.ah_b = b; b += align_up((size_t)Ch * 4);
+  o.eh = b; b += align_up((size_t)N * 2 * 2 * LW * Ch * 4);
+  o.ev = b; b += align_up((size_t)N * 2 * 2 * LH * Ch * 4);
+  o.zero = b; b += 512;
+  o.edge = b; b += align_up(drs_upfuse_edge_image_bytes(Cc, Ch));
+  o.ah_tmp = b; b += align_up((size_t)16 * Ch * 9 * 4);
+  o.uf_tmpw = b; b += align_up((size_t)32 * (Cc + Ch) * 9 * 4);
+  o.uf_tmpb = b; b += align_up((size_t)32 * 4);
+  o.ufp_w = b; b += align_up(drs_upfuse_proj_weight_bytes(Cc > 64 ? 64 : Cc));
+  o.bytes = b + 256;
+  return o;
 }
-extern "C" size_t drs_upconv_fused_workspace_bytes(int N, int Cc, int Ch, int LH, int LW) {
-  size_t o[16];
-  return upfused_sizes(N, Cc, Ch, LH, LW, o);
-}
+extern "C" size_t drs_upconv_fused_workspace_bytes(int N, int Cc, int Ch, int LH, int LW) { return upfused_layout(N, Cc, Ch, LH, LW).bytes; }
 extern "C" int drs_upconv_fused_nchw(const float* h, const float* att, const float* t_w, const float* t_b, const float* v_w,
                                      const float* v_b, const float* post2, const float* fuse_w, const float* fuse_b,
                                      int fuse_dim, float* y, float* y2, int N, int Cc, int Ch, int LH, int LW, void* workspace,
@@ -269,88 +312,68 @@ extern "C" int drs_upconv_fused_nchw(const float* h, const float* att, const flo
   DRS_REQUIRE(!fuse_w || (Ch == 32 && fuse_dim >= 1 && fuse_dim <= 4 && fuse_b && !post2 && !y2), DRS_ERR_SHAPE,
               "upconv_fused: the fused projection needs Ch == 32, fuse_dim <= 4 and no second output");
   DRS_REQUIRE((post2 == nullptr) == (y2 == nullptr), DRS_ERR_ARG, "upconv_fused: post2 and y2 come together");
-  size_t o[16];
-  DRS_REQUIRE(workspace_bytes >= upfused_sizes(N, Cc, Ch, LH, LW, o), DRS_ERR_WORKSPACE, "upconv_fused: workspace too small");
-  char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  const UpfusedWs o = upfused_layout(N, Cc, Ch, LH, LW);
+  DRS_REQUIRE(workspace_bytes >= o.bytes, DRS_ERR_WORKSPACE, "upconv_fused: workspace too small");
+  char* base = aligned_base(workspace);
+  auto at = [base](size_t off) { return (float*)(base + off); };
   const int OH = 2 * LH, OW = 2 * LW;
-  int rc;
-  DRS_CHECK_HIP(hipMemsetAsync(base + o[10], 0, 512, s));
-  if ((rc = drs_launch_nchw_to_sp(h, (float*)(base + o[0]), N, Cc, LH, LW, s))) return rc;
-  if ((rc = drs_launch_nchw_to_sp(att, (float*)(base + o[1]), N, Ch, OH, OW, s))) return rc;
+  DRS_CHECK_HIP(hipMemsetAsync(base + o.zero, 0, 512, s));
+  RUN(drs_launch_nchw_to_sp(h, at(o.h), N, Cc, LH, LW, s));
+  RUN(drs_launch_nchw_to_sp(att, at(o.att), N, Ch, OH, OW, s));
   // the projection folded into both launches' weights where the direct kernel takes the att-half (what the plan's stage 2
   // does: DecStage::ah_proj / uf_proj), else as the matrix-pipe epilogue of the 32-channel layer
   bool fold = false;
-  TapConv ah = conv_desc((const float*)(base + o[1]), N, OH, OW, Ch, Ch, 0, (const float*)(base + o[6]), nullptr, nullptr, 16, 16, 0, 3, 3, 1, 1);
+  TapConv ah = conv_desc(at(o.att), N, OH, OW, Ch, Ch, 0, at(o.ah_w), nullptr, nullptr, 16, 16, 0, 3, 3, 1, 1);
   if (fuse_w) {
-    ah.in_sp = 1; ah.zero_line = base + o[10]; ah.proj = 1; ah.fuse_out = y; ah.fuse_dim = fuse_dim;
+    ah.in_sp = 1; ah.zero_line = base + o.zero; ah.proj = 1; ah.fuse_out = y; ah.fuse_dim = fuse_dim;
     fold = drs_conv3x3_direct_sp_proj_supported(ah, DRS_IMPL_MFMA_BF16X3) && drs_upfuse_proj_supported(Cc, Ch, fuse_dim);
   }
-  const float *uv_w = v_w, *uv_b = v_b;
-  if (fold) {
-    if ((rc = drs_launch_upfuse_fold_proj(v_w, v_b, fuse_w, fuse_b, fuse_dim, Cc, Ch, (float*)(base + o[13]), (float*)(base + o[14]), s))) return rc;
-    uv_w = (const float*)(base + o[13]); uv_b = (const float*)(base + o[14]);
-    if ((rc = drs_launch_upfuse_proj_pack(uv_w, t_w, Cc, Ch, fuse_dim, base + o[15], s))) return rc;
-    if ((rc = drs_launch_fold_proj(v_w, Cc + Ch, Cc, Ch, Ch, fuse_w, fuse_dim, (float*)(base + o[12]), s))) return rc;
-    if ((rc = drs_launch_pack_conv_mfma((const float*)(base + o[12]), nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, base + o[6],
-                                        (float*)(base + o[7]), 16, Ch, 3, 0, DRS_IMPL_MFMA_BF16X3, s, 0, 0, 0, 0, 0)))
-      return rc;
-  }
-  if ((rc = drs_launch_upfuse_pack(uv_w, uv_b, t_w, t_b, Cc, Ch, base + o[4], (float*)(base + o[5]), base + o[11], s))) return rc;
-  if (!fold &&
-      (rc = drs_launch_pack_conv_mfma(v_w, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, base + o[6], (float*)(base + o[7]), Ch,
-                                      Ch, 9, 0, DRS_IMPL_MFMA_BF16X3, s, 0, 0, 0, 0, fuse_w ? 0 : 1, Cc + Ch, Cc)))
-    return rc;
-  const float* aux = (const float*)(base + o[5]);
+  UpfuseDst pd = {base + o.w, at(o.aux), base + o.edge, base + o.ah_w, at(o.ah_b)};
+  if (fold) { pd.ah_tmp = at(o.ah_tmp); pd.uf_tmpw = at(o.uf_tmpw); pd.uf_tmpb = at(o.uf_tmpb); pd.ufp_w = base + o.ufp_w; }
+  RUN(pack_upfuse_stage_images(pd, t_w, t_b, v_w, v_b, fuse_w, fuse_b, fuse_dim, nullptr, 0.f, Cc, Ch, DRS_IMPL_MFMA_BF16X3,
+                               fuse_w ? 0 : 1, s));
+  const float* aux = at(o.aux);
   const size_t mat = (size_t)Cc * Ch;
-  unsigned* fault = (unsigned*)(base + o[10] + 256);
-  {
-    UpFuseEdgeDesc e = {};
-    e.in = (const float*)(base + o[0]); e.in_cs = Cc; e.in_co = 0;
-    e.N = N; e.LH = LH; e.LW = LW; e.Cc = Cc; e.Ch = Ch;
-    e.rt = aux; e.rl = aux + 5 * mat; e.bt = aux + 11 * mat;
-    e.eh = (float*)(base + o[8]); e.ev = (float*)(base + o[9]);
-    e.wimg = base + o[11]; e.zero_line = base + o[10];
-    if ((rc = drs_launch_upfuse_edges(e, s))) return rc;
-  }
-  {
-    TapConv d = conv_desc((const float*)(base + o[1]), N, OH, OW, Ch, Ch, 0, (const float*)(base + o[6]), (const float*)(base + o[7]),
-                          (float*)(base + o[2]), Ch, Ch, 0, 3, 3, 1, 1);
-    d.in_sp = d.out_sp = 1; d.zero_line = base + o[10]; d.fault = fault;
-    if (fold) {
-      if ((rc = drs_launch_conv3x3_direct_sp(ah, s))) return rc;
-    } else {
+  unsigned* fault = (unsigned*)(base + o.zero + 256);
+  UpFuseEdgeDesc e = {};
+  e.in = at(o.h); e.in_cs = Cc; e.in_co = 0;
+  e.N = N; e.LH = LH; e.LW = LW; e.Cc = Cc; e.Ch = Ch;
+  e.rt = aux; e.rl = aux + 5 * mat; e.bt = aux + 11 * mat;
+  e.eh = at(o.eh); e.ev = at(o.ev);
+  e.wimg = base + o.edge; e.zero_line = base + o.zero;
+  RUN(drs_launch_upfuse_edges(e, s));
+  if (fold) {
+    RUN(drs_launch_conv3x3_direct_sp(ah, s));
+  } else {
+    TapConv d = conv_desc(at(o.att), N, OH, OW, Ch, Ch, 0, at(o.ah_w), at(o.ah_b), at(o.part), Ch, Ch, 0, 3, 3, 1, 1);
+    d.in_sp = d.out_sp = 1; d.zero_line = base + o.zero; d.fault = fault;
     if (fuse_w) {  // projected att-half straight into y (the plan's stage 2)
       d.out = nullptr; d.out_sp = 0;
-      d.fuse_w = fuse_w; d.fuse_b = (const float*)(base + o[7]); d.fuse_out = y; d.fuse_dim = fuse_dim;
+      d.fuse_w = fuse_w; d.fuse_b = at(o.ah_b); d.fuse_out = y; d.fuse_dim = fuse_dim;
     }
-    if ((rc = drs_launch_tapconv_mfma(d, DRS_IMPL_MFMA_BF16X3, s))) return rc;
-    }
+    RUN(drs_launch_tapconv_mfma(d, DRS_IMPL_MFMA_BF16X3, s));
   }
-  {
-    UpFuseDesc u = {};
-    u.in = (const float*)(base + o[0]); u.in_cs = Cc; u.in_co = 0;
-    u.N = N; u.LH = LH; u.LW = LW; u.Cc = Cc; u.Ch = Ch;
-    u.w = base + o[4];
-    u.bias = aux + 11 * mat + 9 * Ch;
-    u.res = (const float*)(base + o[2]); u.res_cs = Ch; u.res_co = 0;
-    u.eh = (const float*)(base + o[8]); u.ev = (const float*)(base + o[9]);
-    u.zero_line = base + o[10]; u.fault = fault;
-    if (fuse_w) {
-      u.res = nullptr; u.fuse_acc = 1;
-      if (fold) u.proj = 1;
-      else { u.fuse_w = fuse_w; u.fuse_b = fuse_b; }
-      u.fuse_out = y; u.fuse_dim = fuse_dim;
-    } else {
-      u.out = (float*)(base + o[3]); u.out_cs = Ch; u.out_co = 0;
-      if (y2) { u.out2 = (float*)(base + o[1]); u.out2_cs = Ch; u.out2_co = 0; u.post2 = post2; u.post2_cs = Ch; }  // (att is consumed by now)
-    }
-    if (fold) { u.w = base + o[15]; rc = drs_launch_upfuse_proj(u, s); }
-    else rc = drs_launch_upfuse(u, s);
-    if (rc) return rc;
+  UpFuseDesc u = {};
+  u.in = at(o.h); u.in_cs = Cc; u.in_co = 0;
+  u.N = N; u.LH = LH; u.LW = LW; u.Cc = Cc; u.Ch = Ch;
+  u.w = base + (fold ? o.ufp_w : o.w);
+  u.bias = aux + 11 * mat + 9 * Ch;
+  u.res = at(o.part); u.res_cs = Ch; u.res_co = 0;
+  u.eh = at(o.eh); u.ev = at(o.ev);
+  u.zero_line = base + o.zero; u.fault = fault;
+  if (fuse_w) {
+    u.res = nullptr; u.fuse_acc = 1;
+    if (fold) u.proj = 1;
+    else { u.fuse_w = fuse_w; u.fuse_b = fuse_b; }
+    u.fuse_out = y; u.fuse_dim = fuse_dim;
+  } else {
+    u.out = at(o.res); u.out_cs = Ch; u.out_co = 0;
+    if (y2) { u.out2 = at(o.att); u.out2_cs = Ch; u.out2_co = 0; u.post2 = post2; u.post2_cs = Ch; }  // (att is consumed by now)
   }
+  RUN(fold ? drs_launch_upfuse_proj(u, s) : drs_launch_upfuse(u, s));
   if (!fuse_w) {
-    if ((rc = drs_launch_sp_to_nchw((const float*)(base + o[3]), y, N, Ch, OH, OW, Ch, 0, s))) return rc;
-    if (y2 && (rc = drs_launch_sp_to_nchw((const float*)(base + o[1]), y2, N, Ch, OH, OW, Ch, 0, s))) return rc;
+    RUN(drs_launch_sp_to_nchw(at(o.res), y, N, Ch, OH, OW, Ch, 0, s));
+    if (y2) RUN(drs_launch_sp_to_nchw(at(o.att), y2, N, Ch, OH, OW, Ch, 0, s));
   }
   unsigned word = 0;
   DRS_CHECK_HIP(hipMemcpyAsync(&word, fault, 4, hipMemcpyDeviceToHost, s));
@@ -373,8 +396,9 @@ struct ConvLayer {
   bool out_sp = false;  // this layer stores its output in SP format: weights packed with the output-channel permutation
   size_t w_off = 0, b_off = 0;
   // eval split-bf16 plans: "FL" operand images of a wide 3x3 / 1x1 layer (conv_mfma_fl.hip: fp16 main + block-scaled fp6 cross
-  // terms, derived from the packed split-bf16 images); fl_ok: the folded weights passed the pack-time fp16 range check
-  size_t fl_off = 0;
+  // terms, derived from the packed split-bf16 images), fl_slot = its range flag (-1: no FL image); fl_ok: the folded weights
+  // passed the pack-time fp16 range check
+  size_t fl_img_off = 0;
   int fl_slot = -1;
   bool fl_ok = false;
   int t_Z = -1;         // train plans: pre-BatchNorm tensor
@@ -412,23 +436,21 @@ struct DecStage {
   // and the att-half of up_convs.i packed as its own Ch -> Ch 3x3 convolution (no bias: it is in the composite's)
   bool upfuse = false;
   size_t uf_w_off = 0, uf_aux_off = 0, uf_edge_off = 0, ah_w_off = 0, ah_b_off = 0;
-  size_t ah_fl_off = 0;  // FL images of the att-half (stages 0 / 1)
+  size_t ah_fl_img_off = 0;  // FL images of the att-half (stages 0 / 1)
   int ah_fl_slot = -1;
   bool ah_fl_ok = false;
   // stage 2: the `output` projection folded into the att-half's weights (conv3x3_direct_sp.hip, TapConv::proj): a 16-row image,
   // ah_tmp = the fp32 contraction it is packed from
   bool ah_proj = false;
   size_t ah_tmp_off = 0;
-  // ... and into the composite's (UpFuseDesc::proj): the folded up_convs.2 x-half the composite is packed from
+  // ... and into the composite's (UpFuseDesc::proj), on the streaming kernel (upfuse_proj_sp.hip): the folded up_convs.2
+  // x-half the composite is packed from, and that kernel's own operand image
   bool uf_proj = false;
-  size_t uf_tmpw_off = 0, uf_tmpb_off = 0;
+  size_t uf_tmpw_off = 0, uf_tmpb_off = 0, ufp_w_off = 0;
   // ... and the attention block's `result` convolution folded in as well: the gate stops at psi (attn_gate_sp.hip, PSI_ONLY), the
   // att-half reads the skip tensor and multiplies by psi behind its MFMAs: `att` of the top stage never exists
   bool gate_psi = false;
   size_t ah_tmp2_off = 0, ah_tab_off = 0;
-  // the folded composite on the streaming kernel (upfuse_proj_sp.hip): its own operand image
-  bool uf_stream = false;
-  size_t ufp_w_off = 0;
   int t_PA = -1;                  // att-half partial sums (SP), B x Ch x 2lh x 2lw
   size_t o_eh = 0, o_ev = 0;      // workspace: edge vectors of this forward
 };
@@ -469,7 +491,7 @@ struct drs_plan {
   // FL arithmetic (conv_mfma_fl.hip) for the layers the wave-specialised SP kernel takes at 64 channels per item; per-layer range
   // flags (device words, one per FL image: bit 0 = a folded weight outside what fp16 holds) are read back at pack time
   bool fl = false;
-  bool fl_off = false;  // an activation left fp16's range (drs_unet_check_faults): the plan stays on the split-bf16 kernels
+  bool fl_disabled = false;  // an activation left fp16's range (drs_unet_check_faults): the plan stays on the split-bf16 kernels
   int fl_slots = 0;
   size_t o_fl_flags = 0;
   bool packed_ok = false;
@@ -555,50 +577,19 @@ static const int kRedBlocks = DRS_RED_BLOCKS;  // blocks of a partial-sum reduct
 static const int kDown[5] = {16, 32, 64, 128, 256};
 static const int kUp[5] = {256, 128, 64, 32, 16};
 
-extern "C" int drs_unet_plan_create(drs_plan** out, const drs_unet_config* cfg) {
-  DRS_REQUIRE(out && cfg, DRS_ERR_ARG, "plan_create: null pointer");
-  DRS_REQUIRE(cfg->batch >= 1 && (cfg->lr_batch == cfg->batch || cfg->lr_batch == 1), DRS_ERR_SHAPE,
-              "plan_create: batch=%d lr_batch=%d (lr batch must equal batch or be 1)", cfg->batch, cfg->lr_batch);
-  DRS_REQUIRE(cfg->image_channels >= 1 && cfg->image_channels <= kMaxBands && cfg->out_dim >= 1 && cfg->out_dim <= kMaxBands,
-              DRS_ERR_SHAPE, "plan_create: image_channels=%d out_dim=%d (each 1..%d)", cfg->image_channels, cfg->out_dim,
-              kMaxBands);
-  DRS_REQUIRE(cfg->magnification >= 1 && cfg->height > 0 && cfg->width > 0 && cfg->height % 8 == 0 &&
-                  cfg->width % 8 == 0 && cfg->height % cfg->magnification == 0 && cfg->width % cfg->magnification == 0,
-              DRS_ERR_SHAPE, "plan_create: H=%d W=%d must be divisible by 8 and by magnification=%d", cfg->height,
-              cfg->width, cfg->magnification);
-  DRS_REQUIRE(cfg->impl >= DRS_IMPL_DIRECT && cfg->impl <= DRS_IMPL_MFMA_F16, DRS_ERR_ARG, "plan_create: impl=%d",
-              cfg->impl);
-  DRS_REQUIRE(cfg->variant >= DRS_VARIANT_SUPERRES && cfg->variant <= DRS_VARIANT_GENERATION, DRS_ERR_ARG,
-              "plan_create: variant=%d", cfg->variant);
-  DRS_REQUIRE(cfg->num_classes >= 0, DRS_ERR_ARG, "plan_create: num_classes=%d", cfg->num_classes);
-  drs_plan* p = new drs_plan();
-  p->cfg = *cfg;
-  if (p->cfg.bn_eps <= 0.f) p->cfg.bn_eps = 1e-5f;
-  const int C = cfg->image_channels;
-  if (p->cfg.variant == DRS_VARIANT_SUPERRES && p->cfg.cond_channels == 0) p->cfg.cond_channels = C;
-  if (p->cfg.variant == DRS_VARIANT_GENERATION) p->cfg.cond_channels = 0;
-  const int CC = p->cfg.cond_channels;  // conditioning image channels
-  if (p->cfg.variant != DRS_VARIANT_GENERATION && (CC < 1 || CC > kMaxBands)) {
-    DrsErr::set("plan_create: cond_channels=%d (1..%d)", CC, kMaxBands);
-    delete p;
-    return DRS_ERR_SHAPE;
-  }
-  if (p->cfg.variant == DRS_VARIANT_SAR_TO_NDVI && cfg->magnification != 1) {
-    DrsErr::set("plan_create: the SAR_TO_NDVI variant has no up-sampling (magnification must be 1)");
-    delete p;
-    return DRS_ERR_SHAPE;
-  }
-  {
-    static const bool sp_env = !(getenv("DRS_SP") && atoi(getenv("DRS_SP")) == 0);
-    p->sp = sp_env && !(cfg->flags & DRS_PLAN_TRAIN) && cfg->impl == DRS_IMPL_MFMA_BF16X3;
-  }
-  const bool has_cond = p->cfg.variant != DRS_VARIANT_GENERATION;
-  const std::string enc_name = p->cfg.variant == DRS_VARIANT_SAR_TO_NDVI ? "SAR_encoder" : "LR_encoder";
-  const std::string cond_name = p->cfg.variant == DRS_VARIANT_SAR_TO_NDVI ? "conv_SAR_img" : "conv_upsampled_lr_img";
-  const std::string skip_name = p->cfg.variant == DRS_VARIANT_GENERATION ? "conv_skip" : cond_name;
-
-  // ---- parameters, in a fixed canonical order (names = reference state_dict keys) ----
+// ---- plan creation: one step per job, in this order ----
+static std::string cond_encoder_name(const drs_unet_config& c) { return c.variant == DRS_VARIANT_SAR_TO_NDVI ? "SAR_encoder" : "LR_encoder"; }
+// The parameters in a fixed canonical order (names = reference state_dict keys; the order is the ABI's), each layer entered in
+// the convs / planars / mlps registry the packing and the schedules walk as it is made (same order)
+static void plan_params(drs_plan* p) {
+  const drs_unet_config& cfg = p->cfg;
+  const int C = cfg.image_channels, CC = cfg.cond_channels;  // CC: conditioning image channels
+  const bool has_cond = cfg.variant != DRS_VARIANT_GENERATION;
+  const std::string enc_name = cond_encoder_name(cfg);
+  const std::string cond_name = cfg.variant == DRS_VARIANT_SAR_TO_NDVI ? "conv_SAR_img" : "conv_upsampled_lr_img";
+  const std::string skip_name = cfg.variant == DRS_VARIANT_GENERATION ? "conv_skip" : cond_name;
   p->stem0 = p->mk_planar("conv0", kDown[0], C);
+  p->planars.push_back(&p->stem0);
   if (has_cond) {
     for (int i = 0; i < 3; ++i) {
       p->rrdb[2 * i] = p->mk_planar(enc_name + ".blocks." + std::to_string(i) + ".conv1", CC, CC);
@@ -606,9 +597,11 @@ extern "C" int drs_unet_plan_create(drs_plan** out, const drs_unet_config* cfg) 
     }
     p->rrdb[6] = p->mk_planar(enc_name + ".conv_out", CC, CC);
     p->stemc = p->mk_planar(cond_name, kDown[0], CC);
+    for (PlanarConv& L : p->rrdb) p->planars.push_back(&L);
+    p->planars.push_back(&p->stemc);
   }
-  if (p->cfg.variant == DRS_VARIANT_GENERATION && cfg->num_classes > 0)
-    p->label_emb = p->P("label_emb.weight", (int64_t)cfg->num_classes * 100);
+  if (cfg.variant == DRS_VARIANT_GENERATION && cfg.num_classes > 0)
+    p->label_emb = p->P("label_emb.weight", (int64_t)cfg.num_classes * 100);
   for (int i = 0; i < 4; ++i) {
     const std::string pfx = i < 3 ? "conv_blocks." + std::to_string(i) : std::string("bottle_neck");
     const int ci = kDown[i], co = kDown[i + 1];
@@ -620,6 +613,10 @@ extern "C" int drs_unet_plan_create(drs_plan** out, const drs_unet_config* cfg) 
     rb.has_skip = (i == 0);
     if (rb.has_skip) rb.skip = p->mk_conv(pfx + "." + skip_name, co, ci, 9);
     if (i < 3) p->downs[i] = p->mk_conv("downs." + std::to_string(i), co, co, 9);
+    p->convs.insert(p->convs.end(), {&rb.conv1, &rb.conv2, &rb.shortcut});
+    if (rb.has_skip) p->convs.push_back(&rb.skip);
+    if (i < 3) p->convs.push_back(&p->downs[i]);
+    p->mlps.push_back(&rb.mlp);
   }
   for (int i = 0; i < 3; ++i) {
     const std::string si = std::to_string(i);
@@ -634,130 +631,111 @@ extern "C" int drs_unet_plan_create(drs_plan** out, const drs_unet_config* cfg) 
     d.conv = p->mk_conv("ups." + si + ".conv", Cc, Cc, 9, "ups." + si + ".batch_norm");
     d.transform = p->mk_conv("ups." + si + ".transform", Cc, Cc, 9, "", true);
     d.upconv = p->mk_conv("up_convs." + si, Ch, Cc + Ch, 9);
-  }
-  p->output = p->mk_conv("output", cfg->out_dim, kUp[3], 1);
-  if (p->sp) {
-    for (int i = 0; i < 4; ++i) {
-      p->enc[i].conv1.out_sp = p->enc[i].conv2.out_sp = true;
-      p->enc[i].shortcut.out_sp = true;  // rides inside conv2 as extra K-chunks: same accumulator rows, same permutation
-      if (i < 3) p->downs[i].out_sp = true;
-    }
-    for (int i = 0; i < 3; ++i) {
-      DecStage& d = p->dec[i];
-      d.gate.out_sp = d.result.out_sp = d.conv.out_sp = d.transform.out_sp = true;
-      d.upconv.out_sp = i < 2;  // up_convs.2 feeds the fused / direct output projection in fp32
-    }
-  }
-
-  // ---- registries ----
-  for (int i = 0; i < 4; ++i) {
-    p->convs.push_back(&p->enc[i].conv1);
-    p->convs.push_back(&p->enc[i].conv2);
-    p->convs.push_back(&p->enc[i].shortcut);
-    if (p->enc[i].has_skip) p->convs.push_back(&p->enc[i].skip);
-    p->mlps.push_back(&p->enc[i].mlp);
-    if (i < 3) p->convs.push_back(&p->downs[i]);
-  }
-  for (int i = 0; i < 3; ++i) {
-    DecStage& d = p->dec[i];
-    ConvLayer* ls[] = {&d.gate, &d.wg, &d.wx, &d.psi, &d.result, &d.conv, &d.transform, &d.upconv};
-    for (ConvLayer* l : ls) p->convs.push_back(l);
+    p->convs.insert(p->convs.end(), {&d.gate, &d.wg, &d.wx, &d.psi, &d.result, &d.conv, &d.transform, &d.upconv});
     p->mlps.push_back(&d.mlp);
   }
+  p->output = p->mk_conv("output", cfg.out_dim, kUp[3], 1);
   p->convs.push_back(&p->output);
-  p->planars.push_back(&p->stem0);
-  if (has_cond) {
-    for (int i = 0; i < 7; ++i) p->planars.push_back(&p->rrdb[i]);
-    p->planars.push_back(&p->stemc);
-  }
+}
 
-  // ---- packed buffer layout ----
+// Every shape- and switch-dependent decision: SP activations, each layer's kernel family and form, the fused forms of the
+// decoder stages and which layers get FL images.  (No byte offsets: plan_packed_layout places what is decided here.)
+static void plan_kernel_forms(drs_plan* p) {
+  static const bool sp_env = !(getenv("DRS_SP") && atoi(getenv("DRS_SP")) == 0);
+  static const bool gp_env = !(getenv("DRS_GATE_PSI") && atoi(getenv("DRS_GATE_PSI")) == 0);
+  static const bool fl_env = !(getenv("DRS_FL") && atoi(getenv("DRS_FL")) == 0);
+  const drs_unet_config& cfg = p->cfg;
+  const bool train = (cfg.flags & DRS_PLAN_TRAIN) != 0, keep_all = (cfg.flags & DRS_PLAN_KEEP_ALL) != 0;
+  p->sp = sp_env && !train && cfg.impl == DRS_IMPL_MFMA_BF16X3;
+  for (ConvLayer* L : p->convs) {  // kernel family per layer: decided on shape alone
+    TapConv probe = {};
+    probe.Cin = L->Cin; probe.Cout = L->Cout; probe.ntaps = L->taps;
+    L->mfma = cfg.impl != DRS_IMPL_DIRECT && drs_tapconv_mfma_supported(probe, cfg.impl);
+  }
+  for (ResBlock& rb : p->enc) {
+    // (the shortcut rides inside conv2 as extra K-chunks: same accumulator rows, same permutation)
+    rb.conv1.out_sp = rb.conv2.out_sp = rb.shortcut.out_sp = p->sp;
+    rb.dual = rb.has_skip && !train && cfg.impl == DRS_IMPL_MFMA_BF16X3 && rb.conv1.Cout == 32 && rb.skip.Cout == 32 &&
+              rb.skip.Cin == rb.conv1.Cin;
+  }
+  for (ConvLayer& L : p->downs) L.out_sp = p->sp;
+  for (int i = 0; i < 3; ++i) {
+    DecStage& d = p->dec[i];
+    const int Cc = kUp[i], Ch = kUp[i + 1];
+    d.gate.out_sp = d.result.out_sp = d.conv.out_sp = d.transform.out_sp = p->sp;
+    d.upconv.out_sp = p->sp && i < 2;  // up_convs.2 feeds the fused / direct output projection in fp32
+    d.fused_gate = p->sp && drs_attn_gate_supported(Cc, Ch);
+    // (KEEP_ALL plans stay unfused: ups.i is a parity tap; stage 2 needs the fused output projection: its result is fp32)
+    d.upfuse = p->sp && !keep_all && (i < 2 || (Ch == 32 && cfg.out_dim <= 4)) &&
+               drs_upfuse_supported(Cc, Ch, cfg.height >> (3 - i), cfg.width >> (3 - i));
+    if (i < 2 || !d.upfuse) continue;
+    // stage 2: the `output` projection folded into the att-half's weights where the direct kernel takes that layer
+    TapConv probe = conv_desc((const float*)256, cfg.batch, cfg.height, cfg.width, Ch, Cc + Ch, Cc, (const float*)256, nullptr, nullptr,
+                              16, 16, 0, 3, 3, 1, 1);
+    probe.in_sp = 1; probe.zero_line = (const void*)256; probe.proj = 1; probe.fuse_out = (float*)256; probe.fuse_dim = cfg.out_dim;
+    d.ah_proj = drs_conv3x3_direct_sp_proj_supported(probe, cfg.impl);
+    // the composite's folded form needs the att-half in the output tensor first (fuse_acc): both or neither
+    d.uf_proj = d.ah_proj && drs_upfuse_proj_supported(Cc, Ch, cfg.out_dim);
+    d.gate_psi = gp_env && d.ah_proj && d.fused_gate && Ch == 32 && !keep_all && !(cfg.height & 1) && !(cfg.width & 1);
+  }
+  p->fl = fl_env && p->sp;  // FL images (conv_mfma_fl.hip) for the layers the wave-specialised kernel takes at 64 channels per item
+  if (!p->fl) return;
+  for (ConvLayer* L : p->convs)
+    if ((L->taps == 9 || L->taps == 1) && !L->transposed && L->Cout % 64 == 0 && L->Cin % 32 == 0) L->fl_slot = p->fl_slots++;
+  for (int i = 0; i < 2; ++i)
+    if (p->dec[i].upfuse && kUp[i + 1] % 64 == 0) p->dec[i].ah_fl_slot = p->fl_slots++;
+}
+
+// Offsets in the packed buffer of everything drs_unet_pack_weights writes
+static void plan_packed_layout(drs_plan* p) {
+  const drs_unet_config& cfg = p->cfg;
   size_t cur = 0;
   p->o_inv_freq = cur; cur += align_up(50 * 4);
   for (ConvLayer* L : p->convs) {
     L->w_off = cur;  // room for whichever kernel family's image is largest
-    {
-      size_t need = (size_t)L->Cout * L->Cin * L->taps * 4;
-      for (int im = DRS_IMPL_MFMA_F32; im <= DRS_IMPL_MFMA_F16; ++im) {
-        const size_t m = drs_pack_conv_mfma_bytes(L->Cout, L->Cin, L->taps, im);
-        need = m > need ? m : need;
-      }
-      cur += align_up(need);
-    }
+    size_t need = (size_t)L->Cout * L->Cin * L->taps * 4;
+    for (int im = DRS_IMPL_MFMA_F32; im <= DRS_IMPL_MFMA_F16; ++im) need = std::max(need, drs_pack_conv_mfma_bytes(L->Cout, L->Cin, L->taps, im));
+    cur += align_up(need);
     L->b_off = cur; cur += align_up((size_t)L->Cout * 4);
   }
-  for (int i = 0; i < 4; ++i) {
-    ResBlock& rb = p->enc[i];
-    rb.dual = rb.has_skip && !(cfg->flags & DRS_PLAN_TRAIN) && cfg->impl == DRS_IMPL_MFMA_BF16X3 && rb.conv1.Cout == 32 &&
-              rb.skip.Cout == 32 && rb.skip.Cin == rb.conv1.Cin;
-    if (rb.dual) {
-      rb.dual_w_off = cur; cur += align_up(drs_pack_conv_mfma_bytes(64, rb.conv1.Cin, 9, DRS_IMPL_MFMA_BF16X3));
-      rb.dual_b_off = cur; cur += align_up((size_t)64 * 4);
-    }
+  for (ResBlock& rb : p->enc) {
+    if (!rb.dual) continue;
+    rb.dual_w_off = cur; cur += align_up(drs_pack_conv_mfma_bytes(64, rb.conv1.Cin, 9, DRS_IMPL_MFMA_BF16X3));
+    rb.dual_b_off = cur; cur += align_up((size_t)64 * 4);
+  }
+  for (DecStage& d : p->dec) {
+    if (!d.fused_gate) continue;
+    d.fz_wg_off = cur; cur += align_up(drs_pack_conv_mfma_bytes(d.wg.Cout, d.wg.Cin, 1, DRS_IMPL_MFMA_BF16X3));
+    d.fz_wx_off = cur; cur += align_up(drs_pack_conv_mfma_bytes(d.wx.Cout, d.wx.Cin, 4, DRS_IMPL_MFMA_BF16X3));
+    d.gf_w_off = cur; cur += align_up((size_t)d.gate.Cout * d.gate.Cin * 4);
+    d.gf_b_off = cur; cur += align_up((size_t)d.gate.Cout * 4);
   }
   for (int i = 0; i < 3; ++i) {
     DecStage& d = p->dec[i];
-    d.fused_gate = p->sp && drs_attn_gate_supported(kUp[i], kUp[i + 1]);
-    if (d.fused_gate) {
-      d.fz_wg_off = cur; cur += align_up(drs_pack_conv_mfma_bytes(d.wg.Cout, d.wg.Cin, 1, DRS_IMPL_MFMA_BF16X3));
-      d.fz_wx_off = cur; cur += align_up(drs_pack_conv_mfma_bytes(d.wx.Cout, d.wx.Cin, 4, DRS_IMPL_MFMA_BF16X3));
-      d.gf_w_off = cur; cur += align_up((size_t)d.gate.Cout * d.gate.Cin * 4);
-      d.gf_b_off = cur; cur += align_up((size_t)d.gate.Cout * 4);
-    }
-  }
-  for (int i = 0; i < 3; ++i) {
-    DecStage& d = p->dec[i];
+    if (!d.upfuse) continue;
     const int Cc = kUp[i], Ch = kUp[i + 1];
-    // (KEEP_ALL plans stay unfused: ups.i is a parity tap; stage 2 needs the fused output projection: its result is fp32)
-    d.upfuse = p->sp && !(cfg->flags & DRS_PLAN_KEEP_ALL) && (i < 2 || (Ch == 32 && cfg->out_dim <= 4)) &&
-               drs_upfuse_supported(Cc, Ch, cfg->height >> (3 - i), cfg->width >> (3 - i));
-    if (d.upfuse) {
-      d.uf_w_off = cur; cur += align_up(drs_upfuse_weight_bytes(Cc, Ch));
-      d.uf_aux_off = cur; cur += align_up(drs_upfuse_aux_floats(Cc, Ch) * 4);
-      d.uf_edge_off = cur; cur += align_up(drs_upfuse_edge_image_bytes(Cc, Ch));
-      d.ah_w_off = cur; cur += align_up(drs_pack_conv_mfma_bytes(Ch, Ch, 9, DRS_IMPL_MFMA_BF16X3));
-      d.ah_b_off = cur; cur += align_up((size_t)Ch * 4);
-      if (i == 2) {
-        TapConv probe = conv_desc((const float*)256, cfg->batch, cfg->height, cfg->width, Ch, Cc + Ch, Cc, (const float*)256, nullptr, nullptr,
-                                  16, 16, 0, 3, 3, 1, 1);
-        probe.in_sp = 1; probe.zero_line = (const void*)256; probe.proj = 1; probe.fuse_out = (float*)256; probe.fuse_dim = cfg->out_dim;
-        d.ah_proj = drs_conv3x3_direct_sp_proj_supported(probe, cfg->impl);
-        if (d.ah_proj) { d.ah_tmp_off = cur; cur += align_up((size_t)16 * Ch * 9 * 4); }
-        // the composite's folded form needs the att-half in the output tensor first (fuse_acc): both or neither
-        d.uf_proj = d.ah_proj && drs_upfuse_proj_supported(Cc, Ch, cfg->out_dim);
-        static const bool gp_env = !(getenv("DRS_GATE_PSI") && atoi(getenv("DRS_GATE_PSI")) == 0);
-        d.gate_psi = gp_env && d.ah_proj && d.fused_gate && Ch == 32 && !(cfg->flags & DRS_PLAN_KEEP_ALL) && !(cfg->height & 1) && !(cfg->width & 1);
-        if (d.gate_psi) {
-          d.ah_tmp2_off = cur; cur += align_up((size_t)16 * Ch * 3 * 4);
-          d.ah_tab_off = cur; cur += align_up((size_t)36 * 4);
-        }
-        if (d.uf_proj) {
-          d.uf_tmpw_off = cur; cur += align_up((size_t)32 * (Cc + Ch) * 9 * 4);
-          d.uf_tmpb_off = cur; cur += align_up((size_t)32 * 4);
-          d.uf_stream = true;
-          d.ufp_w_off = cur; cur += align_up(drs_upfuse_proj_weight_bytes(Cc));
-        }
-      }
+    d.uf_w_off = cur; cur += align_up(drs_upfuse_weight_bytes(Cc, Ch));
+    d.uf_aux_off = cur; cur += align_up(drs_upfuse_aux_floats(Cc, Ch) * 4);
+    d.uf_edge_off = cur; cur += align_up(drs_upfuse_edge_image_bytes(Cc, Ch));
+    d.ah_w_off = cur; cur += align_up(drs_pack_conv_mfma_bytes(Ch, Ch, 9, DRS_IMPL_MFMA_BF16X3));
+    d.ah_b_off = cur; cur += align_up((size_t)Ch * 4);
+    if (d.ah_proj) { d.ah_tmp_off = cur; cur += align_up((size_t)16 * Ch * 9 * 4); }
+    if (d.gate_psi) {
+      d.ah_tmp2_off = cur; cur += align_up((size_t)16 * Ch * 3 * 4);
+      d.ah_tab_off = cur; cur += align_up((size_t)36 * 4);
+    }
+    if (d.uf_proj) {
+      d.uf_tmpw_off = cur; cur += align_up((size_t)32 * (Cc + Ch) * 9 * 4);
+      d.uf_tmpb_off = cur; cur += align_up((size_t)32 * 4);
+      d.ufp_w_off = cur; cur += align_up(drs_upfuse_proj_weight_bytes(Cc));
     }
   }
-  {
-    static const bool fl_env = !(getenv("DRS_FL") && atoi(getenv("DRS_FL")) == 0);
-    p->fl = fl_env && p->sp;
-    if (p->fl) {
-      for (ConvLayer* L : p->convs)
-        if ((L->taps == 9 || L->taps == 1) && !L->transposed && L->Cout % 64 == 0 && L->Cin % 32 == 0) {
-          L->fl_off = cur; cur += align_up(drs_fl_image_bytes(L->Cout, L->Cin, L->taps));
-          L->fl_slot = p->fl_slots++;
-        }
-      for (int i = 0; i < 2; ++i) {
-        DecStage& d = p->dec[i];
-        if (d.upfuse && kUp[i + 1] % 64 == 0) {
-          d.ah_fl_off = cur; cur += align_up(drs_fl_image_bytes(kUp[i + 1], kUp[i + 1], 9));
-          d.ah_fl_slot = p->fl_slots++;
-        }
-      }
-      p->o_fl_flags = cur; cur += align_up((size_t)p->fl_slots * 8);  // [range flag, largest |weight|] per image
-    }
+  if (p->fl) {
+    for (ConvLayer* L : p->convs)
+      if (L->fl_slot >= 0) { L->fl_img_off = cur; cur += align_up(drs_fl_image_bytes(L->Cout, L->Cin, L->taps)); }
+    for (int i = 0; i < 2; ++i)
+      if (p->dec[i].ah_fl_slot >= 0) { p->dec[i].ah_fl_img_off = cur; cur += align_up(drs_fl_image_bytes(kUp[i + 1], kUp[i + 1], 9)); }
+    p->o_fl_flags = cur; cur += align_up((size_t)p->fl_slots * 8);  // [range flag, largest |weight|] per image
   }
   for (PlanarConv* L : p->planars) {
     L->w_off = cur; cur += align_up((size_t)L->Cout * L->Cin * 9 * 4);
@@ -770,21 +748,22 @@ extern "C" int drs_unet_plan_create(drs_plan** out, const drs_unet_config* cfg) 
     m->o_b2 = cur; cur += align_up((size_t)m->dim * 4);
   }
   p->o_mlp_table = cur; cur += align_up(p->mlps.size() * 6 * sizeof(long long));
-  p->o_label = cur; cur += align_up((size_t)(cfg->num_classes > 0 ? cfg->num_classes : 0) * 100 * 4);
-  p->o_out_w = cur; cur += align_up((size_t)cfg->out_dim * kUp[3] * 4);
-  p->o_out_b = cur; cur += align_up((size_t)cfg->out_dim * 4);
+  p->o_label = cur; cur += align_up((size_t)(cfg.num_classes > 0 ? cfg.num_classes : 0) * 100 * 4);
+  p->o_out_w = cur; cur += align_up((size_t)cfg.out_dim * kUp[3] * 4);
+  p->o_out_b = cur; cur += align_up((size_t)cfg.out_dim * 4);
   p->o_zero = cur; cur += 256;  // a line of zeros: source of out-of-image pixels for LDS-DMA staging
   p->o_fault = cur; cur += 256;  // TapConv::fault word of the wave-specialised kernels (drs_unet_check_faults)
   p->packed_bytes = cur;
+}
 
-  // ---- workspace layout ----
-  const int B = cfg->batch, Bl = cfg->lr_batch, H = cfg->height, W = cfg->width, mag = cfg->magnification;
-  const int h = H / mag, w = W / mag;
-  size_t ws = 0;
-  const int CCw = CC > 0 ? CC : 1;
+// The forward's tensors and per-forward tables (every plan), from workspace offset `ws` on
+static void plan_eval_workspace(drs_plan* p, size_t& ws) {
+  const drs_unet_config& cfg = p->cfg;
+  const int B = cfg.batch, Bl = cfg.lr_batch, H = cfg.height, W = cfg.width, h = H / cfg.magnification, w = W / cfg.magnification;
+  const int CCw = cfg.cond_channels > 0 ? cfg.cond_channels : 1;
   for (int i = 0; i < 3; ++i) { p->o_lr[i] = ws; ws += align_up((size_t)Bl * CCw * h * w * 4); }
   p->o_temb = ws; ws += align_up((size_t)B * p->temb_total * 4);
-  p->t_lrenc = p->T(enc_name, ws, Bl, CCw, h, w, true);
+  p->t_lrenc = p->T(cond_encoder_name(cfg), ws, Bl, CCw, h, w, true);
   p->t_up = p->T("upsampled_lr_img", ws, Bl, CCw, H, W, true);
   p->t_cond = p->T("cond", ws, Bl, kDown[0], H, W);
   p->t_x0 = p->T("x0", ws, B, kDown[0], H, W);
@@ -811,92 +790,122 @@ extern "C" int drs_unet_plan_create(drs_plan** out, const drs_unet_config* cfg) 
     p->Tview("attention_blocks." + si, p->t_CAT[i], Ch, Cc);
     p->t_X[i] = p->T("up_convs." + si, ws, B, Ch, 2 * lh, 2 * lw);
   }
-  if (p->sp) {
-    for (int i = 0; i < 3; ++i) {
-      const int lh = H >> (3 - i), lw = W >> (3 - i);
-      p->t_XT[i] = p->T("ups." + std::to_string(i) + ".in", ws, B, kUp[i], lh, lw);
+  if (!p->sp) return;
+  for (int i = 0; i < 3; ++i) p->t_XT[i] = p->T("ups." + std::to_string(i) + ".in", ws, B, kUp[i], H >> (3 - i), W >> (3 - i));
+  auto mark = [&](int t) { p->tensors[t].sp = true; };
+  for (int i = 0; i < 3; ++i) {
+    DecStage& d = p->dec[i];
+    if (d.fused_gate) { d.o_gbias = ws; ws += align_up((size_t)B * kUp[i + 1] * 4); }
+    if (!d.upfuse) continue;
+    const int lh = H >> (3 - i), lw = W >> (3 - i), Ch = kUp[i + 1];
+    if (i < 2) {  // (stage 2 hands its att-half over projected, through the output tensor)
+      d.t_PA = p->T("up_convs." + std::to_string(i) + ".att_half", ws, B, Ch, 2 * lh, 2 * lw);
+      mark(d.t_PA);
     }
-    auto mark = [&](int t) { p->tensors[t].sp = true; };
-    for (int i = 0; i < 3; ++i) {
-      DecStage& d = p->dec[i];
-      if (d.fused_gate) { d.o_gbias = ws; ws += align_up((size_t)B * kUp[i + 1] * 4); }
-      if (!d.upfuse) continue;
-      const int lh = H >> (3 - i), lw = W >> (3 - i), Ch = kUp[i + 1];
-      if (i < 2) {  // (stage 2 hands its att-half over projected, through the output tensor)
-        d.t_PA = p->T("up_convs." + std::to_string(i) + ".att_half", ws, B, Ch, 2 * lh, 2 * lw);
-        mark(d.t_PA);
-      }
-      d.o_eh = ws; ws += align_up((size_t)B * 2 * (2 * lw) * Ch * 4);
-      d.o_ev = ws; ws += align_up((size_t)B * 2 * (2 * lh) * Ch * 4);
-    }
-    mark(p->t_x0);
-    for (int i = 0; i < 4; ++i) { mark(p->t_H[i]); mark(p->t_R[i]); if (i < 3) mark(p->t_D[i]); }
-    for (int i = 0; i < 3; ++i) {
-      mark(p->t_G[i]); mark(p->t_U[i]); mark(p->t_CAT[i]); mark(p->t_XT[i]);
-      if (i < 2) mark(p->t_X[i]);
-    }
-    for (WsTensor& t : p->tensors)  // channel-slice views of the concat buffers
-      for (int i = 0; i < 3; ++i)
-        if (t.off == p->tensors[p->t_CAT[i]].off) t.sp = true;
+    d.o_eh = ws; ws += align_up((size_t)B * 2 * (2 * lw) * Ch * 4);
+    d.o_ev = ws; ws += align_up((size_t)B * 2 * (2 * lh) * Ch * 4);
   }
-  if (cfg->flags & DRS_PLAN_TRAIN) {
-    size_t sums_cur = 0;
-    auto addz = [&](ConvLayer& L, const std::string& nm, int hh, int ww) {
-      L.stats_off = ws; ws += align_up(2 * (size_t)L.Cout * 4);
-      L.sums_off = sums_cur; sums_cur += 2 * (size_t)L.Cout * sizeof(double);
-      L.t_Z = p->T(nm + ".pre_bn", ws, B, L.Cout, hh, ww);
-      if (L.taps == 9 && L.Cout % 32 == 0 && hh > 8) L.t_Zsp = p->T(nm + ".dz_sp", ws, B, L.Cout, hh, ww);
-    };
-    for (int i = 0; i < 4; ++i) {
-      const std::string nm = i < 3 ? "conv_blocks." + std::to_string(i) : std::string("bottle_neck");
-      addz(p->enc[i].conv1, nm + ".conv1", H >> i, W >> i);
-      addz(p->enc[i].conv2, nm + ".conv2", H >> i, W >> i);
-      addz(p->enc[i].shortcut, nm + ".shortcut_conv", H >> i, W >> i);
-    }
-    for (int i = 0; i < 3; ++i) {
-      const std::string si = std::to_string(i);
-      const int lh = H >> (3 - i), lw = W >> (3 - i);
-      addz(p->dec[i].gate, "gating_signals." + si, lh, lw);
-      addz(p->dec[i].result, "attention_blocks." + si + ".result", 2 * lh, 2 * lw);
-      addz(p->dec[i].conv, "ups." + si + ".conv_bn", lh, lw);
-    }
-    p->bn_sums_bytes = align_up(sums_cur);
-    p->o_bn_sums = ws; ws += 2 * p->bn_sums_bytes;  // [forward | backward]
-    p->red_bytes = std::max((size_t)kRedBlocks * 2 * 1024 * sizeof(double), (size_t)1024 * (9 * CCw * CCw + CCw) * 4);
-    p->o_red = ws; ws += align_up(p->red_bytes);
+  mark(p->t_x0);
+  for (int i = 0; i < 4; ++i) { mark(p->t_H[i]); mark(p->t_R[i]); if (i < 3) mark(p->t_D[i]); }
+  for (int i = 0; i < 3; ++i) { mark(p->t_G[i]); mark(p->t_U[i]); mark(p->t_CAT[i]); mark(p->t_XT[i]); if (i < 2) mark(p->t_X[i]); }
+  for (WsTensor& t : p->tensors)  // channel-slice views of the concat buffers
+    for (int i = 0; i < 3; ++i)
+      if (t.off == p->tensors[p->t_CAT[i]].off) t.sp = true;
+}
+
+// Train plans: pre-BatchNorm tensors and statistics, reduction regions, and the backward's gradients and scratch
+static void plan_train_workspace(drs_plan* p, size_t& ws) {
+  const drs_unet_config& cfg = p->cfg;
+  const int B = cfg.batch, H = cfg.height, W = cfg.width, h = H / cfg.magnification, w = W / cfg.magnification;
+  const int CCw = cfg.cond_channels > 0 ? cfg.cond_channels : 1;
+  size_t sums_cur = 0;
+  auto addz = [&](ConvLayer& L, const std::string& nm, int hh, int ww) {
+    L.stats_off = ws; ws += align_up(2 * (size_t)L.Cout * 4);
+    L.sums_off = sums_cur; sums_cur += 2 * (size_t)L.Cout * sizeof(double);
+    L.t_Z = p->T(nm + ".pre_bn", ws, B, L.Cout, hh, ww);
+    if (L.taps == 9 && L.Cout % 32 == 0 && hh > 8) L.t_Zsp = p->T(nm + ".dz_sp", ws, B, L.Cout, hh, ww);
+  };
+  for (int i = 0; i < 4; ++i) {
+    const std::string nm = i < 3 ? "conv_blocks." + std::to_string(i) : std::string("bottle_neck");
+    addz(p->enc[i].conv1, nm + ".conv1", H >> i, W >> i);
+    addz(p->enc[i].conv2, nm + ".conv2", H >> i, W >> i);
+    addz(p->enc[i].shortcut, nm + ".shortcut_conv", H >> i, W >> i);
   }
-  if (cfg->flags & DRS_PLAN_TRAIN) {
-    p->o_dtemb = ws; ws += align_up((size_t)B * p->temb_total * 4);
-    p->o_scratch = ws; ws += align_up(64 * 1024);
-    p->o_wgrad = ws; ws += align_up(kWgradPartialBytes);  // partial dW slices of the MFMA weight-gradient kernel
-    p->g_out = p->T("grad.out", ws, B, cfg->out_dim, H, W);
-    p->g_x0 = p->T("grad.x0", ws, B, 32, H, W);  // 16 channels at a 32-float pixel stride (train_bwd.inc: kGx0Stride)
-    p->t_xn = p->T("x.nhwc", ws, B, C, H, W);
-    p->t_upn = p->T("upsampled_lr_img.nhwc", ws, B, CCw, H, W);
-    p->g_upn = p->T("grad.upsampled_lr_img", ws, B, CCw, H, W);
-    for (int i = 0; i < 4; ++i) p->g_lr[i] = p->T("grad.lr." + std::to_string(i), ws, B, CCw, h, w);
-    for (int i = 0; i < 4; ++i) p->t_rn[i] = p->T("LR_encoder.r" + std::to_string(i) + ".nhwc", ws, B, CCw, h, w);
-    for (int i = 0; i < 3; ++i) p->t_an[i] = p->T("LR_encoder.a" + std::to_string(i) + ".nhwc", ws, B, CCw, h, w);
-    for (int i = 0; i < 4; ++i) {
-      const int co = kDown[i + 1], hh = H >> i, ww = W >> i;
-      p->g_R[i] = p->T("grad.R" + std::to_string(i), ws, B, co, hh, ww);
-      p->g_H[i] = p->T("grad.H" + std::to_string(i), ws, B, co, hh, ww);
-      if (i < 3) p->g_D[i] = p->T("grad.D" + std::to_string(i), ws, B, co, hh / 2, ww / 2);
-    }
-    for (int i = 0; i < 3; ++i) {
-      const int Cc = kUp[i], Ch = kUp[i + 1];
-      const int lh = H >> (3 - i), lw = W >> (3 - i);
-      p->g_G[i] = p->T("grad.G" + std::to_string(i), ws, B, Ch, lh, lw);
-      p->g_P[i] = p->T("grad.P" + std::to_string(i), ws, B, Ch, lh, lw);
-      p->g_PSI[i] = p->T("grad.psi" + std::to_string(i), ws, B, 1, lh, lw);
-      p->g_U[i] = p->T("grad.U" + std::to_string(i), ws, B, Cc, lh, lw);
-      p->g_E[i] = p->T("grad.E" + std::to_string(i), ws, B, Ch, 2 * lh, 2 * lw);
-      p->g_CAT[i] = p->T("grad.cat" + std::to_string(i), ws, B, Cc + Ch, 2 * lh, 2 * lw);
-      p->g_X[i] = p->T("grad.X" + std::to_string(i), ws, B, Ch, 2 * lh, 2 * lw);
-    }
+  for (int i = 0; i < 3; ++i) {
+    const std::string si = std::to_string(i);
+    const int lh = H >> (3 - i), lw = W >> (3 - i);
+    addz(p->dec[i].gate, "gating_signals." + si, lh, lw);
+    addz(p->dec[i].result, "attention_blocks." + si + ".result", 2 * lh, 2 * lw);
+    addz(p->dec[i].conv, "ups." + si + ".conv_bn", lh, lw);
   }
+  p->bn_sums_bytes = align_up(sums_cur);
+  p->o_bn_sums = ws; ws += 2 * p->bn_sums_bytes;  // [forward | backward]
+  p->red_bytes = std::max((size_t)kRedBlocks * 2 * 1024 * sizeof(double), (size_t)1024 * (9 * CCw * CCw + CCw) * 4);
+  p->o_red = ws; ws += align_up(p->red_bytes);
+  p->o_dtemb = ws; ws += align_up((size_t)B * p->temb_total * 4);
+  p->o_scratch = ws; ws += align_up(64 * 1024);
+  p->o_wgrad = ws; ws += align_up(kWgradPartialBytes);  // partial dW slices of the MFMA weight-gradient kernel
+  p->g_out = p->T("grad.out", ws, B, cfg.out_dim, H, W);
+  p->g_x0 = p->T("grad.x0", ws, B, 32, H, W);  // 16 channels at a 32-float pixel stride (train_bwd.inc: kGx0Stride)
+  p->t_xn = p->T("x.nhwc", ws, B, cfg.image_channels, H, W);
+  p->t_upn = p->T("upsampled_lr_img.nhwc", ws, B, CCw, H, W);
+  p->g_upn = p->T("grad.upsampled_lr_img", ws, B, CCw, H, W);
+  for (int i = 0; i < 4; ++i) p->g_lr[i] = p->T("grad.lr." + std::to_string(i), ws, B, CCw, h, w);
+  for (int i = 0; i < 4; ++i) p->t_rn[i] = p->T("LR_encoder.r" + std::to_string(i) + ".nhwc", ws, B, CCw, h, w);
+  for (int i = 0; i < 3; ++i) p->t_an[i] = p->T("LR_encoder.a" + std::to_string(i) + ".nhwc", ws, B, CCw, h, w);
+  for (int i = 0; i < 4; ++i) {
+    const int co = kDown[i + 1], hh = H >> i, ww = W >> i;
+    p->g_R[i] = p->T("grad.R" + std::to_string(i), ws, B, co, hh, ww);
+    p->g_H[i] = p->T("grad.H" + std::to_string(i), ws, B, co, hh, ww);
+    if (i < 3) p->g_D[i] = p->T("grad.D" + std::to_string(i), ws, B, co, hh / 2, ww / 2);
+  }
+  for (int i = 0; i < 3; ++i) {
+    const int Cc = kUp[i], Ch = kUp[i + 1];
+    const int lh = H >> (3 - i), lw = W >> (3 - i);
+    p->g_G[i] = p->T("grad.G" + std::to_string(i), ws, B, Ch, lh, lw);
+    p->g_P[i] = p->T("grad.P" + std::to_string(i), ws, B, Ch, lh, lw);
+    p->g_PSI[i] = p->T("grad.psi" + std::to_string(i), ws, B, 1, lh, lw);
+    p->g_U[i] = p->T("grad.U" + std::to_string(i), ws, B, Cc, lh, lw);
+    p->g_E[i] = p->T("grad.E" + std::to_string(i), ws, B, Ch, 2 * lh, 2 * lw);
+    p->g_CAT[i] = p->T("grad.cat" + std::to_string(i), ws, B, Cc + Ch, 2 * lh, 2 * lw);
+    p->g_X[i] = p->T("grad.X" + std::to_string(i), ws, B, Ch, 2 * lh, 2 * lw);
+  }
+}
+
+extern "C" int drs_unet_plan_create(drs_plan** out, const drs_unet_config* cfg) {
+  DRS_REQUIRE(out && cfg, DRS_ERR_ARG, "plan_create: null pointer");
+  DRS_REQUIRE(cfg->batch >= 1 && (cfg->lr_batch == cfg->batch || cfg->lr_batch == 1), DRS_ERR_SHAPE,
+              "plan_create: batch=%d lr_batch=%d (lr batch must equal batch or be 1)", cfg->batch, cfg->lr_batch);
+  DRS_REQUIRE(cfg->image_channels >= 1 && cfg->image_channels <= kMaxBands && cfg->out_dim >= 1 && cfg->out_dim <= kMaxBands,
+              DRS_ERR_SHAPE, "plan_create: image_channels=%d out_dim=%d (each 1..%d)", cfg->image_channels, cfg->out_dim,
+              kMaxBands);
+  DRS_REQUIRE(cfg->magnification >= 1 && cfg->height > 0 && cfg->width > 0 && cfg->height % 8 == 0 &&
+                  cfg->width % 8 == 0 && cfg->height % cfg->magnification == 0 && cfg->width % cfg->magnification == 0,
+              DRS_ERR_SHAPE, "plan_create: H=%d W=%d must be divisible by 8 and by magnification=%d", cfg->height,
+              cfg->width, cfg->magnification);
+  DRS_REQUIRE(cfg->impl >= DRS_IMPL_DIRECT && cfg->impl <= DRS_IMPL_MFMA_F16, DRS_ERR_ARG, "plan_create: impl=%d",
+              cfg->impl);
+  DRS_REQUIRE(cfg->variant >= DRS_VARIANT_SUPERRES && cfg->variant <= DRS_VARIANT_GENERATION, DRS_ERR_ARG,
+              "plan_create: variant=%d", cfg->variant);
+  DRS_REQUIRE(cfg->num_classes >= 0, DRS_ERR_ARG, "plan_create: num_classes=%d", cfg->num_classes);
+  std::unique_ptr<drs_plan> p(new drs_plan());
+  p->cfg = *cfg;
+  if (p->cfg.bn_eps <= 0.f) p->cfg.bn_eps = 1e-5f;
+  if (p->cfg.variant == DRS_VARIANT_SUPERRES && p->cfg.cond_channels == 0) p->cfg.cond_channels = cfg->image_channels;
+  if (p->cfg.variant == DRS_VARIANT_GENERATION) p->cfg.cond_channels = 0;
+  const int CC = p->cfg.cond_channels;
+  DRS_REQUIRE(p->cfg.variant == DRS_VARIANT_GENERATION || (CC >= 1 && CC <= kMaxBands), DRS_ERR_SHAPE,
+              "plan_create: cond_channels=%d (1..%d)", CC, kMaxBands);
+  DRS_REQUIRE(p->cfg.variant != DRS_VARIANT_SAR_TO_NDVI || cfg->magnification == 1, DRS_ERR_SHAPE,
+              "plan_create: the SAR_TO_NDVI variant has no up-sampling (magnification must be 1)");
+  plan_params(p.get());
+  plan_kernel_forms(p.get());
+  plan_packed_layout(p.get());
+  size_t ws = 0;
+  plan_eval_workspace(p.get(), ws);
+  if (cfg->flags & DRS_PLAN_TRAIN) plan_train_workspace(p.get(), ws);
   p->ws_bytes = ws + 256;
-  *out = p;
+  *out = p.release();
   return DRS_OK;
 }
 
@@ -926,7 +935,128 @@ extern "C" int64_t drs_unet_param_numel(const drs_plan* plan, int i) {
 extern "C" size_t drs_unet_packed_bytes(const drs_plan* plan) { return plan ? plan->packed_bytes + 256 : 0; }
 extern "C" size_t drs_unet_workspace_bytes(const drs_plan* plan) { return plan ? plan->ws_bytes : 0; }
 
-static inline char* aligned_base(const void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
+// ---- weight packing: one step per layer family, in this order (it decides which jobs share a batched launch) ----
+namespace {
+struct PackCtx {  // base: the packed buffer's aligned base
+  drs_plan* plan; const void* const* params; char* base; hipStream_t s;
+  const float* F(int i) const { return (const float*)params[i]; }
+};
+}  // namespace
+
+// Every convolution in its kernel family's layout (eval plans: BatchNorm folded in)
+static int pack_layers(const PackCtx& c) {
+  const drs_plan* plan = c.plan;
+  for (const ConvLayer* L : plan->convs) {
+    const float *g = nullptr, *be = nullptr, *rm = nullptr, *rv = nullptr;
+    if (L->bn >= 0 && !(plan->cfg.flags & DRS_PLAN_TRAIN)) { g = c.F(L->bn); be = c.F(L->bn + 1); rm = c.F(L->bn + 2); rv = c.F(L->bn + 3); }
+    if (L->mfma)
+      RUN(drs_launch_pack_conv_mfma(c.F(L->w), c.F(L->b), g, be, rm, rv, plan->cfg.bn_eps, c.base + L->w_off, (float*)(c.base + L->b_off),
+                                    L->Cout, L->Cin, L->taps, L->transposed ? 1 : 0, plan->cfg.impl, c.s, {.perm = L->out_sp}));
+    else
+      RUN(drs_launch_pack_conv(c.F(L->w), c.F(L->b), g, be, rm, rv, plan->cfg.bn_eps, (float*)(c.base + L->w_off),
+                               (float*)(c.base + L->b_off), L->Cout, L->Cin, L->taps, L->transposed ? 1 : 0, 0, c.s));
+  }
+  return DRS_OK;
+}
+
+// conv1 (+BatchNorm1) and the skip convolution of a dual block as one 64-channel image, channels [0, 32) and [32, 64): two
+// partial jobs, like the skip half alone would be, so that they share a launch and an image
+static int pack_dual_pairs(const PackCtx& c) {
+  const drs_plan* plan = c.plan;
+  for (const ResBlock& rb : plan->enc) {
+    if (!rb.dual) continue;
+    const ConvLayer &a = rb.conv1, &b = rb.skip;
+    char* w = c.base + rb.dual_w_off;
+    float* bias = (float*)(c.base + rb.dual_b_off);
+    RUN(drs_launch_pack_conv_mfma(c.F(a.w), c.F(a.b), c.F(a.bn), c.F(a.bn + 1), c.F(a.bn + 2), c.F(a.bn + 3), plan->cfg.bn_eps, w, bias,
+                                  64, a.Cin, 9, 0, plan->cfg.impl, c.s, {.cout_src = 32, .partial = 1, .perm = plan->sp}));
+    RUN(drs_launch_pack_conv_mfma(c.F(b.w), c.F(b.b), nullptr, nullptr, nullptr, nullptr, 0.f, w, bias, 64, b.Cin, 9, 0,
+                                  plan->cfg.impl, c.s, {.cout_src = 32, .co_off = 32, .partial = 1, .perm = plan->sp}));
+  }
+  return DRS_OK;
+}
+
+// Fused attention gates: w_g and w_x once more with the SP output-row permutation, and the fp32 gating weights
+static int pack_fused_gates(const PackCtx& c) {
+  const drs_plan* plan = c.plan;
+  for (const DecStage& d : plan->dec) {
+    if (!d.fused_gate) continue;
+    // (no bias destination: the layers' own jobs - same batched launch - write d.wg.b_off / d.wx.b_off; two jobs of one launch
+    //  storing to one slot was benign only while both computed bit-identical values)
+    RUN(drs_launch_pack_conv_mfma(c.F(d.wg.w), c.F(d.wg.b), nullptr, nullptr, nullptr, nullptr, 0.f, c.base + d.fz_wg_off, nullptr,
+                                  d.wg.Cout, d.wg.Cin, 1, 0, plan->cfg.impl, c.s, {.perm = 1}));
+    RUN(drs_launch_pack_conv_mfma(c.F(d.wx.w), c.F(d.wx.b), nullptr, nullptr, nullptr, nullptr, 0.f, c.base + d.fz_wx_off, nullptr,
+                                  d.wx.Cout, d.wx.Cin, 4, 0, plan->cfg.impl, c.s, {.perm = 1}));
+    // fp32 [Cc][Ch] gating weights, BatchNorm folded (per-image bias of a stage input stored as x + temb)
+    const ConvLayer& G = d.gate;
+    RUN(drs_launch_pack_conv(c.F(G.w), c.F(G.b), c.F(G.bn), c.F(G.bn + 1), c.F(G.bn + 2), c.F(G.bn + 3), plan->cfg.bn_eps,
+                             (float*)(c.base + d.gf_w_off), (float*)(c.base + d.gf_b_off), G.Cout, G.Cin, 1, 0, 0, c.s));
+  }
+  return DRS_OK;
+}
+
+// Decoder stage i on the composite kernel: SP att-half rows in stages 0 / 1; stage 2 hands its att-half over projected
+static int pack_upfuse_stage(const PackCtx& c, int i) {
+  const drs_plan* plan = c.plan;
+  const DecStage& d = plan->dec[i];
+  auto at = [&c](bool used, size_t off) { return used ? (float*)(c.base + off) : nullptr; };
+  const UpfuseDst dst = {c.base + d.uf_w_off, at(true, d.uf_aux_off), c.base + d.uf_edge_off, c.base + d.ah_w_off,
+                         at(true, d.ah_b_off), at(d.ah_proj, d.ah_tmp_off), at(d.gate_psi, d.ah_tmp2_off),
+                         at(d.gate_psi, d.ah_tab_off), at(d.uf_proj, d.uf_tmpw_off), at(d.uf_proj, d.uf_tmpb_off),
+                         at(d.uf_proj, d.ufp_w_off)};
+  const ConvLayer& R = d.result;
+  const float* res[6] = {c.F(R.w), c.F(R.b), c.F(R.bn), c.F(R.bn + 1), c.F(R.bn + 2), c.F(R.bn + 3)};
+  return pack_upfuse_stage_images(dst, c.F(d.transform.w), c.F(d.transform.b), c.F(d.upconv.w), c.F(d.upconv.b),
+                                  c.F(plan->output.w), c.F(plan->output.b), plan->cfg.out_dim, res, plan->cfg.bn_eps, kUp[i],
+                                  kUp[i + 1], plan->cfg.impl, i < 2 ? 1 : 0, c.s);
+}
+
+// Parameters kept verbatim in the packed image: one gather-copy launch (44 hipMemcpyAsync calls before round 4), and the
+// table the time-MLP kernel reads them through
+static int pack_verbatim(const PackCtx& c) {
+  drs_plan* plan = c.plan;
+  std::vector<DrsCopyJob> copies;
+  auto keep = [&](size_t off, int param, long long words) { copies.push_back({c.F(param), (float*)(c.base + off), words}); };
+  for (PlanarConv* L : plan->planars) {
+    keep(L->w_off, L->w, (long long)L->Cout * L->Cin * 9);
+    keep(L->b_off, L->b, L->Cout);
+  }
+  std::vector<long long>& table = plan->mlp_table_host;  // (outlives the async copy)
+  table.clear();
+  for (Mlp* m : plan->mlps) {
+    keep(m->o_w1, m->w1, (long long)m->dim * 100);
+    keep(m->o_b1, m->b1, m->dim);
+    keep(m->o_w2, m->w2, (long long)m->dim * m->dim);
+    keep(m->o_b2, m->b2, m->dim);
+    const long long row[6] = {(long long)m->o_w1, (long long)m->o_b1, (long long)m->o_w2, (long long)m->o_b2, m->dim, m->temb_off};
+    table.insert(table.end(), row, row + 6);
+  }
+  DRS_CHECK_HIP(hipMemcpyAsync(c.base + plan->o_mlp_table, table.data(), table.size() * sizeof(long long), hipMemcpyHostToDevice, c.s));
+  if (plan->label_emb >= 0) keep(plan->o_label, plan->label_emb, (long long)plan->cfg.num_classes * 100);
+  keep(plan->o_out_w, plan->output.w, (long long)plan->cfg.out_dim * kUp[3]);
+  keep(plan->o_out_b, plan->output.b, plan->cfg.out_dim);
+  return drs_launch_gather_copy(copies.data(), (int)copies.size(), c.s);
+}
+
+// FL images from the split-bf16 images just packed + the range check of the folded weights: a layer whose weights fp16 cannot
+// hold keeps the split-bf16 kernel (the flags cross to the host here: one stream synchronisation per pack of an eval plan)
+static int pack_fl_images(const PackCtx& c) {
+  drs_plan* plan = c.plan;
+  unsigned* flags = (unsigned*)(c.base + plan->o_fl_flags);
+  DRS_CHECK_HIP(hipMemsetAsync(flags, 0, (size_t)plan->fl_slots * 8, c.s));
+  for (const ConvLayer* L : plan->convs)
+    if (L->fl_slot >= 0 && L->mfma)
+      RUN(drs_launch_fl_repack(c.base + L->w_off, c.base + L->fl_img_off, L->Cout, L->Cin, L->taps, flags + 2 * L->fl_slot, c.s));
+  for (const DecStage& d : plan->dec)  // (att-halves of stages 0 / 1: Ch -> Ch)
+    if (d.ah_fl_slot >= 0)
+      RUN(drs_launch_fl_repack(c.base + d.ah_w_off, c.base + d.ah_fl_img_off, d.upconv.Cout, d.upconv.Cout, 9, flags + 2 * d.ah_fl_slot, c.s));
+  std::vector<unsigned> host((size_t)plan->fl_slots * 2 + 2, 0u);
+  DRS_CHECK_HIP(hipMemcpyAsync(host.data(), flags, (size_t)plan->fl_slots * 8, hipMemcpyDeviceToHost, c.s));
+  DRS_CHECK_HIP(hipStreamSynchronize(c.s));
+  for (ConvLayer* L : plan->convs) L->fl_ok = L->fl_slot >= 0 && L->mfma && host[2 * L->fl_slot] == 0u;
+  for (DecStage& d : plan->dec) d.ah_fl_ok = d.ah_fl_slot >= 0 && host[2 * d.ah_fl_slot] == 0u;
+  return DRS_OK;
+}
 
 extern "C" int drs_unet_pack_weights(drs_plan* plan, const void* const* params, const float* inv_freq_host,
                                      void* packed, size_t packed_bytes, drs_stream_t stream) {
@@ -935,147 +1065,18 @@ extern "C" int drs_unet_pack_weights(drs_plan* plan, const void* const* params, 
   DRS_REQUIRE(packed_bytes >= drs_unet_packed_bytes(plan), DRS_ERR_WORKSPACE, "pack_weights: packed buffer too small");
   for (size_t i = 0; i < plan->params.size(); ++i)
     DRS_REQUIRE(params[i], DRS_ERR_ARG, "pack_weights: param %s is null", plan->params[i].name.c_str());
-  char* base = aligned_base(packed);
-  auto F = [&](int i) { return (const float*)params[i]; };
-  int rc;
-  DRS_CHECK_HIP(hipMemcpyAsync(base + plan->o_inv_freq, inv_freq_host, 50 * 4, hipMemcpyHostToDevice, s));
-  const int impl = plan->cfg.impl;
+  const PackCtx c{plan, params, aligned_base(packed), s};
+  DRS_CHECK_HIP(hipMemcpyAsync(c.base + plan->o_inv_freq, inv_freq_host, 50 * 4, hipMemcpyHostToDevice, s));
   DrsPackQueueScope pack_queue;  // the MFMA operand images of all layers: a few batched launches at the end (drs_common.h)
-  for (ConvLayer* L : plan->convs) {
-    // kernel family per layer: decided on shape alone
-    TapConv probe = {};
-    probe.Cin = L->Cin; probe.Cout = L->Cout; probe.ntaps = L->taps;
-    L->mfma = impl != DRS_IMPL_DIRECT && drs_tapconv_mfma_supported(probe, impl);
-    const float *g = nullptr, *be = nullptr, *rm = nullptr, *rv = nullptr;
-    if (L->bn >= 0 && !(plan->cfg.flags & DRS_PLAN_TRAIN)) { g = F(L->bn); be = F(L->bn + 1); rm = F(L->bn + 2); rv = F(L->bn + 3); }
-    if (L->mfma)
-      rc = drs_launch_pack_conv_mfma(F(L->w), F(L->b), g, be, rm, rv, plan->cfg.bn_eps, base + L->w_off,
-                                     (float*)(base + L->b_off), L->Cout, L->Cin, L->taps, L->transposed ? 1 : 0, impl, s, 0, 0, 0,
-                                     0, L->out_sp ? 1 : 0);
-    else
-      rc = drs_launch_pack_conv(F(L->w), F(L->b), g, be, rm, rv, plan->cfg.bn_eps, (float*)(base + L->w_off),
-                                (float*)(base + L->b_off), L->Cout, L->Cin, L->taps, L->transposed ? 1 : 0, 0, s);
-    if (rc) return rc;
-  }
-  for (int i = 0; i < 4; ++i) {
-    const ResBlock& rb = plan->enc[i];
-    if (!rb.dual) continue;
-    const ConvLayer& a = rb.conv1;  // channels [0, 32): conv1 with BatchNorm1 folded; [32, 64): the skip convolution
-    const ConvLayer& b = rb.skip;
-    if ((rc = drs_launch_pack_conv_mfma(F(a.w), F(a.b), F(a.bn), F(a.bn + 1), F(a.bn + 2), F(a.bn + 3), plan->cfg.bn_eps,
-                                        base + rb.dual_w_off, (float*)(base + rb.dual_b_off), 64, a.Cin, 9, 0, impl, s, 32, 0, 0, 1,
-                                        plan->sp ? 1 : 0)))  // (partial, like the skip half: the two jobs share a launch and an image)
-      return rc;
-    if ((rc = drs_launch_pack_conv_mfma(F(b.w), F(b.b), nullptr, nullptr, nullptr, nullptr, 0.f, base + rb.dual_w_off,
-                                        (float*)(base + rb.dual_b_off), 64, b.Cin, 9, 0, impl, s, 32, 0, 32, 1,
-                                        plan->sp ? 1 : 0)))
-      return rc;
-  }
-  for (int i = 0; i < 3; ++i) {
-    const DecStage& d = plan->dec[i];
-    if (!d.fused_gate) continue;
-    // (no bias destination: the layers' own jobs - same batched launch - write d.wg.b_off / d.wx.b_off; two jobs of one launch
-    //  storing to one slot was benign only while both computed bit-identical values)
-    if ((rc = drs_launch_pack_conv_mfma(F(d.wg.w), F(d.wg.b), nullptr, nullptr, nullptr, nullptr, 0.f, base + d.fz_wg_off,
-                                        nullptr, d.wg.Cout, d.wg.Cin, 1, 0, impl, s, 0, 0, 0, 0, 1)))
-      return rc;
-    if ((rc = drs_launch_pack_conv_mfma(F(d.wx.w), F(d.wx.b), nullptr, nullptr, nullptr, nullptr, 0.f, base + d.fz_wx_off,
-                                        nullptr, d.wx.Cout, d.wx.Cin, 4, 0, impl, s, 0, 0, 0, 0, 1)))
-      return rc;
-    // fp32 [Cc][Ch] gating weights, BatchNorm folded (per-image bias of a stage input stored as x + temb)
-    if ((rc = drs_launch_pack_conv(F(d.gate.w), F(d.gate.b), F(d.gate.bn), F(d.gate.bn + 1), F(d.gate.bn + 2), F(d.gate.bn + 3),
-                                   plan->cfg.bn_eps, (float*)(base + d.gf_w_off), (float*)(base + d.gf_b_off), d.gate.Cout,
-                                   d.gate.Cin, 1, 0, 0, s)))
-      return rc;
-  }
-  for (int i = 0; i < 3; ++i) {
-    const DecStage& d = plan->dec[i];
-    if (!d.upfuse) continue;
-    const int Cc = kUp[i], Ch = kUp[i + 1];
-    const float *uv_w = F(d.upconv.w), *uv_b = F(d.upconv.b);
-    if (d.uf_proj) {  // `output` folded into up_convs.2: the composite, its edge weights and its bias are built from the folded layer
-      float* tw = (float*)(base + d.uf_tmpw_off);
-      float* tb = (float*)(base + d.uf_tmpb_off);
-      if ((rc = drs_launch_upfuse_fold_proj(uv_w, uv_b, F(plan->output.w), F(plan->output.b), plan->cfg.out_dim, Cc, Ch, tw, tb, s))) return rc;
-      uv_w = tw; uv_b = tb;
-      if (d.uf_stream && (rc = drs_launch_upfuse_proj_pack(tw, F(d.transform.w), Cc, Ch, plan->cfg.out_dim, base + d.ufp_w_off, s))) return rc;
-    }
-    if ((rc = drs_launch_upfuse_pack(uv_w, uv_b, F(d.transform.w), F(d.transform.b), Cc, Ch, base + d.uf_w_off,
-                                     (float*)(base + d.uf_aux_off), base + d.uf_edge_off, s)))
-      return rc;
-    // att-half: input channels [Cc, Cc + Ch) of up_convs.i, zero bias; SP output rows in stages 0 / 1, plain MFMA rows in
-    // stage 2, whose att-half goes through the fused output projection instead of being stored - or, where the direct kernel
-    // takes the layer, has the projection folded into its weights: output o up_convs.2[att half] is ONE 3x3 convolution
-    // Ch -> out_dim (reference :377,:379: no activation or normalisation between the two), half the MFMAs of the 32-channel form
-    if (d.ah_proj) {
-      float* tmp = (float*)(base + d.ah_tmp_off);
-      if ((rc = drs_launch_fold_proj(F(d.upconv.w), Cc + Ch, Cc, Ch, Ch, F(plan->output.w), plan->cfg.out_dim, tmp, s))) return rc;
-      if (d.gate_psi) {  // ... o attention_blocks.2.result (1x1 + BatchNorm, linear): the convolution then reads psi * x_res
-        float* tmp2 = (float*)(base + d.ah_tmp2_off);
-        const ConvLayer& R = d.result;
-        if ((rc = drs_launch_fold_result(tmp, Ch, F(R.w), F(R.b), F(R.bn), F(R.bn + 1), F(R.bn + 2), F(R.bn + 3), plan->cfg.bn_eps, tmp2,
-                                         (float*)(base + d.ah_tab_off), s)))
-          return rc;
-        tmp = tmp2;
-      }
-      if ((rc = drs_launch_pack_conv_mfma(tmp, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, base + d.ah_w_off,
-                                          (float*)(base + d.ah_b_off), 16, Ch, 3, 0, impl, s, 0, 0, 0, 0, 0)))
-        return rc;
-      continue;
-    }
-    if ((rc = drs_launch_pack_conv_mfma(F(d.upconv.w), nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, base + d.ah_w_off,
-                                        (float*)(base + d.ah_b_off), Ch, Ch, 9, 0, impl, s, 0, 0, 0, 0, i < 2 ? 1 : 0, Cc + Ch, Cc)))
-      return rc;
-  }
-  // parameters kept verbatim in the packed image: one gather-copy launch (44 hipMemcpyAsync calls before round 4)
-  std::vector<DrsCopyJob> copies;
-  auto keep = [&](size_t off, int param, long long words) { copies.push_back({F(param), (float*)(base + off), words}); };
-  for (PlanarConv* L : plan->planars) {
-    keep(L->w_off, L->w, (long long)L->Cout * L->Cin * 9);
-    keep(L->b_off, L->b, L->Cout);
-  }
-  for (Mlp* m : plan->mlps) {
-    keep(m->o_w1, m->w1, (long long)m->dim * 100);
-    keep(m->o_b1, m->b1, m->dim);
-    keep(m->o_w2, m->w2, (long long)m->dim * m->dim);
-    keep(m->o_b2, m->b2, m->dim);
-  }
-  {
-    std::vector<long long> table;
-    for (Mlp* m : plan->mlps) {
-      const long long row[6] = {(long long)m->o_w1, (long long)m->o_b1, (long long)m->o_w2, (long long)m->o_b2, m->dim,
-                                m->temb_off};
-      table.insert(table.end(), row, row + 6);
-    }
-    plan->mlp_table_host = table;  // must outlive the async copy
-    DRS_CHECK_HIP(hipMemcpyAsync(base + plan->o_mlp_table, plan->mlp_table_host.data(), table.size() * sizeof(long long),
-                                 hipMemcpyHostToDevice, s));
-    if (plan->label_emb >= 0) keep(plan->o_label, plan->label_emb, (long long)plan->cfg.num_classes * 100);
-    keep(plan->o_out_w, plan->output.w, (long long)plan->cfg.out_dim * kUp[3]);
-    keep(plan->o_out_b, plan->output.b, plan->cfg.out_dim);
-  }
-  if ((rc = drs_launch_gather_copy(copies.data(), (int)copies.size(), s))) return rc;
-  if ((rc = pack_queue.flush(s))) return rc;
-  if (plan->fl) {
-    // FL images from the split-bf16 images just packed + the range check of the folded weights: a layer whose weights fp16 cannot
-    // hold keeps the split-bf16 kernel (the flags cross to the host here: one stream synchronisation per pack of an eval plan)
-    unsigned* flags = (unsigned*)(base + plan->o_fl_flags);
-    DRS_CHECK_HIP(hipMemsetAsync(flags, 0, (size_t)plan->fl_slots * 8, s));
-    for (ConvLayer* L : plan->convs)
-      if (L->fl_off && L->mfma && (rc = drs_launch_fl_repack(base + L->w_off, base + L->fl_off, L->Cout, L->Cin, L->taps, flags + 2 * L->fl_slot, s)))
-        return rc;
-    for (int i = 0; i < 2; ++i) {
-      const DecStage& d = plan->dec[i];
-      if (d.ah_fl_off && (rc = drs_launch_fl_repack(base + d.ah_w_off, base + d.ah_fl_off, kUp[i + 1], kUp[i + 1], 9, flags + 2 * d.ah_fl_slot, s)))
-        return rc;
-    }
-    std::vector<unsigned> host((size_t)plan->fl_slots * 2 + 2, 0u);
-    DRS_CHECK_HIP(hipMemcpyAsync(host.data(), flags, (size_t)plan->fl_slots * 8, hipMemcpyDeviceToHost, s));
-    DRS_CHECK_HIP(hipStreamSynchronize(s));
-    for (ConvLayer* L : plan->convs) L->fl_ok = L->fl_off && L->mfma && host[2 * L->fl_slot] == 0u;
-    for (int i = 0; i < 2; ++i) plan->dec[i].ah_fl_ok = plan->dec[i].ah_fl_off && host[2 * plan->dec[i].ah_fl_slot] == 0u;
-  }
-  DRS_CHECK_HIP(hipMemsetAsync(base + plan->o_zero, 0, 512, s));  // zero line + fault word
+  RUN(pack_layers(c));
+  RUN(pack_dual_pairs(c));
+  RUN(pack_fused_gates(c));
+  for (int i = 0; i < 3; ++i)
+    if (plan->dec[i].upfuse) RUN(pack_upfuse_stage(c, i));
+  RUN(pack_verbatim(c));
+  RUN(pack_queue.flush(s));
+  if (plan->fl) RUN(pack_fl_images(c));
+  DRS_CHECK_HIP(hipMemsetAsync(c.base + plan->o_zero, 0, 512, s));  // zero line + fault word
   plan->param_ptrs.assign(params, params + plan->params.size());
   plan->packed_ok = true;
   plan->packed_ptr = packed;
@@ -1120,7 +1121,7 @@ static int plan_conv(drs_plan* plan, const ConvLayer& L, const TapConv& d_in, hi
   // take get it from a separate pass over the first output
   TapConv d = d_in;
   d.fault = plan->fault_ptr;
-  if (L.fl_ok && !plan->fl_off && !d.w_fl) d.w_fl = aligned_base(plan->packed_ptr) + L.fl_off;
+  if (L.fl_ok && !plan->fl_disabled && !d.w_fl) d.w_fl = aligned_base(plan->packed_ptr) + L.fl_img_off;
   const bool split_out2 = d.out2 && !drs_tapconv_sp_supported(d, plan->cfg.impl) && !drs_tapconv_sp8_supported(d, plan->cfg.impl);
   if (split_out2) d.out2 = nullptr;
   std::string name = plan->params[L.w].name;
@@ -1165,8 +1166,6 @@ struct FwdCtx {
 };
 }  // namespace
 
-// A step of the forward or backward (train_bwd.inc) schedule returns its first non-zero status
-#define RUN(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
 // A profiled op that is not a layer's TapConv (plan_conv brackets those itself)
 template <class Launch>
 static int prof_op(drs_plan* plan, const std::string& name, double flops, double bytes, hipStream_t s, Launch launch) {
@@ -1351,7 +1350,7 @@ static int fwd_encoder_block(FwdCtx& f, int i) {
       d.in2 = xin; d.in2_cs = ci; d.in2_co = 0; d.Cin2 = ci; d.H2 = hh; d.W2 = ww;
       d.w2 = f.PW(rb.shortcut); d.bias2 = f.PB(rb.shortcut);
       d.in2_sp = f.sp;
-      if (rb.shortcut.fl_ok && !plan->fl_off) d.w2_fl = f.pk + rb.shortcut.fl_off;
+      if (rb.shortcut.fl_ok && !plan->fl_disabled) d.w2_fl = f.pk + rb.shortcut.fl_img_off;
     } else {
       d.res = f.TP(plan->t_S[i]); d.res_cs = co; d.res_co = 0; d.res_sp = rb.shortcut.out_sp ? 1 : 0;
     }
@@ -1491,7 +1490,7 @@ static int fwd_composite_tail(FwdCtx& f, int i, bool edges_aside) {
   TapConv d = conv_desc(f.TP(plan->t_CAT[i]), B, 2 * lh, 2 * lw, Ch, Cc + Ch, Cc, (const float*)(f.pk + st.ah_w_off),
                         (const float*)(f.pk + st.ah_b_off), i < 2 ? f.TP(st.t_PA) : nullptr, Ch, Ch, 0, 3, 3, 1, 1);
   d.in_sp = 1; d.out_sp = 1; d.zero_line = f.zero_line; d.fault = plan->fault_ptr;
-  if (i < 2 && st.ah_fl_ok && !plan->fl_off) d.w_fl = f.pk + st.ah_fl_off;
+  if (i < 2 && st.ah_fl_ok && !plan->fl_disabled) d.w_fl = f.pk + st.ah_fl_img_off;
   const double ah_flops = conv_flops(d), ah_bytes = conv_bytes(d);  // (the reference's op, whatever form runs)
   if (i == 2 && st.ah_proj) {
     // projection folded into the weights (pack time): a Ch -> out_dim 3x3 convolution straight into the caller's tensor
@@ -1522,8 +1521,7 @@ static int fwd_composite_tail(FwdCtx& f, int i, bool edges_aside) {
   UpFuseDesc u = {};
   u.in = f.TP(plan->t_U[i]); u.in_cs = Cc; u.in_co = 0;
   u.N = B; u.LH = lh; u.LW = lw; u.Cc = Cc; u.Ch = Ch;
-  const bool stream_kernel = i == 2 && st.uf_stream;  // the folded composite on the streaming kernel: its own operand image
-  u.w = f.pk + (stream_kernel ? st.ufp_w_off : st.uf_w_off);
+  u.w = f.pk + (st.uf_proj ? st.ufp_w_off : st.uf_w_off);  // the folded composite on the streaming kernel: its own operand image
   u.bias = aux + 11 * mat + 9 * Ch;
   if (i < 2) { u.res = f.TP(st.t_PA); u.res_cs = Ch; u.res_co = 0; }
   u.eh = eh; u.ev = ev;
@@ -1547,7 +1545,7 @@ static int fwd_composite_tail(FwdCtx& f, int i, bool edges_aside) {
   // executed work: 6.25 composite taps per output pixel; bytes: h + att-half partial sums + result (+ weights)
   return prof_op(plan, "up_convs." + std::to_string(i) + ".fused", 2.0 * opix * 6.25 * Cc * Ch,
                  4.0 * (opix / 4.0 * Cc + 2.0 * opix * Ch + 25.0 * Cc * Ch), f.s,
-                 [&] { return stream_kernel ? drs_launch_upfuse_proj(u, f.s) : drs_launch_upfuse(u, f.s); });
+                 [&] { return st.uf_proj ? drs_launch_upfuse_proj(u, f.s) : drs_launch_upfuse(u, f.s); });
 }
 // Stage 2 writes the caller's output itself when the `output` 1x1 convolution (:379) rides in its last launch's epilogue
 static bool output_fused(const drs_plan* plan) {
@@ -1690,7 +1688,7 @@ extern "C" int drs_unet_check_faults(drs_plan* plan, const void* packed, drs_str
   const unsigned word = words[0];
   DRS_REQUIRE((word & 1u) == 0, DRS_ERR_HIP, "a wave-specialised kernel timed out on an LDS counter (protocol fault); results are incomplete");
   if (word & 2u) {  // the FL kernel's movers met an activation block whose maximum fp16 cannot hold
-    plan->fl_off = true;
+    plan->fl_disabled = true;
     DRS_CHECK_HIP(hipMemsetAsync(aligned_base(packed) + plan->o_fault, 0, 32, (hipStream_t)stream));
     DRS_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
     DrsErr::set("an activation left fp16's range in the FL arithmetic (last report: layer Cin=%u Cout=%u, %u rows, %s input, block %u "

@@ -108,7 +108,7 @@ static int pack_dgrad(BwdCtx& c, const ConvLayer& L, int kind) {
     // kind 0 (stride-1 convolution): taps flipped in the packed image, so the launch is a standard 3x3 / 1x1
     // convolution and takes the CONV3X3 schedule instead of the generic tap list
     return drs_launch_pack_conv_mfma(w, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, dst, zero_b, dgrad_cout(L), L.Cout,
-                                     L.taps, transposed_read, c.impl, c.s, L.Cin, kind == 0 ? 1 : 0);
+                                     L.taps, transposed_read, c.impl, c.s, {.cout_src = L.Cin, .flip_taps = kind == 0 ? 1 : 0});
   return drs_launch_pack_conv(w, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, (float*)dst, zero_b, L.Cin, L.Cout, L.taps,
                               transposed_read, 0, c.s);
 }

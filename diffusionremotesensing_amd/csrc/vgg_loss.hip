@@ -418,7 +418,7 @@ extern "C" int drs_vgg_pack_weights(drs_vgg_plan* plan, const void* const* param
       // 3 output channels padded to 32 with zero weights
       if (!rc)
         rc = drs_launch_pack_conv_mfma(w, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, pk + plan->o_wd[l], nullptr,
-                                       dgrad_cout(l), kCfg[l], 9, 1, plan->impl, s, cin_of(l), 1);
+                                       dgrad_cout(l), kCfg[l], 9, 1, plan->impl, s, {.cout_src = cin_of(l), .flip_taps = 1});
       if (rc) return rc;
     }
     const int rc = queue.flush(s);
