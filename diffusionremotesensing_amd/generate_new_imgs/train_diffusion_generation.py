@@ -1,9 +1,10 @@
 """Drop-in `Diffusion` / `launch` / CLI of reference generate_new_imgs/train_diffusion_generation.py on the gfx950
 kernels: class-conditional DDPM with classifier-free guidance.
 
-Differences from the super-resolution Diffusion it derives from: no conditioning image, the loader yields
-(img, label), 10% of the training steps drop the label (:393-394), and `sample` runs a conditional and (for
-cfg_scale > 0) an unconditional forward per step combined with torch.lerp (:236-239).
+Overrides what differs from the super-resolution Diffusion it derives from: no conditioning image, the loader yields
+(img, label), 10% of the training steps drop the label (:393-394), and the model call of `sample` is a conditional and
+(for cfg_scale > 0) an unconditional prediction per step, combined with torch.lerp (:236-239) by the base class's reverse
+chain.  `launch` and the CLI are that module's launcher pieces and parser base around this file's dataset, model and flag.
 """
 import os
 
@@ -11,10 +12,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import dist as drs_dist
-from .. import hip_ops
-from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, add_sampling_args, check_sampling_args,
-                                        ddim_chain_noise, ddim_timesteps, run_reverse_chain)
+from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, base_arg_parser, check_sampling_args, launch_device,
+                                        make_loaders, save_final_samples, train_model)
 from .UNet_model_generation import Residual_Attention_UNet_generation
 
 
@@ -43,64 +42,30 @@ class Diffusion(_SuperresDiffusion):
                noise_source=None, sampling_steps=None, eta=0.0):
         """Reference :206-259.  `sampling_steps` / `eta`: a DDIM chain, as in the super-resolution sampler."""
         check_sampling_args(self.noise_steps, sampling_steps, eta)
-        frames = []
         net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
-        model.eval()
-        engine = net.hip_engine()
-        shape = (n, input_channels, self.image_size, self.image_size)
         if target_class is not None:
             ncls = getattr(net, "num_classes", None)
             if not target_class.is_cuda and ncls and target_class.numel() and int(target_class.max()) >= int(ncls):
                 raise IndexError(f"target_class {int(target_class.max())} out of range for num_classes={ncls}")
             target_class = target_class.to(self.device)
-        with torch.no_grad():
-            x = (noise_source(self.noise_steps, shape) if noise_source is not None else torch.randn(shape)).to(self.device)
-            x = x.contiguous()
-            guided = cfg_scale > 0 and target_class is not None
-            if guided:
-                # conditional and unconditional predictions as ONE 2n batch (label -1 = no embedding for that row) and
-                # torch.lerp folded into the update kernel: half the launches of the reference's two forwards (:236-239)
-                labels2 = torch.cat([target_class.to(torch.int64).expand(n) if target_class.numel() == 1
-                                     else target_class.to(torch.int64), torch.full((n,), -1, dtype=torch.int64,
-                                                                                   device=x.device)]).contiguous()
-            t_rows = hip_ops.timestep_table(self.noise_steps, 2 * n, x.device)  # (row i: step i; the unguided forward takes n of the 2n)
-            state = {"first": True}
-            taus = ddim_timesteps(self.noise_steps, sampling_steps) if sampling_steps is not None else None
-            prev = dict(zip(taus, taus[1:] + [0])) if taus is not None else None
+        if cfg_scale > 0 and target_class is not None:
+            # conditional and unconditional predictions as ONE 2n batch (label -1 = no embedding for that row) and
+            # torch.lerp folded into the update kernel: half the launches of the reference's two forwards (:236-239)
+            labels2 = torch.cat([target_class.to(torch.int64).expand(n) if target_class.numel() == 1
+                                 else target_class.to(torch.int64), torch.full((n,), -1, dtype=torch.int64,
+                                                                               device=target_class.device)]).contiguous()
 
-            def step(i):
-                if taus is not None:
-                    noise = ddim_chain_noise(eta, i, prev[i], shape, x, noise_source)
-                elif i > 1:
-                    noise = noise_source(i, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
-                else:
-                    noise = None
-                if guided:
-                    eps2 = engine.forward(x.repeat(2, 1, 1, 1), t_rows[i], None, 1, labels=labels2, check_weights=state["first"])
-                    if taus is not None:
-                        hip_ops.ddim_step_(x, eps2[:n], noise, i, prev[i], eta, self.alpha_hat, eps_uncond=eps2[n:],
-                                           cfg_scale=cfg_scale)
-                    else:
-                        hip_ops.sampler_step_cfg_(x, eps2[:n], eps2[n:], cfg_scale, noise, i, self.alpha, self.alpha_hat,
-                                                  self.beta)
-                else:
-                    # cfg_scale > 0 without a class: lerp(u, u, w) == u, one forward is enough
-                    predicted_noise = engine.forward(x, t_rows[i, :n], None, 1, labels=target_class, check_weights=state["first"])
-                    if taus is not None:
-                        hip_ops.ddim_step_(x, predicted_noise, noise, i, prev[i], eta, self.alpha_hat)
-                    else:
-                        hip_ops.sampler_step_(x, predicted_noise, noise, i, self.alpha, self.alpha_hat, self.beta)
-                state["first"] = False
-                if generate_video:
-                    frames.append(x.clone())
-            run_reverse_chain(engine, x, self.noise_steps, step, frames if generate_video else None,
-                              timesteps=taus)  # (reads the kernels' fault word)
-        if generate_video:
-            from ..video import video_maker
-            video_maker(frames, os.path.join(os.getcwd(), "models_run", self.model_name, "results",
-                                             "video_denoising.mp4"), 100)
-        model.train()
-        return x
+            def predict(engine, x, t, first):
+                eps2 = engine.forward(x.repeat(2, 1, 1, 1), t, None, 1, labels=labels2, check_weights=first)
+                return eps2[:n], eps2[n:]
+        else:
+            def predict(engine, x, t, first):
+                # cfg_scale > 0 without a class: lerp(u, u, w) == u, one forward is enough
+                return engine.forward(x, t[:n], None, 1, labels=target_class, check_weights=first)
+        # (row i of the 2n-wide timestep table: step i; the unguided forward takes n of the 2n)
+        return self._sample_chain(model, (n, input_channels, self.image_size, self.image_size), predict, table_rows=2 * n,
+                                  generate_video=generate_video, noise_source=noise_source, sampling_steps=sampling_steps,
+                                  eta=eta, cfg_scale=cfg_scale)
 
 
 class SyntheticClassDataset(torch.utils.data.Dataset):
@@ -122,21 +87,9 @@ class SyntheticClassDataset(torch.utils.data.Dataset):
 
 def launch(args):
     """Reference launch (:505-636) for the hot path on seeded data: `--dataset_path synthetic[:N[:classes]]`."""
-    from torch.utils.data import DataLoader
-    from torch.utils.data.distributed import DistributedSampler
-
     if args.UNet_type.lower() != "residual attention unet":
         raise ValueError("The UNet type must be Residual Attention UNet")
-    os.makedirs(args.snapshot_folder_path, exist_ok=True)
-    os.makedirs(os.path.join(os.curdir, "models_run", args.model_name, "results"), exist_ok=True)
-    if args.multiple_gpus:
-        drs_dist.init_process_group()
-        device = int(os.environ["LOCAL_RANK"])
-        torch.cuda.set_device(device)
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError("no ROCm device visible: this implementation has no CPU path")
-        device = torch.device("cuda")
+    device = launch_device(args)
     spec = str(args.dataset_path or "")
     if not spec.startswith("synthetic"):
         raise NotImplementedError("image-folder datasets (reference generate_new_imgs/utils.get_data) are outside "
@@ -147,60 +100,21 @@ def launch(args):
     ch = args.inp_out_channels
     train_dataset = SyntheticClassDataset(length, ch, args.image_size, ncls, seed=1)
     val_dataset = SyntheticClassDataset(max(length // 4, 1), ch, args.image_size, ncls, seed=2)
-    if args.multiple_gpus:
-        train_loader = DataLoader(train_dataset, batch_size=args.batch_size, sampler=DistributedSampler(train_dataset))
-        val_loader = DataLoader(val_dataset, batch_size=args.batch_size, sampler=DistributedSampler(val_dataset))
-    else:
-        train_loader = DataLoader(train_dataset, batch_size=args.batch_size, shuffle=True)
-        val_loader = DataLoader(val_dataset, batch_size=args.batch_size, shuffle=True)
+    train_loader, val_loader = make_loaders(args, train_dataset, val_dataset)
     num_classes = len(train_loader.dataset.classes)
     model = Residual_Attention_UNet_generation(ch, ch, num_classes, device).to(device)
-    print("Num params: ", sum(p.numel() for p in model.parameters()))
-    if args.multiple_gpus:
-        drs_dist.broadcast_module(model)
-    diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model,
-                          snapshot_path=os.path.join(args.snapshot_folder_path, args.snapshot_name),
-                          noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02, device=device,
-                          image_size=args.image_size, model_name=args.model_name, multiple_gpus=args.multiple_gpus,
-                          ema_smoothing=args.ema_smoothing)
-    diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
-                    train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
-                    verbose=True)
-    if args.multiple_gpus:
-        drs_dist.destroy_process_group()
-    outs = [diffusion.sample(n=5, model=model, target_class=torch.full((5,), i, dtype=torch.int64), cfg_scale=3,
-                             input_channels=ch, generate_video=False, sampling_steps=getattr(args, "sampling_steps", None),
-                             eta=getattr(args, "eta", 0.0)) for i in range(min(num_classes, 3))]
-    torch.save(torch.cat(outs).cpu(), os.path.join(os.getcwd(), "models_run", args.model_name, "results",
-                                                  "generation_results.pt"))
+    diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader)
+
+    def sample(i, **ddim):
+        return diffusion.sample(n=5, model=model, target_class=torch.full((5,), i, dtype=torch.int64), cfg_scale=3,
+                                input_channels=ch, generate_video=False, **ddim)
+    save_final_samples(args, sample, range(min(num_classes, 3)), "generation_results.pt")
 
 
 def build_arg_parser():
-    """The reference's flags, verbatim (:649-665), and the DDIM flags."""
-    import argparse
-
-    def str2bool(v):
-        return v.lower() in ("yes", "true", "t", "1")
-
-    p = argparse.ArgumentParser(description=" ")
-    p.add_argument("--epochs", type=int, default=501)
-    p.add_argument("--batch_size", type=int, default=32)
-    p.add_argument("--image_size", type=int, default=None)
-    p.add_argument("--lr", type=float, default=3e-4)
-    p.add_argument("--check_preds_epoch", type=int, default=20)
-    p.add_argument("--noise_schedule", type=str, default="cosine")
-    p.add_argument("--snapshot_name", type=str, default="snapshot.pt")
-    p.add_argument("--model_name", type=str)
-    p.add_argument("--noise_steps", type=int, default=200)
-    p.add_argument("--patience", type=int, default=10)
-    p.add_argument("--dataset_path", type=str, default=None)
+    """`base_arg_parser` and the generation flag of the reference (:649-665)."""
+    p = base_arg_parser()
     p.add_argument("--inp_out_channels", type=int, default=3)
-    p.add_argument("--generate_video", type=str2bool, nargs="?", const=True, default=False)
-    p.add_argument("--loss", type=str)
-    p.add_argument("--UNet_type", type=str, default="Residual Attention UNet")
-    p.add_argument("--multiple_gpus", type=str2bool, nargs="?", const=True, default=False)
-    p.add_argument("--ema_smoothing", type=str2bool, nargs="?", const=True, default=False)
-    add_sampling_args(p)
     return p
 
 

@@ -28,10 +28,6 @@ from .UNet_model_superres import EMA, Residual_Attention_UNet_superres
 _DEGRADATIONS = ("downblur", "bsrgan", "downblurnoise")
 
 
-
-CHAIN_CHECK_EVERY = 128  # reverse steps between two reads of the kernels' fault word inside a sampling chain
-
-
 def ddim_timesteps(noise_steps, sampling_steps):
     """The S timesteps a DDIM chain visits, descending: [1 + (k * (T - 2)) // (S - 1) for k in range(S)] reversed, or
     [T - 1] for S = 1 (integer arithmetic only).  S = T - 1 visits the ancestral chain's T - 1 .. 1; the step after the
@@ -172,41 +168,58 @@ class Diffusion:
             lr_img = lr_img.to(self.device).contiguous()
         else:
             lr_img = lr_img.to(self.device).unsqueeze(0).contiguous()
-        frames = []
+        return self._sample_chain(
+            model, (n, input_channels, self.image_size, self.image_size),
+            lambda engine, x, t, first: engine.forward(x, t, lr_img, self.magnification_factor, reuse_cond=not first,
+                                                       check_weights=first),
+            table_rows=n, generate_video=generate_video, noise_source=noise_source, sampling_steps=sampling_steps, eta=eta)
+
+    def _sample_chain(self, model, shape, predict, *, table_rows, generate_video, noise_source, sampling_steps, eta,
+                      cfg_scale=0.0):
+        """The reverse chain all three samplers share (reference :226-255), from x_T to the returned x_0.
+        `predict(engine, x, t, first)` is the sampler's model call for one step: x in its current state, t one row of the
+        (noise_steps, table_rows) timestep table, `first` True on the first call of the chain only (weights checked,
+        conditioning branch computed; not set again after a range-fault rollback).  It returns eps, or (eps_cond, eps_uncond)
+        for classifier-free guidance: torch.lerp(eps_uncond, eps_cond, cfg_scale) is then folded into the update kernel."""
         net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
         model.eval()
         engine = net.hip_engine()
-        shape = (n, input_channels, self.image_size, self.image_size)
+        frames = [] if generate_video else None
         with torch.no_grad():
             if noise_source is not None:
                 x = noise_source(self.noise_steps, shape).to(self.device)
             else:
                 x = torch.randn(shape).to(self.device)  # CPU generator, like the reference (:230)
             x = x.contiguous()
-            t_rows = hip_ops.timestep_table(self.noise_steps, n, x.device)
-            state = {"first": True}
-
+            t_rows = hip_ops.timestep_table(self.noise_steps, table_rows, x.device)
             taus = ddim_timesteps(self.noise_steps, sampling_steps) if sampling_steps is not None else None
             prev = dict(zip(taus, taus[1:] + [0])) if taus is not None else None
+            state = {"first": True}
 
             def step(i):
-                predicted_noise = engine.forward(x, t_rows[i], lr_img, self.magnification_factor, reuse_cond=not state["first"],
-                                                 check_weights=state["first"])
+                eps = predict(engine, x, t_rows[i], state["first"])
                 state["first"] = False
+                eps, eps_uncond = eps if isinstance(eps, tuple) else (eps, None)
                 if taus is not None:
                     noise = ddim_chain_noise(eta, i, prev[i], shape, x, noise_source)
-                    hip_ops.ddim_step_(x, predicted_noise, noise, i, prev[i], eta, self.alpha_hat)
+                elif i > 1:
+                    noise = noise_source(i, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
                 else:
-                    if i > 1:
-                        noise = noise_source(i, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
-                    else:
-                        noise = None  # reference adds zeros at the last step (:248)
-                    hip_ops.sampler_step_(x, predicted_noise, noise, i, self.alpha, self.alpha_hat, self.beta)
+                    noise = None  # reference adds zeros at the last step (:248)
+                if taus is None and eps_uncond is None:
+                    hip_ops.sampler_step_(x, eps, noise, i, self.alpha, self.alpha_hat, self.beta)
+                elif taus is None:
+                    hip_ops.sampler_step_cfg_(x, eps, eps_uncond, cfg_scale, noise, i, self.alpha, self.alpha_hat, self.beta)
+                elif eps_uncond is None:
+                    hip_ops.ddim_step_(x, eps, noise, i, prev[i], eta, self.alpha_hat)
+                else:
+                    hip_ops.ddim_step_(x, eps, noise, i, prev[i], eta, self.alpha_hat, eps_uncond=eps_uncond,
+                                       cfg_scale=cfg_scale)
                 if generate_video:
                     frames.append(x.clone())
             # (the fault word of the wave-specialised kernels - a protocol fault reports itself through it instead of a trap,
             #  csrc/sp_sync.h - is read inside the loop, every CHAIN_CHECK_EVERY steps and at the end)
-            run_reverse_chain(engine, x, self.noise_steps, step, frames if generate_video else None, timesteps=taus)
+            run_reverse_chain(engine, x, self.noise_steps, step, frames, timesteps=taus)
         if generate_video:
             from .video import video_maker  # optional dependency (cv2), same call as reference :253
             video_maker(frames, os.path.join(os.getcwd(), "models_run", self.model_name, "results",
@@ -375,14 +388,65 @@ class SyntheticSuperresDataset(torch.utils.data.Dataset):
         return self.lr[i], self.hr[i]
 
 
+def launch_device(args):
+    """The run directories and the device of a `launch`: RCCL process group + this rank's GPU with --multiple_gpus
+    (reference :586-590), the visible one otherwise."""
+    os.makedirs(args.snapshot_folder_path, exist_ok=True)
+    os.makedirs(os.path.join(os.curdir, "models_run", args.model_name, "results"), exist_ok=True)
+    if args.multiple_gpus:
+        drs_dist.init_process_group()  # RCCL ("nccl" backend on ROCm), env:// rendezvous like reference :586
+        gpu_id = int(os.environ["LOCAL_RANK"])
+        torch.cuda.set_device(gpu_id)
+        return gpu_id
+    if not torch.cuda.is_available():
+        raise RuntimeError("no ROCm device visible: this implementation has no CPU path")
+    return torch.device("cuda")
+
+
+def make_loaders(args, train_dataset, val_dataset):
+    """(train, val) DataLoaders of a dataset pair: one shard per rank with --multiple_gpus, shuffled otherwise."""
+    from torch.utils.data import DataLoader
+    from torch.utils.data.distributed import DistributedSampler
+
+    def loader(ds):
+        if args.multiple_gpus:
+            return DataLoader(ds, batch_size=args.batch_size, shuffle=False, sampler=DistributedSampler(ds))
+        return DataLoader(ds, batch_size=args.batch_size, shuffle=True)
+    return loader(train_dataset), loader(val_dataset)
+
+
+def train_model(args, diffusion_class, model, device, train_loader, val_loader, **diffusion_kwargs):
+    """Same weights on every rank, `diffusion_class(...)` from the flags (a snapshot, if there is one, is loaded here),
+    the training run, and the end of the process group.  Returns the Diffusion."""
+    print("Num params: ", sum(p.numel() for p in model.parameters()))
+    if args.multiple_gpus:
+        drs_dist.broadcast_module(model)  # what the DDP constructor does in the reference (:658)
+    diffusion = diffusion_class(noise_schedule=args.noise_schedule, model=model,
+                                snapshot_path=os.path.join(args.snapshot_folder_path, args.snapshot_name),
+                                noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02, device=device,
+                                image_size=args.image_size, model_name=args.model_name, multiple_gpus=args.multiple_gpus,
+                                ema_smoothing=args.ema_smoothing, **diffusion_kwargs)
+    diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
+                    train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
+                    verbose=True)
+    if args.multiple_gpus:
+        drs_dist.destroy_process_group()
+    return diffusion
+
+
+def save_final_samples(args, sample, conditions, file_name):
+    """The final sampling of a `launch`: `sample(c, sampling_steps=, eta=)` for every c of `conditions` (the DDIM flags, or
+    the ancestral chain), concatenated into models_run/<model_name>/results/<file_name>."""
+    ddim = {"sampling_steps": getattr(args, "sampling_steps", None), "eta": getattr(args, "eta", 0.0)}
+    outs = [sample(c, **ddim) for c in conditions]
+    torch.save(torch.cat(outs).cpu(), os.path.join(os.getcwd(), "models_run", args.model_name, "results", file_name))
+
+
 def launch(args):
     """Reference launch (:513-693) for the hot path: model + Diffusion + train + final sampling.  `--dataset_path` is the
     reference's image folder (`<path>/train_original`, `<path>/val_original`, :597-598: decoded once with Pillow into a uint8
     cache on the device, DownBlur / DownBlurNoise per batch on the device) or `synthetic[:N]` / `synthetic_u8[:N]` (seeded
     patches; float pairs / the same device feed)."""
-    from torch.utils.data import DataLoader
-    from torch.utils.data.distributed import DistributedSampler
-
     if args.Degradation_type.lower() not in _DEGRADATIONS:
         raise ValueError("The degradation type must be either BSRGAN or DownBlur or DownBlurNoise")
     if args.Degradation_type.lower() == "downblur" and args.image_size % args.magnification_factor != 0:
@@ -390,20 +454,8 @@ def launch(args):
     if args.UNet_type.lower() != "residual attention unet":
         raise ValueError("The UNet type must be Residual Attention UNet or Residual MultiHead Attention UNet or "
                          "Residual Visual MultiHeadAttention UNet superres")
-    os.makedirs(args.snapshot_folder_path, exist_ok=True)
-    os.makedirs(os.path.join(os.curdir, "models_run", args.model_name, "results"), exist_ok=True)
-
-    if args.multiple_gpus:
-        print("Using multiple GPUs")
-        drs_dist.init_process_group()  # RCCL ("nccl" backend on ROCm), env:// rendezvous like reference :586
-        gpu_id = int(os.environ["LOCAL_RANK"])
-        torch.cuda.set_device(gpu_id)
-        device = gpu_id
-    else:
-        print("Using single GPU")
-        if not torch.cuda.is_available():
-            raise RuntimeError("no ROCm device visible: this implementation has no CPU path")
-        device = torch.device("cuda")
+    print("Using multiple GPUs" if args.multiple_gpus else "Using single GPU")
+    device = launch_device(args)
 
     spec = str(args.dataset_path or "")
     ch = args.inp_out_channels
@@ -456,48 +508,28 @@ def launch(args):
                     raise ValueError(f"dataset of {len(ds)} images cannot be sharded over {wsz} ranks")
                 return make_feed((ds.hr[r::wsz][:per_rank] * 255).round().clamp(0, 255).to(torch.uint8))
             train_loader, val_loader = feed(train_dataset), feed(val_dataset)
-        elif args.multiple_gpus:
-            train_loader = DataLoader(train_dataset, batch_size=args.batch_size, shuffle=False,
-                                      sampler=DistributedSampler(train_dataset))
-            val_loader = DataLoader(val_dataset, batch_size=args.batch_size, shuffle=False,
-                                    sampler=DistributedSampler(val_dataset))
         else:
-            train_loader = DataLoader(train_dataset, batch_size=args.batch_size, shuffle=True)
-            val_loader = DataLoader(val_dataset, batch_size=args.batch_size, shuffle=True)
+            train_loader, val_loader = make_loaders(args, train_dataset, val_dataset)
 
     print("Using Residual Attention UNet")
     model = Residual_Attention_UNet_superres(ch, ch, device).to(device)
-    print("Num params: ", sum(p.numel() for p in model.parameters()))
-    if args.multiple_gpus:
-        drs_dist.broadcast_module(model)  # what the DDP constructor does in the reference (:658)
-
-    diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model,
-                          snapshot_path=os.path.join(args.snapshot_folder_path, args.snapshot_name),
-                          noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02,
-                          magnification_factor=args.magnification_factor, device=device, image_size=args.image_size,
-                          model_name=args.model_name, Degradation_type=args.Degradation_type,
-                          multiple_gpus=args.multiple_gpus, ema_smoothing=args.ema_smoothing)
-    diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
-                    train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
-                    verbose=True)
-    if args.multiple_gpus:
-        drs_dist.destroy_process_group()
+    diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader,
+                            magnification_factor=args.magnification_factor, Degradation_type=args.Degradation_type)
     if r != 0:
         return  # one rank samples and writes models_run/<name>/results/superres_results.pt (every rank holds the same weights)
-    outs = [diffusion.sample(n=1, model=model, lr_img=lr_i, input_channels=ch, generate_video=args.generate_video,
-                             sampling_steps=getattr(args, "sampling_steps", None), eta=getattr(args, "eta", 0.0))
-            for lr_i in final_lr]
-    torch.save(torch.cat(outs).cpu(), os.path.join(os.getcwd(), "models_run", args.model_name, "results",
-                                                  "superres_results.pt"))
+
+    def sample(lr_i, **ddim):
+        return diffusion.sample(n=1, model=model, lr_img=lr_i, input_channels=ch, generate_video=args.generate_video, **ddim)
+    save_final_samples(args, sample, final_lr, "superres_results.pt")
 
 
-def build_arg_parser():
-    """The reference's flags, verbatim (:703-724), and the DDIM flags (`add_sampling_args`)."""
+def str2bool(v):
+    return v.lower() in ("yes", "true", "t", "1")
+
+
+def base_arg_parser():
+    """The reference's flags that all three trainers have, verbatim (:703-724), and the DDIM flags (`add_sampling_args`)."""
     import argparse
-
-    def str2bool(v):
-        return v.lower() in ("yes", "true", "t", "1")
-
     p = argparse.ArgumentParser(description=" ")
     p.add_argument("--epochs", type=int, default=501)
     p.add_argument("--batch_size", type=int, default=32)
@@ -510,17 +542,23 @@ def build_arg_parser():
     p.add_argument("--noise_steps", type=int, default=200)
     p.add_argument("--patience", type=int, default=10)
     p.add_argument("--dataset_path", type=str, default=None)
-    p.add_argument("--inp_out_channels", type=int, default=3)
     p.add_argument("--generate_video", type=str2bool, nargs="?", const=True, default=False)
     p.add_argument("--loss", type=str)
-    p.add_argument("--magnification_factor", type=int)
     p.add_argument("--UNet_type", type=str, default="Residual Attention UNet")
-    p.add_argument("--Degradation_type", type=str, default="DownBlur")
-    p.add_argument("--num_crops", type=int, default=1)
     p.add_argument("--multiple_gpus", type=str2bool, nargs="?", const=True, default=False)
     p.add_argument("--ema_smoothing", type=str2bool, nargs="?", const=True, default=False)
-    p.add_argument("--Blur_radius", type=str, default="random")
     add_sampling_args(p)
+    return p
+
+
+def build_arg_parser():
+    """`base_arg_parser` and the super-resolution flags of the reference (:703-724)."""
+    p = base_arg_parser()
+    p.add_argument("--inp_out_channels", type=int, default=3)
+    p.add_argument("--magnification_factor", type=int)
+    p.add_argument("--Degradation_type", type=str, default="DownBlur")
+    p.add_argument("--num_crops", type=int, default=1)
+    p.add_argument("--Blur_radius", type=str, default="random")
     return p
 
 
