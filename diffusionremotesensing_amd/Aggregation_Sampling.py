@@ -14,6 +14,11 @@ MI355X-first differences:
 Noise: the reference draws x_T and every z_i tile after tile from the global CPU generator; a batched run cannot
 reproduce that stream order, so by default the n tiles draw one (n,C,S,S) tensor per step.  `noise_source(tile, i,
 shape)` lets a caller (the parity tests) supply the reference's per-tile draws.
+
+Not in the reference: `aggregation="per_step"` (`sample_scene`), the aggregation sampling of StableSR the class is named
+after.  ONE state of scene size is denoised and the tiles' noise predictions are blended at every reverse step, so that
+neighbouring tiles denoise the same pixels of an overlap from the same state instead of hallucinating unrelated detail
+that the final blend can only average.  Opt-in: the default, "final", is the reference's behaviour bit for bit.
 """
 from math import exp, pi, sqrt
 
@@ -113,10 +118,82 @@ class split_aggregation_sampling:
             mine = drs_dist.gather_shards(mine, n)
         return mine
 
-    def aggregation_sampling(self, noise_source=None, sampling_steps=None, eta=0.0):
-        """Reference :76-116 (`sampling_steps` / `eta`: every tile runs a DDIM chain)."""
+    def sample_scene(self, noise_source=None, sampling_steps=None, eta=0.0):
+        """The joint reverse chain of the whole scene: the un-clamped (C, H*m, W*m) state after the last step.
+
+        Protocol.  The state X has scene size.  x_T is `noise_source(T, (1, C, Hs, Ws))` or torch.randn on the CPU
+        generator, the noise of step i `noise_source(i, (1, C, Hs, Ws))` or torch.randn_like(X), under the rules of
+        `Diffusion._sample_chain` (none at i == 1; a DDIM chain draws only when sigma > 0, so eta = 0 draws x_T and nothing
+        else).  Note the signature: a scene-level `noise_source(i, shape)`, not the final mode's per-tile one.
+        One step cuts X into the tiles (`gather_tiles`), runs the UNet on them in chunks of `tile_batch` (the last chunk
+        padded with repeats of its last tile, whose eps is never read), each forward writing its slice of ONE eps buffer,
+        and takes the step with one `blend_step_`: per scene element the Gaussian-weighted mean of the covering tiles' eps,
+        summed in tile index order, then the ancestral / DDIM update of the per-tile samplers.
+        Memory: the eps buffer holds every tile of a step, ceil(n / chunk) * chunk x (C, S, S) fp32: 0.79 MB per 256x256x3
+        tile (38 MB for the 48 tiles of a 896x1152 scene, 3.1 GB for the ~4000 tiles of a 2048x2048 scene at stride 32),
+        next to one chunk of gathered tiles and the plan's workspace.
+        Conditioning: with one chunk the LR branch is computed on the first step and reused; with several chunks the
+        plan's conditioning belongs to whichever chunk ran last, so every forward recomputes it.
+        The loop is `run_reverse_chain`: the fault-word reads and the range-fault roll-back act on the scene state."""
+        from .train_diffusion_superres import check_sampling_args
+        d = self.diffusion_model
+        check_sampling_args(d.noise_steps, sampling_steps, eta)
+        if drs_dist.world_size() > 1:
+            raise NotImplementedError(
+                "aggregation='per_step' runs on one rank: the joint chain would need an all-gather of eps and a shared "
+                "noise draw per step; use aggregation='final', which shards its independent tile chains over the ranks")
         batch_size, channels, height, width = self.img_lr.shape
         m = self.magnification_factor
+        S = self.patch_size * m
+        Hs, Ws = height * m, width * m
+        lr = torch.cat([p[:1] for p in self.patches_lr], dim=0).to(self.device).contiguous()  # (n, C, ps, ps)
+        n = lr.shape[0]
+        chunk = max(1, int(getattr(self, "tile_batch", 0) or TILE_BATCH))
+        size = n if n <= chunk else chunk  # a scene smaller than one chunk runs at its own size, like sample_tiles
+        starts = list(range(0, n, size))
+        lr_chunks = []
+        for c0 in starts:
+            lr_c = lr[c0:c0 + size]
+            if lr_c.shape[0] < size:
+                lr_c = torch.cat([lr_c, lr_c[-1:].expand(size - lr_c.shape[0], -1, -1, -1)], dim=0)
+            lr_chunks.append(lr_c.contiguous())
+        dev = lr.device
+        origins = hip_ops.tile_origins([(info[0], info[2]) for info in self.patches_sr_infos], S, Hs, Ws, dev)
+        weight = self.weight[0, 0].contiguous()
+        eps_buf = torch.empty((len(starts) * size, channels, S, S), dtype=torch.float32, device=dev)
+        x_tiles = torch.empty((size, channels, S, S), dtype=torch.float32, device=dev)
+        uncovered = torch.zeros(1, dtype=torch.int32, device=dev)
+        single = len(starts) == 1
+
+        def predict(engine, x, t, first):
+            for j, c0 in enumerate(starts):
+                hip_ops.gather_tiles(x[0], origins, S, out=x_tiles, first=c0, count=size)
+                engine.forward(x_tiles, t, lr_chunks[j], m, reuse_cond=single and not first,
+                               check_weights=first and j == 0, out=eps_buf[c0:c0 + size])
+            return eps_buf
+
+        def update(x, eps, noise, i, i_prev):
+            hip_ops.blend_step_(x[0], eps, origins, weight, noise[0] if noise is not None else None, i,
+                                alpha_hat=d.alpha_hat, alpha=d.alpha, beta=d.beta, t_prev=i_prev, eta=eta,
+                                uncovered=uncovered)
+
+        x = d._sample_chain(self.model, (1, channels, Hs, Ws), predict, table_rows=size, generate_video=False,
+                            noise_source=noise_source, sampling_steps=sampling_steps, eta=eta, update=update)
+        if int(uncovered.item()) != 0:
+            raise AssertionError("aggregation: some scene pixels are covered by no tile (pixel_count == 0)")
+        return x[0]
+
+    def aggregation_sampling(self, noise_source=None, sampling_steps=None, eta=0.0, aggregation="final"):
+        """Reference :76-116 (`sampling_steps` / `eta`: every tile runs a DDIM chain).  `aggregation`: "final" (the
+        reference: independent tile chains, blended once; `noise_source(tile, i, shape)`) or "per_step" (`sample_scene`:
+        one joint chain, blended at every step; `noise_source(i, scene_shape)`), clamped to [0, 1]."""
+        if aggregation not in ("final", "per_step"):
+            raise ValueError(f"aggregation={aggregation!r} must be 'final' or 'per_step'")
+        batch_size, channels, height, width = self.img_lr.shape
+        m = self.magnification_factor
+        if aggregation == "per_step":
+            out = torch.clamp(self.sample_scene(noise_source, sampling_steps=sampling_steps, eta=eta), 0, 1)
+            return out.unsqueeze(0).expand(batch_size, -1, -1, -1).contiguous()
         tiles = self.sample_tiles(noise_source, sampling_steps=sampling_steps, eta=eta)
         origins = [(info[0], info[2]) for info in self.patches_sr_infos]
         out = hip_ops.aggregate_tiles(tiles, origins, self.weight[0, 0].contiguous(), height * m, width * m)
@@ -151,12 +228,13 @@ def launch(args):
                           Degradation_type=args.Degradation_type, multiple_gpus=False, ema_smoothing=False)
     tiler = split_aggregation_sampling(img_lr, args.patch_size, args.stride, args.magnification_factor, diffusion, device)
     final_pred = tiler.aggregation_sampling(sampling_steps=getattr(args, "sampling_steps", None),
-                                            eta=getattr(args, "eta", 0.0))
+                                            eta=getattr(args, "eta", 0.0),
+                                            aggregation=getattr(args, "aggregation", "final"))
     torch.save(final_pred.squeeze(0).cpu(), args.destination_path)
 
 
 def build_arg_parser():
-    """The reference's flags, verbatim (:217-231), and the DDIM flags."""
+    """The reference's flags, verbatim (:217-231), the DDIM flags and --aggregation."""
     import argparse
 
     from .train_diffusion_superres import add_sampling_args
@@ -176,6 +254,9 @@ def build_arg_parser():
     p.add_argument("--destination_path", type=str)
     p.add_argument("--img_lr_path", type=str)
     add_sampling_args(p)
+    p.add_argument("--aggregation", type=str, choices=("final", "per_step"), default="final",
+                   help="final: independent tile chains blended once (the reference); per_step: one joint chain of the "
+                        "whole scene, the tiles' noise predictions blended at every reverse step")
     return p
 
 

@@ -41,6 +41,9 @@ SIGNATURES = {
     "drs_downblur_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _P, _Z, _P]),
     "drs_add_noise_clip_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "drs_aggregate_tiles": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "drs_gather_tiles": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "drs_blend_step": (_I, [_P] * 6 + [_I] * 6 + [_P, _P, _P, _I, _P]),
+    "drs_blend_step_ddim": (_I, [_P] * 6 + [_I] * 7 + [_F, _P, _I, _P]),
     "drs_conv2d_workspace_bytes": (_Z, [_I] * 11),
     "drs_conv2d_nchw": (_I, [_P, _P, _P, _P] + [_I] * 12 + [_P, _Z, _I, _P]),
     "drs_upconv_fused_workspace_bytes": (_Z, [_I] * 5),

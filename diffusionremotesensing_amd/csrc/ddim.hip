@@ -1,34 +1,23 @@
 // DDIM update (Song et al., "Denoising Diffusion Implicit Models"): the strided-timestep sampler of Diffusion.sample
 // (sampling_steps=S).  Element-wise and HBM-bound like the ancestral update in small_kernels.hip, which it leaves alone.
 #include "drs_common.h"
+#include "step_update.h"
 #include <cmath>
 
 namespace {
 
-// Every thread forms the same three coefficients: ah_t / ah_p are read from the device table (no read-back to the host)
-// and combined in fp64, then rounded to fp32 once.  Near t = T - 1 of the cosine schedule ah_t is ~1e-6: on a long jump
-// A = sqrt(ah_p / ah_t) and the two terms of B are each ~900, and B is their difference, which fp32 terms rounded one by
-// one would leave with ~4 digits.
+// The coefficients (fp64, rounded once) and the per-element update live in step_update.h, shared with the tile blend.
 __global__ __launch_bounds__(256) void ddim_step_kernel(float* __restrict__ x, const float* __restrict__ ec,
                                                         const float* __restrict__ eu, float w,
                                                         const float* __restrict__ noise, int t, int t_prev, float eta,
                                                         const float* __restrict__ alpha_hat, int64_t numel) {
-  const double at = (double)alpha_hat[t], ap = (double)alpha_hat[t_prev];
-  double sig = 0.0;
-  if (t_prev > 0 && eta > 0.f) sig = (double)eta * sqrt((1.0 - ap) / (1.0 - at)) * sqrt(1.0 - at / ap);
-  const double A = sqrt(ap / at);
-  const double B = sqrt(fmax(1.0 - ap - sig * sig, 0.0)) - sqrt(ap) * sqrt(1.0 - at) / sqrt(at);
-  const float a = (float)A, b = (float)B, s = (float)sig;
-  const bool add_noise = noise != nullptr && sig > 0.0;
+  const DrsDdimCoef k = drs_ddim_coef(alpha_hat, t, t_prev, eta);
+  const bool add_noise = noise != nullptr && k.has_sigma;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
     float e = ec[i];
-    if (eu) {
-      // torch.lerp(start = uncond, end = cond, w): |w| < 0.5 ? fma(w, diff, start) : end - diff * (1 - w)
-      const float u = eu[i], d = __fsub_rn(e, u);
-      e = fabsf(w) < 0.5f ? fmaf(w, d, u) : __fsub_rn(e, __fmul_rn(d, __fsub_rn(1.f, w)));
-    }
-    float v = __fadd_rn(__fmul_rn(a, x[i]), __fmul_rn(b, e));
-    if (add_noise) v = __fadd_rn(v, __fmul_rn(s, noise[i]));
+    if (eu) e = drs_cfg_lerp(eu[i], e, w);
+    float v = drs_ddim_update(k, x[i], e);
+    if (add_noise) v = drs_ddim_noise(k, v, noise[i]);
     x[i] = v;
   }
 }

@@ -2,6 +2,7 @@
 // changes at the boundary, the 3-channel planar convolutions of the LR encoder, the stem,
 // bicubic up-sampling, the fused time-embedding MLP and the diffusion element-wise updates.
 #include "drs_common.h"
+#include "step_update.h"
 #include <algorithm>
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -593,13 +594,10 @@ __global__ __launch_bounds__(256) void sampler_step_tab_kernel(float* __restrict
                                                                const float* __restrict__ alpha,
                                                                const float* __restrict__ alpha_hat,
                                                                const float* __restrict__ beta, int64_t numel) {
-  const float a = alpha[t], ah = alpha_hat[t], b = beta[t];
-  const float c_inv = __fdiv_rn(1.f, sqrtf(a));
-  const float c_eps = __fdiv_rn(__fsub_rn(1.f, a), sqrtf(__fsub_rn(1.f, ah)));
-  const float c_sig = sqrtf(b);
+  const DrsAncestralCoef k = drs_ancestral_coef(alpha, alpha_hat, beta, t);  // (step_update.h)
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
-    float v = __fmul_rn(c_inv, __fsub_rn(x[i], __fmul_rn(c_eps, eps[i])));
-    if (noise) v = __fadd_rn(v, __fmul_rn(c_sig, noise[i]));
+    float v = drs_ancestral_update(k, x[i], eps[i]);
+    if (noise) v = drs_ancestral_noise(k, v, noise[i]);
     x[i] = v;
   }
 }
@@ -620,18 +618,12 @@ __global__ void sampler_step_cfg_kernel(float* __restrict__ x, const float* __re
                                         const float* __restrict__ eu, float w, const float* __restrict__ noise, int t,
                                         const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
                                         const float* __restrict__ beta, int64_t numel) {
-  const float a = alpha[t], ah = alpha_hat[t], b = beta[t];
   // same operations, in the same order and without fused multiply-adds, as the reference expressions
-  // (train_diffusion_generation.py:239 torch.lerp, :249 the update)
-  const float c_inv = __fdiv_rn(1.f, sqrtf(a));
-  const float c_eps = __fdiv_rn(__fsub_rn(1.f, a), sqrtf(__fsub_rn(1.f, ah)));
-  const float c_sig = sqrtf(b);
+  // (train_diffusion_generation.py:239 torch.lerp, :249 the update): step_update.h
+  const DrsAncestralCoef k = drs_ancestral_coef(alpha, alpha_hat, beta, t);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
-    const float s = eu[i], e = ec[i], d = __fsub_rn(e, s);
-    // torch.lerp(start = uncond, end = cond, w): |w| < 0.5 ? fma(w, diff, start) : end - diff * (1 - w)
-    const float eps = fabsf(w) < 0.5f ? fmaf(w, d, s) : __fsub_rn(e, __fmul_rn(d, __fsub_rn(1.f, w)));
-    float v = __fmul_rn(c_inv, __fsub_rn(x[i], __fmul_rn(c_eps, eps)));
-    if (noise) v = __fadd_rn(v, __fmul_rn(c_sig, noise[i]));
+    float v = drs_ancestral_update(k, x[i], drs_cfg_lerp(eu[i], ec[i], w));
+    if (noise) v = drs_ancestral_noise(k, v, noise[i]);
     x[i] = v;
   }
 }

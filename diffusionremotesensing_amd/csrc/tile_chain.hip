@@ -1,0 +1,238 @@
+// Per-step tile aggregation (split_aggregation_sampling.sample_scene): ONE state of scene size is denoised; every reverse
+// step cuts it into the tiles the UNet sees (drs_gather_tiles), and blends the tiles' noise predictions back into one
+// eps per scene element before taking the step (drs_blend_step / drs_blend_step_ddim).  Both kernels move each byte once
+// and are bound by HBM traffic; neither has an atomic on its data path and neither clamps.
+#include "drs_common.h"
+#include "step_update.h"
+#include <cmath>
+
+namespace {
+
+// tiles[k] = scene[:, y0:y0+S, x0:x0+S] for the origin of tile min(first + k, n - 1).  blockIdx.y = k * C + c, the x-grid
+// strides over the S * S / V groups of V consecutive elements of one plane.  The tile side is written with V-wide stores
+// (S % V == 0); the scene side is read V-wide where its address is aligned (x0 % V == 0 and Ws % V == 0, uniform over a
+// block) and element by element otherwise (an odd x0 is possible at magnification 1).  An origin that would leave the
+// scene reads nothing: its elements are written as zeros.
+template <int V>
+__global__ __launch_bounds__(256) void gather_tiles_kernel(const float* __restrict__ scene,
+                                                           const int* __restrict__ origins, float* __restrict__ tiles,
+                                                           int first, int n, int C, int S, int Hs, int Ws) {
+  const int k = blockIdx.y / C, c = blockIdx.y % C;
+  const int src = min(first + k, n - 1);
+  const int y0 = origins[2 * src], x0 = origins[2 * src + 1];
+  const bool inside = y0 >= 0 && x0 >= 0 && y0 <= Hs - S && x0 <= Ws - S;
+  const bool wide = V == 4 && (x0 % 4 == 0) && (Ws % 4 == 0);
+  const float* sp = scene + (int64_t)c * Hs * Ws;
+  float* tp = tiles + ((int64_t)k * C + c) * S * S;
+  const int per_row = S / V, groups = S * per_row;
+  for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+    const int ly = g / per_row, lx = (g % per_row) * V;
+    const int64_t from = (int64_t)(y0 + ly) * Ws + x0 + lx;
+    if constexpr (V == 4) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (inside) {
+        if (wide) v = *reinterpret_cast<const float4*>(sp + from);
+        else v = make_float4(sp[from], sp[from + 1], sp[from + 2], sp[from + 3]);
+      }
+      *reinterpret_cast<float4*>(tp + (int64_t)ly * S + lx) = v;
+    } else {
+      tp[(int64_t)ly * S + lx] = inside ? sp[from] : 0.f;
+    }
+  }
+}
+
+// The step of one scene element once its eps is known: ancestral (t) or DDIM (t -> t_prev).  Coefficients and update are
+// those of sampler_step_tab_kernel / ddim_step_kernel (step_update.h), formed by every thread from the device tables.
+template <bool DDIM>
+struct StepCoef;
+template <>
+struct StepCoef<false> {
+  DrsAncestralCoef k;
+  __device__ StepCoef(const float* alpha, const float* alpha_hat, const float* beta, int t, int, float)
+      : k(drs_ancestral_coef(alpha, alpha_hat, beta, t)) {}
+  __device__ bool draws() const { return true; }
+  __device__ float step(float x, float eps) const { return drs_ancestral_update(k, x, eps); }
+  __device__ float add(float v, float z) const { return drs_ancestral_noise(k, v, z); }
+};
+template <>
+struct StepCoef<true> {
+  DrsDdimCoef k;
+  __device__ StepCoef(const float*, const float* alpha_hat, const float*, int t, int t_prev, float eta)
+      : k(drs_ddim_coef(alpha_hat, t, t_prev, eta)) {}
+  __device__ bool draws() const { return k.has_sigma; }
+  __device__ float step(float x, float eps) const { return drs_ddim_update(k, x, eps); }
+  __device__ float add(float v, float z) const { return drs_ddim_noise(k, v, z); }
+};
+
+// One thread per group of V consecutive scene pixels of one row (V = 4 needs Ws % 4 == 0 and S % 4 == 0), channels in
+// chunks of 4.  For every pixel the covering tiles are visited in index order - the summation order of
+// aggregate_tiles_kernel: cnt += w, acc += tile * w, then acc / cnt - so the blended eps does not depend on the launch
+// geometry.  A tile whose window holds the whole group at a 16-byte aligned offset is read with one float4 per plane
+// (weight and eps), any other one element by element under its own bounds check: eps_tiles is only ever indexed with
+// 0 <= ly, lx < S, whatever the origins hold.  A pixel no tile covers gets 0 / 0 = NaN and is counted in `uncovered`.
+template <int V, bool DDIM>
+__global__ __launch_bounds__(256) void blend_step_kernel(float* __restrict__ scene, const float* __restrict__ eps_tiles,
+                                                         const int* __restrict__ origins,
+                                                         const float* __restrict__ weight,
+                                                         const float* __restrict__ noise, int* __restrict__ uncovered,
+                                                         int n, int C, int S, int Hs, int Ws, int t, int t_prev, float eta,
+                                                         const float* __restrict__ alpha,
+                                                         const float* __restrict__ alpha_hat,
+                                                         const float* __restrict__ beta) {
+  const StepCoef<DDIM> coef(alpha, alpha_hat, beta, t, t_prev, eta);
+  const bool add_noise = noise != nullptr && coef.draws();
+  const int per_row = Ws / V;
+  const int64_t groups = (int64_t)Hs * per_row, hw = (int64_t)Hs * Ws, ss = (int64_t)S * S;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(g / per_row), x = (int)(g % per_row) * V;
+    float cnt[V];
+    for (int c0 = 0; c0 < C; c0 += 4) {
+      float acc[4][V];
+#pragma unroll
+      for (int p = 0; p < V; ++p) {
+        cnt[p] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j][p] = 0.f;
+      }
+      for (int i = 0; i < n; ++i) {
+        const int ly = y - origins[2 * i], lx = x - origins[2 * i + 1];
+        if (ly < 0 || ly >= S || lx <= -V || lx >= S) continue;
+        const float* wp = weight + (int64_t)ly * S + lx;
+        const float* ep = eps_tiles + ((int64_t)i * C + c0) * ss + (int64_t)ly * S + lx;
+        if (V == 4 && lx >= 0 && lx + 4 <= S && (lx & 3) == 0) {
+          const float4 w4 = *reinterpret_cast<const float4*>(wp);
+          const float w[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+          for (int p = 0; p < V; ++p) cnt[p] = __fadd_rn(cnt[p], w[p]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (c0 + j < C) {
+              const float4 e4 = *reinterpret_cast<const float4*>(ep + j * ss);
+              const float e[4] = {e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+              for (int p = 0; p < V; ++p) acc[j][p] = __fadd_rn(acc[j][p], __fmul_rn(e[p], w[p]));
+            }
+        } else {
+#pragma unroll
+          for (int p = 0; p < V; ++p) {
+            if (lx + p < 0 || lx + p >= S) continue;
+            const float w = wp[p];
+            cnt[p] = __fadd_rn(cnt[p], w);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (c0 + j < C) acc[j][p] = __fadd_rn(acc[j][p], __fmul_rn(ep[j * ss + p], w));
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (c0 + j >= C) continue;
+        const int64_t at = (int64_t)(c0 + j) * hw + (int64_t)y * Ws + x;
+        float xs[V], zs[V];
+        if constexpr (V == 4) {
+          const float4 x4 = *reinterpret_cast<const float4*>(scene + at);
+          xs[0] = x4.x; xs[1] = x4.y; xs[2] = x4.z; xs[3] = x4.w;
+          if (add_noise) {
+            const float4 z4 = *reinterpret_cast<const float4*>(noise + at);
+            zs[0] = z4.x; zs[1] = z4.y; zs[2] = z4.z; zs[3] = z4.w;
+          }
+        } else {
+          xs[0] = scene[at];
+          if (add_noise) zs[0] = noise[at];
+        }
+#pragma unroll
+        for (int p = 0; p < V; ++p) {
+          float v = coef.step(xs[p], __fdiv_rn(acc[j][p], cnt[p]));
+          if (add_noise) v = coef.add(v, zs[p]);
+          xs[p] = v;
+        }
+        if constexpr (V == 4) *reinterpret_cast<float4*>(scene + at) = make_float4(xs[0], xs[1], xs[2], xs[3]);
+        else scene[at] = xs[0];
+      }
+    }
+    if (uncovered) {
+      int holes = 0;
+#pragma unroll
+      for (int p = 0; p < V; ++p) holes += cnt[p] == 0.f;
+      if (holes) atomicAdd(uncovered, holes);
+    }
+  }
+}
+
+int grid_for(int64_t items) {
+  int64_t b = (items + 255) / 256;
+  if (b > 8192) b = 8192;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+}  // namespace
+
+extern "C" int drs_gather_tiles(const float* scene, const int32_t* origins, float* tiles, int first, int count, int n, int C,
+                                int S, int Hs, int Ws, drs_stream_t stream) {
+  DRS_REQUIRE(scene && origins && tiles, DRS_ERR_ARG, "gather_tiles: null pointer");
+  DRS_REQUIRE(n >= 1 && first >= 0 && first < n && count >= 1, DRS_ERR_ARG, "gather_tiles: first=%d count=%d n=%d", first,
+              count, n);
+  DRS_REQUIRE(C >= 1 && S >= 1 && Hs >= S && Ws >= S, DRS_ERR_SHAPE, "gather_tiles: C=%d S=%d Hs=%d Ws=%d", C, S, Hs, Ws);
+  DRS_REQUIRE((int64_t)count * C <= 65535, DRS_ERR_SHAPE, "gather_tiles: count=%d x C=%d planes exceed one launch", count, C);
+  const unsigned planes = (unsigned)(count * C);
+  if (S % 4 == 0) {
+    DRS_LAUNCH(gather_tiles_kernel<4>, dim3(grid_for((int64_t)S * S / 4), planes), dim3(256), 0, (hipStream_t)stream, scene,
+               origins, tiles, first, n, C, S, Hs, Ws);
+  } else {
+    DRS_LAUNCH(gather_tiles_kernel<1>, dim3(grid_for((int64_t)S * S), planes), dim3(256), 0, (hipStream_t)stream, scene,
+               origins, tiles, first, n, C, S, Hs, Ws);
+  }
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
+}
+
+namespace {
+
+template <bool DDIM>
+int launch_blend(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight, const float* noise,
+                 int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t, int t_prev, float eta, const float* alpha,
+                 const float* alpha_hat, const float* beta, hipStream_t s) {
+  if (S % 4 == 0 && Ws % 4 == 0) {
+    DRS_LAUNCH((blend_step_kernel<4, DDIM>), dim3(grid_for((int64_t)Hs * (Ws / 4))), dim3(256), 0, s, scene, eps_tiles,
+               origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, alpha, alpha_hat, beta);
+  } else {
+    DRS_LAUNCH((blend_step_kernel<1, DDIM>), dim3(grid_for((int64_t)Hs * Ws)), dim3(256), 0, s, scene, eps_tiles, origins,
+               weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, alpha, alpha_hat, beta);
+  }
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
+}
+
+}  // namespace
+
+#define DRS_BLEND_REQUIRE(what)                                                                                           \
+  DRS_REQUIRE(scene && eps_tiles && origins && weight, DRS_ERR_ARG, what ": null pointer");                               \
+  DRS_REQUIRE(n >= 1 && C >= 1 && S >= 1 && Hs >= S && Ws >= S, DRS_ERR_SHAPE, what ": n=%d C=%d S=%d Hs=%d Ws=%d", n, C, S, \
+              Hs, Ws)
+
+extern "C" int drs_blend_step(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight,
+                              const float* noise, int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t,
+                              const float* alpha, const float* alpha_hat, const float* beta, int noise_steps,
+                              drs_stream_t stream) {
+  DRS_BLEND_REQUIRE("blend_step");
+  DRS_REQUIRE(alpha && alpha_hat && beta, DRS_ERR_ARG, "blend_step: null schedule table");
+  DRS_REQUIRE(t >= 0 && t < noise_steps, DRS_ERR_ARG, "blend_step: t=%d outside [0,%d)", t, noise_steps);
+  return launch_blend<false>(scene, eps_tiles, origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, 0, 0.f, alpha,
+                             alpha_hat, beta, (hipStream_t)stream);
+}
+
+extern "C" int drs_blend_step_ddim(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight,
+                                   const float* noise, int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t,
+                                   int t_prev, float eta, const float* alpha_hat, int noise_steps, drs_stream_t stream) {
+  DRS_BLEND_REQUIRE("blend_step_ddim");
+  DRS_REQUIRE(alpha_hat, DRS_ERR_ARG, "blend_step_ddim: null schedule table");
+  DRS_REQUIRE(0 <= t_prev && t_prev < t && t < noise_steps, DRS_ERR_ARG,
+              "blend_step_ddim: need 0 <= t_prev < t < noise_steps, got t_prev=%d t=%d noise_steps=%d", t_prev, t, noise_steps);
+  DRS_REQUIRE(std::isfinite(eta) && eta >= 0.f, DRS_ERR_ARG, "blend_step_ddim: eta=%g must be finite and >= 0", (double)eta);
+  // sigma > 0 exactly when eta > 0 and t_prev > 0 (alpha_hat decreases strictly along the schedule)
+  DRS_REQUIRE(noise || !(eta > 0.f && t_prev > 0), DRS_ERR_ARG,
+              "blend_step_ddim: eta=%g > 0 and t_prev=%d > 0 need a noise tensor", (double)eta, t_prev);
+  return launch_blend<true>(scene, eps_tiles, origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, nullptr,
+                            alpha_hat, nullptr, (hipStream_t)stream);
+}

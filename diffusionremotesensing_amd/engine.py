@@ -163,9 +163,10 @@ class HipUNetEngine:
 
     # -- forward ----------------------------------------------------------------------------
     def forward(self, x, timestep, lr_img, magnification_factor, reuse_cond=False, check_weights=True,
-                _in_autograd_fn=False, labels=None):
+                _in_autograd_fn=False, labels=None, out=None):
         """`lr_img` is the conditioning image (LR image / SAR image; None for the generation variant);
-        `labels` the optional class labels of the generation variant."""
+        `labels` the optional class labels of the generation variant; `out` (eval plans only) a contiguous fp32 device
+        tensor of the output's size to write into instead of a fresh one (a slice of the tiler's per-step eps buffer)."""
         m = self._module()
         train = bool(m.training)
         has_cond = self.variant != "generation"
@@ -175,6 +176,8 @@ class HipUNetEngine:
             raise RuntimeError("the conditioning image must be a tensor on a ROCm device")
         if train and torch.is_grad_enabled() and not _in_autograd_fn and any(p.requires_grad for p in m.parameters()):
             # training step: route through autograd so loss.backward() reaches drs_unet_backward
+            if out is not None:
+                raise RuntimeError("out= is for forwards outside autograd")
             plan = self._get_plan(x.shape[0], lr_img.shape[0] if has_cond else x.shape[0], x.shape[2], x.shape[3],
                                   int(magnification_factor), x.device, True)
             sd = self._tensors(plan.param_names)
@@ -225,7 +228,11 @@ class HipUNetEngine:
                 if plan.cond_key != (lr_img.data_ptr(), lr_img._version):
                     raise RuntimeError("reuse_cond=True but the conditioning in the workspace belongs to another lr_img")
                 flags |= _lib.FWD_REUSE_COND
-            out = torch.empty((B, out_dim, H, W), dtype=torch.float32, device=x.device)
+            if out is None:
+                out = torch.empty((B, out_dim, H, W), dtype=torch.float32, device=x.device)
+            elif not (out.is_cuda and out.device == x.device and out.is_contiguous() and out.dtype == torch.float32
+                      and tuple(out.shape) == (B, out_dim, H, W)):
+                raise RuntimeError(f"out must be a contiguous fp32 tensor of shape {(B, out_dim, H, W)} on {x.device}")
             stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
             st = plan.lib.drs_unet_forward_labels(
                 plan.handle, C.c_void_p(plan.packed.data_ptr()), C.c_void_p(x.data_ptr()),

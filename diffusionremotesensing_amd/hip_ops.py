@@ -216,3 +216,87 @@ def aggregate_tiles(tiles, origins, weight, height, width):
     if int(uncovered.item()) != 0:
         raise AssertionError("aggregation: some output pixels are covered by no tile (pixel_count == 0)")
     return out
+
+
+def tile_origins(origins, S, height, width, device):
+    """The (n, 2) int32 device table of tile origins [(y0, x0), ...] that `gather_tiles` / `blend_step_` take, checked on
+    the host (every window inside the (height, width) scene) and uploaded ONCE per chain, not per step."""
+    org = torch.tensor([[int(y), int(x)] for y, x in origins], dtype=torch.int32).reshape(-1, 2)
+    if org.shape[0] == 0:
+        raise RuntimeError("tile_origins: no tiles")
+    if int(org.min()) < 0 or int(org[:, 0].max()) + S > height or int(org[:, 1].max()) + S > width:
+        raise RuntimeError(f"tile_origins: a {S}x{S} tile window leaves the {height}x{width} scene")
+    return org.to(device)
+
+
+def _req_origins(origins, name):
+    origins = _req(origins, name, torch.int32)
+    if origins.dim() != 2 or origins.shape[1] != 2 or origins.shape[0] < 1:
+        raise RuntimeError(f"{name} must be an (n, 2) int32 device table (hip_ops.tile_origins), got {tuple(origins.shape)}")
+    return origins
+
+
+def gather_tiles(scene, origins, S, out=None, first=0, count=None):
+    """tiles[k] = scene[:, y0:y0+S, x0:x0+S] for the `count` tiles from index `first` of the device table `origins`
+    (`tile_origins`), bit-exact: (count, C, S, S), written into `out` when given.  A chunk that runs past the last tile
+    repeats it (the padding of a fixed-size chunk of tiles)."""
+    lib = _lib.load()
+    scene = _req(scene, "scene")
+    origins = _req_origins(origins, "origins")
+    if scene.dim() != 3:
+        raise RuntimeError(f"gather_tiles: scene must be (C, H, W), got {tuple(scene.shape)}")
+    C_, Hs, Ws = scene.shape
+    n = origins.shape[0]
+    count = n - first if count is None else int(count)
+    if out is None:
+        out = torch.empty((count, C_, S, S), dtype=torch.float32, device=scene.device)
+    elif not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32) or out.numel() != count * C_ * S * S:
+        raise RuntimeError(f"gather_tiles: out must be a contiguous fp32 ROCm tensor of {count * C_ * S * S} elements")
+    with torch.cuda.device(scene.device):
+        st = lib.drs_gather_tiles(_ptr(scene), _ptr(origins), _ptr(out), int(first), count, n, C_, int(S), Hs, Ws,
+                                  _stream(scene.device))
+    _lib.check(st, "drs_gather_tiles")
+    return out
+
+
+def blend_step_(scene, eps_tiles, origins, weight, noise, t, *, alpha_hat, alpha=None, beta=None, t_prev=None, eta=0.0,
+                uncovered=None):
+    """One reverse step of the scene state (C, H, W), in place, from the noise predictions `eps_tiles` (n, C, S, S) of
+    its tiles (only the first n = len(origins) tiles of a longer buffer are read): Gaussian-weighted mean of the covering
+    tiles' eps in tile order, then the update of `sampler_step_` (t_prev None: needs alpha and beta) or of `ddim_step_`
+    (t -> t_prev with eta).  `noise` (scene shape) may be None as for those.  `uncovered`: optional int32 device counter
+    that is increased by the number of pixels no tile covers (include/drs_hip.h: drs_blend_step)."""
+    lib = _lib.load()
+    if not (isinstance(scene, torch.Tensor) and scene.is_cuda and scene.is_contiguous() and scene.dtype == torch.float32):
+        raise RuntimeError("blend_step_: scene must be a contiguous fp32 ROCm tensor (no CPU fallback)")
+    eps_tiles = _req(eps_tiles, "eps_tiles")
+    origins = _req_origins(origins, "origins")
+    weight = _req(weight, "weight")
+    noise = _req(noise, "noise") if noise is not None else None
+    alpha_hat = _req(alpha_hat, "alpha_hat")
+    if scene.dim() != 3 or eps_tiles.dim() != 4:
+        raise RuntimeError(f"blend_step_: scene {tuple(scene.shape)} must be (C, H, W), eps_tiles {tuple(eps_tiles.shape)} "
+                           "(n, C, S, S)")
+    C_, Hs, Ws = scene.shape
+    n = origins.shape[0]
+    S = eps_tiles.shape[2]
+    if eps_tiles.shape[0] < n or eps_tiles.shape[1] != C_ or eps_tiles.shape[3] != S or tuple(weight.shape) != (S, S):
+        raise RuntimeError(f"blend_step_: eps_tiles {tuple(eps_tiles.shape)}, weight {tuple(weight.shape)}, {n} origins, "
+                           f"scene {tuple(scene.shape)}")
+    if noise is not None and noise.numel() != scene.numel():
+        raise RuntimeError(f"blend_step_: noise has {noise.numel()} elements, scene has {scene.numel()}")
+    if uncovered is not None:
+        uncovered = _req(uncovered, "uncovered", torch.int32)
+    with torch.cuda.device(scene.device):
+        if t_prev is None:
+            alpha = _req(alpha, "alpha"); beta = _req(beta, "beta")
+            st = lib.drs_blend_step(_ptr(scene), _ptr(eps_tiles), _ptr(origins), _ptr(weight), _ptr(noise), _ptr(uncovered),
+                                    n, C_, S, Hs, Ws, int(t), _ptr(alpha), _ptr(alpha_hat), _ptr(beta), alpha_hat.numel(),
+                                    _stream(scene.device))
+            _lib.check(st, "drs_blend_step")
+        else:
+            st = lib.drs_blend_step_ddim(_ptr(scene), _ptr(eps_tiles), _ptr(origins), _ptr(weight), _ptr(noise),
+                                         _ptr(uncovered), n, C_, S, Hs, Ws, int(t), int(t_prev), float(eta), _ptr(alpha_hat),
+                                         alpha_hat.numel(), _stream(scene.device))
+            _lib.check(st, "drs_blend_step_ddim")
+    return scene

@@ -175,12 +175,14 @@ class Diffusion:
             table_rows=n, generate_video=generate_video, noise_source=noise_source, sampling_steps=sampling_steps, eta=eta)
 
     def _sample_chain(self, model, shape, predict, *, table_rows, generate_video, noise_source, sampling_steps, eta,
-                      cfg_scale=0.0):
+                      cfg_scale=0.0, update=None):
         """The reverse chain all three samplers share (reference :226-255), from x_T to the returned x_0.
         `predict(engine, x, t, first)` is the sampler's model call for one step: x in its current state, t one row of the
         (noise_steps, table_rows) timestep table, `first` True on the first call of the chain only (weights checked,
         conditioning branch computed; not set again after a range-fault rollback).  It returns eps, or (eps_cond, eps_uncond)
-        for classifier-free guidance: torch.lerp(eps_uncond, eps_cond, cfg_scale) is then folded into the update kernel."""
+        for classifier-free guidance: torch.lerp(eps_uncond, eps_cond, cfg_scale) is then folded into the update kernel.
+        `update(x, eps, noise, i, i_prev)`, when given, takes the step in place of the sampler / DDIM update kernels (i_prev
+        None on the ancestral chain): the tiler's per-step blend, whose state is a scene and whose eps a stack of tiles."""
         net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
         model.eval()
         engine = net.hip_engine()
@@ -206,7 +208,9 @@ class Diffusion:
                     noise = noise_source(i, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
                 else:
                     noise = None  # reference adds zeros at the last step (:248)
-                if taus is None and eps_uncond is None:
+                if update is not None:
+                    update(x, eps, noise, i, prev[i] if taus is not None else None)
+                elif taus is None and eps_uncond is None:
                     hip_ops.sampler_step_(x, eps, noise, i, self.alpha, self.alpha_hat, self.beta)
                 elif taus is None:
                     hip_ops.sampler_step_cfg_(x, eps, eps_uncond, cfg_scale, noise, i, self.alpha, self.alpha_hat, self.beta)

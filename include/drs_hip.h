@@ -144,6 +144,39 @@ DRS_API int drs_ema_multi(const drs_ema_tensor* table, int ntensors, int64_t max
 DRS_API int drs_aggregate_tiles(const float* tiles, const int32_t* origins, const float* weight, float* out, int32_t* uncovered,
                         int n, int C, int S, int H, int W, drs_stream_t stream);
 
+/* Per-step tile aggregation (split_aggregation_sampling.sample_scene; csrc/tile_chain.hip): one state of scene size is
+ * denoised, the tiles' noise predictions are blended at every reverse step.  Not in the reference.
+ *
+ * Cut `count` tiles out of a scene: tiles[k] = scene[:, y0:y0+S, x0:x0+S] with (y0, x0) = origins[min(first + k, n - 1)],
+ * a pure copy (bit-exact).  scene: (C,Hs,Ws); origins: n x 2 int32 (y0, x0) on the device, the table drs_aggregate_tiles
+ * takes; tiles: (count,C,S,S).  `first` / `count` select a chunk of the n tiles without staging the whole set; a chunk
+ * that runs past tile n - 1 repeats the last tile (the padding of a fixed-size chunk).  An origin whose window leaves the
+ * scene is not read: that tile is written as zeros.  Requires 0 <= first < n, count >= 1 (DRS_ERR_ARG) and
+ * 1 <= S <= Hs, Ws (DRS_ERR_SHAPE). */
+DRS_API int drs_gather_tiles(const float* scene, const int32_t* origins, float* tiles, int first, int count, int n, int C,
+                             int S, int Hs, int Ws, drs_stream_t stream);
+
+/* One ancestral reverse step of a scene state, in place and in one launch, from the noise predictions of its n tiles:
+ *   eps[c][y][x] = sum_i w[y-y0_i][x-x0_i] * eps_tiles[i][c][y-y0_i][x-x0_i] / sum_i w[y-y0_i][x-x0_i]
+ * over the tiles i that cover (y, x), in index order (the sums of drs_aggregate_tiles: deterministic, no atomics), without a
+ * clamp, followed by exactly the update of drs_sampler_step with that eps (`noise`, of scene shape, may be NULL: last step).
+ * scene, noise: (C,Hs,Ws); eps_tiles: (n,C,S,S); origins: n x 2 int32 on the device; weight: (S,S).
+ * `uncovered` (device int, may be NULL) is INCREASED by the number of pixels no tile covers (their state becomes NaN); it is
+ * not reset here, so that a chain reads it once.  16-byte accesses need S % 4 == 0 and Ws % 4 == 0; any other shape runs
+ * element by element.  DRS_ERR_ARG: null pointer, t outside [0, noise_steps); DRS_ERR_SHAPE: n, C, S < 1, S > Hs or S > Ws. */
+DRS_API int drs_blend_step(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight,
+                           const float* noise, int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t,
+                           const float* alpha, const float* alpha_hat, const float* beta, int noise_steps,
+                           drs_stream_t stream);
+
+/* The same blend followed by exactly the update of drs_ddim_step (no guidance) from timestep t to t_prev: coefficients
+ * formed in fp64 from the device table and rounded once, deterministic step to t_prev = 0.  `noise` may be NULL unless
+ * eta > 0 and t_prev > 0.  DRS_ERR_ARG: null pointer, not 0 <= t_prev < t < noise_steps, eta negative or not finite,
+ * missing noise when sigma > 0; DRS_ERR_SHAPE as drs_blend_step. */
+DRS_API int drs_blend_step_ddim(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight,
+                                const float* noise, int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t,
+                                int t_prev, float eta, const float* alpha_hat, int noise_steps, drs_stream_t stream);
+
 /* "DownBlur" degradation of the super-resolution data feed on the device, bit-exact with the Pillow calls of the
  * reference's dataset item: x = ToTensor(GaussianBlur(radius)(resize(y, (out_w, out_h), BICUBIC))), y = ToTensor(hr).
  *   hr: (N,C,H,W) uint8;  x_lr: (N,C,out_h,out_w) float32 in [0,1];  y_hr: (N,C,H,W) float32 or NULL;
