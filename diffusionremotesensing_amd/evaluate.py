@@ -1,0 +1,77 @@
+"""`python -m diffusionremotesensing_amd.evaluate`: image quality of a trained super-resolution model on its validation set.
+
+Takes the model and dataset flags of the super-resolution trainer (train_diffusion_superres.build_arg_parser, the DDIM flags
+included), loads the snapshot models_run/<model_name>/weights/<snapshot_name> that trainer wrote, samples the validation
+images (`<dataset_path>/val_original`, or the validation half of `synthetic[:N]` / `synthetic_u8[:N]`, unshuffled) and prints
+PSNR / SSIM / SAM / ERGAS of the samples next to those of the bicubic baseline (`Diffusion.evaluate`, metrics.py), then writes
+them, with the per-image values, as JSON.  One process, one device.
+"""
+import json
+import os
+
+import torch
+
+from .train_diffusion_superres import (METRIC_FORMATS, Diffusion, build_arg_parser, launch_device, make_superres_feeds)
+from .UNet_model_superres import Residual_Attention_UNet_superres
+
+
+def evaluate_arg_parser():
+    p = build_arg_parser()
+    p.description = "Score a trained super-resolution model against the bicubic baseline on its validation set"
+    p.add_argument("--n_images", type=int, default=None, help="score only the first N validation images (default: all)")
+    p.add_argument("--out", type=str, default="results.json", help="where the JSON result goes")
+    return p
+
+
+def format_table(scores):
+    """The means of `Diffusion.evaluate` as a table: PSNR to 0.01 dB, SSIM to 4 decimals, SAM to 0.001 degrees, ERGAS to 4
+    significant digits."""
+    keys = list(scores["model"])
+    lines = [f"{'':10s}" + "".join(f"{METRIC_FORMATS[k][0]:>14s}" for k in keys)]
+    for name in ("model", "bicubic"):
+        if name in scores:
+            lines.append(f"{name:10s}" + "".join(f"{METRIC_FORMATS[k][1].format(scores[name][k]):>14s}" for k in keys))
+    return "\n".join(lines)
+
+
+def unshuffled(loader):
+    """The same validation data in dataset order: an evaluation should score the same images in every run."""
+    if hasattr(loader, "shuffle"):  # DeviceSuperresFeed
+        loader.shuffle = False
+        return loader
+    return torch.utils.data.DataLoader(loader.dataset, batch_size=loader.batch_size, shuffle=False)
+
+
+def main(argv=None):
+    p = evaluate_arg_parser()
+    args = p.parse_args(argv)
+    if args.multiple_gpus:
+        p.error("evaluate runs in one process: --multiple_gpus is not supported")
+    if args.n_images is not None and args.n_images < 1:
+        p.error("--n_images must be >= 1")
+    args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
+    snapshot = os.path.join(args.snapshot_folder_path, args.snapshot_name)
+    if not os.path.exists(snapshot):
+        raise FileNotFoundError(f"no snapshot at {snapshot}: train the model first (train_diffusion_superres)")
+    device = launch_device(args)
+    _, val_loader, _ = make_superres_feeds(args, device)
+    ch = args.inp_out_channels
+    model = Residual_Attention_UNet_superres(ch, ch, device).to(device)
+    diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot,
+                          noise_steps=args.noise_steps, device=device, magnification_factor=args.magnification_factor,
+                          image_size=args.image_size, model_name=args.model_name, Degradation_type=args.Degradation_type)
+    model.eval()
+    scores = diffusion.evaluate(model, unshuffled(val_loader), n_images=args.n_images, sampling_steps=args.sampling_steps,
+                                eta=args.eta)
+    print(f"{scores['n']} validation images, snapshot of epoch {diffusion.epochs_run}, "
+          + (f"DDIM {args.sampling_steps} steps eta {args.eta}" if args.sampling_steps else f"{args.noise_steps - 1} ancestral steps"))
+    print(format_table(scores))
+    scores["args"] = {k: v for k, v in vars(args).items() if isinstance(v, (int, float, str, bool, type(None)))}
+    with open(args.out, "w") as f:
+        json.dump(scores, f, indent=1)
+    print(f"wrote {args.out}")
+    return scores
+
+
+if __name__ == "__main__":
+    main()

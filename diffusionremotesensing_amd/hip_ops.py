@@ -300,3 +300,47 @@ def blend_step_(scene, eps_tiles, origins, weight, noise, t, *, alpha_hat, alpha
                                          alpha_hat.numel(), _stream(scene.device))
             _lib.check(st, "drs_blend_step_ddim")
     return scene
+
+
+def _req_image_pair(sr, hr, what):
+    sr = _req(sr, "sr"); hr = _req(hr, "hr")
+    if sr.dim() != 4 or sr.shape != hr.shape:
+        raise RuntimeError(f"{what}: sr {tuple(sr.shape)} and hr {tuple(hr.shape)} must be the same (B, C, H, W)")
+    if hr.device != sr.device:
+        raise RuntimeError(f"{what}: sr is on {sr.device}, hr on {hr.device}")
+    return sr, hr
+
+
+def metrics_workspace(B, C, H, W, device):
+    """The scratch buffer `metrics_pointwise` and `ssim_mean` take (either call, stream-ordered)."""
+    return torch.empty(max(_lib.load().drs_metrics_workspace_bytes(B, C, H, W), 8), dtype=torch.uint8, device=device)
+
+
+def metrics_pointwise(sr, hr, clamp=True, workspace=None):
+    """Per-image sums of one pass over sr and hr (B, C, H, W): a (B, 2 C + 2) float64 device tensor holding the per-band
+    squared error, the per-band sum of hr, the sum of the per-pixel spectral angles in radians and the number of pixels in
+    that sum (include/drs_hip.h: drs_metrics_pointwise)."""
+    lib = _lib.load()
+    sr, hr = _req_image_pair(sr, hr, "metrics_pointwise")
+    B, C_, H, W = sr.shape
+    ws = metrics_workspace(B, C_, H, W, sr.device) if workspace is None else _req(workspace, "workspace", torch.uint8)
+    out = torch.empty((B, 2 * C_ + 2), dtype=torch.float64, device=sr.device)
+    with torch.cuda.device(sr.device):
+        st = lib.drs_metrics_pointwise(_ptr(sr), _ptr(hr), _ptr(out), B, C_, H, W, int(bool(clamp)), _ptr(ws), ws.numel(),
+                                       _stream(sr.device))
+    _lib.check(st, "drs_metrics_pointwise")
+    return out
+
+
+def ssim_mean(sr, hr, clamp=True, workspace=None):
+    """Per-image mean SSIM over bands and valid window positions: a (B,) float64 device tensor (include/drs_hip.h: drs_ssim)."""
+    lib = _lib.load()
+    sr, hr = _req_image_pair(sr, hr, "ssim_mean")
+    B, C_, H, W = sr.shape
+    ws = metrics_workspace(B, C_, H, W, sr.device) if workspace is None else _req(workspace, "workspace", torch.uint8)
+    out = torch.empty((B,), dtype=torch.float64, device=sr.device)
+    with torch.cuda.device(sr.device):
+        st = lib.drs_ssim(_ptr(sr), _ptr(hr), _ptr(out), B, C_, H, W, int(bool(clamp)), _ptr(ws), ws.numel(),
+                          _stream(sr.device))
+    _lib.check(st, "drs_ssim")
+    return out

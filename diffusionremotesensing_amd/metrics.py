@@ -1,0 +1,71 @@
+"""Image quality of a super-resolved batch `sr` against its ground truth `hr`: PSNR, SSIM, the spectral angle mapper (SAM)
+and ERGAS, per image, computed where the samples live.
+
+The sums over pixels come from two HIP kernels (csrc/metrics.hip through `hip_ops.metrics_pointwise` / `hip_ops.ssim_mean`);
+what is left - a few float64 elements per image - is finalised with torch on the device.  Inputs are (B, C, H, W) fp32
+ROCm tensors with 1 <= C <= 16 (a CPU tensor raises: there is no CPU path); `clamp=True` clamps both to [0, 1] first, as
+the reference does before it shows a sample.  Every function returns a (B,) float64 device tensor.
+
+    PSNR   10 log10(1 / MSE) over C, H, W (data range 1); inf for identical images
+    SSIM   Wang et al. 2004: 11 x 11 Gaussian window (sigma 1.5), K1 = 0.01, K2 = 0.03, valid positions, mean over bands
+    SAM    mean over pixels of the angle between the C-vectors of sr and hr, in degrees; pixels whose vector is exactly zero
+           in either image are left out, an image without any other pixel gives NaN
+    ERGAS  100 / magnification * sqrt(mean over bands of MSE_c / mean(hr_c)^2); a band whose hr mean is 0 makes it inf
+"""
+import math
+
+import torch
+
+from . import hip_ops
+
+
+def _psnr(sums, C, hw):
+    return 10.0 * torch.log10(1.0 / (sums[:, :C].sum(dim=1) / (C * hw)))
+
+
+def _sam(sums, C):
+    return torch.rad2deg(sums[:, 2 * C] / sums[:, 2 * C + 1])  # 0 / 0: no pixel with an angle -> NaN
+
+
+def _ergas(sums, C, hw, magnification_factor):
+    mse, mean = sums[:, :C] / hw, sums[:, C:2 * C] / hw
+    ratio = torch.where(mean == 0, torch.full_like(mse, math.inf), mse / (mean * mean))
+    return 100.0 / magnification_factor * torch.sqrt(ratio.mean(dim=1))
+
+
+def _need_bands(sr):
+    if sr.dim() == 4 and sr.shape[1] < 2:
+        raise ValueError(f"sam: the spectral angle needs at least 2 bands, got {sr.shape[1]}")
+
+
+def psnr(sr, hr, clamp=True):
+    sums = hip_ops.metrics_pointwise(sr, hr, clamp)
+    return _psnr(sums, sr.shape[1], sr.shape[2] * sr.shape[3])
+
+
+def ssim(sr, hr, clamp=True):
+    return hip_ops.ssim_mean(sr, hr, clamp)
+
+
+def sam(sr, hr, clamp=True):
+    _need_bands(sr)
+    return _sam(hip_ops.metrics_pointwise(sr, hr, clamp), sr.shape[1])
+
+
+def ergas(sr, hr, magnification_factor, clamp=True):
+    sums = hip_ops.metrics_pointwise(sr, hr, clamp)
+    return _ergas(sums, sr.shape[1], sr.shape[2] * sr.shape[3], magnification_factor)
+
+
+def image_quality(sr, hr, magnification_factor=None, clamp=True):
+    """{"psnr", "ssim"[, "sam" when C >= 2][, "ergas" when a magnification is given]}: the values of the single functions,
+    from one pointwise launch and one SSIM launch."""
+    sums = hip_ops.metrics_pointwise(sr, hr, clamp)
+    C, hw = sr.shape[1], sr.shape[2] * sr.shape[3]
+    out = {"psnr": _psnr(sums, C, hw), "ssim": hip_ops.ssim_mean(sr, hr, clamp)}
+    if C >= 2:
+        out["sam"] = _sam(sums, C)
+    if magnification_factor is not None:
+        out["ergas"] = _ergas(sums, C, hw, magnification_factor)
+    return out
+

@@ -33,14 +33,29 @@ class Diffusion(_SuperresDiffusion):
     def sample(self, n, model, SAR_img, NDVI_channels=1, generate_video=False, noise_source=None, sampling_steps=None,
                eta=0.0):
         """Reference :204-249.  One (SAR_channels, S, S) image conditions all n chains; its encoder branch is computed
-        once per chain instead of once per step.  `noise_source(i, shape)`, `sampling_steps` and `eta` as in the
+        once per chain instead of once per step; a 4-D batch of n images conditions one chain each.  `noise_source(i, shape)`, `sampling_steps` and `eta` as in the
         super-resolution sampler."""
         check_sampling_args(self.noise_steps, sampling_steps, eta)
-        SAR_img = SAR_img.to(self.device).unsqueeze(0).contiguous()
+        if SAR_img.dim() == 4:
+            # one SAR image per chain, (n, SAR_channels, S, S): what `evaluate` samples a validation batch with
+            if SAR_img.shape[0] != n:
+                raise RuntimeError(f"sample: a batch of {SAR_img.shape[0]} SAR images for n={n} chains")
+            SAR_img = SAR_img.to(self.device).contiguous()
+        else:
+            SAR_img = SAR_img.to(self.device).unsqueeze(0).contiguous()
         return self._sample_chain(
             model, (n, NDVI_channels, self.image_size, self.image_size),
             lambda engine, x, t, first: engine.forward(x, t, SAR_img, 1, reuse_cond=not first, check_weights=first),
             table_rows=n, generate_video=generate_video, noise_source=noise_source, sampling_steps=sampling_steps, eta=eta)
+
+    def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None):
+        """PSNR / SSIM (and the spectral angle when NDVI has several bands) of `sample`'s output against the NDVI truth over
+        the (SAR, NDVI) batches of `loader`: the super-resolution `evaluate` without a magnification, hence without ERGAS, and
+        without a bicubic baseline.  Returns {"model": {metric: mean}, "per_image": {"model": {metric: [...]}}, "n": N}."""
+        def sample(SAR_img, NDVI_img):
+            return self.sample(SAR_img.shape[0], model, SAR_img, NDVI_channels=NDVI_img.shape[1], noise_source=noise_source,
+                               sampling_steps=sampling_steps, eta=eta)
+        return self._evaluate(model, loader, n_images, {"model": sample}, None)
 
 
 class SyntheticSarNdviDataset(torch.utils.data.Dataset):

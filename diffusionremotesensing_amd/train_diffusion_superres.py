@@ -94,6 +94,21 @@ def run_reverse_chain(engine, x, noise_steps, step, frames=None, every=CHAIN_CHE
     return x
 
 
+METRIC_FORMATS = {"psnr": ("PSNR", "{:.2f} dB"), "ssim": ("SSIM", "{:.4f}"), "sam": ("SAM", "{:.3f} deg"),
+                  "ergas": ("ERGAS", "{:.4g}")}
+
+
+def format_scores(scores):
+    """One line of `Diffusion.evaluate`'s means: PSNR to 0.01 dB, SSIM to 4 decimals, SAM to 0.001 degrees, ERGAS to 4
+    significant digits, the model's figures and - where scored - the bicubic baseline's."""
+    parts = []
+    for name in ("model", "bicubic"):
+        if name in scores:
+            parts.append(name + " " + " ".join(f"{METRIC_FORMATS[k][0]} {METRIC_FORMATS[k][1].format(v)}"
+                                               for k, v in scores[name].items()))
+    return " | ".join(parts)
+
+
 class Diffusion:
     def __init__(self, noise_schedule: str, model: nn.Module, snapshot_path: str, noise_steps=1000, beta_start=1e-4,
                  beta_end=0.02, device="cuda", magnification_factor=4, image_size=224, model_name="superres",
@@ -231,6 +246,49 @@ class Diffusion:
         model.train()  # reference side effect (:254)
         return x
 
+    # -- image quality of the samples (metrics.py; not in the reference) ---------------------------
+    def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None, baseline=True):
+        """PSNR / SSIM / SAM / ERGAS (metrics.image_quality) of `sample`'s output against the ground truth over the (lr, hr)
+        batches of `loader`, every batch sampled as one call with n = its size, until `n_images` images are scored (None: the
+        whole loader).  `sampling_steps`, `eta` and `noise_source` are `sample`'s (the source is asked batch after batch).
+        With `baseline` the bicubic up-sampling of lr is scored next to the model.  Returns
+        {"model": {metric: mean}, "bicubic": {metric: mean}, "per_image": {"model": {metric: [...]}, "bicubic": ...}, "n": N}.
+        The model keeps the train / eval mode it came with."""
+        def sample(lr_img, hr_img):
+            return self.sample(lr_img.shape[0], model, lr_img, input_channels=hr_img.shape[1], noise_source=noise_source,
+                               sampling_steps=sampling_steps, eta=eta)
+        scorers = {"model": sample}
+        if baseline:
+            scorers["bicubic"] = lambda lr_img, hr_img: hip_ops.bicubic_upsample(lr_img, self.magnification_factor)
+        return self._evaluate(model, loader, n_images, scorers, self.magnification_factor)
+
+    def _evaluate(self, model, loader, n_images, scorers, magnification_factor):
+        """`evaluate` for the estimators `scorers` = {name: f(conditioning batch, truth batch) -> estimate}."""
+        from . import metrics
+        was_training = model.training
+        per_image, n = {name: {} for name in scorers}, 0
+        for batch in loader:
+            cond, truth = self._split_batch(batch)
+            if n_images is not None:
+                cond, truth = cond[:n_images - n], truth[:n_images - n]
+            if truth.shape[0] == 0:
+                break
+            cond, truth = cond.float().contiguous(), truth.float().contiguous()
+            for name, estimate in scorers.items():
+                for k, v in metrics.image_quality(estimate(cond, truth), truth, magnification_factor).items():
+                    per_image[name].setdefault(k, []).append(v)
+            n += truth.shape[0]
+            if n_images is not None and n >= n_images:
+                break
+        model.train(was_training)
+        if n == 0:
+            raise ValueError("evaluate: the loader holds no image")
+        per_image = {name: {k: torch.cat(v) for k, v in d.items()} for name, d in per_image.items()}
+        out = {name: {k: v.mean().item() for k, v in d.items()} for name, d in per_image.items()}
+        out["per_image"] = {name: {k: v.tolist() for k, v in d.items()} for name, d in per_image.items()}
+        out["n"] = n
+        return out
+
     # -- snapshots (reference :257-308) -----------------------------------------------------------
     def _save_snapshot(self, epoch, model):
         net = model.module if self.multiple_gpus and hasattr(model, "module") else model
@@ -315,7 +373,10 @@ class Diffusion:
         the label 10% of the time, like its reference loop)."""
         return cond
 
-    def train(self, lr, epochs, check_preds_epoch, train_loader, val_loader, patience, loss, verbose):
+    def train(self, lr, epochs, check_preds_epoch, train_loader, val_loader, patience, loss, verbose, eval_metrics=0,
+              sampling_steps=None, eta=0.0):
+        """`eval_metrics=N` (not in the reference; 0 = off): at every epoch with epoch % check_preds_epoch == 0 the network that
+        would be saved is scored on the first N validation images (`evaluate` with `sampling_steps` / `eta`), one line."""
         model = self.model
         optimizer = FusedAdam(model.parameters(), lr=lr)  # torch.optim.Adam's math, one launch (optim.py)
         ema = ema_model = None
@@ -362,6 +423,9 @@ class Diffusion:
                     # every training step the ranks must leave the loop together: one mean over ranks, same branch everywhere
                     running_val_loss = drs_dist.allreduce_mean_scalar(running_val_loss)
                 print(f"Epoch {epoch}: Running Val loss ({loss}){running_val_loss}")
+                if eval_metrics and epoch % check_preds_epoch == 0:
+                    scores = self.evaluate(saved, val_loader, n_images=eval_metrics, sampling_steps=sampling_steps, eta=eta)
+                    print(f"Epoch {epoch}: Val metrics on {scores['n']} images | " + format_scores(scores))
                 if running_val_loss < best_loss:
                     best_loss = running_val_loss
                     epochs_without_improving = 0
@@ -419,7 +483,7 @@ def make_loaders(args, train_dataset, val_dataset):
     return loader(train_dataset), loader(val_dataset)
 
 
-def train_model(args, diffusion_class, model, device, train_loader, val_loader, **diffusion_kwargs):
+def train_model(args, diffusion_class, model, device, train_loader, val_loader, train_kwargs=None, **diffusion_kwargs):
     """Same weights on every rank, `diffusion_class(...)` from the flags (a snapshot, if there is one, is loaded here),
     the training run, and the end of the process group.  Returns the Diffusion."""
     print("Num params: ", sum(p.numel() for p in model.parameters()))
@@ -432,7 +496,7 @@ def train_model(args, diffusion_class, model, device, train_loader, val_loader, 
                                 ema_smoothing=args.ema_smoothing, **diffusion_kwargs)
     diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
                     train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
-                    verbose=True)
+                    verbose=True, **(train_kwargs or {}))
     if args.multiple_gpus:
         drs_dist.destroy_process_group()
     return diffusion
@@ -446,21 +510,9 @@ def save_final_samples(args, sample, conditions, file_name):
     torch.save(torch.cat(outs).cpu(), os.path.join(os.getcwd(), "models_run", args.model_name, "results", file_name))
 
 
-def launch(args):
-    """Reference launch (:513-693) for the hot path: model + Diffusion + train + final sampling.  `--dataset_path` is the
-    reference's image folder (`<path>/train_original`, `<path>/val_original`, :597-598: decoded once with Pillow into a uint8
-    cache on the device, DownBlur / DownBlurNoise per batch on the device) or `synthetic[:N]` / `synthetic_u8[:N]` (seeded
-    patches; float pairs / the same device feed)."""
-    if args.Degradation_type.lower() not in _DEGRADATIONS:
-        raise ValueError("The degradation type must be either BSRGAN or DownBlur or DownBlurNoise")
-    if args.Degradation_type.lower() == "downblur" and args.image_size % args.magnification_factor != 0:
-        raise ValueError("The image size must be a multiple of the magnification factor")
-    if args.UNet_type.lower() != "residual attention unet":
-        raise ValueError("The UNet type must be Residual Attention UNet or Residual MultiHead Attention UNet or "
-                         "Residual Visual MultiHeadAttention UNet superres")
-    print("Using multiple GPUs" if args.multiple_gpus else "Using single GPU")
-    device = launch_device(args)
-
+def make_superres_feeds(args, device):
+    """(train feed, validation feed, the LR images the final sampling conditions on) of `--dataset_path`: the reference's
+    image folder or `synthetic[:N]` / `synthetic_u8[:N]` (see `launch`)."""
     spec = str(args.dataset_path or "")
     ch = args.inp_out_channels
     r, wsz = (drs_dist.rank(), drs_dist.world_size()) if args.multiple_gpus else (0, 1)
@@ -514,10 +566,33 @@ def launch(args):
             train_loader, val_loader = feed(train_dataset), feed(val_dataset)
         else:
             train_loader, val_loader = make_loaders(args, train_dataset, val_dataset)
+    return train_loader, val_loader, final_lr
+
+
+def launch(args):
+    """Reference launch (:513-693) for the hot path: model + Diffusion + train + final sampling.  `--dataset_path` is the
+    reference's image folder (`<path>/train_original`, `<path>/val_original`, :597-598: decoded once with Pillow into a uint8
+    cache on the device, DownBlur / DownBlurNoise per batch on the device) or `synthetic[:N]` / `synthetic_u8[:N]` (seeded
+    patches; float pairs / the same device feed)."""
+    if args.Degradation_type.lower() not in _DEGRADATIONS:
+        raise ValueError("The degradation type must be either BSRGAN or DownBlur or DownBlurNoise")
+    if args.Degradation_type.lower() == "downblur" and args.image_size % args.magnification_factor != 0:
+        raise ValueError("The image size must be a multiple of the magnification factor")
+    if args.UNet_type.lower() != "residual attention unet":
+        raise ValueError("The UNet type must be Residual Attention UNet or Residual MultiHead Attention UNet or "
+                         "Residual Visual MultiHeadAttention UNet superres")
+    print("Using multiple GPUs" if args.multiple_gpus else "Using single GPU")
+    device = launch_device(args)
+    train_loader, val_loader, final_lr = make_superres_feeds(args, device)
+    ch = args.inp_out_channels
+    r = drs_dist.rank() if args.multiple_gpus else 0
 
     print("Using Residual Attention UNet")
     model = Residual_Attention_UNet_superres(ch, ch, device).to(device)
-    diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader,
+    train_kwargs = {}
+    if getattr(args, "eval_metrics", 0):
+        train_kwargs = {"eval_metrics": args.eval_metrics, "sampling_steps": args.sampling_steps, "eta": args.eta}
+    diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader, train_kwargs,
                             magnification_factor=args.magnification_factor, Degradation_type=args.Degradation_type)
     if r != 0:
         return  # one rank samples and writes models_run/<name>/results/superres_results.pt (every rank holds the same weights)
@@ -573,8 +648,23 @@ def add_sampling_args(p):
     p.add_argument("--eta", type=float, default=0.0, help="DDIM eta: 0 deterministic, 1 DDPM-like (with --sampling_steps)")
 
 
+def parse_train_args(argv=None):
+    """The trainer's command line: `build_arg_parser` and `--eval_metrics`, which one process evaluates (no distributed
+    evaluation: rejected together with --multiple_gpus)."""
+    p = build_arg_parser()
+    p.add_argument("--eval_metrics", type=int, default=0,
+                   help="score the network on the first N validation images (PSNR / SSIM / SAM / ERGAS against the bicubic "
+                        "baseline) at every epoch with epoch %% check_preds_epoch == 0; 0 = off")
+    args = p.parse_args(argv)
+    if args.eval_metrics < 0:
+        p.error("--eval_metrics must be >= 0")
+    if args.eval_metrics and args.multiple_gpus:
+        p.error("--eval_metrics runs in one process: it cannot be combined with --multiple_gpus")
+    return args
+
+
 def main(argv=None):
-    args = build_arg_parser().parse_args(argv)
+    args = parse_train_args(argv)
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     launch(args)
 

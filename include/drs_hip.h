@@ -177,6 +177,33 @@ DRS_API int drs_blend_step_ddim(float* scene, const float* eps_tiles, const int3
                                 const float* noise, int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t,
                                 int t_prev, float eta, const float* alpha_hat, int noise_steps, drs_stream_t stream);
 
+/* Image-quality sums of an estimate `sr` against the truth `hr`, per image (csrc/metrics.hip; finalised into PSNR, SSIM, SAM
+ * and ERGAS by diffusionremotesensing_amd/metrics.py).  Not in the reference, which only looks at its samples.
+ *   sr, hr: (B,C,H,W) fp32, 1 <= C <= 16;  clamp != 0: both are clamped to [0, 1] as they are loaded (the reference clamps
+ *   a sample before showing it, superres_and_NDVIgen.py:49; a NaN stays a NaN).
+ * Both entry points reduce deterministically (fp32 in the block, one fp64 partial per block in `workspace`, a fixed-order
+ * sum of the partials; no atomics): two calls on the same inputs write the same bits.  One workspace of
+ * drs_metrics_workspace_bytes(B, C, H, W) bytes serves either call (0 for a shape neither takes).
+ * DRS_ERR_ARG: null pointer; DRS_ERR_SHAPE: B or C < 1, C > 16, B > 65535, H or W < 1 (drs_ssim: < 11);
+ * DRS_ERR_WORKSPACE: workspace too small.
+ *
+ * drs_metrics_pointwise, one pass over both tensors: out is B x (2 C + 2) doubles,
+ *   out[b][c]         = sum over pixels of (sr - hr)^2 of band c
+ *   out[b][C + c]     = sum over pixels of hr of band c
+ *   out[b][2 C]       = sum over pixels of the angle (radians) between the C-vectors of sr and hr at that pixel, formed as
+ *                       2 atan2(|u^ - v^|, |u^ + v^|) on the normalised vectors (exactly 0 for identical vectors)
+ *   out[b][2 C + 1]   = the number of pixels in that sum: a pixel whose vector is exactly zero in either image has no angle
+ * 16-byte loads need H * W % 4 == 0 and 16-byte aligned tensors; anything else runs element by element.
+ *
+ * drs_ssim: out[b] = mean over bands and over the (H - 10) x (W - 10) "valid" window positions of the SSIM of Wang et al.
+ * 2004: 11 x 11 Gaussian window, sigma 1.5, normalised; K1 = 0.01, K2 = 0.03, data range 1.  Moments are formed on values
+ * centred on a per-tile pivot. */
+DRS_API size_t drs_metrics_workspace_bytes(int B, int C, int H, int W);
+DRS_API int drs_metrics_pointwise(const float* sr, const float* hr, double* out, int B, int C, int H, int W, int clamp,
+                                  void* workspace, size_t workspace_bytes, drs_stream_t stream);
+DRS_API int drs_ssim(const float* sr, const float* hr, double* out, int B, int C, int H, int W, int clamp, void* workspace,
+                     size_t workspace_bytes, drs_stream_t stream);
+
 /* "DownBlur" degradation of the super-resolution data feed on the device, bit-exact with the Pillow calls of the
  * reference's dataset item: x = ToTensor(GaussianBlur(radius)(resize(y, (out_w, out_h), BICUBIC))), y = ToTensor(hr).
  *   hr: (N,C,H,W) uint8;  x_lr: (N,C,out_h,out_w) float32 in [0,1];  y_hr: (N,C,H,W) float32 or NULL;
