@@ -40,6 +40,8 @@ SIGNATURES = {
     "drs_downblur_scratch_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "drs_downblur_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _P, _Z, _P]),
     "drs_add_noise_clip_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "drs_gather_pairs_f32": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _P]),
+    "drs_gather_u8_f32": (_I, [_P, _P, _P, _I, _L, _I, _P, _P, _P]),
     "drs_aggregate_tiles": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "drs_gather_tiles": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "drs_blend_step": (_I, [_P] * 6 + [_I] * 6 + [_P, _P, _P, _I, _P]),

@@ -1,10 +1,16 @@
-"""`python -m diffusionremotesensing_amd.evaluate`: image quality of a trained super-resolution model on its validation set.
+"""`python -m diffusionremotesensing_amd.evaluate [--task superres|sar_to_ndvi]`: image quality of a trained model on its
+validation set.
 
 Takes the model and dataset flags of the super-resolution trainer (train_diffusion_superres.build_arg_parser, the DDIM flags
 included), loads the snapshot models_run/<model_name>/weights/<snapshot_name> that trainer wrote, samples the validation
 images (`<dataset_path>/val_original`, or the validation half of `synthetic[:N]` / `synthetic_u8[:N]`, unshuffled) and prints
 PSNR / SSIM / SAM / ERGAS of the samples next to those of the bicubic baseline (`Diffusion.evaluate`, metrics.py), then writes
 them, with the per-image values, as JSON.  One process, one device.
+
+`--task sar_to_ndvi` does the same for a snapshot of the SAR -> NDVI trainer: its flags (train_diffusion_SAR_TO_NDVI.
+train_arg_parser), its model and `Diffusion`, the images of `<dataset_path>/test/{sar,opt}` (or the validation half of
+`synthetic[:N]`) unshuffled; PSNR and SSIM, and SAM for two or more NDVI bands - what that class's `evaluate` returns (no
+magnification, hence no ERGAS and no bicubic baseline).
 """
 import json
 import os
@@ -15,9 +21,19 @@ from .train_diffusion_superres import (METRIC_FORMATS, Diffusion, build_arg_pars
 from .UNet_model_superres import Residual_Attention_UNet_superres
 
 
-def evaluate_arg_parser():
-    p = build_arg_parser()
-    p.description = "Score a trained super-resolution model against the bicubic baseline on its validation set"
+TASKS = ("superres", "sar_to_ndvi")
+
+
+def evaluate_arg_parser(task="superres"):
+    if task == "sar_to_ndvi":
+        from .train_diffusion_SAR_TO_NDVI import train_arg_parser as sar_arg_parser
+        p = sar_arg_parser()
+        p.description = "Score a trained SAR -> NDVI model on its test split"
+    else:
+        p = build_arg_parser()
+        p.description = "Score a trained super-resolution model against the bicubic baseline on its validation set"
+    p.add_argument("--task", type=str, default=task, choices=TASKS,
+                   help="which trainer's snapshot and flags: superres (default) or sar_to_ndvi")
     p.add_argument("--n_images", type=int, default=None, help="score only the first N validation images (default: all)")
     p.add_argument("--out", type=str, default="results.json", help="where the JSON result goes")
     return p
@@ -36,14 +52,41 @@ def format_table(scores):
 
 def unshuffled(loader):
     """The same validation data in dataset order: an evaluation should score the same images in every run."""
-    if hasattr(loader, "shuffle"):  # DeviceSuperresFeed
+    if hasattr(loader, "shuffle"):  # the device feeds
         loader.shuffle = False
         return loader
     return torch.utils.data.DataLoader(loader.dataset, batch_size=loader.batch_size, shuffle=False)
 
 
+def _superres_setup(args, device, snapshot):
+    _, val_loader, _ = make_superres_feeds(args, device)
+    ch = args.inp_out_channels
+    model = Residual_Attention_UNet_superres(ch, ch, device).to(device)
+    diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot,
+                          noise_steps=args.noise_steps, device=device, magnification_factor=args.magnification_factor,
+                          image_size=args.image_size, model_name=args.model_name, Degradation_type=args.Degradation_type)
+    return model, diffusion, val_loader
+
+
+def _sar_setup(args, device, snapshot):
+    from . import train_diffusion_SAR_TO_NDVI as S
+    from .UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
+    if str(args.dataset_path or "").startswith("synthetic"):
+        val_loader = torch.utils.data.DataLoader(S.synthetic_datasets(args)[1], batch_size=args.batch_size, shuffle=False)
+    else:
+        val_loader = S.folder_feed(args, device, "test")
+    model = Residual_Attention_UNet_SAR_TO_NDVI(args.SAR_channels, args.NDVI_channels, device).to(device)
+    diffusion = S.Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot, noise_steps=args.noise_steps,
+                            device=device, image_size=args.image_size, model_name=args.model_name)
+    return model, diffusion, val_loader
+
+
 def main(argv=None):
-    p = evaluate_arg_parser()
+    import argparse
+    pre = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    pre.add_argument("--task", type=str, default="superres", choices=TASKS)
+    task = pre.parse_known_args(argv)[0].task
+    p = evaluate_arg_parser(task)
     args = p.parse_args(argv)
     if args.multiple_gpus:
         p.error("evaluate runs in one process: --multiple_gpus is not supported")
@@ -52,14 +95,10 @@ def main(argv=None):
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     snapshot = os.path.join(args.snapshot_folder_path, args.snapshot_name)
     if not os.path.exists(snapshot):
-        raise FileNotFoundError(f"no snapshot at {snapshot}: train the model first (train_diffusion_superres)")
+        trainer = "train_diffusion_SAR_TO_NDVI" if task == "sar_to_ndvi" else "train_diffusion_superres"
+        raise FileNotFoundError(f"no snapshot at {snapshot}: train the model first ({trainer})")
     device = launch_device(args)
-    _, val_loader, _ = make_superres_feeds(args, device)
-    ch = args.inp_out_channels
-    model = Residual_Attention_UNet_superres(ch, ch, device).to(device)
-    diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot,
-                          noise_steps=args.noise_steps, device=device, magnification_factor=args.magnification_factor,
-                          image_size=args.image_size, model_name=args.model_name, Degradation_type=args.Degradation_type)
+    model, diffusion, val_loader = (_sar_setup if task == "sar_to_ndvi" else _superres_setup)(args, device, snapshot)
     model.eval()
     scores = diffusion.evaluate(model, unshuffled(val_loader), n_images=args.n_images, sampling_steps=args.sampling_steps,
                                 eta=args.eta)

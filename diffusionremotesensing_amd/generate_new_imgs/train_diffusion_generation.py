@@ -4,7 +4,8 @@ kernels: class-conditional DDPM with classifier-free guidance.
 Overrides what differs from the super-resolution Diffusion it derives from: no conditioning image, the loader yields
 (img, label), 10% of the training steps drop the label (:393-394), and the model call of `sample` is a conditional and
 (for cfg_scale > 0) an unconditional prediction per step, combined with torch.lerp (:236-239) by the base class's reverse
-chain.  `launch` and the CLI are that module's launcher pieces and parser base around this file's dataset, model and flag.
+chain.  `launch` and the CLI are that module's launcher pieces and parser base around this file's datasets (the reference's
+class-folder tree through the device feed of feeds.py, or seeded images), model and flag.
 """
 import os
 
@@ -12,6 +13,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .. import dist as drs_dist
 from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, base_arg_parser, check_sampling_args, launch_device,
                                         make_loaders, save_final_samples, train_model)
 from .UNet_model_generation import Residual_Attention_UNet_generation
@@ -85,25 +87,47 @@ class SyntheticClassDataset(torch.utils.data.Dataset):
         return self.img[i], self.label[i]
 
 
+def class_folder_feed(args, device, rank=0, world_size=1):
+    """The device feed of the class-folder tree `--dataset_path` (reference :573-584: ImageFolder + Resize((S, S)) + ToTensor; the
+    path is used as given, the reference's `../` prefix belongs to its working directory)."""
+    from ..feeds import DeviceClassFeed, load_class_folder_u8
+    if not os.path.isdir(args.dataset_path):
+        raise FileNotFoundError(f"--dataset_path {args.dataset_path!r}: expected a folder with one sub-folder of images per "
+                                "class (or synthetic[:N[:classes]])")
+    u8, labels, classes = load_class_folder_u8(args.dataset_path, args.image_size, rank, world_size)
+    if u8.shape[1] != args.inp_out_channels:
+        raise ValueError(f"the images of {args.dataset_path} have {u8.shape[1]} bands, --inp_out_channels is {args.inp_out_channels}")
+    return DeviceClassFeed(u8.to(device), labels.to(device), classes, args.batch_size, shuffle=True)
+
+
 def launch(args):
-    """Reference launch (:505-636) for the hot path on seeded data: `--dataset_path synthetic[:N[:classes]]`."""
+    """Reference launch (:505-636).  `--dataset_path` is the reference's class-folder tree (decoded once with Pillow into a uint8
+    cache on the device, batches gathered there; no validation set, as in the reference) or `synthetic[:N[:classes]]` (seeded
+    images)."""
     if args.UNet_type.lower() != "residual attention unet":
         raise ValueError("The UNet type must be Residual Attention UNet")
-    device = launch_device(args)
     spec = str(args.dataset_path or "")
-    if not spec.startswith("synthetic"):
-        raise NotImplementedError("image-folder datasets (reference generate_new_imgs/utils.get_data) are outside "
-                                  "the hot path; use --dataset_path synthetic[:N[:classes]]")
-    parts = spec.split(":")
-    length = int(parts[1]) if len(parts) > 1 else 4 * args.batch_size
-    ncls = int(parts[2]) if len(parts) > 2 else 10
+    if spec.lower() == "cifar10":
+        raise ValueError("--dataset_path cifar10: the reference downloads CIFAR-10 through torchvision, which is not available "
+                         "here; unpack the images into one folder per class and pass that folder")
+    device = launch_device(args)
     ch = args.inp_out_channels
-    train_dataset = SyntheticClassDataset(length, ch, args.image_size, ncls, seed=1)
-    val_dataset = SyntheticClassDataset(max(length // 4, 1), ch, args.image_size, ncls, seed=2)
-    train_loader, val_loader = make_loaders(args, train_dataset, val_dataset)
+    if not spec.startswith("synthetic"):
+        r, wsz = (drs_dist.rank(), drs_dist.world_size()) if args.multiple_gpus else (0, 1)
+        train_loader, val_loader = class_folder_feed(args, device, r, wsz), None  # (reference :581-584, :625: val_loader=None)
+    else:
+        parts = spec.split(":")
+        length = int(parts[1]) if len(parts) > 1 else 4 * args.batch_size
+        ncls = int(parts[2]) if len(parts) > 2 else 10
+        train_dataset = SyntheticClassDataset(length, ch, args.image_size, ncls, seed=1)
+        val_dataset = SyntheticClassDataset(max(length // 4, 1), ch, args.image_size, ncls, seed=2)
+        train_loader, val_loader = make_loaders(args, train_dataset, val_dataset)
+        r = 0
     num_classes = len(train_loader.dataset.classes)
     model = Residual_Attention_UNet_generation(ch, ch, num_classes, device).to(device)
     diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader)
+    if r != 0:
+        return  # a folder run on several ranks: one rank samples and writes the results
 
     def sample(i, **ddim):
         return diffusion.sample(n=5, model=model, target_class=torch.full((5,), i, dtype=torch.int64), cfg_scale=3,

@@ -12,6 +12,7 @@ import os
 import torch
 import torch.nn as nn
 
+from . import dist as drs_dist
 from .train_diffusion_superres import (Diffusion as _SuperresDiffusion, base_arg_parser, check_sampling_args, launch_device,
                                        make_loaders, save_final_samples, train_model)
 from .UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
@@ -59,8 +60,8 @@ class Diffusion(_SuperresDiffusion):
 
 
 class SyntheticSarNdviDataset(torch.utils.data.Dataset):
-    """Seeded (SAR_img, NDVI_img) pairs with the shapes `get_data_SAR_TO_NDVI` yields (reference utils.py); the
-    image-folder dataset itself is outside the hot path."""
+    """Seeded (SAR_img, NDVI_img) pairs with the shapes `get_data_SAR_TO_NDVI` yields (reference utils.py):
+    `--dataset_path synthetic[:N]`."""
 
     def __init__(self, length, sar_channels, ndvi_channels, image_size, seed=0):
         from . import synthetic
@@ -74,26 +75,62 @@ class SyntheticSarNdviDataset(torch.utils.data.Dataset):
         return self.sar[i], self.ndvi[i]
 
 
+def synthetic_datasets(args):
+    """(train, validation) seeded datasets of `--dataset_path synthetic[:N]`."""
+    spec = str(args.dataset_path or "")
+    length = int(spec.split(":")[1]) if ":" in spec else 4 * args.batch_size
+    return (SyntheticSarNdviDataset(length, args.SAR_channels, args.NDVI_channels, args.image_size, seed=1),
+            SyntheticSarNdviDataset(max(length // 4, 1), args.SAR_channels, args.NDVI_channels, args.image_size, seed=2))
+
+
+def folder_feed(args, device, split, rank=0, world_size=1, limit=None):
+    """The device feed of `<dataset_path>/<split>/{sar,opt}` (reference :567-571: split 'train' or 'test'), checked against the
+    flags: the reference resizes nothing here, so the files must have --image_size and the models' band counts."""
+    from .feeds import DeviceSarNdviFeed, load_sar_ndvi_folder
+    root = os.path.join(args.dataset_path, split)
+    if not os.path.isdir(os.path.join(root, "sar")) or not os.path.isdir(os.path.join(root, "opt")):
+        raise FileNotFoundError(f"--dataset_path {args.dataset_path!r}: expected the folders train/sar, train/opt, test/sar and "
+                                f"test/opt (or synthetic[:N]); {root} lacks sar/ or opt/")
+    sar, ndvi = load_sar_ndvi_folder(root, getattr(args, "data_format", "torch"), rank, world_size, limit)
+    for what, t, flag, want in (("sar", sar, "--SAR_channels", args.SAR_channels), ("opt", ndvi, "--NDVI_channels", args.NDVI_channels)):
+        if t.shape[1] != want:
+            raise ValueError(f"the images of {root}/{what} have {t.shape[1]} bands, {flag} is {want}")
+        if tuple(t.shape[2:]) != (args.image_size, args.image_size):
+            raise ValueError(f"the images of {root}/{what} are {t.shape[2]} x {t.shape[3]}, --image_size is {args.image_size} "
+                             "(this dataset is not resized)")
+    return DeviceSarNdviFeed(sar.to(device), ndvi.to(device), args.batch_size, shuffle=True)
+
+
 def launch(args):
-    """Reference launch (:505-633) for the hot path: model + Diffusion + train + final sampling on seeded data."""
+    """Reference launch (:505-633): model + Diffusion + train + final sampling.  `--dataset_path` is the reference's folder
+    (`<path>/train/{sar,opt}`, `<path>/test/{sar,opt}`, :567-571: read once into a cache on the device, batches gathered there) or
+    `synthetic[:N]` (seeded pairs)."""
     if args.UNet_type.lower() != "residual attention unet":
         raise ValueError("The UNet type must be Residual Attention UNet")
     device = launch_device(args)
-    spec = str(args.dataset_path or "")
-    if not spec.startswith("synthetic"):
-        raise NotImplementedError("image-folder datasets (reference utils.get_data_SAR_TO_NDVI) are outside the hot "
-                                  "path; use --dataset_path synthetic[:N]")
-    length = int(spec.split(":")[1]) if ":" in spec else 4 * args.batch_size
-    train_dataset = SyntheticSarNdviDataset(length, args.SAR_channels, args.NDVI_channels, args.image_size, seed=1)
-    val_dataset = SyntheticSarNdviDataset(max(length // 4, 1), args.SAR_channels, args.NDVI_channels, args.image_size, seed=2)
-    train_loader, val_loader = make_loaders(args, train_dataset, val_dataset)
+    folder = not str(args.dataset_path or "").startswith("synthetic")
+    if folder:
+        r, wsz = (drs_dist.rank(), drs_dist.world_size()) if args.multiple_gpus else (0, 1)
+        train_loader = folder_feed(args, device, "train", r, wsz)  # with --multiple_gpus: this rank's shard only
+        val_loader = folder_feed(args, device, "test", r, wsz)
+    else:
+        train_dataset, val_dataset = synthetic_datasets(args)
+        train_loader, val_loader = make_loaders(args, train_dataset, val_dataset)
     model = Residual_Attention_UNet_SAR_TO_NDVI(args.SAR_channels, args.NDVI_channels, device).to(device)
     diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader)
+    if folder:
+        if r != 0:
+            return  # one rank samples and writes the results, as in the super-resolution launch
+        # train_dataset[0..4] of the WHOLE sorted folder (reference :622-626), whatever this rank's shard holds
+        first = folder_feed(args, device, "train", limit=5)
+        final_sar = [first.item(i)[0] for i in range(first.sar.shape[0])]
+    else:
+        final_sar = [train_dataset[i][0] for i in range(min(5, len(train_dataset)))]
 
-    def sample(i, **ddim):
-        return diffusion.sample(n=1, model=model, SAR_img=train_dataset[i][0], NDVI_channels=args.NDVI_channels,
+    def sample(sar_img, **ddim):
+        return diffusion.sample(n=1, model=model, SAR_img=sar_img, NDVI_channels=args.NDVI_channels,
                                 generate_video=args.generate_video, **ddim)
-    save_final_samples(args, sample, range(min(5, len(train_dataset))), "SAR_TO_NDVI_results.pt")
+    save_final_samples(args, sample, final_sar, "SAR_TO_NDVI_results.pt")
 
 
 def build_arg_parser():
@@ -104,8 +141,17 @@ def build_arg_parser():
     return p
 
 
+def train_arg_parser():
+    """The trainer's command line: `build_arg_parser` and `--data_format`, an argument of the reference's dataset class
+    (utils.py:54) that its launch leaves at the default."""
+    p = build_arg_parser()
+    p.add_argument("--data_format", type=str, default="torch", choices=("torch", "numpy"),
+                   help="file format of a dataset folder: .pt tensors (the reference dataset's default) or .npy arrays")
+    return p
+
+
 def main(argv=None):
-    args = build_arg_parser().parse_args(argv)
+    args = train_arg_parser().parse_args(argv)
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     launch(args)
 

@@ -53,7 +53,7 @@ enum {
 
 /* Threading: a drs_plan (and the buffers bound to it) is used by ONE host thread at a time - its launches, events and side
  * streams are not locked.  Different plans may be driven from different threads and on different devices; the plan-less
- * entry points (noise_images, sampler steps, adam / ema, downblur, aggregate) are re-entrant.  The library's only
+ * entry points (noise_images, sampler steps, adam / ema, downblur, the feed gathers, aggregate) are re-entrant.  The library's only
  * process-wide state is a mutex-guarded per-device cache of kernel attributes, plus kernel-family switches read ONCE per
  * process from the environment (A/B experiments and the variant tests; unset = the shipped defaults): DRS_SP,
  * DRS_FL, DRS_WS, DRS_D3K, DRS_S2K, DRS_NWG, DRS_BLOCKS_PER_CU, DRS_FUSE_GATE, DRS_UPFUSE, DRS_XT_ONLY, DRS_RB0, DRS_DOWNK, DRS_SP8,
@@ -218,6 +218,25 @@ DRS_API int drs_downblur_u8(const uint8_t* hr, int N, int C, int H, int W, int o
  * generator), in its order, by diffusionremotesensing_amd.degradation.reference_noise.
  * Replaces the add and the clip of add_Gaussian_noise, utils.py:27-36 (called at utils.py:163-164). */
 DRS_API int drs_add_noise_clip_f32(float* x, const float* noise_nhwc, int N, int C, int H, int W, drs_stream_t stream);
+
+/* One batch of the SAR -> NDVI data feed from the decoded dataset on the device, both tensors of the pair in one launch:
+ *   sar_out[i, :] = (sar_cache[idx[i], :] + 1) * 0.5,  ndvi_out[i, :] = (ndvi_cache[idx[i], :] + 1) * 0.5   for i < n
+ * sar_cache: (L, sar_row) fp32, ndvi_cache: (L, ndvi_row) fp32 (a row = one C x H x W image as the file holds it, in [-1, 1]);
+ * idx: n int64 on the device; sar_out: (n, sar_row), ndvi_out: (n, ndvi_row).  An index outside [0, L) reads nothing: its two
+ * output rows are zeros.  16-byte loads and stores where a cache row and its output row are aligned alike, element by element
+ * otherwise; no workspace.  Replaces get_data_SAR_TO_NDVI.__getitem__'s `(img + 1) / 2` and the DataLoader's collation,
+ * utils.py:65-91. */
+DRS_API int drs_gather_pairs_f32(const float* sar_cache, const float* ndvi_cache, const int64_t* idx, int n, int64_t L,
+                                 int sar_row, int ndvi_row, float* sar_out, float* ndvi_out, drs_stream_t stream);
+
+/* One batch of the class-folder data feed from the decoded uint8 dataset on the device:
+ *   img_out[i, :] = float(cache_u8[idx[i], :]) / 255 (a true division: ToTensor's `.div(255)`),  labels_out[i] = labels[idx[i]]
+ * cache_u8: (L, row) uint8; labels: L int64; idx: n int64 on the device; img_out: (n, row) fp32; labels_out: n int64.  An index
+ * outside [0, L) reads nothing: its row is zeros, its label -1.  One 16-byte load feeds four 16-byte stores where the rows are
+ * aligned for it; no workspace.  Replaces torchvision's ToTensor on an ImageFolder item and the DataLoader's collation,
+ * generate_new_imgs/train_diffusion_generation.py:574-584. */
+DRS_API int drs_gather_u8_f32(const uint8_t* cache_u8, const int64_t* labels, const int64_t* idx, int n, int64_t L, int row,
+                              float* img_out, int64_t* labels_out, drs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Operator-level entry points (used by the parity tests for every convolution flavour
