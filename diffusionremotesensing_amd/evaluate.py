@@ -11,6 +11,10 @@ them, with the per-image values, as JSON.  One process, one device.
 train_arg_parser), its model and `Diffusion`, the images of `<dataset_path>/test/{sar,opt}` (or the validation half of
 `synthetic[:N]`) unshuffled; PSNR and SSIM, and SAM for two or more NDVI bands - what that class's `evaluate` returns (no
 magnification, hence no ERGAS and no bicubic baseline).
+
+`--known_fraction F [--known_block B]` scores known-pixel sampling instead: every truth image is hidden under seeded blocks that
+cover the fraction F, sampled with the remaining pixels as `known` (`--resample` / `--jump`: RePaint resampling), and
+`psnr_unknown` - the PSNR over the hidden pixels alone - is reported next to the whole-image scores.
 """
 import json
 import os
@@ -39,15 +43,44 @@ def evaluate_arg_parser(task="superres"):
     return p
 
 
+def add_known_args(p):
+    """The known-pixel flags of the command line (`main`), on top of `evaluate_arg_parser`."""
+    p.add_argument("--known_fraction", type=float, default=None,
+                   help="known-pixel sampling: hide this fraction of every truth image under seeded square blocks "
+                        "(synthetic.block_mask), sample it with the rest as known pixels (--resample / --jump apply) and also "
+                        "report psnr_unknown, the PSNR over the hidden pixels; default: sample the whole image")
+    p.add_argument("--known_block", type=int, default=None,
+                   help="side of the hidden blocks of --known_fraction (default: image_size / 8)")
+    p.add_argument("--resample", type=int, default=1,
+                   help="with --known_fraction: visit every block of --jump moves this many times (RePaint resampling); 1 = once")
+    p.add_argument("--jump", type=int, default=1, help="with --known_fraction: moves per resampled block (with --resample)")
+    return p
+
+
 def format_table(scores):
     """The means of `Diffusion.evaluate` as a table: PSNR to 0.01 dB, SSIM to 4 decimals, SAM to 0.001 degrees, ERGAS to 4
     significant digits."""
     keys = list(scores["model"])
     lines = [f"{'':10s}" + "".join(f"{METRIC_FORMATS[k][0]:>14s}" for k in keys)]
     for name in ("model", "bicubic"):
-        if name in scores:
-            lines.append(f"{name:10s}" + "".join(f"{METRIC_FORMATS[k][1].format(scores[name][k]):>14s}" for k in keys))
+        if name in scores:  # (a score only the model has, psnr_unknown, leaves the baseline's cell empty)
+            lines.append(f"{name:10s}" + "".join(
+                f"{METRIC_FORMATS[k][1].format(scores[name][k]) if k in scores[name] else '-':>14s}" for k in keys))
     return "\n".join(lines)
+
+
+def known_mask_fn(args):
+    """The `known_mask_fn` of `Diffusion.evaluate` for --known_fraction / --known_block: seeded block masks, image after image
+    in loader order (None without --known_fraction)."""
+    if args.known_fraction is None:
+        return None
+    from . import synthetic
+    block, seen = args.known_block or max(args.image_size // 8, 1), [0]
+
+    def fn(truth):
+        seen[0] += 1
+        return synthetic.block_mask(f"evaluate.known.{seen[0]}", truth.shape[0], truth.shape[2], args.known_fraction, block)
+    return fn
 
 
 def unshuffled(loader):
@@ -86,12 +119,16 @@ def main(argv=None):
     pre = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     pre.add_argument("--task", type=str, default="superres", choices=TASKS)
     task = pre.parse_known_args(argv)[0].task
-    p = evaluate_arg_parser(task)
+    p = add_known_args(evaluate_arg_parser(task))
     args = p.parse_args(argv)
     if args.multiple_gpus:
         p.error("evaluate runs in one process: --multiple_gpus is not supported")
     if args.n_images is not None and args.n_images < 1:
         p.error("--n_images must be >= 1")
+    if args.known_fraction is not None and not 0.0 < args.known_fraction < 1.0:
+        p.error("--known_fraction must lie in (0, 1)")
+    if args.known_fraction is None and (args.known_block is not None or args.resample != 1 or args.jump != 1):
+        p.error("--known_block / --resample / --jump belong to --known_fraction")
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     snapshot = os.path.join(args.snapshot_folder_path, args.snapshot_name)
     if not os.path.exists(snapshot):
@@ -101,9 +138,11 @@ def main(argv=None):
     model, diffusion, val_loader = (_sar_setup if task == "sar_to_ndvi" else _superres_setup)(args, device, snapshot)
     model.eval()
     scores = diffusion.evaluate(model, unshuffled(val_loader), n_images=args.n_images, sampling_steps=args.sampling_steps,
-                                eta=args.eta)
+                                eta=args.eta, known_mask_fn=known_mask_fn(args), resample=args.resample, jump=args.jump)
     print(f"{scores['n']} validation images, snapshot of epoch {diffusion.epochs_run}, "
-          + (f"DDIM {args.sampling_steps} steps eta {args.eta}" if args.sampling_steps else f"{args.noise_steps - 1} ancestral steps"))
+          + (f"DDIM {args.sampling_steps} steps eta {args.eta}" if args.sampling_steps else f"{args.noise_steps - 1} ancestral steps")
+          + (f", {args.known_fraction:.0%} of every image hidden, the rest known (resample {args.resample}, jump {args.jump})"
+             if args.known_fraction is not None else ""))
     print(format_table(scores))
     scores["args"] = {k: v for k, v in vars(args).items() if isinstance(v, (int, float, str, bool, type(None)))}
     with open(args.out, "w") as f:

@@ -14,8 +14,8 @@ import torch
 import torch.nn as nn
 
 from .. import dist as drs_dist
-from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, base_arg_parser, check_sampling_args, launch_device,
-                                        make_loaders, save_final_samples, train_model)
+from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, base_arg_parser, check_inpaint_args,
+                                        check_sampling_args, launch_device, make_loaders, save_final_samples, train_model)
 from .UNet_model_generation import Residual_Attention_UNet_generation
 
 
@@ -43,7 +43,22 @@ class Diffusion(_SuperresDiffusion):
     def sample(self, n, model, target_class=None, cfg_scale=3, input_channels=3, generate_video=False,
                noise_source=None, sampling_steps=None, eta=0.0):
         """Reference :206-259.  `sampling_steps` / `eta`: a DDIM chain, as in the super-resolution sampler."""
+        return self._sample(n, model, target_class, cfg_scale, input_channels, generate_video, noise_source, sampling_steps,
+                            eta)
+
+    def sample_known(self, n, model, known, known_mask, target_class=None, cfg_scale=3, input_channels=3, resample=1, jump=1,
+                     generate_video=False, noise_source=None, sampling_steps=None, eta=0.0):
+        """Class-conditional inpainting: `sample` with known pixels, as in the super-resolution `sample_known` (the guidance
+        is folded into the same update kernel)."""
+        if known is None and known_mask is None and resample == 1 and jump == 1:
+            raise ValueError("sample_known needs known and known_mask (`sample` draws a whole image)")
+        return self._sample(n, model, target_class, cfg_scale, input_channels, generate_video, noise_source, sampling_steps,
+                            eta, known, known_mask, resample, jump)
+
+    def _sample(self, n, model, target_class, cfg_scale, input_channels, generate_video, noise_source, sampling_steps, eta,
+                known=None, known_mask=None, resample=1, jump=1):
         check_sampling_args(self.noise_steps, sampling_steps, eta)
+        check_inpaint_args((n, input_channels, self.image_size, self.image_size), known, known_mask, resample, jump)
         net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
         if target_class is not None:
             ncls = getattr(net, "num_classes", None)
@@ -67,7 +82,8 @@ class Diffusion(_SuperresDiffusion):
         # (row i of the 2n-wide timestep table: step i; the unguided forward takes n of the 2n)
         return self._sample_chain(model, (n, input_channels, self.image_size, self.image_size), predict, table_rows=2 * n,
                                   generate_video=generate_video, noise_source=noise_source, sampling_steps=sampling_steps,
-                                  eta=eta, cfg_scale=cfg_scale)
+                                  eta=eta, cfg_scale=cfg_scale, known=known, known_mask=known_mask, resample=resample,
+                                  jump=jump)
 
 
 class SyntheticClassDataset(torch.utils.data.Dataset):

@@ -196,6 +196,57 @@ def ddim_step_(x, eps_cond, noise, t, t_prev, eta, alpha_hat, eps_uncond=None, c
     return x
 
 
+def inpaint_step_(x, eps_cond, noise, known, mask, t, *, alpha_hat, alpha=None, beta=None, t_prev=None, eta=0.0,
+                  eps_uncond=None, cfg_scale=0.0):
+    """One reverse move of x (n, C, H, W) with known pixels, in place (include/drs_hip.h: drs_inpaint_step): where `mask`
+    (uint8, (n, 1 | C, H, W)) is zero the update of `sampler_step_` / `sampler_step_cfg_` (t_prev None: t -> t - 1, needs alpha
+    and beta) or of `ddim_step_` (t -> t_prev with eta), elsewhere `known` forward-noised to the level reached with the same
+    `noise`, or `known` itself at level 0.  `noise` may be None only when the move ends at level 0."""
+    lib = _lib.load()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
+        raise RuntimeError("inpaint_step_: x must be a contiguous fp32 ROCm tensor (no CPU fallback)")
+    if x.dim() != 4:
+        raise RuntimeError(f"inpaint_step_: x must be (n, C, H, W), got {tuple(x.shape)}")
+    eps_cond = _req(eps_cond, "eps_cond")
+    eps_uncond = _req(eps_uncond, "eps_uncond") if eps_uncond is not None else None
+    noise = _req(noise, "noise") if noise is not None else None
+    known = _req(known, "known")
+    mask = _req(mask, "mask", torch.uint8)
+    alpha_hat = _req(alpha_hat, "alpha_hat")
+    for name, t_ in (("eps_cond", eps_cond), ("eps_uncond", eps_uncond), ("noise", noise), ("known", known)):
+        if t_ is not None and t_.numel() != x.numel():
+            raise RuntimeError(f"inpaint_step_: {name} has {t_.numel()} elements, x has {x.numel()}")
+    n, C_, H, W = x.shape
+    if mask.dim() != 4 or mask.shape[0] != n or tuple(mask.shape[2:]) != (H, W):
+        raise RuntimeError(f"inpaint_step_: mask {tuple(mask.shape)} must be ({n}, 1 or {C_}, {H}, {W})")
+    ddim = t_prev is not None
+    if not ddim:
+        alpha = _req(alpha, "alpha"); beta = _req(beta, "beta")
+    with torch.cuda.device(x.device):
+        st = lib.drs_inpaint_step(_ptr(x), _ptr(eps_cond), _ptr(eps_uncond), float(cfg_scale), _ptr(noise), _ptr(known),
+                                  _ptr(mask), n, C_, H, W, int(mask.shape[1]), int(ddim), int(t), int(t_prev) if ddim else 0,
+                                  float(eta), _ptr(alpha) if not ddim else _ptr(None), _ptr(alpha_hat),
+                                  _ptr(beta) if not ddim else _ptr(None), alpha_hat.numel(), _stream(x.device))
+    _lib.check(st, "drs_inpaint_step")
+    return x
+
+
+def renoise_(x, noise, s, t, alpha_hat):
+    """In-place forward jump of x from level s to level t > s >= 1 with `noise` (include/drs_hip.h: drs_renoise)."""
+    lib = _lib.load()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
+        raise RuntimeError("renoise_: x must be a contiguous fp32 ROCm tensor (no CPU fallback)")
+    noise = _req(noise, "noise")
+    alpha_hat = _req(alpha_hat, "alpha_hat")
+    if noise.numel() != x.numel():
+        raise RuntimeError(f"renoise_: noise has {noise.numel()} elements, x has {x.numel()}")
+    with torch.cuda.device(x.device):
+        st = lib.drs_renoise(_ptr(x), _ptr(noise), int(s), int(t), _ptr(alpha_hat), alpha_hat.numel(), x.numel(),
+                             _stream(x.device))
+    _lib.check(st, "drs_renoise")
+    return x
+
+
 def aggregate_tiles(tiles, origins, weight, height, width):
     """Gaussian-weighted blend of (n,C,S,S) tiles placed at `origins` [(y0, x0), ...] into a (C,height,width) image,
     normalised by the summed weights and clamped to [0,1] (reference Aggregation_Sampling.py:90-116).

@@ -57,6 +57,16 @@ def ergas(sr, hr, magnification_factor, clamp=True):
     return _ergas(sums, sr.shape[1], sr.shape[2] * sr.shape[3], magnification_factor)
 
 
+def psnr_masked(sr, hr, where, clamp=True):
+    """PSNR over the pixels selected by `where` alone ((B, 1 | C, H, W), nonzero = counted; a single-band selection counts the
+    pixel in every band): the score of the filled-in region of a sample with known pixels.  A few torch operations in
+    float64 on the device; an image with no selected pixel gives NaN."""
+    a, b = (t.double().clamp(0, 1) if clamp else t.double() for t in (sr, hr))
+    w = (where != 0).expand_as(a).double()
+    mse = ((a - b) ** 2 * w).sum(dim=(1, 2, 3)) / w.sum(dim=(1, 2, 3))
+    return 10.0 * torch.log10(1.0 / mse)
+
+
 def image_quality(sr, hr, magnification_factor=None, clamp=True):
     """{"psnr", "ssim"[, "sam" when C >= 2][, "ergas" when a magnification is given]}: the values of the single functions,
     from one pointwise launch and one SSIM launch."""

@@ -64,6 +64,29 @@ def tensor_randint(key, shape, lo, hi, seed=0):
     return torch.from_numpy(a.reshape(shape))
 
 
+def block_mask(name, n, size, fraction, block, seed=0):
+    """(n, 1, size, size) uint8 "cloud" masks, 1 = known: every image hides a union of block x block squares at seeded
+    positions, added one by one until at least `fraction` of its pixels are hidden - so the hidden share lies in
+    [fraction, fraction + block^2 / size^2).  A pure function of its arguments, like the other generators."""
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError(f"block_mask: fraction={fraction} outside [0, 1]")
+    if not 1 <= block <= size:
+        raise ValueError(f"block_mask: block={block} outside [1, size = {size}]")
+    target, span = fraction * size * size, size - block + 1
+    known = np.ones((n, 1, size, size), dtype=np.uint8)
+    for i in range(n):
+        hidden, chunk = 0, 0
+        while hidden < target:
+            pos = np.floor(uniform01(f"{name}.{i}.{chunk}", 512, seed) * span).astype(np.int64)
+            for y, x in zip(pos[0::2], pos[1::2]):
+                if hidden >= target:
+                    break
+                known[i, 0, y:y + block, x:x + block] = 0
+                hidden = known[i, 0].size - int(known[i, 0].sum())
+            chunk += 1
+    return torch.from_numpy(known)
+
+
 def seeded_state_dict(template, seed=0):
     """Fill every entry of `template` (a state_dict: key -> tensor, only shapes and
     dtypes are used) with seeded values.  Aliased BatchNorm registrations

@@ -13,8 +13,8 @@ import torch
 import torch.nn as nn
 
 from . import dist as drs_dist
-from .train_diffusion_superres import (Diffusion as _SuperresDiffusion, base_arg_parser, check_sampling_args, launch_device,
-                                       make_loaders, save_final_samples, train_model)
+from .train_diffusion_superres import (Diffusion as _SuperresDiffusion, base_arg_parser, check_inpaint_args,
+                                       check_sampling_args, launch_device, make_loaders, save_final_samples, train_model)
 from .UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
 
 
@@ -36,7 +36,21 @@ class Diffusion(_SuperresDiffusion):
         """Reference :204-249.  One (SAR_channels, S, S) image conditions all n chains; its encoder branch is computed
         once per chain instead of once per step; a 4-D batch of n images conditions one chain each.  `noise_source(i, shape)`, `sampling_steps` and `eta` as in the
         super-resolution sampler."""
+        return self._sample(n, model, SAR_img, NDVI_channels, generate_video, noise_source, sampling_steps, eta)
+
+    def sample_known(self, n, model, SAR_img, known, known_mask, NDVI_channels=1, resample=1, jump=1, generate_video=False,
+                     noise_source=None, sampling_steps=None, eta=0.0):
+        """`sample` with known NDVI pixels, as in the super-resolution `sample_known`: the pixels that are valid (no cloud or
+        shadow over them) are kept and only the others are sampled."""
+        if known is None and known_mask is None and resample == 1 and jump == 1:
+            raise ValueError("sample_known needs known and known_mask (`sample` draws a whole image)")
+        return self._sample(n, model, SAR_img, NDVI_channels, generate_video, noise_source, sampling_steps, eta, known,
+                            known_mask, resample, jump)
+
+    def _sample(self, n, model, SAR_img, NDVI_channels, generate_video, noise_source, sampling_steps, eta, known=None,
+                known_mask=None, resample=1, jump=1):
         check_sampling_args(self.noise_steps, sampling_steps, eta)
+        check_inpaint_args((n, NDVI_channels, self.image_size, self.image_size), known, known_mask, resample, jump)
         if SAR_img.dim() == 4:
             # one SAR image per chain, (n, SAR_channels, S, S): what `evaluate` samples a validation batch with
             if SAR_img.shape[0] != n:
@@ -47,15 +61,22 @@ class Diffusion(_SuperresDiffusion):
         return self._sample_chain(
             model, (n, NDVI_channels, self.image_size, self.image_size),
             lambda engine, x, t, first: engine.forward(x, t, SAR_img, 1, reuse_cond=not first, check_weights=first),
-            table_rows=n, generate_video=generate_video, noise_source=noise_source, sampling_steps=sampling_steps, eta=eta)
+            table_rows=n, generate_video=generate_video, noise_source=noise_source, sampling_steps=sampling_steps, eta=eta,
+            known=known, known_mask=known_mask, resample=resample, jump=jump)
 
-    def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None):
+    def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None, known_mask_fn=None,
+                 resample=1, jump=1):
         """PSNR / SSIM (and the spectral angle when NDVI has several bands) of `sample`'s output against the NDVI truth over
         the (SAR, NDVI) batches of `loader`: the super-resolution `evaluate` without a magnification, hence without ERGAS, and
-        without a bicubic baseline.  Returns {"model": {metric: mean}, "per_image": {"model": {metric: [...]}}, "n": N}."""
+        without a bicubic baseline; `known_mask_fn` / `resample` / `jump` as there ("psnr_unknown").
+        Returns {"model": {metric: mean}, "per_image": {"model": {metric: [...]}}, "n": N}."""
         def sample(SAR_img, NDVI_img):
-            return self.sample(SAR_img.shape[0], model, SAR_img, NDVI_channels=NDVI_img.shape[1], noise_source=noise_source,
-                               sampling_steps=sampling_steps, eta=eta)
+            args = {"NDVI_channels": NDVI_img.shape[1], "noise_source": noise_source, "sampling_steps": sampling_steps, "eta": eta}
+            if known_mask_fn is None:
+                check_inpaint_args(tuple(NDVI_img.shape), None, None, resample, jump)
+                return self.sample(SAR_img.shape[0], model, SAR_img, **args)
+            return self._score_known(NDVI_img, known_mask_fn(NDVI_img), lambda known, mask: self.sample_known(
+                SAR_img.shape[0], model, SAR_img, known, mask, resample=resample, jump=jump, **args))
         return self._evaluate(model, loader, n_images, {"model": sample}, None)
 
 

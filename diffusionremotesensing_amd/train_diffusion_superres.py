@@ -59,12 +59,71 @@ def ddim_chain_noise(eta, t, t_prev, shape, x, noise_source):
     return None
 
 
+def inpaint_schedule(S, resample=1, jump=1):
+    """The moves of a chain with known pixels (RePaint, Lugmayr et al., CVPR 2022, Algorithm 1) over the positions 0 .. S of
+    its level list (position p holds level L[p]: the ancestral T - 1 .. 1 or the `ddim_timesteps`, then 0): a list of
+    (p, q) pairs, q = p + 1 for a reverse move and q = p - jump for a forward jump.  The walk goes down from 0 to S; on its
+    FIRST arrival at a position p with p % jump == 0 and 0 < p < S it goes, `resample - 1` times, one jump up to p - jump
+    and `jump` moves down again.  That is S + (resample - 1) * jump * ((S - 1) // jump) moves down and (resample - 1) *
+    ((S - 1) // jump) up, none of them up from level 0; resample = 1 is the plain replacement chain whatever `jump` is."""
+    moves, seen, p = [], set(), 0
+    while p < S:
+        moves.append((p, p + 1))
+        p += 1
+        if 0 < p < S and p % jump == 0 and p not in seen:
+            seen.add(p)
+            for _ in range(resample - 1):
+                moves.append((p, p - jump))
+                moves.extend((q, q + 1) for q in range(p - jump, p))
+    return moves
+
+
+def _is_int(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and int(v) == v
+
+
+def check_inpaint_args(shape, known, known_mask, resample=1, jump=1):
+    """ValueError for a known-pixel request `Diffusion.sample` cannot run on chains of `shape` = (n, C, S, S) (checked before
+    the engine is touched): `known` without `known_mask` or the reverse, a `known` that does not broadcast to (n, C, S, S) or
+    a mask that does not to (n, 1 | C, S, S), `resample` / `jump` that are no integers >= 1, or that are set without `known`."""
+    for name, v in (("resample", resample), ("jump", jump)):
+        if not _is_int(v) or v < 1:
+            raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    if (known is None) != (known_mask is None):
+        raise ValueError("known and known_mask go together: got " + ("known without known_mask" if known_mask is None
+                                                                      else "known_mask without known"))
+    if known is None:
+        if resample != 1 or jump != 1:
+            raise ValueError(f"resample={resample} / jump={jump} belong to a chain with known pixels: pass known and known_mask")
+        return
+    n, C, H, W = shape
+    ks, ms = tuple(known.shape), tuple(known_mask.shape)
+    if ks not in ((C, H, W), (n, C, H, W)):
+        raise ValueError(f"known {ks} does not broadcast to {(n, C, H, W)}: pass (C, S, S) or (n, C, S, S)")
+    if ms not in ((H, W), (1, H, W), (C, H, W), (n, 1, H, W), (n, C, H, W)):
+        raise ValueError(f"known_mask {ms} does not broadcast to {(n, 1, H, W)} or {(n, C, H, W)}")
+
+
+def known_tensors(shape, known, known_mask, device):
+    """(`known` as (n, C, S, S) fp32, `known_mask` as (n, 1 | C, S, S) uint8 with 1 = known) on the device, for the update
+    kernel: bool, uint8 or {0, 1} float masks, broadcast over the n chains, converted once per chain."""
+    n, C, H, W = shape
+    known = known.to(device=device, dtype=torch.float32).expand(n, C, H, W).contiguous()
+    m = known_mask.to(device)
+    if m.dim() == 2:
+        m = m.unsqueeze(0)
+    if m.dim() == 3:
+        m = m.unsqueeze(0)
+    return known, (m != 0).to(torch.uint8).expand(n, m.shape[1], H, W).contiguous()
+
+
 CHAIN_CHECK_EVERY = 128  # reverse steps between two reads of the kernels' fault word inside a sampling chain
 
 
 def run_reverse_chain(engine, x, noise_steps, step, frames=None, every=CHAIN_CHECK_EVERY, timesteps=None):
     """The reverse loop of `Diffusion.sample` (reference :234-251): `step(i)` performs reverse step i in place on x, for i =
-    noise_steps - 1 .. 1, or for every entry of the descending list `timesteps` (a DDIM chain).  Every `every` steps (and at
+    noise_steps - 1 .. 1, or for every entry of the list `timesteps` (the descending timesteps of a DDIM chain, or the moves of
+    a chain with known pixels: `inpaint_schedule`).  Every `every` steps (and at
     the end) the fault word of the wave-specialised kernels is read (one 4-byte copy + a stream synchronisation: ~0.1 ms per
     128 steps of ~1.2 ms each).  A protocol fault raises.  DRS_ERR_RANGE - an activation left the range of the FL arithmetic's
     fp16 main operand (csrc/conv_mfma_fl.hip; chains of UNTRAINED weights do that, their amplitude grows without bound) - has
@@ -95,7 +154,7 @@ def run_reverse_chain(engine, x, noise_steps, step, frames=None, every=CHAIN_CHE
 
 
 METRIC_FORMATS = {"psnr": ("PSNR", "{:.2f} dB"), "ssim": ("SSIM", "{:.4f}"), "sam": ("SAM", "{:.3f} deg"),
-                  "ergas": ("ERGAS", "{:.4g}")}
+                  "ergas": ("ERGAS", "{:.4g}"), "psnr_unknown": ("PSNR unknown", "{:.2f} dB")}
 
 
 def format_scores(scores):
@@ -171,8 +230,24 @@ class Diffusion:
         """`noise_source(i, shape)`, when given, supplies x_T (i == noise_steps) and the per-step noise z_i
         instead of torch.randn — used to drive this sampler and the oracle with identical noise.
         `sampling_steps=S` runs a DDIM chain over the S timesteps of `ddim_timesteps` instead of the reference's ancestral
-        chain (None); `eta` moves it from deterministic (0) to DDPM-like (1) sampling."""
+        chain (None); `eta` moves it from deterministic (0) to DDPM-like (1) sampling.  (`sample_known` keeps given pixels.)"""
+        return self._sample(n, model, lr_img, input_channels, generate_video, noise_source, sampling_steps, eta)
+
+    def sample_known(self, n, model, lr_img, known, known_mask, input_channels=3, resample=1, jump=1, generate_video=False,
+                     noise_source=None, sampling_steps=None, eta=0.0):
+        """`sample` with known pixels (RePaint): `known` (C, S, S) or (n, C, S, S), in the model's data range and used as
+        given, with `known_mask` (S, S), (1 | C, S, S) or (n, 1 | C, S, S) (bool, uint8 or {0, 1} float; nonzero = known) -
+        those pixels are kept and the others sampled.  `resample` and `jump` are its resampling (`inpaint_schedule`; 1 =
+        none); everything else is `sample`'s.  See `_sample_chain` for the moves and the noise draws."""
+        if known is None and known_mask is None and resample == 1 and jump == 1:
+            raise ValueError("sample_known needs known and known_mask (`sample` draws a whole image)")
+        return self._sample(n, model, lr_img, input_channels, generate_video, noise_source, sampling_steps, eta, known,
+                            known_mask, resample, jump)
+
+    def _sample(self, n, model, lr_img, input_channels, generate_video, noise_source, sampling_steps, eta, known=None,
+                known_mask=None, resample=1, jump=1):
         check_sampling_args(self.noise_steps, sampling_steps, eta)
+        check_inpaint_args((n, input_channels, self.image_size, self.image_size), known, known_mask, resample, jump)
         if self.Degradation_type.lower() not in _DEGRADATIONS:
             raise ValueError("The degradation type must be either BSRGAN or DownBlur")
         if lr_img.dim() == 4:
@@ -187,17 +262,25 @@ class Diffusion:
             model, (n, input_channels, self.image_size, self.image_size),
             lambda engine, x, t, first: engine.forward(x, t, lr_img, self.magnification_factor, reuse_cond=not first,
                                                        check_weights=first),
-            table_rows=n, generate_video=generate_video, noise_source=noise_source, sampling_steps=sampling_steps, eta=eta)
+            table_rows=n, generate_video=generate_video, noise_source=noise_source, sampling_steps=sampling_steps, eta=eta,
+            known=known, known_mask=known_mask, resample=resample, jump=jump)
 
     def _sample_chain(self, model, shape, predict, *, table_rows, generate_video, noise_source, sampling_steps, eta,
-                      cfg_scale=0.0, update=None):
+                      cfg_scale=0.0, update=None, known=None, known_mask=None, resample=1, jump=1):
         """The reverse chain all three samplers share (reference :226-255), from x_T to the returned x_0.
         `predict(engine, x, t, first)` is the sampler's model call for one step: x in its current state, t one row of the
         (noise_steps, table_rows) timestep table, `first` True on the first call of the chain only (weights checked,
         conditioning branch computed; not set again after a range-fault rollback).  It returns eps, or (eps_cond, eps_uncond)
         for classifier-free guidance: torch.lerp(eps_uncond, eps_cond, cfg_scale) is then folded into the update kernel.
         `update(x, eps, noise, i, i_prev)`, when given, takes the step in place of the sampler / DDIM update kernels (i_prev
-        None on the ancestral chain): the tiler's per-step blend, whose state is a scene and whose eps a stack of tiles."""
+        None on the ancestral chain): the tiler's per-step blend, whose state is a scene and whose eps a stack of tiles.
+        With `known` / `known_mask` (checked by `check_inpaint_args`) the chain runs the moves of `inpaint_schedule` over its
+        levels instead: a reverse move t -> t_prev is one `inpaint_step_` (the known pixels become `known` forward-noised to
+        t_prev, the others take the sampler's step) and draws one noise tensor - `noise_source(t, shape)` - iff t_prev > 0,
+        whatever eta is; a forward jump to level t is one `renoise_` and draws `noise_source(t, shape)`.  On the ancestral
+        chain without resampling these are the draws of the plain sampler."""
+        if known is not None and update is not None:
+            raise ValueError("known pixels cannot be combined with an `update` hook (the tiler's per-step blend)")
         net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
         model.eval()
         engine = net.hip_engine()
@@ -236,9 +319,33 @@ class Diffusion:
                                        cfg_scale=cfg_scale)
                 if generate_video:
                     frames.append(x.clone())
+
+            seq = taus
+            if known is not None:
+                known, known_mask = known_tensors(shape, known, known_mask, x.device)
+                levels = (taus if taus is not None else list(range(self.noise_steps - 1, 0, -1))) + [0]
+                seq = inpaint_schedule(len(levels) - 1, resample, jump)
+
+                def draw(t):
+                    return noise_source(t, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
+
+                def step(move):  # noqa: F811 - the step of a chain with known pixels: one move (p, q) of `seq`
+                    t, t_to = levels[move[0]], levels[move[1]]
+                    if t_to > t:
+                        hip_ops.renoise_(x, draw(t_to), t, t_to, self.alpha_hat)
+                    else:
+                        eps = predict(engine, x, t_rows[t], state["first"])
+                        state["first"] = False
+                        eps, eps_uncond = eps if isinstance(eps, tuple) else (eps, None)
+                        form = ({"alpha": self.alpha, "beta": self.beta} if sampling_steps is None
+                                else {"t_prev": t_to, "eta": eta})
+                        hip_ops.inpaint_step_(x, eps, draw(t) if t_to > 0 else None, known, known_mask, t,
+                                              alpha_hat=self.alpha_hat, eps_uncond=eps_uncond, cfg_scale=cfg_scale, **form)
+                    if generate_video:
+                        frames.append(x.clone())
             # (the fault word of the wave-specialised kernels - a protocol fault reports itself through it instead of a trap,
             #  csrc/sp_sync.h - is read inside the loop, every CHAIN_CHECK_EVERY steps and at the end)
-            run_reverse_chain(engine, x, self.noise_steps, step, frames, timesteps=taus)
+            run_reverse_chain(engine, x, self.noise_steps, step, frames, timesteps=seq)
         if generate_video:
             from .video import video_maker  # optional dependency (cv2), same call as reference :253
             video_maker(frames, os.path.join(os.getcwd(), "models_run", self.model_name, "results",
@@ -247,20 +354,36 @@ class Diffusion:
         return x
 
     # -- image quality of the samples (metrics.py; not in the reference) ---------------------------
-    def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None, baseline=True):
+    def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None, baseline=True,
+                 known_mask_fn=None, resample=1, jump=1):
         """PSNR / SSIM / SAM / ERGAS (metrics.image_quality) of `sample`'s output against the ground truth over the (lr, hr)
         batches of `loader`, every batch sampled as one call with n = its size, until `n_images` images are scored (None: the
         whole loader).  `sampling_steps`, `eta` and `noise_source` are `sample`'s (the source is asked batch after batch).
-        With `baseline` the bicubic up-sampling of lr is scored next to the model.  Returns
+        With `baseline` the bicubic up-sampling of lr is scored next to the model.  `known_mask_fn(truth) -> (n, 1 | C, S, S)`
+        mask, when given, samples every batch with its truth as `known` under that mask (`resample` / `jump` as in `sample`)
+        and adds "psnr_unknown", the PSNR over the hidden pixels alone (metrics.psnr_masked).  Returns
         {"model": {metric: mean}, "bicubic": {metric: mean}, "per_image": {"model": {metric: [...]}, "bicubic": ...}, "n": N}.
         The model keeps the train / eval mode it came with."""
         def sample(lr_img, hr_img):
-            return self.sample(lr_img.shape[0], model, lr_img, input_channels=hr_img.shape[1], noise_source=noise_source,
-                               sampling_steps=sampling_steps, eta=eta)
+            args = {"input_channels": hr_img.shape[1], "noise_source": noise_source, "sampling_steps": sampling_steps, "eta": eta}
+            if known_mask_fn is None:
+                check_inpaint_args(tuple(hr_img.shape), None, None, resample, jump)
+                return self.sample(lr_img.shape[0], model, lr_img, **args)
+            return self._score_known(hr_img, known_mask_fn(hr_img), lambda known, mask: self.sample_known(
+                lr_img.shape[0], model, lr_img, known, mask, resample=resample, jump=jump, **args))
         scorers = {"model": sample}
         if baseline:
             scorers["bicubic"] = lambda lr_img, hr_img: hip_ops.bicubic_upsample(lr_img, self.magnification_factor)
         return self._evaluate(model, loader, n_images, scorers, self.magnification_factor)
+
+    @staticmethod
+    def _score_known(truth, mask, sample_known):
+        """One batch of `evaluate` with known pixels: `sample_known(known, mask)` with the truth as the known image, and the
+        result together with {"psnr_unknown": per-image values over the hidden pixels}."""
+        from . import metrics
+        mask = mask.to(truth.device)
+        out = sample_known(truth, mask)
+        return out, {"psnr_unknown": metrics.psnr_masked(out, truth, mask == 0)}
 
     def _evaluate(self, model, loader, n_images, scorers, magnification_factor):
         """`evaluate` for the estimators `scorers` = {name: f(conditioning batch, truth batch) -> estimate}."""
@@ -275,7 +398,9 @@ class Diffusion:
                 break
             cond, truth = cond.float().contiguous(), truth.float().contiguous()
             for name, estimate in scorers.items():
-                for k, v in metrics.image_quality(estimate(cond, truth), truth, magnification_factor).items():
+                est = estimate(cond, truth)
+                est, more = est if isinstance(est, tuple) else (est, {})  # (`_score_known`: scores of its own)
+                for k, v in {**metrics.image_quality(est, truth, magnification_factor), **more}.items():
                     per_image[name].setdefault(k, []).append(v)
             n += truth.shape[0]
             if n_images is not None and n >= n_images:

@@ -102,6 +102,32 @@ DRS_API int drs_ddim_step(float* x, const float* eps_cond, const float* eps_unco
                           int t, int t_prev, float eta, const float* alpha_hat, int noise_steps, int64_t numel,
                           drs_stream_t stream);
 
+/* One reverse move t -> t_prev with known pixels (RePaint, Lugmayr et al., CVPR 2022, Algorithm 1, lines 4-8), in place on
+ * x and in one pass (csrc/inpaint.hip).  x, eps_cond, eps_uncond, noise, known: (n,C,H,W) fp32; mask: (n,mask_channels,H,W)
+ * uint8 with mask_channels 1 (one entry per pixel, shared by the C bands) or C; a nonzero entry marks a known pixel.
+ *   mask == 0:  the update of drs_sampler_step / drs_sampler_step_cfg (ddim == 0: t_prev = t - 1 is implied, `t_prev` and
+ *               `eta` are ignored, alpha / alpha_hat / beta are read) or of drs_ddim_step (ddim != 0: alpha and beta may be
+ *               NULL), guidance folded in when eps_uncond is given - the same bits as those entries.
+ *   mask != 0:  x = known                                                          for t_prev == 0,
+ *               x = sqrt(alpha_hat[t_prev]) * known + sqrt(1 - alpha_hat[t_prev]) * noise      otherwise
+ *               (q(x_t_prev | known); both factors formed in fp64 and rounded once, products and sum rounded one by one).
+ * One noise tensor serves both branches: an element uses noise[i] either as the sampler's noise or as the forward noise of
+ * its known pixel.  `noise` may be NULL only for t_prev == 0 (DRS_ERR_ARG otherwise, whatever eta is); `known` is used as
+ * given (no clamp).  16-byte accesses need H * W % 4 == 0 and 16-byte aligned pointers; any other shape runs element by
+ * element.  No atomics: two calls give the same bits.  DRS_ERR_ARG: null pointer, ddim == 0 and not 1 <= t < noise_steps,
+ * ddim != 0 and not 0 <= t_prev < t < noise_steps or eta negative or not finite; DRS_ERR_SHAPE: mask_channels not 1 or C. */
+DRS_API int drs_inpaint_step(float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale, const float* noise,
+                             const float* known, const uint8_t* mask, int n, int C, int H, int W, int mask_channels, int ddim,
+                             int t, int t_prev, float eta, const float* alpha, const float* alpha_hat, const float* beta,
+                             int noise_steps, drs_stream_t stream);
+
+/* One forward jump from level s to level t > s >= 1, in place: x = sqrt(r) * x + sqrt(1 - r) * noise with
+ * r = alpha_hat[t] / alpha_hat[s] - the closed form of the t - s single forward steps of RePaint's resampling (Algorithm 1,
+ * line 10).  r and both factors are formed in fp64 from the device table and rounded once (near t = T - 1 of the cosine
+ * schedule alpha_hat is ~1e-6).  DRS_ERR_ARG: null pointer, not 1 <= s < t < noise_steps. */
+DRS_API int drs_renoise(float* x, const float* noise, int s, int t, const float* alpha_hat, int noise_steps, int64_t numel,
+                        drs_stream_t stream);
+
 /* One Adam step over many tensors in ONE launch (torch.optim.Adam defaults: no weight decay, no amsgrad):
  *   m = lerp(m, g, 1-beta1); v = v*beta2 + (1-beta2)*g*g; p -= lr/(1-beta1^step) * m / (sqrt(v)/sqrt(1-beta2^step) + eps)
  * `table` (device): ntensors x drs_adam_tensor {p, g, m, v, n, step}; entries with g == NULL are skipped (parameters
