@@ -7,5 +7,6 @@ The C-ABI underneath is declared in include/drs_hip.h.
 """
 from .UNet_model_superres import EMA, Residual_Attention_UNet_superres  # noqa: F401
 from .train_diffusion_superres import Diffusion, launch  # noqa: F401
+from .ensemble import ensemble_scores, ensemble_statistics  # noqa: F401
 
-__all__ = ["EMA", "Residual_Attention_UNet_superres", "Diffusion", "launch"]
+__all__ = ["EMA", "Residual_Attention_UNet_superres", "Diffusion", "launch", "ensemble_scores", "ensemble_statistics"]

@@ -15,6 +15,10 @@ magnification, hence no ERGAS and no bicubic baseline).
 `--known_fraction F [--known_block B]` scores known-pixel sampling instead: every truth image is hidden under seeded blocks that
 cover the fraction F, sampled with the remaining pixels as `known` (`--resample` / `--jump`: RePaint resampling), and
 `psnr_unknown` - the PSNR over the hidden pixels alone - is reported next to the whole-image scores.
+
+`--ensemble N [--member_batch M]` draws N samples per image (`Diffusion.sample_ensemble`, M members per sampling call): the
+`model` row then scores the per-pixel ensemble mean, a `member` row the single draw reported without the flag, and one more
+line gives CRPS, spread, RMSE of the mean, the spread / skill ratio and the rank histogram (ensemble.py).
 """
 import json
 import os
@@ -57,12 +61,28 @@ def add_known_args(p):
     return p
 
 
+def add_ensemble_args(p):
+    """The ensemble flags of the command line (`main`), on top of `evaluate_arg_parser`."""
+    p.add_argument("--ensemble", type=int, default=None,
+                   help="draw this many samples (2 .. 32) per image: score their per-pixel mean as `model`, one draw as `member`, "
+                        "and report CRPS, spread, RMSE, spread / skill and the rank histogram; default: one sample per image")
+    p.add_argument("--member_batch", type=int, default=None,
+                   help="with --ensemble: members per sampling call (default: all at once)")
+    return p
+
+
+def format_ensemble(ens):
+    """The "ensemble" block of `Diffusion.evaluate(ensemble=N)` as one line."""
+    return (f"ensemble  CRPS {ens['crps']:.4g}  spread {ens['spread']:.4g}  RMSE {ens['rmse']:.4g}  "
+            f"spread/skill {ens['spread_skill']:.3f}  rank histogram {ens['rank_histogram']}")
+
+
 def format_table(scores):
     """The means of `Diffusion.evaluate` as a table: PSNR to 0.01 dB, SSIM to 4 decimals, SAM to 0.001 degrees, ERGAS to 4
     significant digits."""
     keys = list(scores["model"])
     lines = [f"{'':10s}" + "".join(f"{METRIC_FORMATS[k][0]:>14s}" for k in keys)]
-    for name in ("model", "bicubic"):
+    for name in ("model", "member", "bicubic"):
         if name in scores:  # (a score only the model has, psnr_unknown, leaves the baseline's cell empty)
             lines.append(f"{name:10s}" + "".join(
                 f"{METRIC_FORMATS[k][1].format(scores[name][k]) if k in scores[name] else '-':>14s}" for k in keys))
@@ -119,7 +139,7 @@ def main(argv=None):
     pre = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     pre.add_argument("--task", type=str, default="superres", choices=TASKS)
     task = pre.parse_known_args(argv)[0].task
-    p = add_known_args(evaluate_arg_parser(task))
+    p = add_ensemble_args(add_known_args(evaluate_arg_parser(task)))
     args = p.parse_args(argv)
     if args.multiple_gpus:
         p.error("evaluate runs in one process: --multiple_gpus is not supported")
@@ -129,6 +149,12 @@ def main(argv=None):
         p.error("--known_fraction must lie in (0, 1)")
     if args.known_fraction is None and (args.known_block is not None or args.resample != 1 or args.jump != 1):
         p.error("--known_block / --resample / --jump belong to --known_fraction")
+    if args.ensemble is not None and not 2 <= args.ensemble <= 32:
+        p.error("--ensemble must lie in 2 .. 32")
+    if args.member_batch is not None and (args.ensemble is None or args.member_batch < 1):
+        p.error("--member_batch (>= 1) belongs to --ensemble")
+    if args.ensemble is not None and args.known_fraction is not None:
+        p.error("--ensemble and --known_fraction cannot be combined")
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     snapshot = os.path.join(args.snapshot_folder_path, args.snapshot_name)
     if not os.path.exists(snapshot):
@@ -138,12 +164,16 @@ def main(argv=None):
     model, diffusion, val_loader = (_sar_setup if task == "sar_to_ndvi" else _superres_setup)(args, device, snapshot)
     model.eval()
     scores = diffusion.evaluate(model, unshuffled(val_loader), n_images=args.n_images, sampling_steps=args.sampling_steps,
-                                eta=args.eta, known_mask_fn=known_mask_fn(args), resample=args.resample, jump=args.jump)
+                                eta=args.eta, known_mask_fn=known_mask_fn(args), resample=args.resample, jump=args.jump,
+                                **({"ensemble": args.ensemble, "member_batch": args.member_batch} if args.ensemble else {}))
     print(f"{scores['n']} validation images, snapshot of epoch {diffusion.epochs_run}, "
           + (f"DDIM {args.sampling_steps} steps eta {args.eta}" if args.sampling_steps else f"{args.noise_steps - 1} ancestral steps")
           + (f", {args.known_fraction:.0%} of every image hidden, the rest known (resample {args.resample}, jump {args.jump})"
-             if args.known_fraction is not None else ""))
+             if args.known_fraction is not None else "")
+          + (f", ensembles of {args.ensemble} members" if args.ensemble else ""))
     print(format_table(scores))
+    if "ensemble" in scores:
+        print(format_ensemble(scores["ensemble"]))
     scores["args"] = {k: v for k, v in vars(args).items() if isinstance(v, (int, float, str, bool, type(None)))}
     with open(args.out, "w") as f:
         json.dump(scores, f, indent=1)

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import dist as drs_dist
-from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, base_arg_parser, check_inpaint_args,
+from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, _repeat_members, base_arg_parser, check_inpaint_args,
                                         check_sampling_args, launch_device, make_loaders, save_final_samples, train_model)
 from .UNet_model_generation import Residual_Attention_UNet_generation
 
@@ -54,6 +54,22 @@ class Diffusion(_SuperresDiffusion):
             raise ValueError("sample_known needs known and known_mask (`sample` draws a whole image)")
         return self._sample(n, model, target_class, cfg_scale, input_channels, generate_video, noise_source, sampling_steps,
                             eta, known, known_mask, resample, jump)
+
+    def sample_ensemble(self, n_members, model, target_class=None, cfg_scale=3, input_channels=3, member_batch=None,
+                        sampling_steps=None, eta=0.0, noise_source=None, known=None, known_mask=None, resample=1, jump=1):
+        """`n_members` >= 2 images per label of `target_class` (B labels; None: unconditional, B = 1), guided with
+        `cfg_scale`: (n_members, B, C, S, S).  The super-resolution `sample_ensemble` - chunks of `member_batch` members, each
+        one `sample` (with `known` / `known_mask`: `sample_known`) call on the labels repeated member-major."""
+        labels = target_class.reshape(-1) if target_class is not None else None
+        B = labels.numel() if labels is not None else 1
+        args = {"cfg_scale": cfg_scale, "input_channels": input_channels, "noise_source": noise_source,
+                "sampling_steps": sampling_steps, "eta": eta}
+
+        def chunk(m):
+            args["target_class"] = labels.repeat(m) if labels is not None else None
+            return self._ensemble_chunk(m * B, (model,), _repeat_members(known, m), _repeat_members(known_mask, m), resample,
+                                        jump, args)
+        return self._sample_members(n_members, member_batch, B, chunk)
 
     def _sample(self, n, model, target_class, cfg_scale, input_channels, generate_video, noise_source, sampling_steps, eta,
                 known=None, known_mask=None, resample=1, jump=1):

@@ -395,3 +395,72 @@ def ssim_mean(sr, hr, clamp=True, workspace=None):
                           _stream(sr.device))
     _lib.check(st, "drs_ssim")
     return out
+
+
+def _req_members(members, what, truth=None):
+    """The (N, B, C, H, W) members (and the truth) of an ensemble call.  Unlike the other wrappers these refuse a
+    non-contiguous tensor instead of copying it: the members are N times an image batch."""
+    for t, name in ((members, "members"), (truth, "truth"))[:1 if truth is None else 2]:
+        _req(t, name)
+        if not t.is_contiguous():
+            raise RuntimeError(f"{what}: {name} {tuple(t.shape)} with strides {t.stride()} must be contiguous")
+    if members.dim() != 5 or not 2 <= members.shape[0] <= 32:
+        raise RuntimeError(f"{what}: members {tuple(members.shape)} must be (N, B, C, H, W) with 2 <= N <= 32")
+    return members
+
+
+def _clamp_args(clamp, what):
+    """(flag, lo, hi) of a `clamp=None | (lo, hi)` argument."""
+    if clamp is None:
+        return 0, 0.0, 0.0
+    lo, hi = (float(v) for v in clamp)
+    if not lo <= hi:
+        raise ValueError(f"{what}: clamp=({lo}, {hi}) needs lo <= hi")
+    return 1, lo, hi
+
+
+def ensemble_stats(members, quantiles=None, clamp=None, mean=True, std=True):
+    """Per-element statistics over the member axis of `members` (N, B, C, H, W), 2 <= N <= 32: (mean, std, quantiles) as
+    (B, C, H, W), (B, C, H, W) and (Q, B, C, H, W) fp32 device tensors from one pass over the members (include/drs_hip.h:
+    drs_ensemble_stats).  `quantiles`: up to 8 values in [0, 1] (None: no quantile map, an empty list: an empty tensor);
+    `clamp=(lo, hi)` clamps the members first; `mean=False` / `std=False` leave that map out (None in its place)."""
+    lib = _lib.load()
+    members = _req_members(members, "ensemble_stats")
+    N, shape = members.shape[0], tuple(members.shape[1:])
+    flag, lo, hi = _clamp_args(clamp, "ensemble_stats")
+    qs = [float(v) for v in quantiles] if quantiles is not None else []
+    if len(qs) > 8 or any(not 0.0 <= v <= 1.0 for v in qs):
+        raise ValueError(f"ensemble_stats: quantiles {qs} must be at most 8 values in [0, 1]")
+    mean_t = torch.empty(shape, dtype=torch.float32, device=members.device) if mean else None
+    std_t = torch.empty(shape, dtype=torch.float32, device=members.device) if std else None
+    q_t = torch.empty((len(qs),) + shape, dtype=torch.float32, device=members.device) if quantiles is not None else None
+    q_arr = (C.c_double * max(len(qs), 1))(*qs)
+    with torch.cuda.device(members.device):
+        st = lib.drs_ensemble_stats(_ptr(members), _ptr(mean_t), _ptr(std_t), _ptr(q_t) if qs else None,
+                                    C.cast(q_arr, C.c_void_p), len(qs), N, *shape, flag, lo, hi, _stream(members.device))
+    _lib.check(st, "drs_ensemble_stats")
+    return mean_t, std_t, q_t
+
+
+def ensemble_scores(members, truth, clamp=None, crps_map=False):
+    """Scores of `members` (N, B, C, H, W) against `truth` (B, C, H, W): (sums, rank_histogram, crps) = a (B, 3) float64 tensor
+    of the per-image sums over C, H, W of the CRPS, of the unbiased member variance and of (mean - truth)^2, the (B, N + 1)
+    int64 counts of the elements by the rank of the truth among the members, and the (B, C, H, W) fp32 CRPS map (None
+    without `crps_map`); include/drs_hip.h: drs_ensemble_scores.  `clamp=(lo, hi)` clamps members and truth first."""
+    lib = _lib.load()
+    members = _req_members(members, "ensemble_scores", truth)
+    if tuple(truth.shape) != tuple(members.shape[1:]):
+        raise RuntimeError(f"ensemble_scores: truth {tuple(truth.shape)} must be the members' {tuple(members.shape[1:])}")
+    if truth.device != members.device:
+        raise RuntimeError(f"ensemble_scores: members are on {members.device}, truth on {truth.device}")
+    N, (B, C_, H, W) = members.shape[0], truth.shape
+    flag, lo, hi = _clamp_args(clamp, "ensemble_scores")
+    ws = torch.empty(max(lib.drs_ensemble_workspace_bytes(N, B, C_, H, W), 8), dtype=torch.uint8, device=members.device)
+    sums = torch.empty((B, 3), dtype=torch.float64, device=members.device)
+    hist = torch.empty((B, N + 1), dtype=torch.int64, device=members.device)
+    crps = torch.empty_like(truth) if crps_map else None
+    with torch.cuda.device(members.device):
+        st = lib.drs_ensemble_scores(_ptr(members), _ptr(truth), _ptr(crps), _ptr(sums), _ptr(hist), N, B, C_, H, W, flag, lo,
+                                     hi, _ptr(ws), ws.numel(), _stream(members.device))
+    _lib.check(st, "drs_ensemble_scores")
+    return sums, hist, crps

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import dist as drs_dist
-from .train_diffusion_superres import (Diffusion as _SuperresDiffusion, base_arg_parser, check_inpaint_args,
+from .train_diffusion_superres import (Diffusion as _SuperresDiffusion, _repeat_members, base_arg_parser, check_inpaint_args,
                                        check_sampling_args, launch_device, make_loaders, save_final_samples, train_model)
 from .UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
 
@@ -47,6 +47,17 @@ class Diffusion(_SuperresDiffusion):
         return self._sample(n, model, SAR_img, NDVI_channels, generate_video, noise_source, sampling_steps, eta, known,
                             known_mask, resample, jump)
 
+    def sample_ensemble(self, n_members, model, SAR_img, NDVI_channels=1, member_batch=None, sampling_steps=None, eta=0.0,
+                        noise_source=None, known=None, known_mask=None, resample=1, jump=1):
+        """`n_members` >= 2 NDVI samples per SAR image, (n_members, B, NDVI_channels, S, S), for `SAR_img` (B, SAR_channels, S, S)
+        or one (SAR_channels, S, S) image (B = 1): the super-resolution `sample_ensemble` - chunks of `member_batch` members,
+        each one `sample` (with `known` / `known_mask`: `sample_known`) call on the repeated SAR batch."""
+        sar = SAR_img if SAR_img.dim() == 4 else SAR_img.unsqueeze(0)
+        args = {"NDVI_channels": NDVI_channels, "noise_source": noise_source, "sampling_steps": sampling_steps, "eta": eta}
+        return self._sample_members(n_members, member_batch, sar.shape[0], lambda m: self._ensemble_chunk(
+            m * sar.shape[0], (model, sar.repeat(m, 1, 1, 1)), _repeat_members(known, m), _repeat_members(known_mask, m),
+            resample, jump, args))
+
     def _sample(self, n, model, SAR_img, NDVI_channels, generate_video, noise_source, sampling_steps, eta, known=None,
                 known_mask=None, resample=1, jump=1):
         check_sampling_args(self.noise_steps, sampling_steps, eta)
@@ -65,11 +76,18 @@ class Diffusion(_SuperresDiffusion):
             known=known, known_mask=known_mask, resample=resample, jump=jump)
 
     def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None, known_mask_fn=None,
-                 resample=1, jump=1):
+                 resample=1, jump=1, ensemble=None, member_batch=None):
         """PSNR / SSIM (and the spectral angle when NDVI has several bands) of `sample`'s output against the NDVI truth over
         the (SAR, NDVI) batches of `loader`: the super-resolution `evaluate` without a magnification, hence without ERGAS, and
         without a bicubic baseline; `known_mask_fn` / `resample` / `jump` as there ("psnr_unknown").
-        Returns {"model": {metric: mean}, "per_image": {"model": {metric: [...]}}, "n": N}."""
+        Returns {"model": {metric: mean}, "per_image": {"model": {metric: [...]}}, "n": N}; with `ensemble=N` (and
+        `member_batch`) also "member" and "ensemble", as the super-resolution `evaluate` does."""
+        self._check_evaluate_ensemble(ensemble, member_batch, known_mask_fn)
+
+        def members(SAR_img, NDVI_img):
+            return self.sample_ensemble(ensemble, model, SAR_img, NDVI_channels=NDVI_img.shape[1], member_batch=member_batch,
+                                        sampling_steps=sampling_steps, eta=eta, noise_source=noise_source)
+
         def sample(SAR_img, NDVI_img):
             args = {"NDVI_channels": NDVI_img.shape[1], "noise_source": noise_source, "sampling_steps": sampling_steps, "eta": eta}
             if known_mask_fn is None:
@@ -77,7 +95,7 @@ class Diffusion(_SuperresDiffusion):
                 return self.sample(SAR_img.shape[0], model, SAR_img, **args)
             return self._score_known(NDVI_img, known_mask_fn(NDVI_img), lambda known, mask: self.sample_known(
                 SAR_img.shape[0], model, SAR_img, known, mask, resample=resample, jump=jump, **args))
-        return self._evaluate(model, loader, n_images, {"model": sample}, None)
+        return self._evaluate(model, loader, n_images, {"model": sample}, None, members if ensemble else None)
 
 
 class SyntheticSarNdviDataset(torch.utils.data.Dataset):

@@ -117,6 +117,26 @@ def known_tensors(shape, known, known_mask, device):
     return known, (m != 0).to(torch.uint8).expand(n, m.shape[1], H, W).contiguous()
 
 
+def check_ensemble_args(n_members, member_batch):
+    """ValueError for an ensemble request `Diffusion.sample_ensemble` cannot run (checked before the engine is touched)."""
+    if not _is_int(n_members) or n_members < 2:
+        raise ValueError(f"n_members must be an integer >= 2, got {n_members!r} (`sample` draws a single sample)")
+    if member_batch is not None and (not _is_int(member_batch) or member_batch < 1):
+        raise ValueError(f"member_batch must be an integer >= 1, got {member_batch!r}")
+
+
+def ensemble_chunks(n_members, member_batch=None):
+    """The members per `sample` call of `Diffusion.sample_ensemble`: `member_batch` at a time (None: all at once), the rest in
+    the last call - [2, 2, 1] for 5 members in chunks of 2."""
+    m = int(n_members if member_batch is None else min(member_batch, n_members))
+    return [min(m, int(n_members) - k) for k in range(0, int(n_members), m)]
+
+
+def _repeat_members(t, m):
+    """A per-chain (B, ...) 4-D tensor repeated for m members, member-major; anything that broadcasts over the chains as is."""
+    return t.repeat(m, 1, 1, 1) if t is not None and t.dim() == 4 else t
+
+
 CHAIN_CHECK_EVERY = 128  # reverse steps between two reads of the kernels' fault word inside a sampling chain
 
 
@@ -244,6 +264,34 @@ class Diffusion:
         return self._sample(n, model, lr_img, input_channels, generate_video, noise_source, sampling_steps, eta, known,
                             known_mask, resample, jump)
 
+    def sample_ensemble(self, n_members, model, lr_img, input_channels=3, member_batch=None, sampling_steps=None, eta=0.0,
+                        noise_source=None, known=None, known_mask=None, resample=1, jump=1):
+        """`n_members` >= 2 samples per LR image: (n_members, B, C, S, S), un-clamped like `sample`, for `lr_img` (B, C, h, w)
+        or one (C, h, w) image (B = 1) - the input of `ensemble.ensemble_statistics` / `ensemble.ensemble_scores`.
+        The members are drawn `member_batch` at a time (None: all at once; `ensemble_chunks`): every chunk of m members is one
+        ordinary `sample` call with m * B chains, member-major, on the LR batch repeated m times, so memory is bounded by the
+        chunk and `noise_source` is asked chunk after chunk.  With `known` / `known_mask` ((C, S, S) / (S, S) for every chain,
+        or one per image: (B, C, S, S) / (B, 1 | C, S, S)) every chunk is a `sample_known` call instead and all members keep
+        those pixels; `resample` / `jump` as there.  `sampling_steps` / `eta` as in `sample`."""
+        lr = lr_img if lr_img.dim() == 4 else lr_img.unsqueeze(0)
+        args = {"input_channels": input_channels, "noise_source": noise_source, "sampling_steps": sampling_steps, "eta": eta}
+        return self._sample_members(n_members, member_batch, lr.shape[0], lambda m: self._ensemble_chunk(
+            m * lr.shape[0], (model, lr.repeat(m, 1, 1, 1)), _repeat_members(known, m), _repeat_members(known_mask, m), resample,
+            jump, args))
+
+    def _ensemble_chunk(self, n, head, known, known_mask, resample, jump, args):
+        """One chunk of `sample_ensemble`: `sample(n, *head, **args)`, or `sample_known` when known pixels are asked for."""
+        if known is None and known_mask is None and resample == 1 and jump == 1:
+            return self.sample(n, *head, **args)
+        return self.sample_known(n, *head, known, known_mask, resample=resample, jump=jump, **args)
+
+    @staticmethod
+    def _sample_members(n_members, member_batch, B, draw):
+        """(n_members, B, C, S, S) from `draw(m)` -> the (m * B, C, S, S) chains of m members, chunk after chunk."""
+        check_ensemble_args(n_members, member_batch)
+        x = torch.cat([draw(m) for m in ensemble_chunks(n_members, member_batch)])
+        return x.view(int(n_members), B, *x.shape[1:])
+
     def _sample(self, n, model, lr_img, input_channels, generate_video, noise_source, sampling_steps, eta, known=None,
                 known_mask=None, resample=1, jump=1):
         check_sampling_args(self.noise_steps, sampling_steps, eta)
@@ -355,7 +403,7 @@ class Diffusion:
 
     # -- image quality of the samples (metrics.py; not in the reference) ---------------------------
     def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None, baseline=True,
-                 known_mask_fn=None, resample=1, jump=1):
+                 known_mask_fn=None, resample=1, jump=1, ensemble=None, member_batch=None):
         """PSNR / SSIM / SAM / ERGAS (metrics.image_quality) of `sample`'s output against the ground truth over the (lr, hr)
         batches of `loader`, every batch sampled as one call with n = its size, until `n_images` images are scored (None: the
         whole loader).  `sampling_steps`, `eta` and `noise_source` are `sample`'s (the source is asked batch after batch).
@@ -363,7 +411,17 @@ class Diffusion:
         mask, when given, samples every batch with its truth as `known` under that mask (`resample` / `jump` as in `sample`)
         and adds "psnr_unknown", the PSNR over the hidden pixels alone (metrics.psnr_masked).  Returns
         {"model": {metric: mean}, "bicubic": {metric: mean}, "per_image": {"model": {metric: [...]}, "bicubic": ...}, "n": N}.
+        `ensemble=N` draws N members per image (`sample_ensemble`, `member_batch` as there) instead of one sample: "model"
+        then scores the ensemble MEAN, "member" member 0 - the single-draw figure reported without `ensemble` - and
+        "ensemble" holds the means of `ensemble.ensemble_scores` (crps, spread, rmse, spread_skill) and the summed
+        "rank_histogram", everything on members and truth clamped to [0, 1] like the image scores; see `_evaluate`.
         The model keeps the train / eval mode it came with."""
+        self._check_evaluate_ensemble(ensemble, member_batch, known_mask_fn)
+
+        def members(lr_img, hr_img):
+            return self.sample_ensemble(ensemble, model, lr_img, input_channels=hr_img.shape[1], member_batch=member_batch,
+                                        sampling_steps=sampling_steps, eta=eta, noise_source=noise_source)
+
         def sample(lr_img, hr_img):
             args = {"input_channels": hr_img.shape[1], "noise_source": noise_source, "sampling_steps": sampling_steps, "eta": eta}
             if known_mask_fn is None:
@@ -374,7 +432,19 @@ class Diffusion:
         scorers = {"model": sample}
         if baseline:
             scorers["bicubic"] = lambda lr_img, hr_img: hip_ops.bicubic_upsample(lr_img, self.magnification_factor)
-        return self._evaluate(model, loader, n_images, scorers, self.magnification_factor)
+        return self._evaluate(model, loader, n_images, scorers, self.magnification_factor, members if ensemble else None)
+
+    @staticmethod
+    def _check_evaluate_ensemble(ensemble, member_batch, known_mask_fn):
+        if ensemble is None:
+            if member_batch is not None:
+                raise ValueError("member_batch belongs to ensemble=N")
+            return
+        check_ensemble_args(ensemble, member_batch)
+        if ensemble > 32:
+            raise ValueError(f"ensemble={ensemble}: the ensemble kernels take at most 32 members")
+        if known_mask_fn is not None:
+            raise ValueError("evaluate: ensemble=N and known_mask_fn cannot be combined")
 
     @staticmethod
     def _score_known(truth, mask, sample_known):
@@ -385,10 +455,24 @@ class Diffusion:
         out = sample_known(truth, mask)
         return out, {"psnr_unknown": metrics.psnr_masked(out, truth, mask == 0)}
 
-    def _evaluate(self, model, loader, n_images, scorers, magnification_factor):
-        """`evaluate` for the estimators `scorers` = {name: f(conditioning batch, truth batch) -> estimate}."""
-        from . import metrics
+    def _evaluate(self, model, loader, n_images, scorers, magnification_factor, members=None):
+        """`evaluate` for the estimators `scorers` = {name: f(conditioning batch, truth batch) -> estimate}.  With `members` =
+        f(conditioning batch, truth batch) -> (N, B, C, S, S) the "model" scorer is replaced by the mean of those members,
+        "member" scores member 0 and "ensemble" collects `ensemble.ensemble_scores` of the batch."""
+        from . import ensemble, metrics
         was_training = model.training
+        ens = {}
+        if members is not None:
+            drawn = {}
+
+            def draw(cond, truth):
+                drawn["x"] = members(cond, truth)
+                ens_b = ensemble.ensemble_scores(drawn["x"], truth, clamp=(0.0, 1.0))
+                for k, v in ens_b.items():
+                    ens.setdefault(k, []).append(v)
+                return hip_ops.ensemble_stats(drawn["x"], None, (0.0, 1.0), std=False)[0]
+            scorers = {"model": draw, "member": lambda cond, truth: drawn["x"][0],
+                       **{k: f for k, f in scorers.items() if k != "model"}}
         per_image, n = {name: {} for name in scorers}, 0
         for batch in loader:
             cond, truth = self._split_batch(batch)
@@ -411,6 +495,10 @@ class Diffusion:
         per_image = {name: {k: torch.cat(v) for k, v in d.items()} for name, d in per_image.items()}
         out = {name: {k: v.mean().item() for k, v in d.items()} for name, d in per_image.items()}
         out["per_image"] = {name: {k: v.tolist() for k, v in d.items()} for name, d in per_image.items()}
+        if ens:
+            ens = {k: torch.cat(v) for k, v in ens.items()}
+            out["ensemble"] = {k: (v.sum(dim=0).tolist() if k == "rank_histogram" else v.mean().item()) for k, v in ens.items()}
+            out["per_image"]["ensemble"] = {k: v.tolist() for k, v in ens.items()}
         out["n"] = n
         return out
 

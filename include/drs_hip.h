@@ -230,6 +230,34 @@ DRS_API int drs_metrics_pointwise(const float* sr, const float* hr, double* out,
 DRS_API int drs_ssim(const float* sr, const float* hr, double* out, int B, int C, int H, int W, int clamp, void* workspace,
                      size_t workspace_bytes, drs_stream_t stream);
 
+/* Per-pixel statistics and scores of an ensemble of N samples of one conditional distribution (csrc/ensemble.hip; public
+ * API in diffusionremotesensing_amd/ensemble.py).  The reference draws its n_generations samples and plots them.
+ *   members: (N,B,C,H,W) fp32, member axis first, 2 <= N <= 32;  truth: (B,C,H,W) fp32;  clamp != 0: members and truth are
+ *   clamped to [lo, hi] as they are loaded (a NaN stays a NaN).  With the sorted members s_0 <= ... <= s_{N-1} of an element:
+ *     mean = sum(s) / N;  std = sqrt(sum (s_i - mean)^2 / (N - 1));
+ *     quantile(q): pos = q (N - 1), k = floor(pos), s_k + (pos - k) (s_{min(k+1,N-1)} - s_k)   (q = 0, 1: min and max exactly);
+ *     crps = 1/N sum |s_i - y| - 1/N^2 sum_i (2 i - N + 1) s_i;  rank = #{i : s_i < y}.
+ *   The sort and the comparisons are exact fp32; the sums, the interpolation and the CRPS are fp64 over the sorted order and
+ *   are rounded to fp32 once, at the store of a map.  An element with a NaN member (or a NaN truth, in drs_ensemble_scores)
+ *   gets NaN in its maps, is left out of the rank histogram and makes its image's three sums NaN.  Each member element is
+ *   read once; 16-byte loads need an element count divisible by 4 (B C H W for the maps, C H W for the scores) and 16-byte
+ *   aligned tensors, anything else runs element by element.  Two calls on the same inputs write the same bits.
+ * DRS_ERR_ARG: null pointer where one is not allowed, lo > hi; DRS_ERR_SHAPE: N outside 2 .. 32, Q outside 0 .. 8, a q outside
+ * [0, 1], B, C, H or W < 1, B > 65535; DRS_ERR_WORKSPACE: workspace too small.  All are reported before anything is launched.
+ *
+ * drs_ensemble_stats: mean, std (B,C,H,W) and quantiles (Q,B,C,H,W); each may be NULL (quantiles only with Q == 0) and is then
+ *   not computed.  q: Q host doubles.
+ * drs_ensemble_scores: crps_map (B,C,H,W) or NULL; sums: B x 3 doubles = per image the sum over C, H, W of crps | of the
+ *   variance sum (s_i - mean)^2 / (N - 1) | of (mean - y)^2, from the fp64 per-element values; rank_histogram: B x (N + 1)
+ *   counts of the elements of the image by rank.  Partials go through `workspace`, drs_ensemble_workspace_bytes(N, B, C, H,
+ *   W) bytes (0 for arguments the call does not take), and are added in a fixed order: no floating-point atomics. */
+DRS_API size_t drs_ensemble_workspace_bytes(int N, int B, int C, int H, int W);
+DRS_API int drs_ensemble_stats(const float* members, float* mean, float* std, float* quantiles, const double* q, int Q, int N,
+                               int B, int C, int H, int W, int clamp, float lo, float hi, drs_stream_t stream);
+DRS_API int drs_ensemble_scores(const float* members, const float* truth, float* crps_map, double* sums,
+                                int64_t* rank_histogram, int N, int B, int C, int H, int W, int clamp, float lo, float hi,
+                                void* workspace, size_t workspace_bytes, drs_stream_t stream);
+
 /* "DownBlur" degradation of the super-resolution data feed on the device, bit-exact with the Pillow calls of the
  * reference's dataset item: x = ToTensor(GaussianBlur(radius)(resize(y, (out_w, out_h), BICUBIC))), y = ToTensor(hr).
  *   hr: (N,C,H,W) uint8;  x_lr: (N,C,out_h,out_w) float32 in [0,1];  y_hr: (N,C,H,W) float32 or NULL;
