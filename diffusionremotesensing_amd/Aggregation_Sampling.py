@@ -135,7 +135,7 @@ class split_aggregation_sampling:
         Conditioning: with one chunk the LR branch is computed on the first step and reused; with several chunks the
         plan's conditioning belongs to whichever chunk ran last, so every forward recomputes it.
         The loop is `run_reverse_chain`: the fault-word reads and the range-fault roll-back act on the scene state."""
-        from .train_diffusion_superres import check_sampling_args
+        from .sampling import check_sampling_args
         d = self.diffusion_model
         check_sampling_args(d.noise_steps, sampling_steps, eta)
         if drs_dist.world_size() > 1:

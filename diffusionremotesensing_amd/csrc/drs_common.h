@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <algorithm>
+#include <cmath>
 
 #include "../../include/drs_hip.h"
 
@@ -121,6 +123,32 @@ struct DrsErr {
   } while (0)
 
 static inline int drs_cdiv(int a, int b) { return (a + b - 1) / b; }
+// grid of an element-wise grid-stride kernel: 256-thread blocks, one thread per item, 1 .. 8192 blocks
+static inline int ew_blocks(int64_t items) { return (int)std::min<int64_t>(std::max<int64_t>((items + 255) / 256, 1), 8192); }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// The argument checks of one reverse move, for every entry point that takes one (reverse_step.hip, tile_chain.hip); `what` is
+// the caller's name in the message.  Ancestral form: t -> t - 1 with t_min <= t < noise_steps; DDIM form: t -> t_prev with a
+// finite eta >= 0.  A null noise tensor is refused for the moves `needs_noise` names: none, those with sigma > 0 (eta > 0 and
+// t_prev > 0: alpha_hat decreases strictly), or all that end above level 0 (known pixels: z is their forward noise too).
+enum DrsNeedsNoise { DRS_NOISE_OPTIONAL, DRS_NOISE_IF_SIGMA, DRS_NOISE_ABOVE_0 };
+static inline int drs_check_move(const char* what, bool ddim, int t_min, int t, int t_prev, float eta, int noise_steps,
+                                 const void* noise, DrsNeedsNoise needs_noise) {
+  if (ddim) {
+    DRS_REQUIRE(0 <= t_prev && t_prev < t && t < noise_steps, DRS_ERR_ARG,
+                "%s: need 0 <= t_prev < t < noise_steps, got t_prev=%d t=%d noise_steps=%d", what, t_prev, t, noise_steps);
+    DRS_REQUIRE(std::isfinite(eta) && eta >= 0.f, DRS_ERR_ARG, "%s: eta=%g must be finite and >= 0", what, (double)eta);
+  } else {
+    DRS_REQUIRE(t_min <= t && t < noise_steps, DRS_ERR_ARG, "%s: t=%d outside [%d,%d)", what, t, t_min, noise_steps);
+    t_prev = t - 1;
+  }
+  if (needs_noise == DRS_NOISE_IF_SIGMA)
+    DRS_REQUIRE(noise || !(eta > 0.f && t_prev > 0), DRS_ERR_ARG, "%s: eta=%g > 0 and t_prev=%d > 0 need a noise tensor", what,
+                (double)eta, t_prev);
+  if (needs_noise == DRS_NOISE_ABOVE_0)
+    DRS_REQUIRE(noise || t_prev == 0, DRS_ERR_ARG, "%s: t_prev=%d > 0 needs a noise tensor", what, t_prev);
+  return DRS_OK;
+}
 // ReLU and the other activation maxima: IEEE 754-2019 `maximum` (v_maximum3_f32), which PROPAGATES a NaN like torch.relu does.
 // fmaxf (v_max_f32) returns the other operand: a NaN accumulator would leave a ReLU as 0 and the divergence it signals
 // would be gone from the output (tests/test_gpu_parity.py: test_nan_reaches_the_output).

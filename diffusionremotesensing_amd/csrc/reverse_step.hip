@@ -1,16 +1,85 @@
-// Known-pixel conditioning of the reverse chain (RePaint, Lugmayr et al., CVPR 2022, Algorithm 1): drs_inpaint_step is one
-// reverse move t -> t_prev in which the unknown pixels take the sampler's step (lines 6-7 of the algorithm) and the known
-// ones are set to the known image forward-noised to level t_prev (lines 4-5), merged by a per-element select (line 8);
-// drs_renoise is the closed form of the forward steps of its resampling (line 10).  Both are element-wise and HBM-bound:
-// every byte moves once (x, eps, z, known read, x written: 20 B per element + 1 / C B of mask), no atomics, no clamp.
+// The reverse-step entry points, element-wise and HBM-bound (every byte moves once; no atomics, no clamp): the reference's
+// ancestral update (drs_sampler_step, with guidance drs_sampler_step_cfg), the DDIM update of Diffusion.sample(sampling_steps=S)
+// (drs_ddim_step; Song et al., "Denoising Diffusion Implicit Models") and either with known pixels (drs_inpaint_step; RePaint,
+// Lugmayr et al., CVPR 2022, Algorithm 1: the unknown pixels take the sampler's step, lines 6-7, the known ones become the known
+// image forward-noised to t_prev, lines 4-5, merged by a per-element select, line 8); drs_renoise is the closed form of the
+// forward steps of its resampling (line 10).  Coefficients and per-element update: step_update.h, shared with tile_chain.hip.
 #include "drs_common.h"
 #include "step_update.h"
-#include <cmath>
+
+// The three schedule coefficients of one step are read back once per plan of T steps by the host
+// wrapper (they are T-long tables living on the device); here they arrive as device tables and a scalar t,
+// and a 1-thread prologue would cost a launch, so the kernel below reads them itself.
+__global__ __launch_bounds__(256) void sampler_step_tab_kernel(float* __restrict__ x, const float* __restrict__ eps,
+                                                               const float* __restrict__ noise, int t,
+                                                               const float* __restrict__ alpha,
+                                                               const float* __restrict__ alpha_hat,
+                                                               const float* __restrict__ beta, int64_t numel) {
+  const DrsAncestralCoef k = drs_ancestral_coef(alpha, alpha_hat, beta, t);  // (step_update.h)
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
+    float v = drs_ancestral_update(k, x[i], eps[i]);
+    if (noise) v = drs_ancestral_noise(k, v, noise[i]);
+    x[i] = v;
+  }
+}
+
+extern "C" int drs_sampler_step(float* x, const float* eps_pred, const float* noise, int t, const float* alpha,
+                                const float* alpha_hat, const float* beta, int noise_steps, int64_t numel,
+                                drs_stream_t stream) {
+  DRS_REQUIRE(x && eps_pred && alpha && alpha_hat && beta, DRS_ERR_ARG, "sampler_step: null pointer");
+  if (int st = drs_check_move("sampler_step", false, 0, t, 0, 0.f, noise_steps, noise, DRS_NOISE_OPTIONAL)) return st;
+  if (numel <= 0) return DRS_OK;
+  DRS_LAUNCH(sampler_step_tab_kernel, dim3(ew_blocks(numel)), dim3(256), 0, (hipStream_t)stream, x, eps_pred,
+                     noise, t, alpha, alpha_hat, beta, numel);
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
+}
+
+__global__ void sampler_step_cfg_kernel(float* __restrict__ x, const float* __restrict__ ec,
+                                        const float* __restrict__ eu, float w, const float* __restrict__ noise, int t,
+                                        const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
+                                        const float* __restrict__ beta, int64_t numel) {
+  // same operations, in the same order and without fused multiply-adds, as the reference expressions
+  // (train_diffusion_generation.py:239 torch.lerp, :249 the update): step_update.h
+  const DrsAncestralCoef k = drs_ancestral_coef(alpha, alpha_hat, beta, t);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
+    float v = drs_ancestral_update(k, x[i], drs_cfg_lerp(eu[i], ec[i], w));
+    if (noise) v = drs_ancestral_noise(k, v, noise[i]);
+    x[i] = v;
+  }
+}
+extern "C" int drs_sampler_step_cfg(float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                                    const float* noise, int t, const float* alpha, const float* alpha_hat,
+                                    const float* beta, int noise_steps, int64_t numel, drs_stream_t stream) {
+  DRS_REQUIRE(x && eps_cond && eps_uncond && alpha && alpha_hat && beta, DRS_ERR_ARG, "sampler_step_cfg: null pointer");
+  if (int st = drs_check_move("sampler_step_cfg", false, 0, t, 0, 0.f, noise_steps, noise, DRS_NOISE_OPTIONAL)) return st;
+  if (numel <= 0) return DRS_OK;
+  DRS_LAUNCH(sampler_step_cfg_kernel, dim3(ew_blocks(numel)), dim3(256), 0, (hipStream_t)stream, x, eps_cond,
+                     eps_uncond, cfg_scale, noise, t, alpha, alpha_hat, beta, numel);
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
+}
 
 namespace {
 
-// The unknown branch: the update of sampler_step_tab_kernel / sampler_step_cfg_kernel (small_kernels.hip) or of
-// ddim_step_kernel (ddim.hip), bit for bit.  The coefficients come from the functions of step_update.h.  The per-element
+// The coefficients (fp64, rounded once) and the per-element update live in step_update.h, shared with the tile blend.
+__global__ __launch_bounds__(256) void ddim_step_kernel(float* __restrict__ x, const float* __restrict__ ec,
+                                                        const float* __restrict__ eu, float w,
+                                                        const float* __restrict__ noise, int t, int t_prev, float eta,
+                                                        const float* __restrict__ alpha_hat, int64_t numel) {
+  const DrsDdimCoef k = drs_ddim_coef(alpha_hat, t, t_prev, eta);
+  const bool add_noise = noise != nullptr && k.has_sigma;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
+    float e = ec[i];
+    if (eu) e = drs_cfg_lerp(eu[i], e, w);
+    float v = drs_ddim_update(k, x[i], e);
+    if (add_noise) v = drs_ddim_noise(k, v, noise[i]);
+    x[i] = v;
+  }
+}
+
+// The unknown branch: the update of sampler_step_tab_kernel / sampler_step_cfg_kernel or of ddim_step_kernel
+// above, bit for bit.  The coefficients come from the functions of step_update.h.  The per-element
 // expressions of that header are plain products and sums (HIP's __fmul_rn / __fadd_rn are), which the compiler contracts
 // into fused multiply-adds as the surrounding code suggests to it - differently in this kernel's unrolled groups than in
 // the siblings' loops.  So the forms the siblings are compiled to are written out here, under contract(off):
@@ -166,16 +235,6 @@ __global__ __launch_bounds__(256) void renoise_kernel(float* __restrict__ x, con
   for (int64_t i = groups * 4 + tid; i < numel; i += stride) x[i] = jump_to(A, x[i], B, z[i]);
 }
 
-// grid-stride with a capped grid (ew_blocks of the sibling updates: at most 8192 blocks of 256 threads)
-int ew_blocks(int64_t items) {
-  int64_t b = (items + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 template <bool DDIM>
 int launch_inpaint(const InpaintArgs& a, hipStream_t s) {
   const bool wide = a.hw % 4 == 0 && aligned16(a.x) && aligned16(a.ec) && aligned16(a.known) && ((uintptr_t)a.mask & 3u) == 0 &&
@@ -192,6 +251,19 @@ int launch_inpaint(const InpaintArgs& a, hipStream_t s) {
 
 }  // namespace
 
+extern "C" int drs_ddim_step(float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                             const float* noise, int t, int t_prev, float eta, const float* alpha_hat, int noise_steps,
+                             int64_t numel, drs_stream_t stream) {
+  DRS_REQUIRE(x && eps_cond && alpha_hat, DRS_ERR_ARG, "ddim_step: null pointer");
+  if (int st = drs_check_move("ddim_step", true, 0, t, t_prev, eta, noise_steps, noise, DRS_NOISE_IF_SIGMA)) return st;
+  DRS_REQUIRE(numel >= 0, DRS_ERR_SHAPE, "ddim_step: numel=%lld", (long long)numel);
+  if (numel == 0) return DRS_OK;
+  DRS_LAUNCH(ddim_step_kernel, dim3(ew_blocks(numel)), dim3(256), 0, (hipStream_t)stream, x, eps_cond, eps_uncond,
+             cfg_scale, noise, t, t_prev, eta, alpha_hat, numel);
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
+}
+
 extern "C" int drs_inpaint_step(float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale, const float* noise,
                                 const float* known, const uint8_t* mask, int n, int C, int H, int W, int mask_channels,
                                 int ddim, int t, int t_prev, float eta, const float* alpha, const float* alpha_hat,
@@ -201,17 +273,10 @@ extern "C" int drs_inpaint_step(float* x, const float* eps_cond, const float* ep
   DRS_REQUIRE(mask_channels == 1 || mask_channels == C, DRS_ERR_SHAPE,
               "inpaint_step: a mask of %d bands for an image of %d (1 or %d)", mask_channels, C, C);
   DRS_REQUIRE((int64_t)n * C <= INT32_MAX, DRS_ERR_SHAPE, "inpaint_step: n=%d x C=%d planes", n, C);
-  if (ddim) {
-    DRS_REQUIRE(0 <= t_prev && t_prev < t && t < noise_steps, DRS_ERR_ARG,
-                "inpaint_step: need 0 <= t_prev < t < noise_steps, got t_prev=%d t=%d noise_steps=%d", t_prev, t, noise_steps);
-    DRS_REQUIRE(std::isfinite(eta) && eta >= 0.f, DRS_ERR_ARG, "inpaint_step: eta=%g must be finite and >= 0", (double)eta);
-  } else {
-    DRS_REQUIRE(alpha && beta, DRS_ERR_ARG, "inpaint_step: the ancestral form needs the alpha and beta tables");
-    DRS_REQUIRE(1 <= t && t < noise_steps, DRS_ERR_ARG, "inpaint_step: t=%d outside [1,%d)", t, noise_steps);
-    t_prev = t - 1;
-  }
+  if (!ddim) DRS_REQUIRE(alpha && beta, DRS_ERR_ARG, "inpaint_step: the ancestral form needs the alpha and beta tables");
   // above level 0 every element reads z: the unknown ones as the sampler's noise, the known ones as their forward noise
-  DRS_REQUIRE(noise || t_prev == 0, DRS_ERR_ARG, "inpaint_step: t_prev=%d > 0 needs a noise tensor", t_prev);
+  if (int st = drs_check_move("inpaint_step", ddim, 1, t, t_prev, eta, noise_steps, noise, DRS_NOISE_ABOVE_0)) return st;
+  if (!ddim) t_prev = t - 1;
   if (n == 0 || H == 0 || W == 0) return DRS_OK;
   InpaintArgs a;
   a.x = x; a.ec = eps_cond; a.eu = eps_uncond; a.w = cfg_scale; a.noise = noise; a.known = known; a.mask = mask;

@@ -1,8 +1,7 @@
 // HBM-bound and tiny kernels of the denoising path: weight packing (BatchNorm fold), layout
 // changes at the boundary, the 3-channel planar convolutions of the LR encoder, the stem,
-// bicubic up-sampling, the fused time-embedding MLP and the diffusion element-wise updates.
+// bicubic up-sampling, the fused time-embedding MLP, the forward noising and the final tile blend.
 #include "drs_common.h"
-#include "step_update.h"
 #include <algorithm>
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -125,12 +124,6 @@ __global__ void sp_add_rowvec_kernel(const char* __restrict__ src, char* __restr
     *reinterpret_cast<u32x4*>(dst + off) = oh;
     *reinterpret_cast<u32x4*>(dst + off + 64) = ol;
   }
-}
-static inline int ew_blocks(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 int drs_launch_nchw_to_nhwc(const float* src, float* dst, int N, int C, int H, int W, int dst_cs, int dst_co,
                             hipStream_t s) {
@@ -556,7 +549,7 @@ int drs_launch_time_mlp_multi(const int64_t* t, const float* inv_freq, const cha
 }
 
 // ---------------------------------------------------------------------------------------------
-// Diffusion element-wise updates (float4 streaming, HBM-bound)
+// Forward noising q(x_t | x_0) (element-wise, HBM-bound); the reverse-step updates are in reverse_step.hip
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void noise_images_kernel(const float* __restrict__ x0, const float* __restrict__ eps,
                                                            const int64_t* __restrict__ t,
@@ -582,59 +575,6 @@ extern "C" int drs_noise_images(const float* x0, const float* eps, const int64_t
   if (bx > 2048) bx = 2048;
   DRS_LAUNCH(noise_images_kernel, dim3(bx, n), dim3(256), 0, (hipStream_t)stream, x0, eps, t, alpha_hat, x_t,
                      chw);
-  DRS_CHECK_HIP(hipGetLastError());
-  return DRS_OK;
-}
-
-// The three schedule coefficients of one step are read back once per plan of T steps by the host
-// wrapper (they are T-long tables living on the device); here they arrive as device tables and a scalar t,
-// and a 1-thread prologue would cost a launch, so the kernel below reads them itself.
-__global__ __launch_bounds__(256) void sampler_step_tab_kernel(float* __restrict__ x, const float* __restrict__ eps,
-                                                               const float* __restrict__ noise, int t,
-                                                               const float* __restrict__ alpha,
-                                                               const float* __restrict__ alpha_hat,
-                                                               const float* __restrict__ beta, int64_t numel) {
-  const DrsAncestralCoef k = drs_ancestral_coef(alpha, alpha_hat, beta, t);  // (step_update.h)
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
-    float v = drs_ancestral_update(k, x[i], eps[i]);
-    if (noise) v = drs_ancestral_noise(k, v, noise[i]);
-    x[i] = v;
-  }
-}
-
-extern "C" int drs_sampler_step(float* x, const float* eps_pred, const float* noise, int t, const float* alpha,
-                                const float* alpha_hat, const float* beta, int noise_steps, int64_t numel,
-                                drs_stream_t stream) {
-  DRS_REQUIRE(x && eps_pred && alpha && alpha_hat && beta, DRS_ERR_ARG, "sampler_step: null pointer");
-  DRS_REQUIRE(t >= 0 && t < noise_steps, DRS_ERR_ARG, "sampler_step: t=%d outside [0,%d)", t, noise_steps);
-  if (numel <= 0) return DRS_OK;
-  DRS_LAUNCH(sampler_step_tab_kernel, dim3(ew_blocks(numel)), dim3(256), 0, (hipStream_t)stream, x, eps_pred,
-                     noise, t, alpha, alpha_hat, beta, numel);
-  DRS_CHECK_HIP(hipGetLastError());
-  return DRS_OK;
-}
-
-__global__ void sampler_step_cfg_kernel(float* __restrict__ x, const float* __restrict__ ec,
-                                        const float* __restrict__ eu, float w, const float* __restrict__ noise, int t,
-                                        const float* __restrict__ alpha, const float* __restrict__ alpha_hat,
-                                        const float* __restrict__ beta, int64_t numel) {
-  // same operations, in the same order and without fused multiply-adds, as the reference expressions
-  // (train_diffusion_generation.py:239 torch.lerp, :249 the update): step_update.h
-  const DrsAncestralCoef k = drs_ancestral_coef(alpha, alpha_hat, beta, t);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
-    float v = drs_ancestral_update(k, x[i], drs_cfg_lerp(eu[i], ec[i], w));
-    if (noise) v = drs_ancestral_noise(k, v, noise[i]);
-    x[i] = v;
-  }
-}
-extern "C" int drs_sampler_step_cfg(float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
-                                    const float* noise, int t, const float* alpha, const float* alpha_hat,
-                                    const float* beta, int noise_steps, int64_t numel, drs_stream_t stream) {
-  DRS_REQUIRE(x && eps_cond && eps_uncond && alpha && alpha_hat && beta, DRS_ERR_ARG, "sampler_step_cfg: null pointer");
-  DRS_REQUIRE(t >= 0 && t < noise_steps, DRS_ERR_ARG, "sampler_step_cfg: t=%d outside [0,%d)", t, noise_steps);
-  if (numel <= 0) return DRS_OK;
-  DRS_LAUNCH(sampler_step_cfg_kernel, dim3(ew_blocks(numel)), dim3(256), 0, (hipStream_t)stream, x, eps_cond,
-                     eps_uncond, cfg_scale, noise, t, alpha, alpha_hat, beta, numel);
   DRS_CHECK_HIP(hipGetLastError());
   return DRS_OK;
 }

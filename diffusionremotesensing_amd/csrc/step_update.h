@@ -1,6 +1,7 @@
-// The per-element arithmetic of the reverse-step updates, shared by every kernel that applies one: the ancestral update
-// (small_kernels.hip: drs_sampler_step, drs_sampler_step_cfg), the DDIM update (ddim.hip: drs_ddim_step) and the per-step
-// tile blend, which forms eps itself and then takes the same step (tile_chain.hip: drs_blend_step, drs_blend_step_ddim).
+// The per-element arithmetic of the reverse-step updates, shared by every kernel that applies one: the ancestral and the DDIM
+// update (reverse_step.hip: drs_sampler_step, drs_sampler_step_cfg, drs_ddim_step; drs_inpaint_step takes the coefficients)
+// and the per-step tile blend, which forms eps itself and then takes the same step (tile_chain.hip: drs_blend_step,
+// drs_blend_step_ddim).
 // One definition, so that a scene state and a tile state that see the same eps move by the same bits.
 #pragma once
 #include <hip/hip_runtime.h>

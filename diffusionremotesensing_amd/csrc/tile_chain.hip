@@ -4,7 +4,6 @@
 // and are bound by HBM traffic; neither has an atomic on its data path and neither clamps.
 #include "drs_common.h"
 #include "step_update.h"
-#include <cmath>
 
 namespace {
 
@@ -159,13 +158,6 @@ __global__ __launch_bounds__(256) void blend_step_kernel(float* __restrict__ sce
   }
 }
 
-int grid_for(int64_t items) {
-  int64_t b = (items + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 }  // namespace
 
 extern "C" int drs_gather_tiles(const float* scene, const int32_t* origins, float* tiles, int first, int count, int n, int C,
@@ -177,10 +169,10 @@ extern "C" int drs_gather_tiles(const float* scene, const int32_t* origins, floa
   DRS_REQUIRE((int64_t)count * C <= 65535, DRS_ERR_SHAPE, "gather_tiles: count=%d x C=%d planes exceed one launch", count, C);
   const unsigned planes = (unsigned)(count * C);
   if (S % 4 == 0) {
-    DRS_LAUNCH(gather_tiles_kernel<4>, dim3(grid_for((int64_t)S * S / 4), planes), dim3(256), 0, (hipStream_t)stream, scene,
+    DRS_LAUNCH(gather_tiles_kernel<4>, dim3(ew_blocks((int64_t)S * S / 4), planes), dim3(256), 0, (hipStream_t)stream, scene,
                origins, tiles, first, n, C, S, Hs, Ws);
   } else {
-    DRS_LAUNCH(gather_tiles_kernel<1>, dim3(grid_for((int64_t)S * S), planes), dim3(256), 0, (hipStream_t)stream, scene,
+    DRS_LAUNCH(gather_tiles_kernel<1>, dim3(ew_blocks((int64_t)S * S), planes), dim3(256), 0, (hipStream_t)stream, scene,
                origins, tiles, first, n, C, S, Hs, Ws);
   }
   DRS_CHECK_HIP(hipGetLastError());
@@ -194,10 +186,10 @@ int launch_blend(float* scene, const float* eps_tiles, const int32_t* origins, c
                  int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t, int t_prev, float eta, const float* alpha,
                  const float* alpha_hat, const float* beta, hipStream_t s) {
   if (S % 4 == 0 && Ws % 4 == 0) {
-    DRS_LAUNCH((blend_step_kernel<4, DDIM>), dim3(grid_for((int64_t)Hs * (Ws / 4))), dim3(256), 0, s, scene, eps_tiles,
+    DRS_LAUNCH((blend_step_kernel<4, DDIM>), dim3(ew_blocks((int64_t)Hs * (Ws / 4))), dim3(256), 0, s, scene, eps_tiles,
                origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, alpha, alpha_hat, beta);
   } else {
-    DRS_LAUNCH((blend_step_kernel<1, DDIM>), dim3(grid_for((int64_t)Hs * Ws)), dim3(256), 0, s, scene, eps_tiles, origins,
+    DRS_LAUNCH((blend_step_kernel<1, DDIM>), dim3(ew_blocks((int64_t)Hs * Ws)), dim3(256), 0, s, scene, eps_tiles, origins,
                weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, alpha, alpha_hat, beta);
   }
   DRS_CHECK_HIP(hipGetLastError());
@@ -217,7 +209,7 @@ extern "C" int drs_blend_step(float* scene, const float* eps_tiles, const int32_
                               drs_stream_t stream) {
   DRS_BLEND_REQUIRE("blend_step");
   DRS_REQUIRE(alpha && alpha_hat && beta, DRS_ERR_ARG, "blend_step: null schedule table");
-  DRS_REQUIRE(t >= 0 && t < noise_steps, DRS_ERR_ARG, "blend_step: t=%d outside [0,%d)", t, noise_steps);
+  if (int st = drs_check_move("blend_step", false, 0, t, 0, 0.f, noise_steps, noise, DRS_NOISE_OPTIONAL)) return st;
   return launch_blend<false>(scene, eps_tiles, origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, 0, 0.f, alpha,
                              alpha_hat, beta, (hipStream_t)stream);
 }
@@ -227,12 +219,7 @@ extern "C" int drs_blend_step_ddim(float* scene, const float* eps_tiles, const i
                                    int t_prev, float eta, const float* alpha_hat, int noise_steps, drs_stream_t stream) {
   DRS_BLEND_REQUIRE("blend_step_ddim");
   DRS_REQUIRE(alpha_hat, DRS_ERR_ARG, "blend_step_ddim: null schedule table");
-  DRS_REQUIRE(0 <= t_prev && t_prev < t && t < noise_steps, DRS_ERR_ARG,
-              "blend_step_ddim: need 0 <= t_prev < t < noise_steps, got t_prev=%d t=%d noise_steps=%d", t_prev, t, noise_steps);
-  DRS_REQUIRE(std::isfinite(eta) && eta >= 0.f, DRS_ERR_ARG, "blend_step_ddim: eta=%g must be finite and >= 0", (double)eta);
-  // sigma > 0 exactly when eta > 0 and t_prev > 0 (alpha_hat decreases strictly along the schedule)
-  DRS_REQUIRE(noise || !(eta > 0.f && t_prev > 0), DRS_ERR_ARG,
-              "blend_step_ddim: eta=%g > 0 and t_prev=%d > 0 need a noise tensor", (double)eta, t_prev);
+  if (int st = drs_check_move("blend_step_ddim", true, 0, t, t_prev, eta, noise_steps, noise, DRS_NOISE_IF_SIGMA)) return st;
   return launch_blend<true>(scene, eps_tiles, origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, nullptr,
                             alpha_hat, nullptr, (hipStream_t)stream);
 }

@@ -14,8 +14,9 @@ import torch
 import torch.nn as nn
 
 from .. import dist as drs_dist
-from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, _repeat_members, base_arg_parser, check_inpaint_args,
-                                        check_sampling_args, launch_device, make_loaders, save_final_samples, train_model)
+from ..sampling import _repeat_members, asks_for_known_pixels, check_inpaint_args, check_sampling_args
+from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, base_arg_parser, launch_device, make_loaders,
+                                        save_final_samples, train_model)
 from .UNet_model_generation import Residual_Attention_UNet_generation
 
 
@@ -50,8 +51,7 @@ class Diffusion(_SuperresDiffusion):
                      generate_video=False, noise_source=None, sampling_steps=None, eta=0.0):
         """Class-conditional inpainting: `sample` with known pixels, as in the super-resolution `sample_known` (the guidance
         is folded into the same update kernel)."""
-        if known is None and known_mask is None and resample == 1 and jump == 1:
-            raise ValueError("sample_known needs known and known_mask (`sample` draws a whole image)")
+        asks_for_known_pixels(known, known_mask, resample, jump, required=True)
         return self._sample(n, model, target_class, cfg_scale, input_channels, generate_video, noise_source, sampling_steps,
                             eta, known, known_mask, resample, jump)
 

@@ -28,6 +28,17 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _req_state(x, op, name="x"):  # the tensor an in-place step updates is used as it is
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
+        raise RuntimeError(f"{op}: {name} must be a contiguous fp32 ROCm tensor (no CPU fallback)")
+
+
+def _req_numel(op, x, named, state="x"):  # named = ((name, tensor or None), ...): as many elements as the state x
+    for name, t in named:
+        if t is not None and t.numel() != x.numel():
+            raise RuntimeError(f"{op}: {name} has {t.numel()} elements, {state} has {x.numel()}")
+
+
 def conv2d(x, w, b=None, stride=1, padding=0, transposed=False, output_padding=0, relu=False, impl="direct"):
     """F.conv2d / F.conv_transpose2d for the flavours the UNet uses (NCHW, fp32)."""
     lib = _lib.load()
@@ -148,8 +159,7 @@ def timestep_table(noise_steps, n, device):
 def sampler_step_(x, eps_pred, noise, t, alpha, alpha_hat, beta):
     """In-place ancestral update of x for the scalar timestep t (noise may be None)."""
     lib = _lib.load()
-    if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
-        raise RuntimeError("sampler_step_: x must be a contiguous fp32 ROCm tensor (no CPU fallback)")
+    _req_state(x, "sampler_step_")
     eps_pred = _req(eps_pred, "eps_pred")
     noise = _req(noise, "noise") if noise is not None else None
     with torch.cuda.device(x.device):
@@ -163,8 +173,7 @@ def sampler_step_cfg_(x, eps_cond, eps_uncond, cfg_scale, noise, t, alpha, alpha
     """In-place ancestral update with eps = torch.lerp(eps_uncond, eps_cond, cfg_scale) folded in
     (reference generate_new_imgs/train_diffusion_generation.py:236-249)."""
     lib = _lib.load()
-    if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
-        raise RuntimeError("sampler_step_cfg_: x must be a contiguous fp32 ROCm tensor (no CPU fallback)")
+    _req_state(x, "sampler_step_cfg_")
     eps_cond = _req(eps_cond, "eps_cond")
     eps_uncond = _req(eps_uncond, "eps_uncond")
     noise = _req(noise, "noise") if noise is not None else None
@@ -180,15 +189,12 @@ def ddim_step_(x, eps_cond, noise, t, t_prev, eta, alpha_hat, eps_uncond=None, c
     """In-place DDIM update of x from timestep t to t_prev (include/drs_hip.h: drs_ddim_step); with `eps_uncond` the
     prediction is torch.lerp(eps_uncond, eps_cond, cfg_scale).  `noise` may be None when eta == 0 or t_prev == 0."""
     lib = _lib.load()
-    if not (x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
-        raise RuntimeError("ddim_step_: x must be a contiguous fp32 ROCm tensor (no CPU fallback)")
+    _req_state(x, "ddim_step_")
     eps_cond = _req(eps_cond, "eps_cond")
     eps_uncond = _req(eps_uncond, "eps_uncond") if eps_uncond is not None else None
     noise = _req(noise, "noise") if noise is not None else None
     alpha_hat = _req(alpha_hat, "alpha_hat")
-    for name, t_ in (("eps_cond", eps_cond), ("eps_uncond", eps_uncond), ("noise", noise)):
-        if t_ is not None and t_.numel() != x.numel():
-            raise RuntimeError(f"ddim_step_: {name} has {t_.numel()} elements, x has {x.numel()}")
+    _req_numel("ddim_step_", x, (("eps_cond", eps_cond), ("eps_uncond", eps_uncond), ("noise", noise)))
     with torch.cuda.device(x.device):
         st = lib.drs_ddim_step(_ptr(x), _ptr(eps_cond), _ptr(eps_uncond), float(cfg_scale), _ptr(noise), int(t),
                                int(t_prev), float(eta), _ptr(alpha_hat), alpha_hat.numel(), x.numel(), _stream(x.device))
@@ -203,8 +209,7 @@ def inpaint_step_(x, eps_cond, noise, known, mask, t, *, alpha_hat, alpha=None, 
     and beta) or of `ddim_step_` (t -> t_prev with eta), elsewhere `known` forward-noised to the level reached with the same
     `noise`, or `known` itself at level 0.  `noise` may be None only when the move ends at level 0."""
     lib = _lib.load()
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
-        raise RuntimeError("inpaint_step_: x must be a contiguous fp32 ROCm tensor (no CPU fallback)")
+    _req_state(x, "inpaint_step_")
     if x.dim() != 4:
         raise RuntimeError(f"inpaint_step_: x must be (n, C, H, W), got {tuple(x.shape)}")
     eps_cond = _req(eps_cond, "eps_cond")
@@ -213,9 +218,7 @@ def inpaint_step_(x, eps_cond, noise, known, mask, t, *, alpha_hat, alpha=None, 
     known = _req(known, "known")
     mask = _req(mask, "mask", torch.uint8)
     alpha_hat = _req(alpha_hat, "alpha_hat")
-    for name, t_ in (("eps_cond", eps_cond), ("eps_uncond", eps_uncond), ("noise", noise), ("known", known)):
-        if t_ is not None and t_.numel() != x.numel():
-            raise RuntimeError(f"inpaint_step_: {name} has {t_.numel()} elements, x has {x.numel()}")
+    _req_numel("inpaint_step_", x, (("eps_cond", eps_cond), ("eps_uncond", eps_uncond), ("noise", noise), ("known", known)))
     n, C_, H, W = x.shape
     if mask.dim() != 4 or mask.shape[0] != n or tuple(mask.shape[2:]) != (H, W):
         raise RuntimeError(f"inpaint_step_: mask {tuple(mask.shape)} must be ({n}, 1 or {C_}, {H}, {W})")
@@ -234,17 +237,31 @@ def inpaint_step_(x, eps_cond, noise, known, mask, t, *, alpha_hat, alpha=None, 
 def renoise_(x, noise, s, t, alpha_hat):
     """In-place forward jump of x from level s to level t > s >= 1 with `noise` (include/drs_hip.h: drs_renoise)."""
     lib = _lib.load()
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_contiguous() and x.dtype == torch.float32):
-        raise RuntimeError("renoise_: x must be a contiguous fp32 ROCm tensor (no CPU fallback)")
+    _req_state(x, "renoise_")
     noise = _req(noise, "noise")
     alpha_hat = _req(alpha_hat, "alpha_hat")
-    if noise.numel() != x.numel():
-        raise RuntimeError(f"renoise_: noise has {noise.numel()} elements, x has {x.numel()}")
+    _req_numel("renoise_", x, (("noise", noise),))
     with torch.cuda.device(x.device):
         st = lib.drs_renoise(_ptr(x), _ptr(noise), int(s), int(t), _ptr(alpha_hat), alpha_hat.numel(), x.numel(),
                              _stream(x.device))
     _lib.check(st, "drs_renoise")
     return x
+
+
+def reverse_step_(x, eps, noise, t, t_prev, *, alpha, alpha_hat, beta, ddim=False, eta=0.0, eps_uncond=None, cfg_scale=0.0,
+                  known=None, known_mask=None):
+    """One reverse move t -> t_prev of x, in place, by the wrapper that takes this kind of move: `inpaint_step_` with `known`
+    / `known_mask`, else `ddim_step_` on a DDIM chain (`ddim`; t_prev and eta count there only) and `sampler_step_` /
+    `sampler_step_cfg_` (with `eps_uncond`) on the ancestral one, where t_prev is t - 1."""
+    guided = {"eps_uncond": eps_uncond, "cfg_scale": cfg_scale}
+    if known is not None:
+        form = {"t_prev": t_prev, "eta": eta} if ddim else {"alpha": alpha, "beta": beta}
+        return inpaint_step_(x, eps, noise, known, known_mask, t, alpha_hat=alpha_hat, **guided, **form)
+    if ddim:
+        return ddim_step_(x, eps, noise, t, t_prev, eta, alpha_hat, **(guided if eps_uncond is not None else {}))
+    if eps_uncond is None:
+        return sampler_step_(x, eps, noise, t, alpha, alpha_hat, beta)
+    return sampler_step_cfg_(x, eps, eps_uncond, cfg_scale, noise, t, alpha, alpha_hat, beta)
 
 
 def aggregate_tiles(tiles, origins, weight, height, width):
@@ -318,8 +335,7 @@ def blend_step_(scene, eps_tiles, origins, weight, noise, t, *, alpha_hat, alpha
     (t -> t_prev with eta).  `noise` (scene shape) may be None as for those.  `uncovered`: optional int32 device counter
     that is increased by the number of pixels no tile covers (include/drs_hip.h: drs_blend_step)."""
     lib = _lib.load()
-    if not (isinstance(scene, torch.Tensor) and scene.is_cuda and scene.is_contiguous() and scene.dtype == torch.float32):
-        raise RuntimeError("blend_step_: scene must be a contiguous fp32 ROCm tensor (no CPU fallback)")
+    _req_state(scene, "blend_step_", "scene")
     eps_tiles = _req(eps_tiles, "eps_tiles")
     origins = _req_origins(origins, "origins")
     weight = _req(weight, "weight")
@@ -334,8 +350,7 @@ def blend_step_(scene, eps_tiles, origins, weight, noise, t, *, alpha_hat, alpha
     if eps_tiles.shape[0] < n or eps_tiles.shape[1] != C_ or eps_tiles.shape[3] != S or tuple(weight.shape) != (S, S):
         raise RuntimeError(f"blend_step_: eps_tiles {tuple(eps_tiles.shape)}, weight {tuple(weight.shape)}, {n} origins, "
                            f"scene {tuple(scene.shape)}")
-    if noise is not None and noise.numel() != scene.numel():
-        raise RuntimeError(f"blend_step_: noise has {noise.numel()} elements, scene has {scene.numel()}")
+    _req_numel("blend_step_", scene, (("noise", noise),), "scene")
     if uncovered is not None:
         uncovered = _req(uncovered, "uncovered", torch.int32)
     with torch.cuda.device(scene.device):

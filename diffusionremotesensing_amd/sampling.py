@@ -1,0 +1,221 @@
+"""The reverse chain all three samplers and the tiler share: its moves (`chain_moves`), the argument checks, the loop with its
+fault checks and roll-back (`run_reverse_chain`) and the chain itself (`sample_chain`), whose one `step` takes every move."""
+import math
+import sys
+from typing import NamedTuple
+
+import torch
+
+from . import _lib, hip_ops
+
+
+def ddim_timesteps(noise_steps, sampling_steps):
+    """The S timesteps a DDIM chain visits, descending: [1 + (k * (T - 2)) // (S - 1) for k in range(S)] reversed, or
+    [T - 1] for S = 1 (integer arithmetic only).  S = T - 1 visits the ancestral chain's T - 1 .. 1; the step after the
+    last entry goes to timestep 0."""
+    T, S = int(noise_steps), int(sampling_steps)
+    if not 1 <= S <= T - 1:
+        raise ValueError(f"sampling_steps={sampling_steps} outside [1, noise_steps - 1 = {T - 1}]")
+    if S == 1:
+        return [T - 1]
+    return [1 + (k * (T - 2)) // (S - 1) for k in reversed(range(S))]
+
+
+def check_sampling_args(noise_steps, sampling_steps, eta):
+    """ValueError for a DDIM request `Diffusion.sample` cannot run (checked before the engine is touched)."""
+    if sampling_steps is not None:
+        if isinstance(sampling_steps, bool) or int(sampling_steps) != sampling_steps:
+            raise ValueError(f"sampling_steps must be an integer, got {sampling_steps!r}")
+        if not 1 <= sampling_steps <= noise_steps - 1:
+            raise ValueError(f"sampling_steps={sampling_steps} outside [1, noise_steps - 1 = {noise_steps - 1}]")
+    if not (math.isfinite(eta) and eta >= 0):
+        raise ValueError(f"eta={eta} must be finite and >= 0")
+
+
+def ddim_chain_noise(eta, t, t_prev, shape, x, noise_source):
+    """Noise of the DDIM move t -> t_prev: drawn only when sigma > 0 (eta > 0 and t_prev > 0), from `noise_source(t, shape)`
+    or torch.randn_like(x); None otherwise, so an eta = 0 chain draws x_T and nothing else."""
+    if eta > 0 and t_prev > 0:
+        return noise_source(t, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
+    return None
+
+
+def inpaint_schedule(S, resample=1, jump=1):
+    """The moves of a chain with known pixels (RePaint, Lugmayr et al., CVPR 2022, Algorithm 1) over the positions 0 .. S of
+    its level list (position p holds level L[p]: the ancestral T - 1 .. 1 or the `ddim_timesteps`, then 0): a list of
+    (p, q) pairs, q = p + 1 for a reverse move and q = p - jump for a forward jump.  The walk goes down from 0 to S; on its
+    FIRST arrival at a position p with p % jump == 0 and 0 < p < S it goes, `resample - 1` times, one jump up to p - jump
+    and `jump` moves down again.  That is S + (resample - 1) * jump * ((S - 1) // jump) moves down and (resample - 1) *
+    ((S - 1) // jump) up, none of them up from level 0; resample = 1 is the plain replacement chain whatever `jump` is."""
+    moves, seen, p = [], set(), 0
+    while p < S:
+        moves.append((p, p + 1))
+        p += 1
+        if 0 < p < S and p % jump == 0 and p not in seen:
+            seen.add(p)
+            for _ in range(resample - 1):
+                moves.append((p, p - jump))
+                moves.extend((q, q + 1) for q in range(p - jump, p))
+    return moves
+
+
+def _is_int(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and int(v) == v
+
+
+def check_inpaint_args(shape, known, known_mask, resample=1, jump=1):
+    """ValueError for a known-pixel request `Diffusion.sample` cannot run on chains of `shape` = (n, C, S, S) (checked before
+    the engine is touched): `known` without `known_mask` or the reverse, a `known` that does not broadcast to (n, C, S, S) or
+    a mask that does not to (n, 1 | C, S, S), `resample` / `jump` that are no integers >= 1, or that are set without `known`."""
+    for name, v in (("resample", resample), ("jump", jump)):
+        if not _is_int(v) or v < 1:
+            raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    if (known is None) != (known_mask is None):
+        raise ValueError("known and known_mask go together: got " + ("known without known_mask" if known_mask is None
+                                                                      else "known_mask without known"))
+    if known is None:
+        if resample != 1 or jump != 1:
+            raise ValueError(f"resample={resample} / jump={jump} belong to a chain with known pixels: pass known and known_mask")
+        return
+    n, C, H, W = shape
+    ks, ms = tuple(known.shape), tuple(known_mask.shape)
+    if ks not in ((C, H, W), (n, C, H, W)):
+        raise ValueError(f"known {ks} does not broadcast to {(n, C, H, W)}: pass (C, S, S) or (n, C, S, S)")
+    if ms not in ((H, W), (1, H, W), (C, H, W), (n, 1, H, W), (n, C, H, W)):
+        raise ValueError(f"known_mask {ms} does not broadcast to {(n, 1, H, W)} or {(n, C, H, W)}")
+
+
+def known_tensors(shape, known, known_mask, device):
+    """(`known` as (n, C, S, S) fp32, `known_mask` as (n, 1 | C, S, S) uint8 with 1 = known) on the device, for the update
+    kernel: bool, uint8 or {0, 1} float masks, broadcast over the n chains, converted once per chain."""
+    n, C, H, W = shape
+    known = known.to(device=device, dtype=torch.float32).expand(n, C, H, W).contiguous()
+    m = known_mask.to(device)
+    if m.dim() == 2:
+        m = m.unsqueeze(0)
+    if m.dim() == 3:
+        m = m.unsqueeze(0)
+    return known, (m != 0).to(torch.uint8).expand(n, m.shape[1], H, W).contiguous()
+
+
+def check_ensemble_args(n_members, member_batch):
+    """ValueError for an ensemble request `Diffusion.sample_ensemble` cannot run (checked before the engine is touched)."""
+    if not _is_int(n_members) or n_members < 2:
+        raise ValueError(f"n_members must be an integer >= 2, got {n_members!r} (`sample` draws a single sample)")
+    if member_batch is not None and (not _is_int(member_batch) or member_batch < 1):
+        raise ValueError(f"member_batch must be an integer >= 1, got {member_batch!r}")
+
+
+def ensemble_chunks(n_members, member_batch=None):
+    """The members per `sample` call of `Diffusion.sample_ensemble`: `member_batch` at a time (None: all at once), the rest in
+    the last call - [2, 2, 1] for 5 members in chunks of 2."""
+    m = int(n_members if member_batch is None else min(member_batch, n_members))
+    return [min(m, int(n_members) - k) for k in range(0, int(n_members), m)]
+
+
+def _repeat_members(t, m):
+    """A per-chain (B, ...) 4-D tensor repeated for m members, member-major; anything that broadcasts over the chains as is."""
+    return t.repeat(m, 1, 1, 1) if t is not None and t.dim() == 4 else t
+
+
+CHAIN_CHECK_EVERY = 128  # reverse steps between two reads of the kernels' fault word inside a sampling chain
+
+
+def run_reverse_chain(engine, x, noise_steps, step, frames=None, every=CHAIN_CHECK_EVERY, timesteps=None):
+    """The reverse loop of `Diffusion.sample` (reference :234-251): `step(i)` performs reverse step i in place on x, for i =
+    noise_steps - 1 .. 1, or for every entry of the list `timesteps` (the descending timesteps of a DDIM chain, or the moves of
+    a chain with known pixels: `inpaint_schedule`).  Every `every` steps (and at
+    the end) the fault word of the wave-specialised kernels is read (one 4-byte copy + a stream synchronisation: ~0.1 ms per
+    128 steps of ~1.2 ms each).  A protocol fault raises.  DRS_ERR_RANGE - an activation left the range of the FL arithmetic's
+    fp16 main operand (csrc/conv_mfma_fl.hip; chains of UNTRAINED weights do that, their amplitude grows without bound) - has
+    already switched the plan to the split-bf16 kernels: the chain goes back to its last checkpoint (x as of the last clean
+    check, a position in the step list) and continues from there."""
+    seq = range(noise_steps - 1, 0, -1) if timesteps is None else list(timesteps)
+    k = 0
+    ckpt_k, ckpt_x, ckpt_frames, since = k, x.clone(), 0, 0
+    while k < len(seq):
+        step(seq[k])
+        k += 1
+        since += 1
+        if since >= every or k == len(seq):
+            since = 0
+            try:
+                engine.check_faults()
+            except _lib.RangeFault as e:
+                print(f"[drs] {e}\n[drs] resuming the chain at step {seq[ckpt_k]} on the split-bf16 kernels", file=sys.stderr)
+                x.copy_(ckpt_x)
+                k = ckpt_k
+                if frames is not None:
+                    del frames[ckpt_frames:]
+                continue
+            ckpt_k = k
+            ckpt_x.copy_(x)
+            ckpt_frames = len(frames) if frames is not None else 0
+    return x
+
+
+def asks_for_known_pixels(known, known_mask, resample, jump, required=False):
+    """Whether a request names anything of a chain with known pixels; ValueError if it must (`sample_known`) and does not."""
+    asks = not (known is None and known_mask is None and resample == 1 and jump == 1)
+    if required and not asks:
+        raise ValueError("sample_known needs known and known_mask (`sample` draws a whole image)")
+    return asks
+
+
+class Move(NamedTuple):
+    """A reverse step (t_to < t) or a forward jump (t_to > t) of a chain; `run_reverse_chain`'s roll-back line prints its t."""
+    t: int
+    t_to: int
+
+    def __str__(self):
+        return str(self.t)
+
+
+def chain_moves(noise_steps, sampling_steps=None, resample=1, jump=1):
+    """The moves of a chain, in order, over its levels: the ancestral T - 1 .. 1 (`sampling_steps` None) or the `ddim_timesteps`,
+    then 0.  Without resampling it steps from each level to the next; `resample` / `jump` walk them as `inpaint_schedule` says."""
+    levels = (ddim_timesteps(noise_steps, sampling_steps) if sampling_steps is not None
+              else list(range(int(noise_steps) - 1, 0, -1))) + [0]
+    return [Move(levels[p], levels[q]) for p, q in inpaint_schedule(len(levels) - 1, resample, jump)]
+
+
+def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=None, sampling_steps=None, eta=0.0,
+                 cfg_scale=0.0, update=None, known=None, known_mask=None, resample=1, jump=1, frames=None):
+    """The reverse chain from x_T to the returned x_0 (arguments: `Diffusion._sample_chain`).  `schedule` holds noise_steps, the
+    alpha / alpha_hat / beta tables and their device (a Diffusion); `frames`, when a list, gets a copy of x after every move.
+    One `step` takes every move of `chain_moves`.  A forward jump to level t_to is one `renoise_` with the draw for t_to.  A
+    reverse move t -> t_to is one `predict`, at most one draw - for t - and the `update` hook or one `hip_ops.reverse_step_`;
+    it draws iff it ends above level 0 and adds noise there: always on the ancestral chain and with known pixels (whose
+    forward noise it also is), on a DDIM chain without them only when eta > 0."""
+    ddim = sampling_steps is not None
+    with torch.no_grad():
+        x = noise_source(schedule.noise_steps, shape) if noise_source is not None else torch.randn(shape)  # (CPU generator, :230)
+        x = x.to(schedule.device).contiguous()
+        t_rows = hip_ops.timestep_table(schedule.noise_steps, table_rows, x.device)
+        if known is not None:
+            known, known_mask = known_tensors(shape, known, known_mask, x.device)
+        state = {"first": True}  # (not set again after a roll-back)
+
+        def draw(t):
+            return noise_source(t, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
+
+        def step(move):
+            t, t_to = move
+            if t_to > t:
+                hip_ops.renoise_(x, draw(t_to), t, t_to, schedule.alpha_hat)
+            else:
+                eps = predict(engine, x, t_rows[t], state["first"])
+                state["first"] = False
+                eps, eps_uncond = eps if isinstance(eps, tuple) else (eps, None)
+                noise = draw(t) if t_to > 0 and (known is not None or not ddim or eta > 0) else None
+                if update is not None:
+                    update(x, eps, noise, t, t_to if ddim else None)
+                else:
+                    hip_ops.reverse_step_(x, eps, noise, t, t_to, alpha=schedule.alpha, alpha_hat=schedule.alpha_hat,
+                                          beta=schedule.beta, ddim=ddim, eta=eta, eps_uncond=eps_uncond, cfg_scale=cfg_scale,
+                                          known=known, known_mask=known_mask)
+            if frames is not None:
+                frames.append(x.clone())
+        run_reverse_chain(engine, x, schedule.noise_steps, step, frames,
+                          timesteps=chain_moves(schedule.noise_steps, sampling_steps, resample, jump))
+    return x

@@ -13,8 +13,9 @@ import torch
 import torch.nn as nn
 
 from . import dist as drs_dist
-from .train_diffusion_superres import (Diffusion as _SuperresDiffusion, _repeat_members, base_arg_parser, check_inpaint_args,
-                                       check_sampling_args, launch_device, make_loaders, save_final_samples, train_model)
+from .sampling import _repeat_members, asks_for_known_pixels, check_inpaint_args, check_sampling_args
+from .train_diffusion_superres import (Diffusion as _SuperresDiffusion, base_arg_parser, launch_device, make_loaders,
+                                       save_final_samples, train_model)
 from .UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
 
 
@@ -42,8 +43,7 @@ class Diffusion(_SuperresDiffusion):
                      noise_source=None, sampling_steps=None, eta=0.0):
         """`sample` with known NDVI pixels, as in the super-resolution `sample_known`: the pixels that are valid (no cloud or
         shadow over them) are kept and only the others are sampled."""
-        if known is None and known_mask is None and resample == 1 and jump == 1:
-            raise ValueError("sample_known needs known and known_mask (`sample` draws a whole image)")
+        asks_for_known_pixels(known, known_mask, resample, jump, required=True)
         return self._sample(n, model, SAR_img, NDVI_channels, generate_video, noise_source, sampling_steps, eta, known,
                             known_mask, resample, jump)
 
@@ -82,20 +82,9 @@ class Diffusion(_SuperresDiffusion):
         without a bicubic baseline; `known_mask_fn` / `resample` / `jump` as there ("psnr_unknown").
         Returns {"model": {metric: mean}, "per_image": {"model": {metric: [...]}}, "n": N}; with `ensemble=N` (and
         `member_batch`) also "member" and "ensemble", as the super-resolution `evaluate` does."""
-        self._check_evaluate_ensemble(ensemble, member_batch, known_mask_fn)
-
-        def members(SAR_img, NDVI_img):
-            return self.sample_ensemble(ensemble, model, SAR_img, NDVI_channels=NDVI_img.shape[1], member_batch=member_batch,
-                                        sampling_steps=sampling_steps, eta=eta, noise_source=noise_source)
-
-        def sample(SAR_img, NDVI_img):
-            args = {"NDVI_channels": NDVI_img.shape[1], "noise_source": noise_source, "sampling_steps": sampling_steps, "eta": eta}
-            if known_mask_fn is None:
-                check_inpaint_args(tuple(NDVI_img.shape), None, None, resample, jump)
-                return self.sample(SAR_img.shape[0], model, SAR_img, **args)
-            return self._score_known(NDVI_img, known_mask_fn(NDVI_img), lambda known, mask: self.sample_known(
-                SAR_img.shape[0], model, SAR_img, known, mask, resample=resample, jump=jump, **args))
-        return self._evaluate(model, loader, n_images, {"model": sample}, None, members if ensemble else None)
+        sample, members = self._evaluate_samplers(model, "NDVI_channels", sampling_steps, eta, noise_source, known_mask_fn,
+                                                  resample, jump, ensemble, member_batch)
+        return self._evaluate(model, loader, n_images, {"model": sample}, None, members)
 
 
 class SyntheticSarNdviDataset(torch.utils.data.Dataset):

@@ -13,165 +13,20 @@ Deliberately different (documented in DESIGN.md):
     DistributedDataParallel(find_unused_parameters=True) (:658).
 """
 import copy
-import math
 import os
-import sys
 
 import torch
 import torch.nn as nn
 
 from . import dist as drs_dist
-from . import _lib, hip_ops
+from . import hip_ops
 from .optim import FusedAdam
+from .sampling import (CHAIN_CHECK_EVERY, _is_int, _repeat_members, asks_for_known_pixels,  # noqa: F401 - re-exported
+                       check_ensemble_args, check_inpaint_args, check_sampling_args, ddim_chain_noise, ddim_timesteps,
+                       ensemble_chunks, inpaint_schedule, known_tensors, run_reverse_chain, sample_chain)
 from .UNet_model_superres import EMA, Residual_Attention_UNet_superres
 
 _DEGRADATIONS = ("downblur", "bsrgan", "downblurnoise")
-
-
-def ddim_timesteps(noise_steps, sampling_steps):
-    """The S timesteps a DDIM chain visits, descending: [1 + (k * (T - 2)) // (S - 1) for k in range(S)] reversed, or
-    [T - 1] for S = 1 (integer arithmetic only).  S = T - 1 visits the ancestral chain's T - 1 .. 1; the step after the
-    last entry goes to timestep 0."""
-    T, S = int(noise_steps), int(sampling_steps)
-    if not 1 <= S <= T - 1:
-        raise ValueError(f"sampling_steps={sampling_steps} outside [1, noise_steps - 1 = {T - 1}]")
-    if S == 1:
-        return [T - 1]
-    return [1 + (k * (T - 2)) // (S - 1) for k in reversed(range(S))]
-
-
-def check_sampling_args(noise_steps, sampling_steps, eta):
-    """ValueError for a DDIM request `Diffusion.sample` cannot run (checked before the engine is touched)."""
-    if sampling_steps is not None:
-        if isinstance(sampling_steps, bool) or int(sampling_steps) != sampling_steps:
-            raise ValueError(f"sampling_steps must be an integer, got {sampling_steps!r}")
-        if not 1 <= sampling_steps <= noise_steps - 1:
-            raise ValueError(f"sampling_steps={sampling_steps} outside [1, noise_steps - 1 = {noise_steps - 1}]")
-    if not (math.isfinite(eta) and eta >= 0):
-        raise ValueError(f"eta={eta} must be finite and >= 0")
-
-
-def ddim_chain_noise(eta, t, t_prev, shape, x, noise_source):
-    """Noise of the DDIM move t -> t_prev: drawn only when sigma > 0 (eta > 0 and t_prev > 0), from `noise_source(t, shape)`
-    or torch.randn_like(x); None otherwise, so an eta = 0 chain draws x_T and nothing else."""
-    if eta > 0 and t_prev > 0:
-        return noise_source(t, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
-    return None
-
-
-def inpaint_schedule(S, resample=1, jump=1):
-    """The moves of a chain with known pixels (RePaint, Lugmayr et al., CVPR 2022, Algorithm 1) over the positions 0 .. S of
-    its level list (position p holds level L[p]: the ancestral T - 1 .. 1 or the `ddim_timesteps`, then 0): a list of
-    (p, q) pairs, q = p + 1 for a reverse move and q = p - jump for a forward jump.  The walk goes down from 0 to S; on its
-    FIRST arrival at a position p with p % jump == 0 and 0 < p < S it goes, `resample - 1` times, one jump up to p - jump
-    and `jump` moves down again.  That is S + (resample - 1) * jump * ((S - 1) // jump) moves down and (resample - 1) *
-    ((S - 1) // jump) up, none of them up from level 0; resample = 1 is the plain replacement chain whatever `jump` is."""
-    moves, seen, p = [], set(), 0
-    while p < S:
-        moves.append((p, p + 1))
-        p += 1
-        if 0 < p < S and p % jump == 0 and p not in seen:
-            seen.add(p)
-            for _ in range(resample - 1):
-                moves.append((p, p - jump))
-                moves.extend((q, q + 1) for q in range(p - jump, p))
-    return moves
-
-
-def _is_int(v):
-    return not isinstance(v, bool) and isinstance(v, (int, float)) and int(v) == v
-
-
-def check_inpaint_args(shape, known, known_mask, resample=1, jump=1):
-    """ValueError for a known-pixel request `Diffusion.sample` cannot run on chains of `shape` = (n, C, S, S) (checked before
-    the engine is touched): `known` without `known_mask` or the reverse, a `known` that does not broadcast to (n, C, S, S) or
-    a mask that does not to (n, 1 | C, S, S), `resample` / `jump` that are no integers >= 1, or that are set without `known`."""
-    for name, v in (("resample", resample), ("jump", jump)):
-        if not _is_int(v) or v < 1:
-            raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
-    if (known is None) != (known_mask is None):
-        raise ValueError("known and known_mask go together: got " + ("known without known_mask" if known_mask is None
-                                                                      else "known_mask without known"))
-    if known is None:
-        if resample != 1 or jump != 1:
-            raise ValueError(f"resample={resample} / jump={jump} belong to a chain with known pixels: pass known and known_mask")
-        return
-    n, C, H, W = shape
-    ks, ms = tuple(known.shape), tuple(known_mask.shape)
-    if ks not in ((C, H, W), (n, C, H, W)):
-        raise ValueError(f"known {ks} does not broadcast to {(n, C, H, W)}: pass (C, S, S) or (n, C, S, S)")
-    if ms not in ((H, W), (1, H, W), (C, H, W), (n, 1, H, W), (n, C, H, W)):
-        raise ValueError(f"known_mask {ms} does not broadcast to {(n, 1, H, W)} or {(n, C, H, W)}")
-
-
-def known_tensors(shape, known, known_mask, device):
-    """(`known` as (n, C, S, S) fp32, `known_mask` as (n, 1 | C, S, S) uint8 with 1 = known) on the device, for the update
-    kernel: bool, uint8 or {0, 1} float masks, broadcast over the n chains, converted once per chain."""
-    n, C, H, W = shape
-    known = known.to(device=device, dtype=torch.float32).expand(n, C, H, W).contiguous()
-    m = known_mask.to(device)
-    if m.dim() == 2:
-        m = m.unsqueeze(0)
-    if m.dim() == 3:
-        m = m.unsqueeze(0)
-    return known, (m != 0).to(torch.uint8).expand(n, m.shape[1], H, W).contiguous()
-
-
-def check_ensemble_args(n_members, member_batch):
-    """ValueError for an ensemble request `Diffusion.sample_ensemble` cannot run (checked before the engine is touched)."""
-    if not _is_int(n_members) or n_members < 2:
-        raise ValueError(f"n_members must be an integer >= 2, got {n_members!r} (`sample` draws a single sample)")
-    if member_batch is not None and (not _is_int(member_batch) or member_batch < 1):
-        raise ValueError(f"member_batch must be an integer >= 1, got {member_batch!r}")
-
-
-def ensemble_chunks(n_members, member_batch=None):
-    """The members per `sample` call of `Diffusion.sample_ensemble`: `member_batch` at a time (None: all at once), the rest in
-    the last call - [2, 2, 1] for 5 members in chunks of 2."""
-    m = int(n_members if member_batch is None else min(member_batch, n_members))
-    return [min(m, int(n_members) - k) for k in range(0, int(n_members), m)]
-
-
-def _repeat_members(t, m):
-    """A per-chain (B, ...) 4-D tensor repeated for m members, member-major; anything that broadcasts over the chains as is."""
-    return t.repeat(m, 1, 1, 1) if t is not None and t.dim() == 4 else t
-
-
-CHAIN_CHECK_EVERY = 128  # reverse steps between two reads of the kernels' fault word inside a sampling chain
-
-
-def run_reverse_chain(engine, x, noise_steps, step, frames=None, every=CHAIN_CHECK_EVERY, timesteps=None):
-    """The reverse loop of `Diffusion.sample` (reference :234-251): `step(i)` performs reverse step i in place on x, for i =
-    noise_steps - 1 .. 1, or for every entry of the list `timesteps` (the descending timesteps of a DDIM chain, or the moves of
-    a chain with known pixels: `inpaint_schedule`).  Every `every` steps (and at
-    the end) the fault word of the wave-specialised kernels is read (one 4-byte copy + a stream synchronisation: ~0.1 ms per
-    128 steps of ~1.2 ms each).  A protocol fault raises.  DRS_ERR_RANGE - an activation left the range of the FL arithmetic's
-    fp16 main operand (csrc/conv_mfma_fl.hip; chains of UNTRAINED weights do that, their amplitude grows without bound) - has
-    already switched the plan to the split-bf16 kernels: the chain goes back to its last checkpoint (x as of the last clean
-    check, a position in the step list) and continues from there."""
-    seq = range(noise_steps - 1, 0, -1) if timesteps is None else list(timesteps)
-    k = 0
-    ckpt_k, ckpt_x, ckpt_frames, since = k, x.clone(), 0, 0
-    while k < len(seq):
-        step(seq[k])
-        k += 1
-        since += 1
-        if since >= every or k == len(seq):
-            since = 0
-            try:
-                engine.check_faults()
-            except _lib.RangeFault as e:
-                print(f"[drs] {e}\n[drs] resuming the chain at step {seq[ckpt_k]} on the split-bf16 kernels", file=sys.stderr)
-                x.copy_(ckpt_x)
-                k = ckpt_k
-                if frames is not None:
-                    del frames[ckpt_frames:]
-                continue
-            ckpt_k = k
-            ckpt_x.copy_(x)
-            ckpt_frames = len(frames) if frames is not None else 0
-    return x
-
 
 METRIC_FORMATS = {"psnr": ("PSNR", "{:.2f} dB"), "ssim": ("SSIM", "{:.4f}"), "sam": ("SAM", "{:.3f} deg"),
                   "ergas": ("ERGAS", "{:.4g}"), "psnr_unknown": ("PSNR unknown", "{:.2f} dB")}
@@ -259,8 +114,7 @@ class Diffusion:
         given, with `known_mask` (S, S), (1 | C, S, S) or (n, 1 | C, S, S) (bool, uint8 or {0, 1} float; nonzero = known) -
         those pixels are kept and the others sampled.  `resample` and `jump` are its resampling (`inpaint_schedule`; 1 =
         none); everything else is `sample`'s.  See `_sample_chain` for the moves and the noise draws."""
-        if known is None and known_mask is None and resample == 1 and jump == 1:
-            raise ValueError("sample_known needs known and known_mask (`sample` draws a whole image)")
+        asks_for_known_pixels(known, known_mask, resample, jump, required=True)
         return self._sample(n, model, lr_img, input_channels, generate_video, noise_source, sampling_steps, eta, known,
                             known_mask, resample, jump)
 
@@ -281,7 +135,7 @@ class Diffusion:
 
     def _ensemble_chunk(self, n, head, known, known_mask, resample, jump, args):
         """One chunk of `sample_ensemble`: `sample(n, *head, **args)`, or `sample_known` when known pixels are asked for."""
-        if known is None and known_mask is None and resample == 1 and jump == 1:
+        if not asks_for_known_pixels(known, known_mask, resample, jump):
             return self.sample(n, *head, **args)
         return self.sample_known(n, *head, known, known_mask, resample=resample, jump=jump, **args)
 
@@ -322,78 +176,19 @@ class Diffusion:
         for classifier-free guidance: torch.lerp(eps_uncond, eps_cond, cfg_scale) is then folded into the update kernel.
         `update(x, eps, noise, i, i_prev)`, when given, takes the step in place of the sampler / DDIM update kernels (i_prev
         None on the ancestral chain): the tiler's per-step blend, whose state is a scene and whose eps a stack of tiles.
-        With `known` / `known_mask` (checked by `check_inpaint_args`) the chain runs the moves of `inpaint_schedule` over its
-        levels instead: a reverse move t -> t_prev is one `inpaint_step_` (the known pixels become `known` forward-noised to
-        t_prev, the others take the sampler's step) and draws one noise tensor - `noise_source(t, shape)` - iff t_prev > 0,
-        whatever eta is; a forward jump to level t is one `renoise_` and draws `noise_source(t, shape)`.  On the ancestral
-        chain without resampling these are the draws of the plain sampler."""
+        With `known` / `known_mask` (checked by `check_inpaint_args`) a reverse move t -> t_prev is one `inpaint_step_` (the
+        known pixels become `known` forward-noised to t_prev, the others take the sampler's step) and draws one noise tensor -
+        `noise_source(t, shape)` - iff t_prev > 0, whatever eta is; a forward jump of `inpaint_schedule` to level t is one
+        `renoise_` and draws `noise_source(t, shape)`.  On the ancestral chain without resampling these are the draws of the
+        plain sampler.  The chain is `sampling.sample_chain`; this method adds the eval mode around it and the video."""
         if known is not None and update is not None:
             raise ValueError("known pixels cannot be combined with an `update` hook (the tiler's per-step blend)")
         net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
         model.eval()
-        engine = net.hip_engine()
         frames = [] if generate_video else None
-        with torch.no_grad():
-            if noise_source is not None:
-                x = noise_source(self.noise_steps, shape).to(self.device)
-            else:
-                x = torch.randn(shape).to(self.device)  # CPU generator, like the reference (:230)
-            x = x.contiguous()
-            t_rows = hip_ops.timestep_table(self.noise_steps, table_rows, x.device)
-            taus = ddim_timesteps(self.noise_steps, sampling_steps) if sampling_steps is not None else None
-            prev = dict(zip(taus, taus[1:] + [0])) if taus is not None else None
-            state = {"first": True}
-
-            def step(i):
-                eps = predict(engine, x, t_rows[i], state["first"])
-                state["first"] = False
-                eps, eps_uncond = eps if isinstance(eps, tuple) else (eps, None)
-                if taus is not None:
-                    noise = ddim_chain_noise(eta, i, prev[i], shape, x, noise_source)
-                elif i > 1:
-                    noise = noise_source(i, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
-                else:
-                    noise = None  # reference adds zeros at the last step (:248)
-                if update is not None:
-                    update(x, eps, noise, i, prev[i] if taus is not None else None)
-                elif taus is None and eps_uncond is None:
-                    hip_ops.sampler_step_(x, eps, noise, i, self.alpha, self.alpha_hat, self.beta)
-                elif taus is None:
-                    hip_ops.sampler_step_cfg_(x, eps, eps_uncond, cfg_scale, noise, i, self.alpha, self.alpha_hat, self.beta)
-                elif eps_uncond is None:
-                    hip_ops.ddim_step_(x, eps, noise, i, prev[i], eta, self.alpha_hat)
-                else:
-                    hip_ops.ddim_step_(x, eps, noise, i, prev[i], eta, self.alpha_hat, eps_uncond=eps_uncond,
-                                       cfg_scale=cfg_scale)
-                if generate_video:
-                    frames.append(x.clone())
-
-            seq = taus
-            if known is not None:
-                known, known_mask = known_tensors(shape, known, known_mask, x.device)
-                levels = (taus if taus is not None else list(range(self.noise_steps - 1, 0, -1))) + [0]
-                seq = inpaint_schedule(len(levels) - 1, resample, jump)
-
-                def draw(t):
-                    return noise_source(t, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
-
-                def step(move):  # noqa: F811 - the step of a chain with known pixels: one move (p, q) of `seq`
-                    t, t_to = levels[move[0]], levels[move[1]]
-                    if t_to > t:
-                        hip_ops.renoise_(x, draw(t_to), t, t_to, self.alpha_hat)
-                    else:
-                        eps = predict(engine, x, t_rows[t], state["first"])
-                        state["first"] = False
-                        eps, eps_uncond = eps if isinstance(eps, tuple) else (eps, None)
-                        form = ({"alpha": self.alpha, "beta": self.beta} if sampling_steps is None
-                                else {"t_prev": t_to, "eta": eta})
-                        hip_ops.inpaint_step_(x, eps, draw(t) if t_to > 0 else None, known, known_mask, t,
-                                              alpha_hat=self.alpha_hat, eps_uncond=eps_uncond, cfg_scale=cfg_scale, **form)
-                    if generate_video:
-                        frames.append(x.clone())
-            # (the fault word of the wave-specialised kernels - a protocol fault reports itself through it instead of a trap,
-            #  csrc/sp_sync.h - is read inside the loop, every CHAIN_CHECK_EVERY steps and at the end)
-            run_reverse_chain(engine, x, self.noise_steps, step, frames, timesteps=seq)
+        x = sample_chain(self, net.hip_engine(), shape, predict, table_rows=table_rows, noise_source=noise_source,
+                         sampling_steps=sampling_steps, eta=eta, cfg_scale=cfg_scale, update=update, known=known,
+                         known_mask=known_mask, resample=resample, jump=jump, frames=frames)
         if generate_video:
             from .video import video_maker  # optional dependency (cv2), same call as reference :253
             video_maker(frames, os.path.join(os.getcwd(), "models_run", self.model_name, "results",
@@ -416,23 +211,31 @@ class Diffusion:
         "ensemble" holds the means of `ensemble.ensemble_scores` (crps, spread, rmse, spread_skill) and the summed
         "rank_histogram", everything on members and truth clamped to [0, 1] like the image scores; see `_evaluate`.
         The model keeps the train / eval mode it came with."""
-        self._check_evaluate_ensemble(ensemble, member_batch, known_mask_fn)
-
-        def members(lr_img, hr_img):
-            return self.sample_ensemble(ensemble, model, lr_img, input_channels=hr_img.shape[1], member_batch=member_batch,
-                                        sampling_steps=sampling_steps, eta=eta, noise_source=noise_source)
-
-        def sample(lr_img, hr_img):
-            args = {"input_channels": hr_img.shape[1], "noise_source": noise_source, "sampling_steps": sampling_steps, "eta": eta}
-            if known_mask_fn is None:
-                check_inpaint_args(tuple(hr_img.shape), None, None, resample, jump)
-                return self.sample(lr_img.shape[0], model, lr_img, **args)
-            return self._score_known(hr_img, known_mask_fn(hr_img), lambda known, mask: self.sample_known(
-                lr_img.shape[0], model, lr_img, known, mask, resample=resample, jump=jump, **args))
+        sample, members = self._evaluate_samplers(model, "input_channels", sampling_steps, eta, noise_source, known_mask_fn,
+                                                  resample, jump, ensemble, member_batch)
         scorers = {"model": sample}
         if baseline:
             scorers["bicubic"] = lambda lr_img, hr_img: hip_ops.bicubic_upsample(lr_img, self.magnification_factor)
-        return self._evaluate(model, loader, n_images, scorers, self.magnification_factor, members if ensemble else None)
+        return self._evaluate(model, loader, n_images, scorers, self.magnification_factor, members)
+
+    def _evaluate_samplers(self, model, channels_kw, sampling_steps, eta, noise_source, known_mask_fn, resample, jump, ensemble,
+                           member_batch):
+        """`evaluate`'s (`sample`, `members`), both f(conditioning batch, truth batch): one `sample` / `sample_known` call, and
+        one `sample_ensemble` call (None without `ensemble`).  `channels_kw`: the sampler's name for the truth's band count."""
+        self._check_evaluate_ensemble(ensemble, member_batch, known_mask_fn)
+
+        def members(cond, truth):
+            return self.sample_ensemble(ensemble, model, cond, member_batch=member_batch, sampling_steps=sampling_steps,
+                                        eta=eta, noise_source=noise_source, **{channels_kw: truth.shape[1]})
+
+        def sample(cond, truth):
+            args = {channels_kw: truth.shape[1], "noise_source": noise_source, "sampling_steps": sampling_steps, "eta": eta}
+            if known_mask_fn is None:
+                check_inpaint_args(tuple(truth.shape), None, None, resample, jump)
+                return self.sample(cond.shape[0], model, cond, **args)
+            return self._score_known(truth, known_mask_fn(truth), lambda known, mask: self.sample_known(
+                cond.shape[0], model, cond, known, mask, resample=resample, jump=jump, **args))
+        return sample, members if ensemble else None
 
     @staticmethod
     def _check_evaluate_ensemble(ensemble, member_batch, known_mask_fn):

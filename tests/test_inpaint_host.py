@@ -314,3 +314,49 @@ def test_run_reverse_chain_rolls_back_to_a_position_in_the_move_list(capsys):
     assert done1 == moves[:8] + moves[4:]
     assert torch.equal(x0, x1) and len(frames1) == len(moves) and all(torch.equal(a, b) for a, b in zip(frames0, frames1))
     assert f"resuming the chain at step {moves[4]}" in capsys.readouterr().err
+
+
+# ---------------------------------------------------------------------------------------------
+# the one move list of every chain kind
+# ---------------------------------------------------------------------------------------------
+# (t, t_to) at noise_steps = 8, written down from the three forms the samplers used to keep: range(T - 1, 0, -1) for the
+# ancestral chain, the `ddim_timesteps` with their successors for DDIM, `inpaint_schedule` mapped onto the levels with known pixels
+_DOWN7 = [(7, 6), (6, 5), (5, 4), (4, 3), (3, 2), (2, 1), (1, 0)]
+CHAIN_MOVES_T8 = {
+    # (sampling_steps, resample, jump)
+    (None, 1, 1): _DOWN7,
+    (1, 1, 1): [(7, 0)],
+    (3, 1, 1): [(7, 4), (4, 1), (1, 0)],
+    (7, 1, 1): _DOWN7,
+    (None, 2, 1): [(7, 6), (6, 7), (7, 6), (6, 5), (5, 6), (6, 5), (5, 4), (4, 5), (5, 4), (4, 3), (3, 4), (4, 3), (3, 2), (2, 3),
+                   (3, 2), (2, 1), (1, 2), (2, 1), (1, 0)],
+    (None, 2, 2): [(7, 6), (6, 5), (5, 7), (7, 6), (6, 5), (5, 4), (4, 3), (3, 5), (5, 4), (4, 3), (3, 2), (2, 1), (1, 3), (3, 2),
+                   (2, 1), (1, 0)],
+    (None, 3, 2): [(7, 6), (6, 5), (5, 7), (7, 6), (6, 5), (5, 7), (7, 6), (6, 5), (5, 4), (4, 3), (3, 5), (5, 4), (4, 3), (3, 5),
+                   (5, 4), (4, 3), (3, 2), (2, 1), (1, 3), (3, 2), (2, 1), (1, 3), (3, 2), (2, 1), (1, 0)],
+    (3, 2, 1): [(7, 4), (4, 7), (7, 4), (4, 1), (1, 4), (4, 1), (1, 0)],
+    (3, 2, 2): [(7, 4), (4, 1), (1, 7), (7, 4), (4, 1), (1, 0)],
+    (3, 3, 2): [(7, 4), (4, 1), (1, 7), (7, 4), (4, 1), (1, 7), (7, 4), (4, 1), (1, 0)],
+}
+
+
+@pytest.mark.parametrize("key", list(CHAIN_MOVES_T8), ids=lambda k: f"S{k[0]}-r{k[1]}-j{k[2]}")
+def test_chain_moves_are_the_three_former_step_lists(key):
+    from diffusionremotesensing_amd.sampling import chain_moves
+    sampling_steps, resample, jump = key
+    moves = chain_moves(8, sampling_steps, resample, jump)
+    assert moves == CHAIN_MOVES_T8[key] and all(type(t) is int and type(t_to) is int for t, t_to in moves)
+    # the counts of `inpaint_schedule`'s docstring, none of the jumps up from level 0
+    S = 7 if sampling_steps is None else sampling_steps
+    down, up = [m for m in moves if m[1] < m[0]], [m for m in moves if m[1] > m[0]]
+    assert len(down) == S + (resample - 1) * jump * ((S - 1) // jump) and len(up) == (resample - 1) * ((S - 1) // jump)
+    assert len(down) + len(up) == len(moves) and all(t >= 1 for t, _ in up) and moves[-1][1] == 0
+    # in the roll-back line of `run_reverse_chain` a move reads as the level it starts from
+    assert f"{moves[0]}" == "7" and moves[0].t == 7 and moves[0].t_to == CHAIN_MOVES_T8[key][0][1]
+
+
+def test_chain_moves_without_resampling_ignore_jump_and_check_the_steps():
+    from diffusionremotesensing_amd.sampling import chain_moves
+    assert chain_moves(8, None, 1, 3) == _DOWN7 and chain_moves(8) == _DOWN7
+    with pytest.raises(ValueError, match="outside"):
+        chain_moves(8, 8)
