@@ -128,7 +128,8 @@ class split_aggregation_sampling:
         One step cuts X into the tiles (`gather_tiles`), runs the UNet on them in chunks of `tile_batch` (the last chunk
         padded with repeats of its last tile, whose eps is never read), each forward writing its slice of ONE eps buffer,
         and takes the step with one `blend_step_`: per scene element the Gaussian-weighted mean of the covering tiles' eps,
-        summed in tile index order, then the ancestral / DDIM update of the per-tile samplers.
+        summed in tile index order, then the ancestral / DDIM / DPM-Solver++(2M) update of the per-tile samplers (the last with
+        `sampling_steps=sampling_plan(S, solver="dpmpp_2m")`; its history is one more tensor of scene size, owned by the chain).
         Memory: the eps buffer holds every tile of a step, ceil(n / chunk) * chunk x (C, S, S) fp32: 0.79 MB per 256x256x3
         tile (38 MB for the 48 tiles of a 896x1152 scene, 3.1 GB for the ~4000 tiles of a 2048x2048 scene at stride 32),
         next to one chunk of gathered tiles and the plan's workspace.
@@ -172,10 +173,10 @@ class split_aggregation_sampling:
                                check_weights=first and j == 0, out=eps_buf[c0:c0 + size])
             return eps_buf
 
-        def update(x, eps, noise, i, i_prev):
+        def update(x, eps, noise, i, i_prev, hist=None, t_q=-1):
             hip_ops.blend_step_(x[0], eps, origins, weight, noise[0] if noise is not None else None, i,
                                 alpha_hat=d.alpha_hat, alpha=d.alpha, beta=d.beta, t_prev=i_prev, eta=eta,
-                                uncovered=uncovered)
+                                uncovered=uncovered, hist=hist[0] if hist is not None else None, t_q=t_q)
 
         x = d._sample_chain(self.model, (1, channels, Hs, Ws), predict, table_rows=size, generate_video=False,
                             noise_source=noise_source, sampling_steps=sampling_steps, eta=eta, update=update)
@@ -207,7 +208,7 @@ def launch(args):
     (1,C,H,W) in [0,1], `--destination_path` receives a `.pt` tensor."""
     import os
 
-    from .train_diffusion_superres import Diffusion
+    from .train_diffusion_superres import Diffusion, cli_sampling_steps
     from .UNet_model_superres import Residual_Attention_UNet_superres
     device = args.device
     if args.UNet_type.lower() != "residual attention unet":
@@ -227,7 +228,7 @@ def launch(args):
                           image_size=args.model_input_size, model_name=args.model_name,
                           Degradation_type=args.Degradation_type, multiple_gpus=False, ema_smoothing=False)
     tiler = split_aggregation_sampling(img_lr, args.patch_size, args.stride, args.magnification_factor, diffusion, device)
-    final_pred = tiler.aggregation_sampling(sampling_steps=getattr(args, "sampling_steps", None),
+    final_pred = tiler.aggregation_sampling(sampling_steps=cli_sampling_steps(args),
                                             eta=getattr(args, "eta", 0.0),
                                             aggregation=getattr(args, "aggregation", "final"))
     torch.save(final_pred.squeeze(0).cpu(), args.destination_path)
@@ -237,7 +238,7 @@ def build_arg_parser():
     """The reference's flags, verbatim (:217-231), the DDIM flags and --aggregation."""
     import argparse
 
-    from .train_diffusion_superres import add_sampling_args
+    from .train_diffusion_superres import add_sampling_args, add_solver_args
     p = argparse.ArgumentParser(description=" ")
     p.add_argument("--noise_schedule", type=str, default="cosine")
     p.add_argument("--snapshot_name", type=str, default="snapshot.pt")
@@ -254,6 +255,7 @@ def build_arg_parser():
     p.add_argument("--destination_path", type=str)
     p.add_argument("--img_lr_path", type=str)
     add_sampling_args(p)
+    add_solver_args(p)
     p.add_argument("--aggregation", type=str, choices=("final", "per_step"), default="final",
                    help="final: independent tile chains blended once (the reference); per_step: one joint chain of the "
                         "whole scene, the tiles' noise predictions blended at every reverse step")

@@ -35,6 +35,7 @@ SIGNATURES = {
     "drs_sampler_step": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _L, _P]),
     "drs_sampler_step_cfg": (_I, [_P, _P, _P, C.c_float, _P, _I, _P, _P, _P, _I, C.c_int64, _P]),
     "drs_ddim_step": (_I, [_P, _P, _P, C.c_float, _P, _I, _I, C.c_float, _P, _I, C.c_int64, _P]),
+    "drs_dpm_step": (_I, [_P, _P, _P, _F, _P, _I, _I, _I, _P, _I, _L, _P]),
     "drs_inpaint_step": (_I, [_P, _P, _P, _F, _P, _P, _P] + [_I] * 8 + [_F, _P, _P, _P, _I, _P]),
     "drs_renoise": (_I, [_P, _P, _I, _I, _P, _I, _L, _P]),
     "drs_adam_multi": (_I, [_P, _I, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
@@ -48,6 +49,7 @@ SIGNATURES = {
     "drs_gather_tiles": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "drs_blend_step": (_I, [_P] * 6 + [_I] * 6 + [_P, _P, _P, _I, _P]),
     "drs_blend_step_ddim": (_I, [_P] * 6 + [_I] * 7 + [_F, _P, _I, _P]),
+    "drs_blend_step_dpm": (_I, [_P] * 6 + [_I] * 8 + [_P, _I, _P]),
     "drs_metrics_workspace_bytes": (_Z, [_I] * 4),
     "drs_metrics_pointwise": (_I, [_P, _P, _P] + [_I] * 5 + [_P, _Z, _P]),
     "drs_ssim": (_I, [_P, _P, _P] + [_I] * 5 + [_P, _Z, _P]),

@@ -149,6 +149,16 @@ static inline int drs_check_move(const char* what, bool ddim, int t_min, int t, 
     DRS_REQUIRE(noise || t_prev == 0, DRS_ERR_ARG, "%s: t_prev=%d > 0 needs a noise tensor", what, t_prev);
   return DRS_OK;
 }
+// The argument checks of one DPM-Solver++(2M) move t -> t_p whose previous move left level t_q (-1: none, a first-order move):
+// 0 <= t_p < t < noise_steps, t < t_q < noise_steps, and no history on the move to level 0 (its logSNR may be infinite).
+static inline int drs_check_dpm_move(const char* what, int t_q, int t, int t_p, int noise_steps) {
+  DRS_REQUIRE(0 <= t_p && t_p < t && t < noise_steps, DRS_ERR_ARG,
+              "%s: need 0 <= t_p < t < noise_steps, got t_p=%d t=%d noise_steps=%d", what, t_p, t, noise_steps);
+  DRS_REQUIRE(t_q == -1 || (t < t_q && t_q < noise_steps), DRS_ERR_ARG,
+              "%s: need t_q == -1 or t < t_q < noise_steps, got t_q=%d t=%d noise_steps=%d", what, t_q, t, noise_steps);
+  DRS_REQUIRE(t_q == -1 || t_p > 0, DRS_ERR_ARG, "%s: the move to level 0 is first order, got t_q=%d with t_p=0", what, t_q);
+  return DRS_OK;
+}
 // ReLU and the other activation maxima: IEEE 754-2019 `maximum` (v_maximum3_f32), which PROPAGATES a NaN like torch.relu does.
 // fmaxf (v_max_f32) returns the other operand: a NaN accumulator would leave a ReLU as 0 and the divergence it signals
 // would be gone from the output (tests/test_gpu_parity.py: test_nan_reaches_the_output).

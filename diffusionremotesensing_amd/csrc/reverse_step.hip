@@ -3,7 +3,8 @@
 // (drs_ddim_step; Song et al., "Denoising Diffusion Implicit Models") and either with known pixels (drs_inpaint_step; RePaint,
 // Lugmayr et al., CVPR 2022, Algorithm 1: the unknown pixels take the sampler's step, lines 6-7, the known ones become the known
 // image forward-noised to t_prev, lines 4-5, merged by a per-element select, line 8); drs_renoise is the closed form of the
-// forward steps of its resampling (line 10).  Coefficients and per-element update: step_update.h, shared with tile_chain.hip.
+// forward steps of its resampling (line 10); drs_dpm_step is the DPM-Solver++(2M) move (Lu et al., 2022), which also keeps
+// the x0 prediction of the move before.  Coefficients and per-element update: step_update.h, shared with tile_chain.hip.
 #include "drs_common.h"
 #include "step_update.h"
 
@@ -235,6 +236,46 @@ __global__ __launch_bounds__(256) void renoise_kernel(float* __restrict__ x, con
   for (int64_t i = groups * 4 + tid; i < numel; i += stride) x[i] = jump_to(A, x[i], B, z[i]);
 }
 
+// x0 = cx x + ce eps -> hist, x = A x + B eps + C hist (read before it is written, by a second-order move only): float4
+// groups (`vec`: every pointer 16-byte aligned), then the numel % 4 tail.  Three reads and two writes per element.
+__global__ __launch_bounds__(256) void dpm_step_kernel(float* __restrict__ x, const float* __restrict__ ec,
+                                                       const float* __restrict__ eu, float w, float* __restrict__ hist,
+                                                       int t_q, int t, int t_p, const float* __restrict__ alpha_hat,
+                                                       int64_t numel, bool vec) {
+  const DrsDpmCoef k = drs_dpm_coef(alpha_hat, t_q, t, t_p);
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t groups = vec ? numel / 4 : 0;
+  for (int64_t g = tid; g < groups; g += stride) {
+    const float4 x4 = reinterpret_cast<const float4*>(x)[g];
+    const float4 e4 = reinterpret_cast<const float4*>(ec)[g];
+    float xs[4] = {x4.x, x4.y, x4.z, x4.w}, es[4] = {e4.x, e4.y, e4.z, e4.w}, hs[4] = {0.f, 0.f, 0.f, 0.f};
+    if (eu) {
+      const float4 u4 = reinterpret_cast<const float4*>(eu)[g];
+      es[0] = drs_cfg_lerp(u4.x, es[0], w); es[1] = drs_cfg_lerp(u4.y, es[1], w);
+      es[2] = drs_cfg_lerp(u4.z, es[2], w); es[3] = drs_cfg_lerp(u4.w, es[3], w);
+    }
+    if (k.second) {
+      const float4 h4 = reinterpret_cast<const float4*>(hist)[g];
+      hs[0] = h4.x; hs[1] = h4.y; hs[2] = h4.z; hs[3] = h4.w;
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const float x0 = drs_dpm_x0(k, xs[p], es[p]);
+      xs[p] = drs_dpm_update(k, xs[p], es[p], hs[p]);
+      hs[p] = x0;
+    }
+    reinterpret_cast<float4*>(hist)[g] = make_float4(hs[0], hs[1], hs[2], hs[3]);
+    reinterpret_cast<float4*>(x)[g] = make_float4(xs[0], xs[1], xs[2], xs[3]);
+  }
+  for (int64_t i = groups * 4 + tid; i < numel; i += stride) {
+    float e = ec[i];
+    if (eu) e = drs_cfg_lerp(eu[i], e, w);
+    const float xv = x[i], h = k.second ? hist[i] : 0.f;
+    hist[i] = drs_dpm_x0(k, xv, e);
+    x[i] = drs_dpm_update(k, xv, e, h);
+  }
+}
+
 template <bool DDIM>
 int launch_inpaint(const InpaintArgs& a, hipStream_t s) {
   const bool wide = a.hw % 4 == 0 && aligned16(a.x) && aligned16(a.ec) && aligned16(a.known) && ((uintptr_t)a.mask & 3u) == 0 &&
@@ -260,6 +301,19 @@ extern "C" int drs_ddim_step(float* x, const float* eps_cond, const float* eps_u
   if (numel == 0) return DRS_OK;
   DRS_LAUNCH(ddim_step_kernel, dim3(ew_blocks(numel)), dim3(256), 0, (hipStream_t)stream, x, eps_cond, eps_uncond,
              cfg_scale, noise, t, t_prev, eta, alpha_hat, numel);
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
+}
+
+extern "C" int drs_dpm_step(float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale, float* x0_hist, int t_q,
+                            int t, int t_p, const float* alpha_hat, int noise_steps, int64_t numel, drs_stream_t stream) {
+  DRS_REQUIRE(x && eps_cond && x0_hist && alpha_hat, DRS_ERR_ARG, "dpm_step: null pointer");
+  if (int st = drs_check_dpm_move("dpm_step", t_q, t, t_p, noise_steps)) return st;
+  DRS_REQUIRE(numel >= 0, DRS_ERR_ARG, "dpm_step: numel=%lld", (long long)numel);
+  if (numel == 0) return DRS_OK;
+  const bool vec = aligned16(x) && aligned16(eps_cond) && aligned16(x0_hist) && (!eps_uncond || aligned16(eps_uncond));
+  DRS_LAUNCH(dpm_step_kernel, dim3(ew_blocks(vec ? (numel + 3) / 4 : numel)), dim3(256), 0, (hipStream_t)stream, x, eps_cond,
+             eps_uncond, cfg_scale, x0_hist, t_q, t, t_p, alpha_hat, numel, vec);
   DRS_CHECK_HIP(hipGetLastError());
   return DRS_OK;
 }

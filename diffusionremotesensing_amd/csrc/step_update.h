@@ -1,7 +1,7 @@
 // The per-element arithmetic of the reverse-step updates, shared by every kernel that applies one: the ancestral and the DDIM
 // update (reverse_step.hip: drs_sampler_step, drs_sampler_step_cfg, drs_ddim_step; drs_inpaint_step takes the coefficients)
 // and the per-step tile blend, which forms eps itself and then takes the same step (tile_chain.hip: drs_blend_step,
-// drs_blend_step_ddim).
+// drs_blend_step_ddim), and the DPM-Solver++(2M) move of both (drs_dpm_step, drs_blend_step_dpm).
 // One definition, so that a scene state and a tile state that see the same eps move by the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -60,4 +60,59 @@ __device__ __forceinline__ float drs_ddim_update(const DrsDdimCoef& k, float x, 
 }
 __device__ __forceinline__ float drs_ddim_noise(const DrsDdimCoef& k, float v, float z) {
   return __fadd_rn(v, __fmul_rn(k.s, z));
+}
+
+// DPM-Solver++(2M) move t -> t_p (Lu et al., "DPM-Solver++", Algorithm 2, data prediction), with the level t_q > t of the
+// previous move, or t_q = -1 for a first-order move (no valid history, or the move to level 0):
+//   a = sqrt(ah), s = sqrt(1 - ah), E = (s_p / a_p) (a_t / s_t) = exp(-h), phi = a_p (1 - E), lam = ln(a / s),
+//   r = (lam_t - lam_q) / (lam_p - lam_t)
+//   x0 = cx x + ce eps,  cx = 1 / a_t,  ce = -s_t / a_t
+//   x' = A x + B eps + C x0_prev,  k0 = phi (1 + 1 / (2 r)) | phi,  A = s_p / s_t + k0 / a_t,  B = -k0 s_t / a_t,
+//                                  C = -phi / (2 r) | 0
+// E is formed without logarithms, so the move to level 0 (ah_0 = 1: E = 0, x' = x0) takes none; r needs them only when
+// t_q >= 0, and then t_p > 0 (checked on the host).  Every thread forms the coefficients in fp64 from the fp32 table and
+// rounds them once, for the reason given at drs_ddim_coef.  Products and sums are rounded one by one (no contraction), so
+// that the scene state of the tile blend and a sampler state that see the same eps move by the same bits.
+struct DrsDpmCoef {
+  float cx, ce, a, b, c;
+  bool second;  // the move reads x0_prev
+};
+__device__ __forceinline__ DrsDpmCoef drs_dpm_coef(const float* __restrict__ alpha_hat, int t_q, int t, int t_p) {
+  const double aht = (double)alpha_hat[t], ahp = (double)alpha_hat[t_p];
+  const double a_t = sqrt(aht), s_t = sqrt(1.0 - aht), a_p = sqrt(ahp), s_p = sqrt(fmax(1.0 - ahp, 0.0));
+  const double E = (s_p / a_p) * (a_t / s_t);
+  const double phi = a_p * (1.0 - E);
+  double k0 = phi, C = 0.0;
+  DrsDpmCoef k;
+  k.second = t_q >= 0;
+  if (k.second) {
+    const double ahq = (double)alpha_hat[t_q];
+    const double lam_t = 0.5 * log(aht / (1.0 - aht)), lam_q = 0.5 * log(ahq / (1.0 - ahq));
+    const double lam_p = 0.5 * log(ahp / (1.0 - ahp));
+    const double inv_2r = 0.5 * (lam_p - lam_t) / (lam_t - lam_q);
+    k0 = phi * (1.0 + inv_2r);
+    C = -phi * inv_2r;
+  }
+  k.cx = (float)(1.0 / a_t);
+  k.ce = (float)(-s_t / a_t);
+  k.a = (float)(s_p / s_t + k0 / a_t);
+  k.b = (float)(-k0 * s_t / a_t);
+  k.c = (float)C;
+  return k;
+}
+__device__ __forceinline__ float drs_dpm_x0(const DrsDpmCoef& k, float x, float eps) {
+#pragma clang fp contract(off)
+  const float p = k.cx * x, q = k.ce * eps;
+  return p + q;
+}
+// `x0_prev` is used by a second-order move only (a first-order one may be handed anything)
+__device__ __forceinline__ float drs_dpm_update(const DrsDpmCoef& k, float x, float eps, float x0_prev) {
+#pragma clang fp contract(off)
+  const float p = k.a * x, q = k.b * eps;
+  float v = p + q;
+  if (k.second) {
+    const float h = k.c * x0_prev;
+    v = v + h;
+  }
+  return v;
 }

@@ -1,9 +1,11 @@
 // Per-step tile aggregation (split_aggregation_sampling.sample_scene): ONE state of scene size is denoised; every reverse
 // step cuts it into the tiles the UNet sees (drs_gather_tiles), and blends the tiles' noise predictions back into one
-// eps per scene element before taking the step (drs_blend_step / drs_blend_step_ddim).  Both kernels move each byte once
-// and are bound by HBM traffic; neither has an atomic on its data path and neither clamps.
+// eps per scene element before taking the step (drs_blend_step / drs_blend_step_ddim / drs_blend_step_dpm).  Both kernels
+// move each byte once and are bound by HBM traffic; neither has an atomic on its data path and neither clamps.
 #include "drs_common.h"
 #include "step_update.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -63,13 +65,30 @@ struct StepCoef<true> {
   __device__ float add(float v, float z) const { return drs_ddim_noise(k, v, z); }
 };
 
+// The DPM-Solver++(2M) move of dpm_step_kernel (step_update.h): `step` also returns the x0 prediction the history keeps.
+struct DpmStepCoef {
+  DrsDpmCoef k;
+  __device__ DpmStepCoef(const float* alpha_hat, int t_q, int t, int t_p) : k(drs_dpm_coef(alpha_hat, t_q, t, t_p)) {}
+  __device__ float step(float x, float eps, float& h) const {
+    const float x0 = drs_dpm_x0(k, x, eps);
+    const float v = drs_dpm_update(k, x, eps, h);
+    h = x0;
+    return v;
+  }
+};
+
+enum BlendMode { kAncestral, kDdim, kDpm };
+
 // One thread per group of V consecutive scene pixels of one row (V = 4 needs Ws % 4 == 0 and S % 4 == 0), channels in
 // chunks of 4.  For every pixel the covering tiles are visited in index order - the summation order of
 // aggregate_tiles_kernel: cnt += w, acc += tile * w, then acc / cnt - so the blended eps does not depend on the launch
 // geometry.  A tile whose window holds the whole group at a 16-byte aligned offset is read with one float4 per plane
 // (weight and eps), any other one element by element under its own bounds check: eps_tiles is only ever indexed with
 // 0 <= ly, lx < S, whatever the origins hold.  A pixel no tile covers gets 0 / 0 = NaN and is counted in `uncovered`.
-template <int V, bool DDIM>
+// MODE kDpm: `hist` (scene shape) holds the x0 prediction of the move before, read by a second-order move (t_q >= 0) and
+// written by every move; it draws no noise.  With V = 4 it is accessed like `scene` and `noise`: one float4 per group at the
+// group's element offset, so it wants the alignment of `scene` (both are whole torch allocations in `blend_step_`).
+template <int V, BlendMode MODE>
 __global__ __launch_bounds__(256) void blend_step_kernel(float* __restrict__ scene, const float* __restrict__ eps_tiles,
                                                          const int* __restrict__ origins,
                                                          const float* __restrict__ weight,
@@ -77,9 +96,14 @@ __global__ __launch_bounds__(256) void blend_step_kernel(float* __restrict__ sce
                                                          int n, int C, int S, int Hs, int Ws, int t, int t_prev, float eta,
                                                          const float* __restrict__ alpha,
                                                          const float* __restrict__ alpha_hat,
-                                                         const float* __restrict__ beta) {
-  const StepCoef<DDIM> coef(alpha, alpha_hat, beta, t, t_prev, eta);
-  const bool add_noise = noise != nullptr && coef.draws();
+                                                         const float* __restrict__ beta, float* __restrict__ hist, int t_q) {
+  using Coef = std::conditional_t<MODE == kDpm, DpmStepCoef, StepCoef<MODE == kDdim>>;
+  const Coef coef = [&] {
+    if constexpr (MODE == kDpm) return Coef(alpha_hat, t_q, t, t_prev);
+    else return Coef(alpha, alpha_hat, beta, t, t_prev, eta);
+  }();
+  bool add_noise = false;
+  if constexpr (MODE != kDpm) add_noise = noise != nullptr && coef.draws();
   const int per_row = Ws / V;
   const int64_t groups = (int64_t)Hs * per_row, hw = (int64_t)Hs * Ws, ss = (int64_t)S * S;
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (int64_t)gridDim.x * blockDim.x) {
@@ -139,11 +163,27 @@ __global__ __launch_bounds__(256) void blend_step_kernel(float* __restrict__ sce
           xs[0] = scene[at];
           if (add_noise) zs[0] = noise[at];
         }
+        if constexpr (MODE == kDpm) {
+          float hs[V] = {};
+          if (coef.k.second) {
+            if constexpr (V == 4) {
+              const float4 h4 = *reinterpret_cast<const float4*>(hist + at);
+              hs[0] = h4.x; hs[1] = h4.y; hs[2] = h4.z; hs[3] = h4.w;
+            } else {
+              hs[0] = hist[at];
+            }
+          }
 #pragma unroll
-        for (int p = 0; p < V; ++p) {
-          float v = coef.step(xs[p], __fdiv_rn(acc[j][p], cnt[p]));
-          if (add_noise) v = coef.add(v, zs[p]);
-          xs[p] = v;
+          for (int p = 0; p < V; ++p) xs[p] = coef.step(xs[p], __fdiv_rn(acc[j][p], cnt[p]), hs[p]);
+          if constexpr (V == 4) *reinterpret_cast<float4*>(hist + at) = make_float4(hs[0], hs[1], hs[2], hs[3]);
+          else hist[at] = hs[0];
+        } else {
+#pragma unroll
+          for (int p = 0; p < V; ++p) {
+            float v = coef.step(xs[p], __fdiv_rn(acc[j][p], cnt[p]));
+            if (add_noise) v = coef.add(v, zs[p]);
+            xs[p] = v;
+          }
         }
         if constexpr (V == 4) *reinterpret_cast<float4*>(scene + at) = make_float4(xs[0], xs[1], xs[2], xs[3]);
         else scene[at] = xs[0];
@@ -181,16 +221,16 @@ extern "C" int drs_gather_tiles(const float* scene, const int32_t* origins, floa
 
 namespace {
 
-template <bool DDIM>
+template <BlendMode MODE>
 int launch_blend(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight, const float* noise,
                  int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t, int t_prev, float eta, const float* alpha,
-                 const float* alpha_hat, const float* beta, hipStream_t s) {
+                 const float* alpha_hat, const float* beta, hipStream_t s, float* hist = nullptr, int t_q = -1) {
   if (S % 4 == 0 && Ws % 4 == 0) {
-    DRS_LAUNCH((blend_step_kernel<4, DDIM>), dim3(ew_blocks((int64_t)Hs * (Ws / 4))), dim3(256), 0, s, scene, eps_tiles,
-               origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, alpha, alpha_hat, beta);
+    DRS_LAUNCH((blend_step_kernel<4, MODE>), dim3(ew_blocks((int64_t)Hs * (Ws / 4))), dim3(256), 0, s, scene, eps_tiles,
+               origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, alpha, alpha_hat, beta, hist, t_q);
   } else {
-    DRS_LAUNCH((blend_step_kernel<1, DDIM>), dim3(ew_blocks((int64_t)Hs * Ws)), dim3(256), 0, s, scene, eps_tiles, origins,
-               weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, alpha, alpha_hat, beta);
+    DRS_LAUNCH((blend_step_kernel<1, MODE>), dim3(ew_blocks((int64_t)Hs * Ws)), dim3(256), 0, s, scene, eps_tiles, origins,
+               weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, alpha, alpha_hat, beta, hist, t_q);
   }
   DRS_CHECK_HIP(hipGetLastError());
   return DRS_OK;
@@ -210,8 +250,8 @@ extern "C" int drs_blend_step(float* scene, const float* eps_tiles, const int32_
   DRS_BLEND_REQUIRE("blend_step");
   DRS_REQUIRE(alpha && alpha_hat && beta, DRS_ERR_ARG, "blend_step: null schedule table");
   if (int st = drs_check_move("blend_step", false, 0, t, 0, 0.f, noise_steps, noise, DRS_NOISE_OPTIONAL)) return st;
-  return launch_blend<false>(scene, eps_tiles, origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, 0, 0.f, alpha,
-                             alpha_hat, beta, (hipStream_t)stream);
+  return launch_blend<kAncestral>(scene, eps_tiles, origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, 0, 0.f, alpha,
+                                  alpha_hat, beta, (hipStream_t)stream);
 }
 
 extern "C" int drs_blend_step_ddim(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight,
@@ -220,6 +260,16 @@ extern "C" int drs_blend_step_ddim(float* scene, const float* eps_tiles, const i
   DRS_BLEND_REQUIRE("blend_step_ddim");
   DRS_REQUIRE(alpha_hat, DRS_ERR_ARG, "blend_step_ddim: null schedule table");
   if (int st = drs_check_move("blend_step_ddim", true, 0, t, t_prev, eta, noise_steps, noise, DRS_NOISE_IF_SIGMA)) return st;
-  return launch_blend<true>(scene, eps_tiles, origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, nullptr,
-                            alpha_hat, nullptr, (hipStream_t)stream);
+  return launch_blend<kDdim>(scene, eps_tiles, origins, weight, noise, uncovered, n, C, S, Hs, Ws, t, t_prev, eta, nullptr,
+                             alpha_hat, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int drs_blend_step_dpm(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight,
+                                  float* x0_hist, int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t_q, int t,
+                                  int t_p, const float* alpha_hat, int noise_steps, drs_stream_t stream) {
+  DRS_BLEND_REQUIRE("blend_step_dpm");
+  DRS_REQUIRE(x0_hist && alpha_hat, DRS_ERR_ARG, "blend_step_dpm: null history or schedule table");
+  if (int st = drs_check_dpm_move("blend_step_dpm", t_q, t, t_p, noise_steps)) return st;
+  return launch_blend<kDpm>(scene, eps_tiles, origins, weight, nullptr, uncovered, n, C, S, Hs, Ws, t, t_p, 0.f, nullptr,
+                            alpha_hat, nullptr, (hipStream_t)stream, x0_hist, t_q);
 }

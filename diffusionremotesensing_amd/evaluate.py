@@ -25,7 +25,9 @@ import os
 
 import torch
 
-from .train_diffusion_superres import (METRIC_FORMATS, Diffusion, build_arg_parser, launch_device, make_superres_feeds)
+from .sampling import plan_of
+from .train_diffusion_superres import (METRIC_FORMATS, Diffusion, add_solver_args, build_arg_parser, cli_sampling_steps,
+                                       launch_device, make_superres_feeds)
 from .UNet_model_superres import Residual_Attention_UNet_superres
 
 
@@ -134,12 +136,20 @@ def _sar_setup(args, device, snapshot):
     return model, diffusion, val_loader
 
 
+def sampling_line(sampling_steps, eta):
+    """The summary line's words for a chain of `sampling_steps` levels: solver, steps, eta and - unless it is plain DDIM on
+    uniform levels, whose words stay what they were - the spacing `plan_of` resolves."""
+    solver, spacing = plan_of(sampling_steps)
+    line = f"{'DPM-Solver++(2M)' if solver == 'dpmpp_2m' else 'DDIM'} {int(sampling_steps)} steps eta {eta}"
+    return line if (solver, spacing) == ("ddim", "uniform") else f"{line}, {spacing}-spaced levels"
+
+
 def main(argv=None):
     import argparse
     pre = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     pre.add_argument("--task", type=str, default="superres", choices=TASKS)
     task = pre.parse_known_args(argv)[0].task
-    p = add_ensemble_args(add_known_args(evaluate_arg_parser(task)))
+    p = add_solver_args(add_ensemble_args(add_known_args(evaluate_arg_parser(task))))
     args = p.parse_args(argv)
     if args.multiple_gpus:
         p.error("evaluate runs in one process: --multiple_gpus is not supported")
@@ -163,11 +173,11 @@ def main(argv=None):
     device = launch_device(args)
     model, diffusion, val_loader = (_sar_setup if task == "sar_to_ndvi" else _superres_setup)(args, device, snapshot)
     model.eval()
-    scores = diffusion.evaluate(model, unshuffled(val_loader), n_images=args.n_images, sampling_steps=args.sampling_steps,
+    scores = diffusion.evaluate(model, unshuffled(val_loader), n_images=args.n_images, sampling_steps=cli_sampling_steps(args),
                                 eta=args.eta, known_mask_fn=known_mask_fn(args), resample=args.resample, jump=args.jump,
                                 **({"ensemble": args.ensemble, "member_batch": args.member_batch} if args.ensemble else {}))
     print(f"{scores['n']} validation images, snapshot of epoch {diffusion.epochs_run}, "
-          + (f"DDIM {args.sampling_steps} steps eta {args.eta}" if args.sampling_steps else f"{args.noise_steps - 1} ancestral steps")
+          + (sampling_line(cli_sampling_steps(args), args.eta) if args.sampling_steps else f"{args.noise_steps - 1} ancestral steps")
           + (f", {args.known_fraction:.0%} of every image hidden, the rest known (resample {args.resample}, jump {args.jump})"
              if args.known_fraction is not None else "")
           + (f", ensembles of {args.ensemble} members" if args.ensemble else ""))

@@ -202,6 +202,35 @@ def ddim_step_(x, eps_cond, noise, t, t_prev, eta, alpha_hat, eps_uncond=None, c
     return x
 
 
+def _req_history(op, x, hist, t_q, state="x"):
+    """The x0 history of a DPM-Solver++(2M) move: as the state it goes with, used as it is, and memory of its own - the kernels
+    take both as __restrict__, so no byte of `hist` may lie inside `state` (a shifted view of one buffer is refused too)."""
+    _req_state(hist, op, "hist")
+    _req_numel(op, x, (("hist", hist),), state)
+    nbytes = x.numel() * x.element_size()
+    if hist.data_ptr() < x.data_ptr() + nbytes and x.data_ptr() < hist.data_ptr() + nbytes:
+        raise RuntimeError(f"{op}: hist must not overlap {state}")
+    return -1 if t_q is None else int(t_q)
+
+
+def dpm_step_(x, eps_cond, hist, t_q, t, t_p, alpha_hat, eps_uncond=None, cfg_scale=0.0):
+    """In-place DPM-Solver++(2M) move of x from level t to t_p (include/drs_hip.h: drs_dpm_step); `hist` (as x) receives the x0
+    prediction of this move and, when `t_q` - the level the previous move left - is given, supplies that move's: the move is
+    then second order.  `t_q` None or -1: first order, `hist` is only written.  Guidance as in `ddim_step_`."""
+    lib = _lib.load()
+    _req_state(x, "dpm_step_")
+    eps_cond = _req(eps_cond, "eps_cond")
+    eps_uncond = _req(eps_uncond, "eps_uncond") if eps_uncond is not None else None
+    alpha_hat = _req(alpha_hat, "alpha_hat")
+    t_q = _req_history("dpm_step_", x, hist, t_q)
+    _req_numel("dpm_step_", x, (("eps_cond", eps_cond), ("eps_uncond", eps_uncond)))
+    with torch.cuda.device(x.device):
+        st = lib.drs_dpm_step(_ptr(x), _ptr(eps_cond), _ptr(eps_uncond), float(cfg_scale), _ptr(hist), t_q, int(t), int(t_p),
+                              _ptr(alpha_hat), alpha_hat.numel(), x.numel(), _stream(x.device))
+    _lib.check(st, "drs_dpm_step")
+    return x
+
+
 def inpaint_step_(x, eps_cond, noise, known, mask, t, *, alpha_hat, alpha=None, beta=None, t_prev=None, eta=0.0,
                   eps_uncond=None, cfg_scale=0.0):
     """One reverse move of x (n, C, H, W) with known pixels, in place (include/drs_hip.h: drs_inpaint_step): where `mask`
@@ -249,11 +278,15 @@ def renoise_(x, noise, s, t, alpha_hat):
 
 
 def reverse_step_(x, eps, noise, t, t_prev, *, alpha, alpha_hat, beta, ddim=False, eta=0.0, eps_uncond=None, cfg_scale=0.0,
-                  known=None, known_mask=None):
-    """One reverse move t -> t_prev of x, in place, by the wrapper that takes this kind of move: `inpaint_step_` with `known`
-    / `known_mask`, else `ddim_step_` on a DDIM chain (`ddim`; t_prev and eta count there only) and `sampler_step_` /
-    `sampler_step_cfg_` (with `eps_uncond`) on the ancestral one, where t_prev is t - 1."""
+                  known=None, known_mask=None, hist=None, t_q=-1):
+    """One reverse move t -> t_prev of x, in place, by the wrapper that takes this kind of move: `dpm_step_` with a history
+    `hist` (and `t_q`), `inpaint_step_` with `known` / `known_mask`, else `ddim_step_` on a DDIM chain (`ddim`; t_prev and eta
+    count there only) and `sampler_step_` / `sampler_step_cfg_` (with `eps_uncond`) on the ancestral one, where t_prev is t - 1."""
     guided = {"eps_uncond": eps_uncond, "cfg_scale": cfg_scale}
+    if hist is not None:
+        if known is not None or noise is not None:
+            raise RuntimeError("reverse_step_: a DPM-Solver++(2M) move takes neither known pixels nor noise")
+        return dpm_step_(x, eps, hist, t_q, t, t_prev, alpha_hat, **(guided if eps_uncond is not None else {}))
     if known is not None:
         form = {"t_prev": t_prev, "eta": eta} if ddim else {"alpha": alpha, "beta": beta}
         return inpaint_step_(x, eps, noise, known, known_mask, t, alpha_hat=alpha_hat, **guided, **form)
@@ -328,12 +361,13 @@ def gather_tiles(scene, origins, S, out=None, first=0, count=None):
 
 
 def blend_step_(scene, eps_tiles, origins, weight, noise, t, *, alpha_hat, alpha=None, beta=None, t_prev=None, eta=0.0,
-                uncovered=None):
+                uncovered=None, hist=None, t_q=-1):
     """One reverse step of the scene state (C, H, W), in place, from the noise predictions `eps_tiles` (n, C, S, S) of
     its tiles (only the first n = len(origins) tiles of a longer buffer are read): Gaussian-weighted mean of the covering
     tiles' eps in tile order, then the update of `sampler_step_` (t_prev None: needs alpha and beta) or of `ddim_step_`
     (t -> t_prev with eta).  `noise` (scene shape) may be None as for those.  `uncovered`: optional int32 device counter
-    that is increased by the number of pixels no tile covers (include/drs_hip.h: drs_blend_step)."""
+    that is increased by the number of pixels no tile covers (include/drs_hip.h: drs_blend_step).  With `hist` (scene shape) the
+    update is that of `dpm_step_` from t to t_prev, `t_q` as there; it takes no noise (drs_blend_step_dpm)."""
     lib = _lib.load()
     _req_state(scene, "blend_step_", "scene")
     eps_tiles = _req(eps_tiles, "eps_tiles")
@@ -353,8 +387,17 @@ def blend_step_(scene, eps_tiles, origins, weight, noise, t, *, alpha_hat, alpha
     _req_numel("blend_step_", scene, (("noise", noise),), "scene")
     if uncovered is not None:
         uncovered = _req(uncovered, "uncovered", torch.int32)
+    if hist is not None:
+        if noise is not None or t_prev is None:
+            raise RuntimeError("blend_step_: a DPM-Solver++(2M) move (hist) needs t_prev and takes no noise")
+        t_q = _req_history("blend_step_", scene, hist, t_q, "scene")
     with torch.cuda.device(scene.device):
-        if t_prev is None:
+        if hist is not None:
+            st = lib.drs_blend_step_dpm(_ptr(scene), _ptr(eps_tiles), _ptr(origins), _ptr(weight), _ptr(hist), _ptr(uncovered),
+                                        n, C_, S, Hs, Ws, t_q, int(t), int(t_prev), _ptr(alpha_hat), alpha_hat.numel(),
+                                        _stream(scene.device))
+            _lib.check(st, "drs_blend_step_dpm")
+        elif t_prev is None:
             alpha = _req(alpha, "alpha"); beta = _req(beta, "beta")
             st = lib.drs_blend_step(_ptr(scene), _ptr(eps_tiles), _ptr(origins), _ptr(weight), _ptr(noise), _ptr(uncovered),
                                     n, C_, S, Hs, Ws, int(t), _ptr(alpha), _ptr(alpha_hat), _ptr(beta), alpha_hat.numel(),

@@ -4,6 +4,7 @@ import math
 import sys
 from typing import NamedTuple
 
+import numpy as np
 import torch
 
 from . import _lib, hip_ops
@@ -21,8 +22,87 @@ def ddim_timesteps(noise_steps, sampling_steps):
     return [1 + (k * (T - 2)) // (S - 1) for k in reversed(range(S))]
 
 
+SOLVERS = ("ddim", "dpmpp_2m")
+SPACINGS = ("uniform", "logsnr")
+
+
+class SamplingSteps(int):
+    """The `sampling_steps` of a chain that is not plain DDIM: the integer S, which also names the `solver` that takes the S steps
+    and the `spacing` of their levels.  It is an int, so everything that hands `sampling_steps` on - `sample_known`,
+    `sample_ensemble`, `evaluate`, the tiler, the trainers - hands the solver on with it.  Hand it on as it is: `int(plan)` and
+    arithmetic on it (`plan + 1`) give a plain integer, which is DDIM on uniform levels.  ValueError for a name that is no
+    solver or spacing, or steps that are no integer.  Usually made by `sampling_plan`."""
+    solver = "ddim"
+    spacing = None
+
+    def __new__(cls, steps, solver="ddim", spacing=None):
+        if solver not in SOLVERS:
+            raise ValueError(f"solver={solver!r} must be one of {SOLVERS}")
+        if spacing is not None and spacing not in SPACINGS:
+            raise ValueError(f"spacing={spacing!r} must be None or one of {SPACINGS}")
+        if isinstance(steps, bool) or int(steps) != steps:
+            raise ValueError(f"sampling_steps must be an integer, got {steps!r}")
+        self = super().__new__(cls, int(steps))
+        self.solver, self.spacing = solver, spacing
+        return self
+
+    def __repr__(self):
+        return f"SamplingSteps({int(self)}, solver={self.solver!r}, spacing={self.spacing!r})"
+
+
+def sampling_plan(steps, solver="ddim", spacing=None):
+    """`sampling_steps=sampling_plan(S, solver="dpmpp_2m")` for `Diffusion.sample` and everything that takes its
+    `sampling_steps`: S steps of `solver` - "ddim" or "dpmpp_2m" (DPM-Solver++(2M): second order, one forward per step,
+    deterministic) - on levels placed by `spacing`: "uniform" in t (`ddim_timesteps`), "logsnr" (`logsnr_timesteps`) or None,
+    which is uniform for "ddim" and logsnr for "dpmpp_2m".  A plain integer S is `sampling_plan(S)`: DDIM on uniform levels.
+    ValueError as `SamplingSteps`, and for a solver or spacing without steps."""
+    if steps is None:
+        raise ValueError(f"solver={solver!r} / spacing={spacing!r} belong to a chain of sampling_steps levels: pass the steps")
+    return SamplingSteps(steps, solver, spacing)
+
+
+def plan_of(sampling_steps):
+    """(solver, spacing) of a `sampling_steps` argument, the spacing resolved; ("ddim", "uniform") for a plain integer or None."""
+    solver = getattr(sampling_steps, "solver", "ddim")
+    spacing = getattr(sampling_steps, "spacing", None)
+    return solver, spacing if spacing is not None else ("logsnr" if solver == "dpmpp_2m" else "uniform")
+
+
+def logsnr_timesteps(alpha_hat, sampling_steps):
+    """S levels, descending and distinct, in [1, T - 1], as uniform in lam_t = 0.5 ln(ah_t / (1 - ah_t)) as the table allows
+    (float64 arithmetic on the fp32 table, one read-back per chain): for each of linspace(lam_{T-1}, lam_1, S) the nearest t
+    (ties: the larger t), then t_k = min(t_k, t_{k-1} - 1) going down the list and t_k = max(t_k, S - k) going back up, so
+    that the last entry is at least 1.  The step after the last entry goes to level 0, as after `ddim_timesteps`."""
+    ah = torch.as_tensor(alpha_hat).detach().to("cpu", torch.float64)
+    T, S = ah.numel(), int(sampling_steps)
+    if not 1 <= S <= T - 1:
+        raise ValueError(f"sampling_steps={sampling_steps} outside [1, noise_steps - 1 = {T - 1}]")
+    ah = ah.numpy()
+    lam = 0.5 * np.log(ah[1:] / (1.0 - ah[1:]))  # lam[t - 1] = lam_t, decreasing in t
+    targets = np.linspace(lam[-1], lam[0], S)
+    dist = np.abs(lam[None, ::-1] - targets[:, None])  # (S, T - 1), column j: t = T - 1 - j
+    ts = [T - 1 - int(j) for j in np.argmin(dist, axis=1)]  # the nearest t; np.argmin takes the first: the larger t of a tie
+    for k in range(1, S):
+        ts[k] = min(ts[k], ts[k - 1] - 1)
+    for k in range(S - 1, -1, -1):
+        ts[k] = max(ts[k], S - k)
+    return ts
+
+
+def chain_levels(noise_steps, sampling_steps=None, spacing="uniform", alpha_hat=None):
+    """The levels a chain visits, descending, without the final 0: the ancestral T - 1 .. 1 (`sampling_steps` None), the
+    `ddim_timesteps`, or the `logsnr_timesteps` of `alpha_hat`."""
+    if sampling_steps is None:
+        return list(range(int(noise_steps) - 1, 0, -1))
+    if spacing == "logsnr":
+        if alpha_hat is None or len(alpha_hat) != noise_steps:
+            raise ValueError("spacing='logsnr' needs the alpha_hat table of the noise_steps levels")
+        return logsnr_timesteps(alpha_hat, sampling_steps)
+    return ddim_timesteps(noise_steps, sampling_steps)
+
+
 def check_sampling_args(noise_steps, sampling_steps, eta):
-    """ValueError for a DDIM request `Diffusion.sample` cannot run (checked before the engine is touched)."""
+    """ValueError for a DDIM or DPM-Solver++(2M) request `Diffusion.sample` cannot run (checked before the engine is touched)."""
     if sampling_steps is not None:
         if isinstance(sampling_steps, bool) or int(sampling_steps) != sampling_steps:
             raise ValueError(f"sampling_steps must be an integer, got {sampling_steps!r}")
@@ -30,6 +110,15 @@ def check_sampling_args(noise_steps, sampling_steps, eta):
             raise ValueError(f"sampling_steps={sampling_steps} outside [1, noise_steps - 1 = {noise_steps - 1}]")
     if not (math.isfinite(eta) and eta >= 0):
         raise ValueError(f"eta={eta} must be finite and >= 0")
+    if plan_of(sampling_steps)[0] == "dpmpp_2m" and eta > 0:
+        raise ValueError(f"solver='dpmpp_2m' is deterministic: eta={eta} must be 0")
+
+
+def check_solver_known(sampling_steps, known, known_mask):
+    """ValueError for known pixels on a DPM-Solver++(2M) chain (checked before the engine is touched)."""
+    if plan_of(sampling_steps)[0] == "dpmpp_2m" and (known is not None or known_mask is not None):
+        raise ValueError("solver='dpmpp_2m' cannot keep known pixels: their replacement and the forward jumps of the "
+                         "resampling invalidate the multistep history (use solver='ddim' or the ancestral chain)")
 
 
 def ddim_chain_noise(eta, t, t_prev, shape, x, noise_source):
@@ -171,11 +260,11 @@ class Move(NamedTuple):
         return str(self.t)
 
 
-def chain_moves(noise_steps, sampling_steps=None, resample=1, jump=1):
-    """The moves of a chain, in order, over its levels: the ancestral T - 1 .. 1 (`sampling_steps` None) or the `ddim_timesteps`,
-    then 0.  Without resampling it steps from each level to the next; `resample` / `jump` walk them as `inpaint_schedule` says."""
-    levels = (ddim_timesteps(noise_steps, sampling_steps) if sampling_steps is not None
-              else list(range(int(noise_steps) - 1, 0, -1))) + [0]
+def chain_moves(noise_steps, sampling_steps=None, resample=1, jump=1, spacing="uniform", alpha_hat=None):
+    """The moves of a chain, in order, over its levels: the ancestral T - 1 .. 1 (`sampling_steps` None), the `ddim_timesteps`
+    or - `spacing` "logsnr" - the `logsnr_timesteps` of `alpha_hat`, then 0 (`chain_levels`).  Without resampling it steps from
+    each level to the next; `resample` / `jump` walk them as `inpaint_schedule` says."""
+    levels = chain_levels(noise_steps, sampling_steps, spacing, alpha_hat) + [0]
     return [Move(levels[p], levels[q]) for p, q in inpaint_schedule(len(levels) - 1, resample, jump)]
 
 
@@ -186,15 +275,27 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
     One `step` takes every move of `chain_moves`.  A forward jump to level t_to is one `renoise_` with the draw for t_to.  A
     reverse move t -> t_to is one `predict`, at most one draw - for t - and the `update` hook or one `hip_ops.reverse_step_`;
     it draws iff it ends above level 0 and adds noise there: always on the ancestral chain and with known pixels (whose
-    forward noise it also is), on a DDIM chain without them only when eta > 0."""
+    forward noise it also is), on a DDIM chain without them only when eta > 0.
+    `sampling_steps` may be a `sampling_plan`; its solver "dpmpp_2m" (DPM-Solver++(2M): eta = 0, no known pixels: checked
+    by the caller, `check_sampling_args` in every `Diffusion._sample` and `check_solver_known` in `_sample_chain`) takes every
+    move with `hip_ops.dpm_step_` - or the `update` hook, which then also gets `hist=` and `t_q=` - and draws nothing but x_T.
+    The chain owns the history `hist` (state shape, allocated once: the x0 prediction of the move that wrote it last) and
+    `hist_level`, that move's t.  A move is second order iff `hist_level` is the level before its t in the level list and it does
+    not end at level 0; so the first move is first order, and so is the move a roll-back of `run_reverse_chain` resumes at
+    (the history then holds the x0 of a later move).  Its spacing places the levels (`plan_of`)."""
     ddim = sampling_steps is not None
+    solver, spacing = plan_of(sampling_steps)
+    dpm = solver == "dpmpp_2m"
+    moves = chain_moves(schedule.noise_steps, sampling_steps, resample, jump, spacing, schedule.alpha_hat if ddim else None)
     with torch.no_grad():
         x = noise_source(schedule.noise_steps, shape) if noise_source is not None else torch.randn(shape)  # (CPU generator, :230)
         x = x.to(schedule.device).contiguous()
         t_rows = hip_ops.timestep_table(schedule.noise_steps, table_rows, x.device)
         if known is not None:
             known, known_mask = known_tensors(shape, known, known_mask, x.device)
-        state = {"first": True}  # (not set again after a roll-back)
+        state = {"first": True, "hist_level": None}  # (`first` is not set again after a roll-back)
+        hist = torch.empty_like(x) if dpm else None
+        level_before = {m.t: before.t for before, m in zip(moves, moves[1:])} if dpm else {}
 
         def draw(t):
             return noise_source(t, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
@@ -208,7 +309,16 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
                 state["first"] = False
                 eps, eps_uncond = eps if isinstance(eps, tuple) else (eps, None)
                 noise = draw(t) if t_to > 0 and (known is not None or not ddim or eta > 0) else None
-                if update is not None:
+                if dpm:
+                    second = t_to > 0 and state["hist_level"] is not None and state["hist_level"] == level_before.get(t)
+                    order = {"hist": hist, "t_q": state["hist_level"] if second else -1}
+                    state["hist_level"] = t
+                    if update is not None:
+                        update(x, eps, None, t, t_to, **order)
+                    else:
+                        hip_ops.reverse_step_(x, eps, None, t, t_to, alpha=schedule.alpha, alpha_hat=schedule.alpha_hat,
+                                              beta=schedule.beta, ddim=True, eps_uncond=eps_uncond, cfg_scale=cfg_scale, **order)
+                elif update is not None:
                     update(x, eps, noise, t, t_to if ddim else None)
                 else:
                     hip_ops.reverse_step_(x, eps, noise, t, t_to, alpha=schedule.alpha, alpha_hat=schedule.alpha_hat,
@@ -216,6 +326,5 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
                                           known=known, known_mask=known_mask)
             if frames is not None:
                 frames.append(x.clone())
-        run_reverse_chain(engine, x, schedule.noise_steps, step, frames,
-                          timesteps=chain_moves(schedule.noise_steps, sampling_steps, resample, jump))
+        run_reverse_chain(engine, x, schedule.noise_steps, step, frames, timesteps=moves)
     return x

@@ -22,8 +22,9 @@ from . import dist as drs_dist
 from . import hip_ops
 from .optim import FusedAdam
 from .sampling import (CHAIN_CHECK_EVERY, _is_int, _repeat_members, asks_for_known_pixels,  # noqa: F401 - re-exported
-                       check_ensemble_args, check_inpaint_args, check_sampling_args, ddim_chain_noise, ddim_timesteps,
-                       ensemble_chunks, inpaint_schedule, known_tensors, run_reverse_chain, sample_chain)
+                       check_ensemble_args, check_inpaint_args, check_sampling_args, check_solver_known, ddim_chain_noise,
+                       ddim_timesteps, ensemble_chunks, inpaint_schedule, known_tensors, run_reverse_chain, sample_chain,
+                       sampling_plan)
 from .UNet_model_superres import EMA, Residual_Attention_UNet_superres
 
 _DEGRADATIONS = ("downblur", "bsrgan", "downblurnoise")
@@ -105,7 +106,10 @@ class Diffusion:
         """`noise_source(i, shape)`, when given, supplies x_T (i == noise_steps) and the per-step noise z_i
         instead of torch.randn — used to drive this sampler and the oracle with identical noise.
         `sampling_steps=S` runs a DDIM chain over the S timesteps of `ddim_timesteps` instead of the reference's ancestral
-        chain (None); `eta` moves it from deterministic (0) to DDPM-like (1) sampling.  (`sample_known` keeps given pixels.)"""
+        chain (None); `eta` moves it from deterministic (0) to DDPM-like (1) sampling.  (`sample_known` keeps given pixels.)
+        `sampling_steps=sampling_plan(S, solver="dpmpp_2m")` takes the S steps with DPM-Solver++(2M) instead - second order, one
+        forward per step like DDIM, deterministic (eta = 0) - on logSNR-spaced levels; `sampling_plan(S, spacing="logsnr")` is
+        DDIM on those levels (`sampling.sampling_plan`).  Whatever takes `sampling_steps` takes such a plan."""
         return self._sample(n, model, lr_img, input_channels, generate_video, noise_source, sampling_steps, eta)
 
     def sample_known(self, n, model, lr_img, known, known_mask, input_channels=3, resample=1, jump=1, generate_video=False,
@@ -180,7 +184,10 @@ class Diffusion:
         known pixels become `known` forward-noised to t_prev, the others take the sampler's step) and draws one noise tensor -
         `noise_source(t, shape)` - iff t_prev > 0, whatever eta is; a forward jump of `inpaint_schedule` to level t is one
         `renoise_` and draws `noise_source(t, shape)`.  On the ancestral chain without resampling these are the draws of the
-        plain sampler.  The chain is `sampling.sample_chain`; this method adds the eval mode around it and the video."""
+        plain sampler.  With a `sampling_plan` of solver "dpmpp_2m" the moves are `dpm_step_`s and the `update` hook also gets
+        `hist=` and `t_q=`, as `sampling.sample_chain` says.  The chain is `sampling.sample_chain`; this method adds the eval
+        mode around it and the video."""
+        check_solver_known(sampling_steps, known, known_mask)
         if known is not None and update is not None:
             raise ValueError("known pixels cannot be combined with an `update` hook (the tiler's per-step blend)")
         net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
@@ -655,6 +662,23 @@ def build_arg_parser():
     p.add_argument("--num_crops", type=int, default=1)
     p.add_argument("--Blur_radius", type=str, default="random")
     return p
+
+
+def add_solver_args(p):
+    """--solver / --spacing for the command lines that take them next to --sampling_steps (`cli_sampling_steps`)."""
+    p.add_argument("--solver", type=str, choices=("ddim", "dpmpp_2m"), default="ddim",
+                   help="how the --sampling_steps steps are taken: ddim, or dpmpp_2m (DPM-Solver++(2M): second order, eta 0)")
+    p.add_argument("--spacing", type=str, choices=("uniform", "logsnr"), default=None,
+                   help="where the --sampling_steps levels lie: uniform in t or uniform in logSNR; default: uniform for ddim, "
+                        "logsnr for dpmpp_2m")
+    return p
+
+
+def cli_sampling_steps(args):
+    """The `sampling_steps` argument of a command line: --sampling_steps, as a `sampling_plan` when --solver / --spacing say more."""
+    solver, spacing = getattr(args, "solver", "ddim"), getattr(args, "spacing", None)
+    steps = getattr(args, "sampling_steps", None)
+    return steps if solver == "ddim" and spacing is None else sampling_plan(steps, solver, spacing)
 
 
 def add_sampling_args(p):

@@ -102,6 +102,24 @@ DRS_API int drs_ddim_step(float* x, const float* eps_cond, const float* eps_unco
                           int t, int t_prev, float eta, const float* alpha_hat, int noise_steps, int64_t numel,
                           drs_stream_t stream);
 
+/* One DPM-Solver++(2M) move (Lu et al., "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models",
+ * 2022, Algorithm 2), in place on x, from level t to t_p, with the level t_q > t the previous move left (-1: none).  With
+ * a = sqrt(ah), s = sqrt(1 - ah), lam = ln(a / s), E = (s_p / a_p)(a_t / s_t), phi = a_p (1 - E) and
+ * r = (lam_t - lam_q) / (lam_p - lam_t):
+ *   eps  = eps_uncond ? lerp(eps_uncond, eps_cond, cfg_scale) : eps_cond            (as drs_ddim_step)
+ *   x0   = (x - s_t eps) / a_t
+ *   x    = (s_p / s_t) x + phi ((1 + 1 / (2 r)) x0 - 1 / (2 r) x0_hist)             t_q >= 0 (second order)
+ *   x    = (s_p / s_t) x + phi x0                                                    t_q == -1 (first order: the DDIM
+ *                                                                                    eta = 0 move)
+ * and x0 is then stored to x0_hist (numel fp32; written by every move, read by a second-order one only, so it may be
+ * uninitialised at the first move of a chain).  The move is applied as x0 = cx x + ce eps, x = A x + B eps + C x0_hist with
+ * five coefficients formed in fp64 from the device table and rounded to fp32 once; products and sums are fp32, rounded one
+ * by one.  E is formed without logarithms: the move to level 0 must be first order (alpha_hat[0] may be 1).  16-byte
+ * accesses when every pointer is 16-byte aligned, element by element otherwise.  DRS_ERR_ARG: null pointer (eps_uncond may
+ * be NULL), not 0 <= t_p < t < noise_steps, t_q neither -1 nor in (t, noise_steps), t_q >= 0 with t_p == 0, numel < 0. */
+DRS_API int drs_dpm_step(float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale, float* x0_hist, int t_q,
+                         int t, int t_p, const float* alpha_hat, int noise_steps, int64_t numel, drs_stream_t stream);
+
 /* One reverse move t -> t_prev with known pixels (RePaint, Lugmayr et al., CVPR 2022, Algorithm 1, lines 4-8), in place on
  * x and in one pass (csrc/inpaint.hip).  x, eps_cond, eps_uncond, noise, known: (n,C,H,W) fp32; mask: (n,mask_channels,H,W)
  * uint8 with mask_channels 1 (one entry per pixel, shared by the C bands) or C; a nonzero entry marks a known pixel.
@@ -202,6 +220,15 @@ DRS_API int drs_blend_step(float* scene, const float* eps_tiles, const int32_t* 
 DRS_API int drs_blend_step_ddim(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight,
                                 const float* noise, int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t,
                                 int t_prev, float eta, const float* alpha_hat, int noise_steps, drs_stream_t stream);
+
+/* The same blend followed by exactly the move of drs_dpm_step (no guidance) from level t to t_p on the scene state, with a
+ * history `x0_hist` of scene shape (C,Hs,Ws) and the previous level t_q (-1: first order).  It draws no noise.  `x0_hist` is
+ * accessed like `scene` and `noise` (16 bytes per access when S and Ws are multiples of 4; unlike drs_dpm_step there is no
+ * element-wise path for a base pointer that is not 16-byte aligned) and must not overlap `scene`.
+ * DRS_ERR_ARG: null pointer, or a move drs_dpm_step refuses; DRS_ERR_SHAPE as drs_blend_step. */
+DRS_API int drs_blend_step_dpm(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight,
+                               float* x0_hist, int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t_q, int t,
+                               int t_p, const float* alpha_hat, int noise_steps, drs_stream_t stream);
 
 /* Image-quality sums of an estimate `sr` against the truth `hr`, per image (csrc/metrics.hip; finalised into PSNR, SSIM, SAM
  * and ERGAS by diffusionremotesensing_amd/metrics.py).  Not in the reference, which only looks at its samples.
