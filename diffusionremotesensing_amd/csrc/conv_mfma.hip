@@ -464,7 +464,7 @@ bool drs_tapconv_mfma_supported(const TapConv& d, int impl) {
   if (d.in2 && d.in2_sp != d.in_sp) return false;
   if ((d.out2 || d.dual) && !drs_tapconv_sp_supported(d, impl) && !(d.dual && drs_tapconv_ws_supported(d, impl)) &&
       !(d.out2 && !d.dual && drs_tapconv_sp8_supported(d, impl)))
-    return false;  // second outputs / fused pairs come from the wave-specialised kernels only (plan.hip has the fallbacks)
+    return false;  // second outputs / fused pairs come from the wave-specialised kernels only (unet_forward.hip has the fallbacks)
   if (d.in_sp && (d.in_add || (d.in_co & 31) || (d.in_cs != 16 && (d.in_cs & 31)))) return false;
   if (d.in2_sp && ((d.in2_co & 31) || (d.in2_cs != 16 && (d.in2_cs & 31)))) return false;
   if (d.out_sp && ((d.out_co & 31) || (d.out_cs & 31) || d.fuse_out || (d.out2 && ((d.out2_co & 31) || (d.out2_cs & 31))))) return false;

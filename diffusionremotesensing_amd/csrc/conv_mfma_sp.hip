@@ -30,7 +30,7 @@
 // DUAL = conv1 + skip convolution of the first residual block from one 64-channel operand image; F32OUT = SP-format input,
 // fp32 channels-last output through the general epilogue (residual accumulate included): the data-gradient convolutions of
 // the training step, whose inputs (dZ of a BatchNorm backward) are written in SP form by bn_bwd_apply_kernel and whose
-// outputs feed fp32 consumers (train_bwd.inc).
+// outputs feed fp32 consumers (unet_backward.hip).
 #include <stdio.h>
 #include <stdlib.h>
 

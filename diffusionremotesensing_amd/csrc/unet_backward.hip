@@ -1,11 +1,18 @@
-// Backward schedule of one training step through the UNet (included at the end of plan.hip: same translation unit,
-// it works on drs_plan's layer tables and workspace tensors).
+// Backward schedule of one training step through the UNet (its own translation unit;
+// it works on drs_plan's layer tables and workspace tensors through unet_plan.h).
 //
 // Mirrors what autograd does for the reference graph (UNet_model_superres.py:337-379 under model.train()), given
 // d(loss)/d(output).  Data gradients are tap-convolutions with re-packed weights (same kernels as the forward);
 // weight gradients use wgrad_kernel; BatchNorm uses the batch statistics saved by the train-mode forward.
 // Requires: a train plan (DRS_PLAN_TRAIN), lr_batch == batch, and the workspace exactly as the last
 // drs_unet_forward on this plan left it.
+
+#include <stdlib.h>
+#include <string.h>
+#include <algorithm>
+#include <utility>
+
+#include "unet_plan.h"
 
 // Output channels of a layer's data-gradient convolution as the MFMA kernels run it: the layer's Cin, with the 16-channel
 // case (gradient w.r.t. x0) padded to the 32-channel tile (zero weights; the gradient tensor has a 32-float pixel stride).

@@ -121,7 +121,7 @@ DRS_API int drs_dpm_step(float* x, const float* eps_cond, const float* eps_uncon
                          int t, int t_p, const float* alpha_hat, int noise_steps, int64_t numel, drs_stream_t stream);
 
 /* One reverse move t -> t_prev with known pixels (RePaint, Lugmayr et al., CVPR 2022, Algorithm 1, lines 4-8), in place on
- * x and in one pass (csrc/inpaint.hip).  x, eps_cond, eps_uncond, noise, known: (n,C,H,W) fp32; mask: (n,mask_channels,H,W)
+ * x and in one pass (csrc/reverse_step.hip).  x, eps_cond, eps_uncond, noise, known: (n,C,H,W) fp32; mask: (n,mask_channels,H,W)
  * uint8 with mask_channels 1 (one entry per pixel, shared by the C bands) or C; a nonzero entry marks a known pixel.
  *   mask == 0:  the update of drs_sampler_step / drs_sampler_step_cfg (ddim == 0: t_prev = t - 1 is implied, `t_prev` and
  *               `eta` are ignored, alpha / alpha_hat / beta are read) or of drs_ddim_step (ddim != 0: alpha and beta may be

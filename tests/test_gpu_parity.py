@@ -897,7 +897,7 @@ def test_conv_kernel_variants_in_subprocess(env):
                          ids=["exact-fp32-backward", "exact-data-gradients", "exact-weight-gradients",
                               "in-order-weight-gradients"])
 def test_backward_product_arithmetic_variants(env):
-    """Training default: exact-fp32 forward, backward PRODUCTS (data gradients: csrc/train_bwd.inc, weight gradients:
+    """Training default: exact-fp32 forward, backward PRODUCTS (data gradients: csrc/unet_backward.hip, weight gradients:
     csrc/wgrad_mfma_bf16.hip) on split bf16 with fp32 accumulation - the golden gradient test holds at its fp32 tolerance
     (2e-4) and the full-size configs[2] step at 1e-3 either way, because the gradient error of split-bf16 TRAINING comes from
     the forward activations (amplified by the BatchNorm-backward cancellations), not from the backward products.  The
