@@ -184,22 +184,42 @@ class split_aggregation_sampling:
             raise AssertionError("aggregation: some scene pixels are covered by no tile (pixel_count == 0)")
         return x[0]
 
-    def aggregation_sampling(self, noise_source=None, sampling_steps=None, eta=0.0, aggregation="final"):
+    def aggregation_sampling(self, noise_source=None, sampling_steps=None, eta=0.0, aggregation="final", color_fix=None,
+                             color_fix_levels=5):
         """Reference :76-116 (`sampling_steps` / `eta`: every tile runs a DDIM chain).  `aggregation`: "final" (the
         reference: independent tile chains, blended once; `noise_source(tile, i, shape)`) or "per_step" (`sample_scene`:
-        one joint chain, blended at every step; `noise_source(i, scene_shape)`), clamped to [0, 1]."""
+        one joint chain, blended at every step; `noise_source(i, scene_shape)`), clamped to [0, 1].
+        `color_fix`: None (the default: nothing changes), "wavelet" (with `color_fix_levels`) or "adain" - the finished, clamped
+        scene is corrected once as a whole, never per tile, against the bicubic up-sampling of img_lr's first image
+        (`colorfix.color_fix`) and clamped to [0, 1] again."""
         if aggregation not in ("final", "per_step"):
             raise ValueError(f"aggregation={aggregation!r} must be 'final' or 'per_step'")
+        fix = self._color_fix(color_fix, color_fix_levels)
         batch_size, channels, height, width = self.img_lr.shape
         m = self.magnification_factor
         if aggregation == "per_step":
-            out = torch.clamp(self.sample_scene(noise_source, sampling_steps=sampling_steps, eta=eta), 0, 1)
+            out = fix(torch.clamp(self.sample_scene(noise_source, sampling_steps=sampling_steps, eta=eta), 0, 1))
             return out.unsqueeze(0).expand(batch_size, -1, -1, -1).contiguous()
         tiles = self.sample_tiles(noise_source, sampling_steps=sampling_steps, eta=eta)
         origins = [(info[0], info[2]) for info in self.patches_sr_infos]
-        out = hip_ops.aggregate_tiles(tiles, origins, self.weight[0, 0].contiguous(), height * m, width * m)
+        out = fix(hip_ops.aggregate_tiles(tiles, origins, self.weight[0, 0].contiguous(), height * m, width * m))
         # the reference broadcasts the single chain of each tile over the batch dimension of img_lr
         return out.unsqueeze(0).expand(batch_size, -1, -1, -1).contiguous()
+
+    def _color_fix(self, method, levels):
+        """f(clamped scene (C, Hs, Ws)) -> the scene `aggregation_sampling` returns: the identity without a method (checked
+        here, before anything is sampled)."""
+        if method is None:
+            return lambda scene: scene
+        from .colorfix import color_fix, fix_levels
+        levels = fix_levels(method, levels)
+
+        def fix(scene):
+            lr = self.img_lr[:1].to(scene.device, torch.float32).contiguous()
+            fixed = color_fix(scene.unsqueeze(0), lr, magnification_factor=self.magnification_factor, method=method,
+                              levels=levels)
+            return torch.clamp(fixed[0], 0, 1)
+        return fix
 
 
 def launch(args):
@@ -208,6 +228,7 @@ def launch(args):
     (1,C,H,W) in [0,1], `--destination_path` receives a `.pt` tensor."""
     import os
 
+    from .colorfix import cli_color_fix
     from .train_diffusion_superres import Diffusion, cli_sampling_steps
     from .UNet_model_superres import Residual_Attention_UNet_superres
     device = args.device
@@ -230,14 +251,16 @@ def launch(args):
     tiler = split_aggregation_sampling(img_lr, args.patch_size, args.stride, args.magnification_factor, diffusion, device)
     final_pred = tiler.aggregation_sampling(sampling_steps=cli_sampling_steps(args),
                                             eta=getattr(args, "eta", 0.0),
-                                            aggregation=getattr(args, "aggregation", "final"))
+                                            aggregation=getattr(args, "aggregation", "final"),
+                                            **cli_color_fix(args))
     torch.save(final_pred.squeeze(0).cpu(), args.destination_path)
 
 
 def build_arg_parser():
-    """The reference's flags, verbatim (:217-231), the DDIM flags and --aggregation."""
+    """The reference's flags, verbatim (:217-231), the DDIM flags, --aggregation and the colour-correction flags."""
     import argparse
 
+    from .colorfix import add_color_fix_args
     from .train_diffusion_superres import add_sampling_args, add_solver_args
     p = argparse.ArgumentParser(description=" ")
     p.add_argument("--noise_schedule", type=str, default="cosine")
@@ -259,6 +282,7 @@ def build_arg_parser():
     p.add_argument("--aggregation", type=str, choices=("final", "per_step"), default="final",
                    help="final: independent tile chains blended once (the reference); per_step: one joint chain of the "
                         "whole scene, the tiles' noise predictions blended at every reverse step")
+    add_color_fix_args(p)
     return p
 
 

@@ -8,5 +8,8 @@ The C-ABI underneath is declared in include/drs_hip.h.
 from .UNet_model_superres import EMA, Residual_Attention_UNet_superres  # noqa: F401
 from .train_diffusion_superres import Diffusion, launch  # noqa: F401
 from .ensemble import ensemble_scores, ensemble_statistics  # noqa: F401
+from . import colorfix  # noqa: F401
+from .colorfix import color_fix  # noqa: F401
 
-__all__ = ["EMA", "Residual_Attention_UNet_superres", "Diffusion", "launch", "ensemble_scores", "ensemble_statistics"]
+__all__ = ["EMA", "Residual_Attention_UNet_superres", "Diffusion", "launch", "ensemble_scores", "ensemble_statistics",
+           "colorfix", "color_fix"]

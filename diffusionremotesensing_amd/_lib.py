@@ -56,6 +56,9 @@ SIGNATURES = {
     "drs_ensemble_workspace_bytes": (_Z, [_I] * 5),
     "drs_ensemble_stats": (_I, [_P] * 5 + [_I] * 7 + [_F, _F, _P]),
     "drs_ensemble_scores": (_I, [_P] * 5 + [_I] * 6 + [_F, _F, _P, _Z, _P]),
+    "drs_colorfix_wavelet": (_I, [_P, _P, _P] + [_I] * 5 + [_P]),
+    "drs_colorfix_adain_workspace_bytes": (_Z, [_I] * 4),
+    "drs_colorfix_adain": (_I, [_P, _P, _P] + [_I] * 4 + [_P, _Z, _P]),
     "drs_conv2d_workspace_bytes": (_Z, [_I] * 11),
     "drs_conv2d_nchw": (_I, [_P, _P, _P, _P] + [_I] * 12 + [_P, _Z, _I, _P]),
     "drs_upconv_fused_workspace_bytes": (_Z, [_I] * 5),

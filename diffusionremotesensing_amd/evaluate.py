@@ -19,12 +19,16 @@ cover the fraction F, sampled with the remaining pixels as `known` (`--resample`
 `--ensemble N [--member_batch M]` draws N samples per image (`Diffusion.sample_ensemble`, M members per sampling call): the
 `model` row then scores the per-pixel ensemble mean, a `member` row the single draw reported without the flag, and one more
 line gives CRPS, spread, RMSE of the mean, the spread / skill ratio and the rank histogram (ensemble.py).
+
+`--color_fix wavelet|adain [--color_fix_levels L]` (superres only: the task with an LR guide) adds a `model_fixed` row: the
+same samples, colour-corrected against the up-sampled LR image (colorfix.py).
 """
 import json
 import os
 
 import torch
 
+from .colorfix import add_color_fix_args, cli_color_fix
 from .sampling import plan_of
 from .train_diffusion_superres import (METRIC_FORMATS, Diffusion, add_solver_args, build_arg_parser, cli_sampling_steps,
                                        launch_device, make_superres_feeds)
@@ -83,10 +87,11 @@ def format_table(scores):
     """The means of `Diffusion.evaluate` as a table: PSNR to 0.01 dB, SSIM to 4 decimals, SAM to 0.001 degrees, ERGAS to 4
     significant digits."""
     keys = list(scores["model"])
-    lines = [f"{'':10s}" + "".join(f"{METRIC_FORMATS[k][0]:>14s}" for k in keys)]
-    for name in ("model", "member", "bicubic"):
+    w = 12 if "model_fixed" in scores else 10
+    lines = [f"{'':{w}s}" + "".join(f"{METRIC_FORMATS[k][0]:>14s}" for k in keys)]
+    for name in ("model", "model_fixed", "member", "bicubic"):
         if name in scores:  # (a score only the model has, psnr_unknown, leaves the baseline's cell empty)
-            lines.append(f"{name:10s}" + "".join(
+            lines.append(f"{name:{w}s}" + "".join(
                 f"{METRIC_FORMATS[k][1].format(scores[name][k]) if k in scores[name] else '-':>14s}" for k in keys))
     return "\n".join(lines)
 
@@ -144,12 +149,19 @@ def sampling_line(sampling_steps, eta):
     return line if (solver, spacing) == ("ddim", "uniform") else f"{line}, {spacing}-spaced levels"
 
 
+def cli_arg_parser(task="superres"):
+    """The whole command line of `main` for `task`: `evaluate_arg_parser` with the known-pixel, ensemble and solver flags and,
+    for superres (the task with an LR guide), --color_fix / --color_fix_levels."""
+    p = add_solver_args(add_ensemble_args(add_known_args(evaluate_arg_parser(task))))
+    return add_color_fix_args(p) if task == "superres" else p
+
+
 def main(argv=None):
     import argparse
     pre = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     pre.add_argument("--task", type=str, default="superres", choices=TASKS)
     task = pre.parse_known_args(argv)[0].task
-    p = add_solver_args(add_ensemble_args(add_known_args(evaluate_arg_parser(task))))
+    p = cli_arg_parser(task)
     args = p.parse_args(argv)
     if args.multiple_gpus:
         p.error("evaluate runs in one process: --multiple_gpus is not supported")
@@ -165,6 +177,11 @@ def main(argv=None):
         p.error("--member_batch (>= 1) belongs to --ensemble")
     if args.ensemble is not None and args.known_fraction is not None:
         p.error("--ensemble and --known_fraction cannot be combined")
+    fix = cli_color_fix(args)
+    if fix and (args.ensemble is not None or args.known_fraction is not None):
+        p.error("--color_fix cannot be combined with --ensemble or --known_fraction")
+    if fix and fix["color_fix"] == "adain" and fix["color_fix_levels"] != 5:
+        p.error("--color_fix_levels belongs to --color_fix wavelet")
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     snapshot = os.path.join(args.snapshot_folder_path, args.snapshot_name)
     if not os.path.exists(snapshot):
@@ -175,12 +192,14 @@ def main(argv=None):
     model.eval()
     scores = diffusion.evaluate(model, unshuffled(val_loader), n_images=args.n_images, sampling_steps=cli_sampling_steps(args),
                                 eta=args.eta, known_mask_fn=known_mask_fn(args), resample=args.resample, jump=args.jump,
-                                **({"ensemble": args.ensemble, "member_batch": args.member_batch} if args.ensemble else {}))
+                                **({"ensemble": args.ensemble, "member_batch": args.member_batch} if args.ensemble else {}),
+                                **fix)
     print(f"{scores['n']} validation images, snapshot of epoch {diffusion.epochs_run}, "
           + (sampling_line(cli_sampling_steps(args), args.eta) if args.sampling_steps else f"{args.noise_steps - 1} ancestral steps")
           + (f", {args.known_fraction:.0%} of every image hidden, the rest known (resample {args.resample}, jump {args.jump})"
              if args.known_fraction is not None else "")
-          + (f", ensembles of {args.ensemble} members" if args.ensemble else ""))
+          + (f", ensembles of {args.ensemble} members" if args.ensemble else "")
+          + (f", model_fixed: {fix['color_fix']} colour correction against the up-sampled LR image" if fix else ""))
     print(format_table(scores))
     if "ensemble" in scores:
         print(format_ensemble(scores["ensemble"]))

@@ -522,3 +522,41 @@ def ensemble_scores(members, truth, clamp=None, crps_map=False):
                                      hi, _ptr(ws), ws.numel(), _stream(members.device))
     _lib.check(st, "drs_ensemble_scores")
     return sums, hist, crps
+
+
+def _req_colorfix(sr, guide, what):
+    """The (B, C, H, W) pair of a colour-correction call.  Like the ensemble wrappers these refuse a non-contiguous tensor
+    instead of copying it."""
+    for t, name in ((sr, "sr"), (guide, "guide")):
+        _req(t, name)
+        if not t.is_contiguous():
+            raise RuntimeError(f"{what}: {name} {tuple(t.shape)} with strides {t.stride()} must be contiguous")
+    if sr.dim() != 4 or sr.shape != guide.shape:
+        raise RuntimeError(f"{what}: sr {tuple(sr.shape)} and guide {tuple(guide.shape)} must be the same (B, C, H, W)")
+    if guide.device != sr.device:
+        raise RuntimeError(f"{what}: sr is on {sr.device}, guide on {guide.device}")
+
+
+def colorfix_wavelet(sr, guide, levels=5):
+    """sr + low(guide - sr) per plane of (B, C, H, W), `low` = `levels` (1 .. 5) dilated 3 x 3 binomial blurs on replicate
+    padding: the sample's detail on the guide's large-scale content (include/drs_hip.h: drs_colorfix_wavelet)."""
+    lib = _lib.load()
+    _req_colorfix(sr, guide, "colorfix_wavelet")
+    out = torch.empty_like(sr)
+    with torch.cuda.device(sr.device):
+        st = lib.drs_colorfix_wavelet(_ptr(sr), _ptr(guide), _ptr(out), *sr.shape, int(levels), _stream(sr.device))
+    _lib.check(st, "drs_colorfix_wavelet")
+    return out
+
+
+def colorfix_adain(sr, guide):
+    """a sr + b per plane of (B, C, H, W), with the plane's mean and unbiased standard deviation moved onto the guide's
+    (include/drs_hip.h: drs_colorfix_adain)."""
+    lib = _lib.load()
+    _req_colorfix(sr, guide, "colorfix_adain")
+    out = torch.empty_like(sr)
+    ws = torch.empty(max(lib.drs_colorfix_adain_workspace_bytes(*sr.shape), 8), dtype=torch.uint8, device=sr.device)
+    with torch.cuda.device(sr.device):
+        st = lib.drs_colorfix_adain(_ptr(sr), _ptr(guide), _ptr(out), *sr.shape, _ptr(ws), ws.numel(), _stream(sr.device))
+    _lib.check(st, "drs_colorfix_adain")
+    return out

@@ -35,9 +35,9 @@ METRIC_FORMATS = {"psnr": ("PSNR", "{:.2f} dB"), "ssim": ("SSIM", "{:.4f}"), "sa
 
 def format_scores(scores):
     """One line of `Diffusion.evaluate`'s means: PSNR to 0.01 dB, SSIM to 4 decimals, SAM to 0.001 degrees, ERGAS to 4
-    significant digits, the model's figures and - where scored - the bicubic baseline's."""
+    significant digits, the model's figures and - where scored - the colour-corrected model's and the bicubic baseline's."""
     parts = []
-    for name in ("model", "bicubic"):
+    for name in ("model", "model_fixed", "bicubic"):
         if name in scores:
             parts.append(name + " " + " ".join(f"{METRIC_FORMATS[k][0]} {METRIC_FORMATS[k][1].format(v)}"
                                                for k, v in scores[name].items()))
@@ -205,7 +205,7 @@ class Diffusion:
 
     # -- image quality of the samples (metrics.py; not in the reference) ---------------------------
     def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None, baseline=True,
-                 known_mask_fn=None, resample=1, jump=1, ensemble=None, member_batch=None):
+                 known_mask_fn=None, resample=1, jump=1, ensemble=None, member_batch=None, color_fix=None, color_fix_levels=5):
         """PSNR / SSIM / SAM / ERGAS (metrics.image_quality) of `sample`'s output against the ground truth over the (lr, hr)
         batches of `loader`, every batch sampled as one call with n = its size, until `n_images` images are scored (None: the
         whole loader).  `sampling_steps`, `eta` and `noise_source` are `sample`'s (the source is asked batch after batch).
@@ -217,13 +217,37 @@ class Diffusion:
         then scores the ensemble MEAN, "member" member 0 - the single-draw figure reported without `ensemble` - and
         "ensemble" holds the means of `ensemble.ensemble_scores` (crps, spread, rmse, spread_skill) and the summed
         "rank_histogram", everything on members and truth clamped to [0, 1] like the image scores; see `_evaluate`.
+        `color_fix` ("wavelet" with `color_fix_levels`, or "adain"; not with `ensemble` or `known_mask_fn`) adds a third
+        estimate, "model_fixed": the very sample "model" scored - each batch is still sampled once - clamped to [0, 1] as
+        the scores clamp it and corrected against the bicubic up-sampling of its lr batch (`colorfix.color_fix`).
         The model keeps the train / eval mode it came with."""
+        fix = self._evaluate_color_fix(color_fix, color_fix_levels, ensemble, known_mask_fn)
         sample, members = self._evaluate_samplers(model, "input_channels", sampling_steps, eta, noise_source, known_mask_fn,
                                                   resample, jump, ensemble, member_batch)
         scorers = {"model": sample}
         if baseline:
             scorers["bicubic"] = lambda lr_img, hr_img: hip_ops.bicubic_upsample(lr_img, self.magnification_factor)
+        if fix is not None:
+            kept = {}  # the batch's sample, as `drawn` keeps the members of an ensemble: "model" runs before "model_fixed"
+
+            def sample_kept(lr_img, hr_img):
+                kept["x"] = sample(lr_img, hr_img)
+                return kept["x"]
+            scorers["model"] = sample_kept
+            scorers["model_fixed"] = lambda lr_img, hr_img: fix(kept["x"], lr_img)
         return self._evaluate(model, loader, n_images, scorers, self.magnification_factor, members)
+
+    def _evaluate_color_fix(self, method, levels, ensemble, known_mask_fn):
+        """`evaluate`'s f(sample batch, lr batch) -> corrected batch, None without a method; ValueError for a request it does
+        not take (checked before anything is sampled)."""
+        if method is None:
+            return None
+        from .colorfix import color_fix, fix_levels
+        levels = fix_levels(method, levels)
+        if ensemble is not None or known_mask_fn is not None:
+            raise ValueError("evaluate: color_fix cannot be combined with ensemble=N or known_mask_fn")
+        return lambda x, lr_img: color_fix(torch.clamp(x, 0, 1), lr_img, magnification_factor=self.magnification_factor,
+                                           method=method, levels=levels)
 
     def _evaluate_samplers(self, model, channels_kw, sampling_steps, eta, noise_source, known_mask_fn, resample, jump, ensemble,
                            member_batch):

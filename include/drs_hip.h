@@ -285,6 +285,35 @@ DRS_API int drs_ensemble_scores(const float* members, const float* truth, float*
                                 int64_t* rank_histogram, int N, int B, int C, int H, int W, int clamp, float lo, float hi,
                                 void* workspace, size_t workspace_bytes, drs_stream_t stream);
 
+/* Colour correction of a super-resolved batch against a guide of its size - the up-sampled LR observation - per (image, band)
+ * plane (csrc/colorfix.hip; public API in diffusionremotesensing_amd/colorfix.py).  A diffusion super-resolver drifts
+ * radiometrically; this post-process keeps the sample's fine detail and takes the large-scale content of the guide (the colour
+ * fix StableSR ships next to its aggregation sampling).  Not in the reference.
+ *   sr, guide, out: (B,C,H,W) fp32, 1 <= C <= 16;  `out` must not overlap `sr` or `guide`.  Nothing is clamped; a NaN goes where
+ *   the arithmetic takes it.  Two calls on the same inputs write the same bits.
+ * DRS_ERR_ARG: null pointer, `out` overlapping an input; DRS_ERR_SHAPE: B, C, H or W < 1, C > 16, levels outside 1 .. 5, H W < 2
+ * (drs_colorfix_adain); DRS_ERR_WORKSPACE: workspace too small.  All are reported before anything is launched.
+ *
+ * drs_colorfix_wavelet: with k = (1/4, 1/2, 1/4) and
+ *     blur_d(x)[y][x] = sum_{i,j in -1..1} k_i k_j x[clamp(y + i d, 0, H-1)][clamp(x + j d, 0, W-1)]
+ *   (a 3 x 3 convolution of dilation d on replicate padding) and low_L = blur_{2^(L-1)} o ... o blur_2 o blur_1, L = levels:
+ *     out = sr + low_L(guide - sr)      (= (sr - low_L(sr)) + low_L(guide): the map is linear)
+ *   One launch for all levels: a workgroup stages guide - sr of a 64 x 64 tile and its halo of 2^L - 1 pixels (clipped to the
+ *   image) in LDS and runs the L separable blurs there, clamping in image coordinates.  guide == sr returns sr bit for bit.
+ *   Any H, W >= 1; 16-byte stores need W % 4 == 0 and 16-byte aligned sr and out, anything else is written element by element.
+ *
+ * drs_colorfix_adain: with mean and unbiased variance (divisor H W - 1) of each plane of sr and of guide, std = sqrt(var + 1e-5):
+ *     out = a sr + b,   a = std_guide / std_sr,   b = mean_guide - a mean_sr
+ *   The sums of x and x^2 are carried in fp64 (per thread, per block in `workspace`, then added in a fixed order: no atomics),
+ *   a and b are formed in fp64 and rounded to fp32 once, out = fma(a, sr, b).  `workspace`: 8-byte aligned,
+ *   drs_colorfix_adain_workspace_bytes(B, C, H, W) bytes (0 for a shape the call does not take).  16-byte accesses need
+ *   H W % 4 == 0 and 16-byte aligned tensors; anything else runs element by element. */
+DRS_API int drs_colorfix_wavelet(const float* sr, const float* guide, float* out, int B, int C, int H, int W, int levels,
+                                 drs_stream_t stream);
+DRS_API size_t drs_colorfix_adain_workspace_bytes(int B, int C, int H, int W);
+DRS_API int drs_colorfix_adain(const float* sr, const float* guide, float* out, int B, int C, int H, int W, void* workspace,
+                               size_t workspace_bytes, drs_stream_t stream);
+
 /* "DownBlur" degradation of the super-resolution data feed on the device, bit-exact with the Pillow calls of the
  * reference's dataset item: x = ToTensor(GaussianBlur(radius)(resize(y, (out_w, out_h), BICUBIC))), y = ToTensor(hr).
  *   hr: (N,C,H,W) uint8;  x_lr: (N,C,out_h,out_w) float32 in [0,1];  y_hr: (N,C,H,W) float32 or NULL;
