@@ -19,6 +19,10 @@ Not in the reference: `aggregation="per_step"` (`sample_scene`), the aggregation
 after.  ONE state of scene size is denoised and the tiles' noise predictions are blended at every reverse step, so that
 neighbouring tiles denoise the same pixels of an overlap from the same state instead of hallucinating unrelated detail
 that the final blend can only average.  Opt-in: the default, "final", is the reference's behaviour bit for bit.
+
+Not in the reference either: known pixels (`known` / `known_mask`, RePaint as in `Diffusion.sample_known`) in both modes, and
+a sampled state whose channels and data range are not the conditioning image's (`out_channels`, `clamp`), so that the
+SAR -> NDVI model fills the clouded part of a whole NDVI scene.
 """
 from math import exp, pi, sqrt
 
@@ -34,7 +38,11 @@ TILE_BATCH = 16
 
 
 class split_aggregation_sampling:
-    def __init__(self, img_lr, patch_size, stride, magnification_factor, diffusion_model, device):
+    def __init__(self, img_lr, patch_size, stride, magnification_factor, diffusion_model, device, *, out_channels=None,
+                 clamp=(0.0, 1.0)):
+        """`out_channels`: channels of the sampled state (None: those of `img_lr`, the super-resolution case; NDVI_channels
+        with a SAR -> NDVI `Diffusion`, a SAR scene as `img_lr` and `magnification_factor=1`).  `clamp`: the (lo, hi) range
+        `aggregation_sampling` clamps to, None for none (NDVI lives in [-1, 1])."""
         assert stride <= patch_size
         self.img_lr = img_lr
         self.patch_size = patch_size
@@ -44,6 +52,8 @@ class split_aggregation_sampling:
         self.device = device
         self.model = diffusion_model.model
         batch_size, channels, height, width = img_lr.shape
+        self.out_channels = channels if out_channels is None else int(out_channels)
+        self.clamp = None if clamp is None else hip_ops._clamp_args(clamp, "split_aggregation_sampling")[1:]
         self.patches_lr, self.patches_sr_infos = self.patchifier(img_lr, patch_size, stride, magnification_factor)
         self.weight = self.gaussian_weights(patch_size * magnification_factor, patch_size * magnification_factor,
                                             batch_size)
@@ -78,13 +88,53 @@ class split_aggregation_sampling:
         weights = torch.tensor(np.outer(y_probs, x_probs)).to(torch.float32).to(self.device)
         return torch.tile(weights, (nbatches, 3, 1, 1))
 
-    def sample_tiles(self, noise_source=None, sampling_steps=None, eta=0.0):
-        """Super-resolve every tile: (n_tiles, C, S, S) on this rank's device.  One batched chain (sharded over the
-        ranks of an initialised process group); `sampling_steps` / `eta` select a DDIM chain (`Diffusion.sample`)."""
+    def _scene_size(self):
+        batch_size, channels, height, width = self.img_lr.shape
+        return height * self.magnification_factor, width * self.magnification_factor
+
+    def check_known(self, sampling_steps, known, known_mask, resample=1, jump=1):
+        """ValueError for a known-pixel request on this scene (checked before the engine is touched): `known` that is not
+        (out_channels, Hs, Ws), a `known_mask` that is not (Hs, Ws) or (1 | out_channels, Hs, Ws), one without the other,
+        `resample` / `jump` without `known`, or a "dpmpp_2m" plan with known pixels."""
+        from .sampling import check_inpaint_args, check_solver_known
+        Hs, Ws = self._scene_size()
+        C = self.out_channels
+        if known is not None and tuple(known.shape) != (C, Hs, Ws):
+            raise ValueError(f"known {tuple(known.shape)} must be the scene {(C, Hs, Ws)}")
+        if known_mask is not None and tuple(known_mask.shape) not in ((Hs, Ws), (1, Hs, Ws), (C, Hs, Ws)):
+            raise ValueError(f"known_mask {tuple(known_mask.shape)} must be {(Hs, Ws)} or (1 | {C}, {Hs}, {Ws})")
+        check_inpaint_args((1, C, Hs, Ws), known, known_mask, resample, jump)
+        check_solver_known(sampling_steps, known, known_mask)
+
+    def known_tiles(self, known, known_mask):
+        """The crops of `known` (C, Hs, Ws) and `known_mask` ((Hs, Ws) or (1 | C, Hs, Ws)) at the tiles' windows
+        (`patches_sr_infos`): (n, C, S, S) and (n, 1 | C, S, S), the per-chain tensors of `sample_known`."""
+        mask = known_mask if known_mask.dim() == 3 else known_mask.unsqueeze(0)
+        return (torch.stack([known[:, y0:y1, x0:x1] for (y0, y1, x0, x1) in self.patches_sr_infos]),
+                torch.stack([mask[:, y0:y1, x0:x1] for (y0, y1, x0, x1) in self.patches_sr_infos]))
+
+    @staticmethod
+    def _chunk(t, c0, c1, size):
+        """t[c0:c1], padded to `size` entries with repeats of its last one (a fixed-size chunk of tiles)."""
+        t_c = t[c0:c1]
+        if size > c1 - c0:
+            t_c = torch.cat([t_c, t_c[-1:].expand(size - (c1 - c0), -1, -1, -1)], dim=0).contiguous()
+        return t_c
+
+    def sample_tiles(self, noise_source=None, sampling_steps=None, eta=0.0, known=None, known_mask=None, resample=1, jump=1):
+        """Sample every tile: (n_tiles, C, S, S) on this rank's device.  One batched chain (sharded over the
+        ranks of an initialised process group); `sampling_steps` / `eta` select a DDIM chain (`Diffusion.sample`).
+        With `known` / `known_mask` of scene size (`check_known`) every chunk is a `sample_known` call on the tiles' crops of
+        both (`known_tiles`), chunked, padded and sharded like the LR tiles; `resample` / `jump` as there, and
+        `noise_source(tile, i, shape)` is asked at that chain's draws."""
         d = self.diffusion_model
+        self.check_known(sampling_steps, known, known_mask, resample, jump)
         lr = torch.cat([p[:1] for p in self.patches_lr], dim=0).to(self.device).contiguous()  # (n, C, ps, ps)
         n = lr.shape[0]
         lo, hi = drs_dist.shard_range(n) if drs_dist.world_size() > 1 else (0, n)
+        kn = mk = None
+        if known is not None:
+            kn, mk = self.known_tiles(known.to(self.device), known_mask.to(self.device))
         src = None
         if noise_source is not None:
             def src(i, shape, lo=lo):  # stack the per-tile draws of this rank's tiles
@@ -95,14 +145,13 @@ class split_aggregation_sampling:
         chunk = max(1, int(getattr(self, "tile_batch", 0) or TILE_BATCH))
         # the DDIM arguments are passed only when set: the default call is the reference's, whatever sampler `d` is
         ddim = {"sampling_steps": sampling_steps, "eta": eta} if sampling_steps is not None or eta != 0.0 else {}
+        S = self.patch_size * self.magnification_factor
         outs = []
         for c0 in range(lo, hi, chunk):
             c1 = min(c0 + chunk, hi)
             take = c1 - c0
             size = take if (hi - lo) <= chunk else chunk  # a scene smaller than one chunk runs at its own size
-            lr_c = lr[c0:c1]
-            if size > take:
-                lr_c = torch.cat([lr_c, lr_c[-1:].expand(size - take, -1, -1, -1)], dim=0).contiguous()
+            lr_c = self._chunk(lr, c0, c1, size)
             csrc = None
             if src is not None:
                 def csrc(i, shape, c0=c0, take=take):
@@ -110,15 +159,20 @@ class split_aggregation_sampling:
                     if shape[0] > take:
                         real = torch.cat([real, real[-1:].expand(shape[0] - take, -1, -1, -1)], dim=0)
                     return real
-            out_c = d.sample(size, self.model, lr_c, input_channels=lr.shape[1], generate_video=False, noise_source=csrc,
-                             **ddim)
+            # the channel count goes positionally: `input_channels` of one sampler is `NDVI_channels` of the other
+            if kn is None:
+                out_c = d.sample(size, self.model, lr_c, self.out_channels, generate_video=False, noise_source=csrc, **ddim)
+            else:
+                out_c = d.sample_known(size, self.model, lr_c, self._chunk(kn, c0, c1, size), self._chunk(mk, c0, c1, size),
+                                       self.out_channels, resample=resample, jump=jump, generate_video=False,
+                                       noise_source=csrc, **ddim)
             outs.append(out_c[:take])
-        mine = torch.cat(outs, dim=0) if outs else lr.new_zeros((0, lr.shape[1], d.image_size, d.image_size))
+        mine = torch.cat(outs, dim=0) if outs else lr.new_zeros((0, self.out_channels, S, S))
         if drs_dist.world_size() > 1:
             mine = drs_dist.gather_shards(mine, n)
         return mine
 
-    def sample_scene(self, noise_source=None, sampling_steps=None, eta=0.0):
+    def sample_scene(self, noise_source=None, sampling_steps=None, eta=0.0, known=None, known_mask=None, resample=1, jump=1):
         """The joint reverse chain of the whole scene: the un-clamped (C, H*m, W*m) state after the last step.
 
         Protocol.  The state X has scene size.  x_T is `noise_source(T, (1, C, Hs, Ws))` or torch.randn on the CPU
@@ -135,15 +189,25 @@ class split_aggregation_sampling:
         next to one chunk of gathered tiles and the plan's workspace.
         Conditioning: with one chunk the LR branch is computed on the first step and reused; with several chunks the
         plan's conditioning belongs to whichever chunk ran last, so every forward recomputes it.
-        The loop is `run_reverse_chain`: the fault-word reads and the range-fault roll-back act on the scene state."""
+        The loop is `run_reverse_chain`: the fault-word reads and the range-fault roll-back act on the scene state.
+        Known pixels.  `known` (C, Hs, Ws, in the model's data range, used as given) with `known_mask` ((Hs, Ws) or
+        (1 | C, Hs, Ws); bool, uint8 or {0, 1} float, nonzero = known) keeps those pixels of the scene (RePaint, as
+        `Diffusion.sample_known` does per image): the moves are `chain_moves(..., resample, jump)`; a reverse move is the same
+        gather / forwards / one `blend_step_`, which then also replaces the known elements of the scene state by `known`
+        forward-noised to the level reached (`known` itself at level 0) with the move's draw - `noise_source(i, scene shape)`,
+        drawn iff the move ends above level 0, whatever eta is; a forward jump to level t is one `renoise_` of the scene state
+        with `noise_source(t, scene shape)`.  The known pixels of the returned scene are `known`, exactly.  Memory: `known` and
+        its uint8 mask, once, at scene size (4 + 1 bytes per element read per move).  ValueError as `check_known`."""
         from .sampling import check_sampling_args
         d = self.diffusion_model
         check_sampling_args(d.noise_steps, sampling_steps, eta)
+        self.check_known(sampling_steps, known, known_mask, resample, jump)
         if drs_dist.world_size() > 1:
             raise NotImplementedError(
                 "aggregation='per_step' runs on one rank: the joint chain would need an all-gather of eps and a shared "
                 "noise draw per step; use aggregation='final', which shards its independent tile chains over the ranks")
-        batch_size, channels, height, width = self.img_lr.shape
+        batch_size, _, height, width = self.img_lr.shape
+        channels = self.out_channels
         m = self.magnification_factor
         S = self.patch_size * m
         Hs, Ws = height * m, width * m
@@ -173,42 +237,57 @@ class split_aggregation_sampling:
                                check_weights=first and j == 0, out=eps_buf[c0:c0 + size])
             return eps_buf
 
-        def update(x, eps, noise, i, i_prev, hist=None, t_q=-1):
+        def update(x, eps, noise, i, i_prev, hist=None, t_q=-1, known=None, known_mask=None):
+            kept = {"known": known[0], "known_mask": known_mask[0]} if known is not None else {}
             hip_ops.blend_step_(x[0], eps, origins, weight, noise[0] if noise is not None else None, i,
                                 alpha_hat=d.alpha_hat, alpha=d.alpha, beta=d.beta, t_prev=i_prev, eta=eta,
-                                uncovered=uncovered, hist=hist[0] if hist is not None else None, t_q=t_q)
+                                uncovered=uncovered, hist=hist[0] if hist is not None else None, t_q=t_q, **kept)
 
+        kept = {"known": known, "known_mask": known_mask, "resample": resample, "jump": jump} if known is not None else {}
         x = d._sample_chain(self.model, (1, channels, Hs, Ws), predict, table_rows=size, generate_video=False,
-                            noise_source=noise_source, sampling_steps=sampling_steps, eta=eta, update=update)
+                            noise_source=noise_source, sampling_steps=sampling_steps, eta=eta, update=update, **kept)
         if int(uncovered.item()) != 0:
             raise AssertionError("aggregation: some scene pixels are covered by no tile (pixel_count == 0)")
         return x[0]
 
     def aggregation_sampling(self, noise_source=None, sampling_steps=None, eta=0.0, aggregation="final", color_fix=None,
-                             color_fix_levels=5):
+                             color_fix_levels=5, known=None, known_mask=None, resample=1, jump=1):
         """Reference :76-116 (`sampling_steps` / `eta`: every tile runs a DDIM chain).  `aggregation`: "final" (the
         reference: independent tile chains, blended once; `noise_source(tile, i, shape)`) or "per_step" (`sample_scene`:
-        one joint chain, blended at every step; `noise_source(i, scene_shape)`), clamped to [0, 1].
+        one joint chain, blended at every step; `noise_source(i, scene_shape)`), clamped to [0, 1] (the constructor's `clamp`).
         `color_fix`: None (the default: nothing changes), "wavelet" (with `color_fix_levels`) or "adain" - the finished, clamped
         scene is corrected once as a whole, never per tile, against the bicubic up-sampling of img_lr's first image
-        (`colorfix.color_fix`) and clamped to [0, 1] again."""
+        (`colorfix.color_fix`) and clamped to [0, 1] again.
+        `known` / `known_mask` of scene size (`sample_scene`), with `resample` / `jump`, keep those pixels in either mode: the
+        tiles' chains (`sample_tiles`) or the joint chain keep them at every step, and the known pixels of the blended scene are
+        `known` under the clamp, exactly (in the final mode one `aggregate_tiles(..., known=, known_mask=)`)."""
         if aggregation not in ("final", "per_step"):
             raise ValueError(f"aggregation={aggregation!r} must be 'final' or 'per_step'")
         fix = self._color_fix(color_fix, color_fix_levels)
+        self.check_known(sampling_steps, known, known_mask, resample, jump)
         batch_size, channels, height, width = self.img_lr.shape
         m = self.magnification_factor
+        kept = {"known": known, "known_mask": known_mask, "resample": resample, "jump": jump} if known is not None else {}
         if aggregation == "per_step":
-            out = fix(torch.clamp(self.sample_scene(noise_source, sampling_steps=sampling_steps, eta=eta), 0, 1))
+            out = fix(self._clamp(self.sample_scene(noise_source, sampling_steps=sampling_steps, eta=eta, **kept)))
             return out.unsqueeze(0).expand(batch_size, -1, -1, -1).contiguous()
-        tiles = self.sample_tiles(noise_source, sampling_steps=sampling_steps, eta=eta)
+        tiles = self.sample_tiles(noise_source, sampling_steps=sampling_steps, eta=eta, **kept)
         origins = [(info[0], info[2]) for info in self.patches_sr_infos]
-        out = fix(hip_ops.aggregate_tiles(tiles, origins, self.weight[0, 0].contiguous(), height * m, width * m))
+        blend = {"clamp": self.clamp}
+        if known is not None:
+            from .sampling import known_tensors
+            kn, mk = known_tensors((1, self.out_channels, height * m, width * m), known, known_mask, tiles.device)
+            blend.update(known=kn[0], known_mask=mk[0])
+        out = fix(hip_ops.aggregate_tiles(tiles, origins, self.weight[0, 0].contiguous(), height * m, width * m, **blend))
         # the reference broadcasts the single chain of each tile over the batch dimension of img_lr
         return out.unsqueeze(0).expand(batch_size, -1, -1, -1).contiguous()
 
+    def _clamp(self, scene):
+        return scene if self.clamp is None else torch.clamp(scene, self.clamp[0], self.clamp[1])
+
     def _color_fix(self, method, levels):
         """f(clamped scene (C, Hs, Ws)) -> the scene `aggregation_sampling` returns: the identity without a method (checked
-        here, before anything is sampled)."""
+        here, before anything is sampled); the corrected scene is clamped like the sampled one (the constructor's `clamp`)."""
         if method is None:
             return lambda scene: scene
         from .colorfix import color_fix, fix_levels
@@ -218,46 +297,93 @@ class split_aggregation_sampling:
             lr = self.img_lr[:1].to(scene.device, torch.float32).contiguous()
             fixed = color_fix(scene.unsqueeze(0), lr, magnification_factor=self.magnification_factor, method=method,
                               levels=levels)
-            return torch.clamp(fixed[0], 0, 1)
+            return self._clamp(fixed[0])
         return fix
+
+
+def _load_tensor(path):
+    """A `.pt` / `.npy` tensor file, as `--img_lr_path` takes it."""
+    return torch.from_numpy(np.load(path)) if path.endswith(".npy") else torch.load(path)
+
+
+def cli_clamp(args):
+    """The tiler's `clamp` of the command line: `--clamp none` or `LO,HI`; unset it is [0, 1] for super-resolution and none
+    for SAR -> NDVI (whose data range the reference leaves to the dataset)."""
+    text = getattr(args, "clamp", None)
+    if text is None:
+        return None if getattr(args, "task", "superres") == "sar_to_ndvi" else (0.0, 1.0)
+    if text.strip().lower() == "none":
+        return None
+    parts = text.split(",")
+    if len(parts) != 2:
+        raise ValueError(f"--clamp {text!r} must be 'none' or 'LO,HI'")
+    return float(parts[0]), float(parts[1])
 
 
 def launch(args):
     """Reference launch (:140-212): model + snapshot + Diffusion + tiler.  The image file I/O of the reference
     (PIL / torchvision.transforms) is outside the hot path: `--img_lr_path` takes a `.pt` / `.npy` tensor (C,H,W) or
-    (1,C,H,W) in [0,1], `--destination_path` receives a `.pt` tensor."""
+    (1,C,H,W) in [0,1], `--destination_path` receives a `.pt` tensor.  `--task sar_to_ndvi` builds the SAR -> NDVI model and
+    `Diffusion` instead (`--SAR_channels`, `--NDVI_channels`; `--img_lr_path` is then the SAR scene and
+    `--magnification_factor` must be 1); `--known_path` / `--known_mask_path` hold the known scene (C_out,Hs,Ws) and its mask."""
     import os
 
     from .colorfix import cli_color_fix
-    from .train_diffusion_superres import Diffusion, cli_sampling_steps
-    from .UNet_model_superres import Residual_Attention_UNet_superres
+    from .train_diffusion_superres import cli_sampling_steps
     device = args.device
+    task = getattr(args, "task", "superres")
     if args.UNet_type.lower() != "residual attention unet":
         raise ValueError("The UNet type must be Residual Attention UNet")
-    model = Residual_Attention_UNet_superres(args.inp_out_channels, args.inp_out_channels, device).to(device)
+    snapshot_path = os.path.join(args.snapshot_folder_path, args.snapshot_name)
+    if task == "sar_to_ndvi":
+        from .train_diffusion_SAR_TO_NDVI import Diffusion
+        from .UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
+        if args.magnification_factor != 1:
+            raise ValueError(f"--task sar_to_ndvi samples at the SAR scene's size: --magnification_factor must be 1, got "
+                             f"{args.magnification_factor}")
+        model = Residual_Attention_UNet_SAR_TO_NDVI(args.SAR_channels, args.NDVI_channels, device).to(device)
+        diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot_path,
+                              noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02, device=device,
+                              image_size=args.model_input_size, model_name=args.model_name, multiple_gpus=False,
+                              ema_smoothing=False)
+        out_channels = args.NDVI_channels
+    elif task == "superres":
+        from .train_diffusion_superres import Diffusion
+        from .UNet_model_superres import Residual_Attention_UNet_superres
+        model = Residual_Attention_UNet_superres(args.inp_out_channels, args.inp_out_channels, device).to(device)
+        diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot_path,
+                              noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02,
+                              magnification_factor=args.magnification_factor, device=device,
+                              image_size=args.model_input_size, model_name=args.model_name,
+                              Degradation_type=args.Degradation_type, multiple_gpus=False, ema_smoothing=False)
+        out_channels = None
+    else:
+        raise ValueError(f"--task {task!r} must be 'superres' or 'sar_to_ndvi'")
     print(f"You are using {args.UNet_type} model")
-    path = args.img_lr_path
-    img_lr = torch.from_numpy(np.load(path)) if path.endswith(".npy") else torch.load(path)
-    img_lr = img_lr.float()
+    img_lr = _load_tensor(args.img_lr_path).float()
     if img_lr.dim() == 3:
         img_lr = img_lr.unsqueeze(0)
     img_lr = img_lr.to(device)
-    diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model,
-                          snapshot_path=os.path.join(args.snapshot_folder_path, args.snapshot_name),
-                          noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02,
-                          magnification_factor=args.magnification_factor, device=device,
-                          image_size=args.model_input_size, model_name=args.model_name,
-                          Degradation_type=args.Degradation_type, multiple_gpus=False, ema_smoothing=False)
-    tiler = split_aggregation_sampling(img_lr, args.patch_size, args.stride, args.magnification_factor, diffusion, device)
+    kept = {}
+    if getattr(args, "known_path", None) or getattr(args, "known_mask_path", None):
+        if not (getattr(args, "known_path", None) and getattr(args, "known_mask_path", None)):
+            raise ValueError("--known_path and --known_mask_path go together")
+        kept = {"known": _load_tensor(args.known_path).float(), "known_mask": _load_tensor(args.known_mask_path)}
+    resample, jump = getattr(args, "known_resample", 1), getattr(args, "known_jump", 1)
+    if resample != 1 or jump != 1 or kept:
+        kept.update(resample=resample, jump=jump)
+    tiler = split_aggregation_sampling(img_lr, args.patch_size, args.stride, args.magnification_factor, diffusion, device,
+                                       out_channels=out_channels, clamp=cli_clamp(args))
     final_pred = tiler.aggregation_sampling(sampling_steps=cli_sampling_steps(args),
                                             eta=getattr(args, "eta", 0.0),
                                             aggregation=getattr(args, "aggregation", "final"),
-                                            **cli_color_fix(args))
+                                            **cli_color_fix(args), **kept)
     torch.save(final_pred.squeeze(0).cpu(), args.destination_path)
 
 
 def build_arg_parser():
-    """The reference's flags, verbatim (:217-231), the DDIM flags, --aggregation and the colour-correction flags."""
+    """The reference's flags, verbatim (:217-231), the DDIM flags, --aggregation, the colour-correction flags, the known-pixel
+    flags and --task / --clamp."""
     import argparse
 
     from .colorfix import add_color_fix_args
@@ -283,6 +409,21 @@ def build_arg_parser():
                    help="final: independent tile chains blended once (the reference); per_step: one joint chain of the "
                         "whole scene, the tiles' noise predictions blended at every reverse step")
     add_color_fix_args(p)
+    p.add_argument("--known_path", type=str, default=None,
+                   help=".pt / .npy scene (C_out,Hs,Ws) whose pixels under --known_mask_path are kept (RePaint)")
+    p.add_argument("--known_mask_path", type=str, default=None,
+                   help=".pt / .npy mask (Hs,Ws) or (1 | C_out,Hs,Ws), nonzero = known")
+    p.add_argument("--resample", dest="known_resample", type=int, default=1,
+                   help="RePaint resampling rounds per jump (1: none); needs --known_path")
+    p.add_argument("--jump", dest="known_jump", type=int, default=1,
+                   help="RePaint jump length in chain positions; needs --known_path")
+    p.add_argument("--task", type=str, choices=("superres", "sar_to_ndvi"), default="superres",
+                   help="sar_to_ndvi: --img_lr_path is a SAR scene, sampled to NDVI at --magnification_factor 1")
+    p.add_argument("--SAR_channels", type=int, default=2)
+    p.add_argument("--NDVI_channels", type=int, default=1)
+    p.add_argument("--clamp", type=str, default=None,
+                   help="'none' or 'LO,HI' (--clamp=-1,1 for a negative bound): the range of the returned scene; default 0,1 for "
+                        "superres, none for sar_to_ndvi")
     return p
 
 

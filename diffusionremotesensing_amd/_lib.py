@@ -46,10 +46,12 @@ SIGNATURES = {
     "drs_gather_pairs_f32": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _P]),
     "drs_gather_u8_f32": (_I, [_P, _P, _P, _I, _L, _I, _P, _P, _P]),
     "drs_aggregate_tiles": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "drs_aggregate_tiles_known": (_I, [_P] * 7 + [_I] * 7 + [_F, _F, _P]),
     "drs_gather_tiles": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "drs_blend_step": (_I, [_P] * 6 + [_I] * 6 + [_P, _P, _P, _I, _P]),
     "drs_blend_step_ddim": (_I, [_P] * 6 + [_I] * 7 + [_F, _P, _I, _P]),
     "drs_blend_step_dpm": (_I, [_P] * 6 + [_I] * 8 + [_P, _I, _P]),
+    "drs_blend_step_known": (_I, [_P] * 8 + [_I] * 9 + [_F, _P, _P, _P, _I, _P]),
     "drs_metrics_workspace_bytes": (_Z, [_I] * 4),
     "drs_metrics_pointwise": (_I, [_P, _P, _P] + [_I] * 5 + [_P, _Z, _P]),
     "drs_ssim": (_I, [_P, _P, _P] + [_I] * 5 + [_P, _Z, _P]),

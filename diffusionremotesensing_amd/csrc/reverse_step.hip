@@ -122,22 +122,6 @@ struct MoveCoef<true> {
   __device__ float add(float v, float z) const { return fmaf(k.s, z, v); }
 };
 
-// q(x_t | x_0) of one element at level t_prev: fl(a * known) + fl(b * z), a = sqrt(ah), b = sqrt(1 - ah) formed in fp64
-// from the fp32 table entry and rounded once (as drs_ddim_coef does), no contraction into a fused multiply-add.
-struct KnownCoef {
-  float a, b;
-  __device__ KnownCoef(const float* __restrict__ alpha_hat, int t_prev) {
-    const double ah = (double)alpha_hat[t_prev];
-    a = (float)sqrt(ah);
-    b = (float)sqrt(1.0 - ah);
-  }
-  __device__ float at(float known, float z) const {
-#pragma clang fp contract(off)
-    const float p = a * known, q = b * z;
-    return p + q;
-  }
-};
-
 struct InpaintArgs {
   float* x;
   const float* ec;
@@ -160,7 +144,7 @@ struct InpaintArgs {
 template <int V, bool DDIM>
 __global__ __launch_bounds__(256) void inpaint_step_kernel(const InpaintArgs a) {
   const MoveCoef<DDIM> coef(a.alpha, a.alpha_hat, a.beta, a.t, a.t_prev, a.eta);
-  const KnownCoef kc(a.alpha_hat, a.t_prev);
+  const DrsKnownCoef kc(a.alpha_hat, a.t_prev);  // (step_update.h, shared with the tile blend)
   const bool add_noise = a.noise != nullptr && coef.draws();
   const bool to_zero = a.t_prev == 0;  // the known pixels arrive at the known image itself; z is not read for them
   const int64_t groups = a.hw / V;

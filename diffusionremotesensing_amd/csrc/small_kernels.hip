@@ -621,6 +621,62 @@ extern "C" int drs_aggregate_tiles(const float* tiles, const int32_t* origins, c
   return DRS_OK;
 }
 
+// drs_aggregate_tiles_known: the blend of aggregate_tiles_kernel - the same sums in the same order, repeated here so that
+// kernel stays as it is compiled - with the clamp as an argument (`clamp` 0: none) and, with `known` / `mask` (Cm = 1 | C
+// planes of H x W bytes, nonzero = known), the known pixels written as `known` under the same clamp.  `uncovered` counts the
+// pixels no tile covers, known or not.
+__global__ void aggregate_tiles_known_kernel(const float* __restrict__ tiles, const int* __restrict__ origins,
+                                             const float* __restrict__ weight, const float* __restrict__ known,
+                                             const unsigned char* __restrict__ mask, float* __restrict__ out,
+                                             int* __restrict__ uncovered, int n, int C, int Cm, int S, int H, int W, int clamp,
+                                             float lo, float hi) {
+  const int64_t hw = (int64_t)H * W;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < hw; p += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(p / W), x = (int)(p % W);
+    float cnt = 0.f;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int c0 = 0; c0 < C; c0 += 4) {
+      cnt = 0.f;
+      acc[0] = acc[1] = acc[2] = acc[3] = 0.f;
+      for (int i = 0; i < n; ++i) {
+        const int ly = y - origins[2 * i], lx = x - origins[2 * i + 1];
+        if (ly < 0 || ly >= S || lx < 0 || lx >= S) continue;
+        const float w = weight[ly * S + lx];
+        cnt = __fadd_rn(cnt, w);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (c0 + j < C) acc[j] = __fadd_rn(acc[j], __fmul_rn(tiles[(((int64_t)i * C + c0 + j) * S + ly) * S + lx], w));
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (c0 + j >= C) continue;
+        const int64_t at = (int64_t)(c0 + j) * hw + p;
+        float v = __fdiv_rn(acc[j], cnt);
+        if (mask && mask[Cm == 1 ? p : at]) v = known[at];
+        out[at] = clamp ? fminf(fmaxf(v, lo), hi) : v;
+      }
+    }
+    if (cnt == 0.f && uncovered) atomicAdd(uncovered, 1);
+  }
+}
+extern "C" int drs_aggregate_tiles_known(const float* tiles, const int32_t* origins, const float* weight, const float* known,
+                                         const uint8_t* mask, float* out, int32_t* uncovered, int n, int C, int S, int H, int W,
+                                         int mask_channels, int clamp, float lo, float hi, drs_stream_t stream) {
+  DRS_REQUIRE(tiles && origins && weight && out, DRS_ERR_ARG, "aggregate_tiles_known: null pointer");
+  DRS_REQUIRE((known == nullptr) == (mask == nullptr), DRS_ERR_ARG, "aggregate_tiles_known: known and mask go together");
+  DRS_REQUIRE(n >= 1 && C >= 1 && S >= 1 && H >= S && W >= S, DRS_ERR_SHAPE, "aggregate_tiles_known: n=%d C=%d S=%d H=%d W=%d",
+              n, C, S, H, W);
+  if (mask)
+    DRS_REQUIRE(mask_channels == 1 || mask_channels == C, DRS_ERR_SHAPE,
+                "aggregate_tiles_known: a mask of %d bands for an image of %d (1 or %d)", mask_channels, C, C);
+  if (clamp) DRS_REQUIRE(lo <= hi, DRS_ERR_ARG, "aggregate_tiles_known: clamp range [%g, %g]", (double)lo, (double)hi);
+  if (uncovered) DRS_CHECK_HIP(hipMemsetAsync(uncovered, 0, sizeof(int32_t), (hipStream_t)stream));
+  DRS_LAUNCH(aggregate_tiles_known_kernel, dim3(ew_blocks((int64_t)H * W)), dim3(256), 0, (hipStream_t)stream, tiles, origins,
+             weight, known, mask, out, uncovered, n, C, mask_channels, S, H, W, clamp, lo, hi);
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
+}
+
 extern "C" int drs_bicubic_upsample_nchw(const float* x, float* y, int N, int C, int H, int W, int scale,
                                          drs_stream_t stream) {
   DRS_REQUIRE(x && y, DRS_ERR_ARG, "bicubic: null pointer");

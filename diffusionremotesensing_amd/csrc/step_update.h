@@ -1,7 +1,8 @@
 // The per-element arithmetic of the reverse-step updates, shared by every kernel that applies one: the ancestral and the DDIM
 // update (reverse_step.hip: drs_sampler_step, drs_sampler_step_cfg, drs_ddim_step; drs_inpaint_step takes the coefficients)
 // and the per-step tile blend, which forms eps itself and then takes the same step (tile_chain.hip: drs_blend_step,
-// drs_blend_step_ddim), and the DPM-Solver++(2M) move of both (drs_dpm_step, drs_blend_step_dpm).
+// drs_blend_step_ddim), the DPM-Solver++(2M) move of both (drs_dpm_step, drs_blend_step_dpm), and the forward-noised known
+// element of the moves with known pixels (drs_inpaint_step, drs_blend_step_known).
 // One definition, so that a scene state and a tile state that see the same eps move by the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -116,3 +117,20 @@ __device__ __forceinline__ float drs_dpm_update(const DrsDpmCoef& k, float x, fl
   }
   return v;
 }
+
+// q(x_t | x_0) of one known element at level t_prev (drs_inpaint_step, drs_blend_step_known): fl(a * known) + fl(b * z), a =
+// sqrt(ah), b = sqrt(1 - ah) formed in fp64 from the fp32 table entry and rounded once (as drs_ddim_coef does), no contraction
+// into a fused multiply-add.
+struct DrsKnownCoef {
+  float a, b;
+  __device__ DrsKnownCoef(const float* __restrict__ alpha_hat, int t_prev) {
+    const double ah = (double)alpha_hat[t_prev];
+    a = (float)sqrt(ah);
+    b = (float)sqrt(1.0 - ah);
+  }
+  __device__ float at(float known, float z) const {
+#pragma clang fp contract(off)
+    const float p = a * known, q = b * z;
+    return p + q;
+  }
+};

@@ -297,23 +297,55 @@ def reverse_step_(x, eps, noise, t, t_prev, *, alpha, alpha_hat, beta, ddim=Fals
     return sampler_step_cfg_(x, eps, eps_uncond, cfg_scale, noise, t, alpha, alpha_hat, beta)
 
 
-def aggregate_tiles(tiles, origins, weight, height, width):
+def _req_known(op, known, mask, shape, state):
+    """The known image and its mask of a scene-level call: `known` fp32 of `shape` = (C, H, W), `mask` uint8 (1 | C, H, W), both
+    on the device of `state` and given together; (known, mask), contiguous."""
+    if (known is None) != (mask is None):
+        raise RuntimeError(f"{op}: known and known_mask go together, got " +
+                           ("known without known_mask" if mask is None else "known_mask without known"))
+    known = _req(known, "known")
+    mask = _req(mask, "known_mask", torch.uint8)
+    C_, H, W = shape
+    if known.device != state.device or mask.device != state.device:
+        raise RuntimeError(f"{op}: known is on {known.device}, known_mask on {mask.device}, the scene on {state.device}")
+    if tuple(known.shape) != (C_, H, W):
+        raise RuntimeError(f"{op}: known {tuple(known.shape)} must be {(C_, H, W)}")
+    if mask.dim() != 3 or mask.shape[0] not in (1, C_) or tuple(mask.shape[1:]) != (H, W):
+        raise RuntimeError(f"{op}: known_mask {tuple(mask.shape)} must be (1 or {C_}, {H}, {W})")
+    return known, mask
+
+
+def aggregate_tiles(tiles, origins, weight, height, width, clamp=(0.0, 1.0), known=None, known_mask=None):
     """Gaussian-weighted blend of (n,C,S,S) tiles placed at `origins` [(y0, x0), ...] into a (C,height,width) image,
     normalised by the summed weights and clamped to [0,1] (reference Aggregation_Sampling.py:90-116).
-    Raises like the reference's `assert torch.all(pixel_count != 0)` when a pixel is covered by no tile."""
+    Raises like the reference's `assert torch.all(pixel_count != 0)` when a pixel is covered by no tile.
+    `clamp=(lo, hi)` clamps to another range and `clamp=None` not at all; `known` (C,height,width) with `known_mask` (uint8,
+    (1 | C,height,width), nonzero = known) writes those pixels as `known`, clamped like the rest (include/drs_hip.h:
+    drs_aggregate_tiles_known; the default arguments call drs_aggregate_tiles)."""
     lib = _lib.load()
     tiles = _req(tiles, "tiles")
     weight = _req(weight, "weight")
     n, C, S, S2 = tiles.shape
     if S != S2 or tuple(weight.shape) != (S, S) or len(origins) != n:
         raise RuntimeError(f"aggregate_tiles: tiles {tuple(tiles.shape)}, weight {tuple(weight.shape)}, {len(origins)} origins")
+    flag, lo, hi = _clamp_args(clamp, "aggregate_tiles")
+    plain = known is None and known_mask is None and (flag, lo, hi) == (1, 0.0, 1.0)
+    if known is not None or known_mask is not None:
+        known, known_mask = _req_known("aggregate_tiles", known, known_mask, (C, int(height), int(width)), tiles)
     org = torch.tensor([[int(y), int(x)] for y, x in origins], dtype=torch.int32).to(tiles.device)
     out = torch.empty((C, int(height), int(width)), dtype=torch.float32, device=tiles.device)
     uncovered = torch.zeros(1, dtype=torch.int32, device=tiles.device)
     with torch.cuda.device(tiles.device):
-        st = lib.drs_aggregate_tiles(_ptr(tiles), _ptr(org), _ptr(weight), _ptr(out), _ptr(uncovered), n, C, S,
-                                     int(height), int(width), _stream(tiles.device))
-    _lib.check(st, "drs_aggregate_tiles")
+        if plain:
+            st = lib.drs_aggregate_tiles(_ptr(tiles), _ptr(org), _ptr(weight), _ptr(out), _ptr(uncovered), n, C, S,
+                                         int(height), int(width), _stream(tiles.device))
+            _lib.check(st, "drs_aggregate_tiles")
+        else:
+            st = lib.drs_aggregate_tiles_known(_ptr(tiles), _ptr(org), _ptr(weight), _ptr(known), _ptr(known_mask), _ptr(out),
+                                               _ptr(uncovered), n, C, S, int(height), int(width),
+                                               int(known_mask.shape[0]) if known_mask is not None else 1, flag, lo, hi,
+                                               _stream(tiles.device))
+            _lib.check(st, "drs_aggregate_tiles_known")
     if int(uncovered.item()) != 0:
         raise AssertionError("aggregation: some output pixels are covered by no tile (pixel_count == 0)")
     return out
@@ -361,13 +393,17 @@ def gather_tiles(scene, origins, S, out=None, first=0, count=None):
 
 
 def blend_step_(scene, eps_tiles, origins, weight, noise, t, *, alpha_hat, alpha=None, beta=None, t_prev=None, eta=0.0,
-                uncovered=None, hist=None, t_q=-1):
+                uncovered=None, hist=None, t_q=-1, known=None, known_mask=None):
     """One reverse step of the scene state (C, H, W), in place, from the noise predictions `eps_tiles` (n, C, S, S) of
     its tiles (only the first n = len(origins) tiles of a longer buffer are read): Gaussian-weighted mean of the covering
     tiles' eps in tile order, then the update of `sampler_step_` (t_prev None: needs alpha and beta) or of `ddim_step_`
     (t -> t_prev with eta).  `noise` (scene shape) may be None as for those.  `uncovered`: optional int32 device counter
     that is increased by the number of pixels no tile covers (include/drs_hip.h: drs_blend_step).  With `hist` (scene shape) the
-    update is that of `dpm_step_` from t to t_prev, `t_q` as there; it takes no noise (drs_blend_step_dpm)."""
+    update is that of `dpm_step_` from t to t_prev, `t_q` as there; it takes no noise (drs_blend_step_dpm).
+    With `known` (scene shape, used as given) and `known_mask` (uint8, (1 | C, H, W), nonzero = known) the step is followed by
+    the select of `inpaint_step_` in the same launch: the masked elements become `known` forward-noised to the level reached
+    with the same `noise`, or `known` itself at level 0, the others are the step's, bit for bit.  `noise` may then be None
+    only when the move ends at level 0; a DPM-Solver++(2M) move keeps no known pixels (drs_blend_step_known)."""
     lib = _lib.load()
     _req_state(scene, "blend_step_", "scene")
     eps_tiles = _req(eps_tiles, "eps_tiles")
@@ -391,8 +427,22 @@ def blend_step_(scene, eps_tiles, origins, weight, noise, t, *, alpha_hat, alpha
         if noise is not None or t_prev is None:
             raise RuntimeError("blend_step_: a DPM-Solver++(2M) move (hist) needs t_prev and takes no noise")
         t_q = _req_history("blend_step_", scene, hist, t_q, "scene")
-    with torch.cuda.device(scene.device):
+    if known is not None or known_mask is not None:
         if hist is not None:
+            raise RuntimeError("blend_step_: a DPM-Solver++(2M) move (hist) keeps no known pixels")
+        known, known_mask = _req_known("blend_step_", known, known_mask, (C_, Hs, Ws), scene)
+    with torch.cuda.device(scene.device):
+        if known is not None:
+            ddim = t_prev is not None
+            if not ddim:
+                alpha = _req(alpha, "alpha"); beta = _req(beta, "beta")
+            st = lib.drs_blend_step_known(_ptr(scene), _ptr(eps_tiles), _ptr(origins), _ptr(weight), _ptr(noise), _ptr(known),
+                                          _ptr(known_mask), _ptr(uncovered), n, C_, S, Hs, Ws, int(known_mask.shape[0]), int(ddim),
+                                          int(t), int(t_prev) if ddim else 0, float(eta), _ptr(alpha) if not ddim else _ptr(None),
+                                          _ptr(alpha_hat), _ptr(beta) if not ddim else _ptr(None), alpha_hat.numel(),
+                                          _stream(scene.device))
+            _lib.check(st, "drs_blend_step_known")
+        elif hist is not None:
             st = lib.drs_blend_step_dpm(_ptr(scene), _ptr(eps_tiles), _ptr(origins), _ptr(weight), _ptr(hist), _ptr(uncovered),
                                         n, C_, S, Hs, Ws, t_q, int(t), int(t_prev), _ptr(alpha_hat), alpha_hat.numel(),
                                         _stream(scene.device))

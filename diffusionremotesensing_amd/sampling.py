@@ -275,7 +275,8 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
     One `step` takes every move of `chain_moves`.  A forward jump to level t_to is one `renoise_` with the draw for t_to.  A
     reverse move t -> t_to is one `predict`, at most one draw - for t - and the `update` hook or one `hip_ops.reverse_step_`;
     it draws iff it ends above level 0 and adds noise there: always on the ancestral chain and with known pixels (whose
-    forward noise it also is), on a DDIM chain without them only when eta > 0.
+    forward noise it also is), on a DDIM chain without them only when eta > 0.  With known pixels the `update` hook also gets
+    `known=` / `known_mask=`, converted by `known_tensors` for the chain's `shape` (the tiler's scene), and the move's draw.
     `sampling_steps` may be a `sampling_plan`; its solver "dpmpp_2m" (DPM-Solver++(2M): eta = 0, no known pixels: checked
     by the caller, `check_sampling_args` in every `Diffusion._sample` and `check_solver_known` in `_sample_chain`) takes every
     move with `hip_ops.dpm_step_` - or the `update` hook, which then also gets `hist=` and `t_q=` - and draws nothing but x_T.
@@ -319,7 +320,8 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
                         hip_ops.reverse_step_(x, eps, None, t, t_to, alpha=schedule.alpha, alpha_hat=schedule.alpha_hat,
                                               beta=schedule.beta, ddim=True, eps_uncond=eps_uncond, cfg_scale=cfg_scale, **order)
                 elif update is not None:
-                    update(x, eps, noise, t, t_to if ddim else None)
+                    kept = {"known": known, "known_mask": known_mask} if known is not None else {}
+                    update(x, eps, noise, t, t_to if ddim else None, **kept)
                 else:
                     hip_ops.reverse_step_(x, eps, noise, t, t_to, alpha=schedule.alpha, alpha_hat=schedule.alpha_hat,
                                           beta=schedule.beta, ddim=ddim, eta=eta, eps_uncond=eps_uncond, cfg_scale=cfg_scale,

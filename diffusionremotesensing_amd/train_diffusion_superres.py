@@ -184,12 +184,12 @@ class Diffusion:
         known pixels become `known` forward-noised to t_prev, the others take the sampler's step) and draws one noise tensor -
         `noise_source(t, shape)` - iff t_prev > 0, whatever eta is; a forward jump of `inpaint_schedule` to level t is one
         `renoise_` and draws `noise_source(t, shape)`.  On the ancestral chain without resampling these are the draws of the
-        plain sampler.  With a `sampling_plan` of solver "dpmpp_2m" the moves are `dpm_step_`s and the `update` hook also gets
+        plain sampler.  With an `update` hook as well (the tiler's scene with known pixels) the moves are the same and a
+        reverse move calls `update(x, eps, noise, i, i_prev, known=, known_mask=)` with the converted tensors and that draw; a
+        forward jump is the `renoise_` of the scene state.  With a `sampling_plan` of solver "dpmpp_2m" the moves are `dpm_step_`s and the `update` hook also gets
         `hist=` and `t_q=`, as `sampling.sample_chain` says.  The chain is `sampling.sample_chain`; this method adds the eval
         mode around it and the video."""
         check_solver_known(sampling_steps, known, known_mask)
-        if known is not None and update is not None:
-            raise ValueError("known pixels cannot be combined with an `update` hook (the tiler's per-step blend)")
         net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
         model.eval()
         frames = [] if generate_video else None

@@ -188,6 +188,18 @@ DRS_API int drs_ema_multi(const drs_ema_tensor* table, int ntensors, int64_t max
 DRS_API int drs_aggregate_tiles(const float* tiles, const int32_t* origins, const float* weight, float* out, int32_t* uncovered,
                         int n, int C, int S, int H, int W, drs_stream_t stream);
 
+/* drs_aggregate_tiles with the clamp as an argument and optional known pixels (the final blend of a tiled scene whose data
+ * range is not [0,1], NDVI in [-1,1] for one, or that keeps given pixels): the same sums in the same order, then
+ *   out = known          where mask != 0 (known, mask: both NULL or both given),
+ *   out = clamp(out, lo, hi)   when clamp != 0, known pixels included; clamp == 0 writes the quotient as it is.
+ * known: (C,H,W) fp32; mask: (mask_channels,H,W) uint8 with mask_channels 1 or C, nonzero = known.  `uncovered` as in
+ * drs_aggregate_tiles (a covered-by-no-tile pixel counts whether it is known or not).  With clamp = (0, 1) and no known
+ * pixels the output is that of drs_aggregate_tiles, bit for bit.  DRS_ERR_ARG: null pointer, known without mask or the
+ * reverse, lo > hi; DRS_ERR_SHAPE: as drs_aggregate_tiles, mask_channels not 1 or C. */
+DRS_API int drs_aggregate_tiles_known(const float* tiles, const int32_t* origins, const float* weight, const float* known,
+                                      const uint8_t* mask, float* out, int32_t* uncovered, int n, int C, int S, int H, int W,
+                                      int mask_channels, int clamp, float lo, float hi, drs_stream_t stream);
+
 /* Per-step tile aggregation (split_aggregation_sampling.sample_scene; csrc/tile_chain.hip): one state of scene size is
  * denoised, the tiles' noise predictions are blended at every reverse step.  Not in the reference.
  *
@@ -229,6 +241,25 @@ DRS_API int drs_blend_step_ddim(float* scene, const float* eps_tiles, const int3
 DRS_API int drs_blend_step_dpm(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight,
                                float* x0_hist, int32_t* uncovered, int n, int C, int S, int Hs, int Ws, int t_q, int t,
                                int t_p, const float* alpha_hat, int noise_steps, drs_stream_t stream);
+
+/* drs_blend_step / drs_blend_step_ddim (`ddim` selects the form, as in drs_inpaint_step: ddim == 0 implies t_prev = t - 1,
+ * ignores `t_prev` and `eta` and reads alpha / alpha_hat / beta; ddim != 0 reads alpha_hat only) followed, in the same launch,
+ * by the known-pixel select of drs_inpaint_step on the scene state (RePaint over a tiled scene).  known: (C,Hs,Ws) fp32, used
+ * as given; mask: (mask_channels,Hs,Ws) uint8 with mask_channels 1 or C, nonzero = known.  Per element, after the blended eps
+ * and the step:
+ *   mask == 0:  the value drs_blend_step / drs_blend_step_ddim writes, bit for bit;
+ *   mask != 0:  known for t_prev == 0, else sqrt(alpha_hat[t_prev]) * known + sqrt(1 - alpha_hat[t_prev]) * noise, the
+ *               arithmetic (and the bits) of drs_inpaint_step.
+ * One noise tensor serves both branches; `noise` may be NULL only for t_prev == 0 (DRS_ERR_ARG otherwise, whatever eta is).
+ * `uncovered` and the 16-byte path (S % 4 == 0 and Ws % 4 == 0) as in drs_blend_step; there `known` is read 16 bytes and the
+ * mask 4 bytes at a time when their base pointers are so aligned, element by element otherwise.  No atomics on the data path:
+ * two calls give the same bits.  DRS_ERR_ARG: null pointer, a move drs_inpaint_step refuses; DRS_ERR_SHAPE as
+ * drs_blend_step, mask_channels not 1 or C. */
+DRS_API int drs_blend_step_known(float* scene, const float* eps_tiles, const int32_t* origins, const float* weight,
+                                 const float* noise, const float* known, const uint8_t* mask, int32_t* uncovered, int n, int C,
+                                 int S, int Hs, int Ws, int mask_channels, int ddim, int t, int t_prev, float eta,
+                                 const float* alpha, const float* alpha_hat, const float* beta, int noise_steps,
+                                 drs_stream_t stream);
 
 /* Image-quality sums of an estimate `sr` against the truth `hr`, per image (csrc/metrics.hip; finalised into PSNR, SSIM, SAM
  * and ERGAS by diffusionremotesensing_amd/metrics.py).  Not in the reference, which only looks at its samples.
