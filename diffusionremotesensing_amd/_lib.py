@@ -100,6 +100,10 @@ SIGNATURES = {
     "drs_vgg_profile_enable": (_I, [_P, _I]),
     "drs_vgg_profile_num_ops": (_I, [_P]),
     "drs_vgg_profile_read": (_I, [_P, _I, C.c_char_p, _I, C.POINTER(_F), C.POINTER(C.c_double)]),
+    "drs_vgg_num_tensors": (_I, [_P]),
+    "drs_vgg_tensor_name": (C.c_char_p, [_P, _I]),
+    "drs_vgg_tensor_shape": (_I, [_P, _I] + [C.POINTER(_I)] * 4),
+    "drs_vgg_read_tensor": (_I, [_P, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -19,7 +19,7 @@ void DrsErr::set(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* drs_last_error(void) { return g_err; }
-extern "C" int drs_abi_version(void) { return 7; }
+extern "C" int drs_abi_version(void) { return 8; }
 
 int drs_kernel_prepare(const void* kernel, int max_dynamic_lds, int* num_cu) {
   static std::mutex mu;

@@ -579,6 +579,41 @@ extern "C" int drs_vgg_backward(drs_vgg_plan* plan, const void* packed, const fl
   return DRS_OK;
 }
 
+// ---- introspection: the tensors a forward leaves in the workspace (parity tests) --------------------------------------------
+// 0: x0 (2B, 4, H0, W0), 1 .. 16: conv1 .. conv16 (B, C, h, w) - the saved prediction-half ReLU outputs, 17: features
+namespace {
+constexpr int kVggTensors = kConvs + 2;
+const char* const kVggTensorNames[kVggTensors] = {"x0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv8",
+                                                  "conv9", "conv10", "conv11", "conv12", "conv13", "conv14", "conv15", "conv16",
+                                                  "features"};
+struct VggTensor { size_t off; int n, c, h, w; };
+VggTensor vgg_tensor(const drs_vgg_plan* p, int i) {
+  if (i == 0) return {p->o_x0, 2 * p->B, 4, p->H0, p->W0};
+  if (i == kVggTensors - 1) return {p->o_feat, 2 * p->B, 512, p->LH[4] >> 1, p->LW[4] >> 1};
+  const int l = i - 1, v = level_of(l);
+  return {p->o_save[l], p->B, kCfg[l], p->LH[v], p->LW[v]};
+}
+}  // namespace
+
+extern "C" int drs_vgg_num_tensors(const drs_vgg_plan* plan) { return plan ? kVggTensors : 0; }
+extern "C" const char* drs_vgg_tensor_name(const drs_vgg_plan* plan, int i) {
+  return (plan && i >= 0 && i < kVggTensors) ? kVggTensorNames[i] : nullptr;
+}
+extern "C" int drs_vgg_tensor_shape(const drs_vgg_plan* plan, int i, int* n, int* c, int* h, int* w) {
+  DRS_REQUIRE(plan && i >= 0 && i < kVggTensors && n && c && h && w, DRS_ERR_ARG, "vgg_tensor_shape: bad index");
+  const VggTensor t = vgg_tensor(plan, i);
+  *n = t.n; *c = t.c; *h = t.h; *w = t.w;
+  return DRS_OK;
+}
+extern "C" int drs_vgg_read_tensor(const drs_vgg_plan* plan, int i, const void* workspace, float* dst, drs_stream_t stream) {
+  DRS_REQUIRE(plan && workspace && dst && i >= 0 && i < kVggTensors, DRS_ERR_ARG, "vgg_read_tensor: bad args");
+  DRS_REQUIRE(plan->saved || i == 0 || i == kVggTensors - 1, DRS_ERR_STATE,
+              "vgg_read_tensor: %s is kept only by a forward with save = 1", kVggTensorNames[i]);
+  const VggTensor t = vgg_tensor(plan, i);
+  return drs_launch_nhwc_to_nchw((const float*)(base256(workspace) + t.off), dst, t.n, t.c, t.h, t.w, t.c, 0,
+                                 (hipStream_t)stream);
+}
+
 extern "C" int drs_vgg_profile_enable(drs_vgg_plan* plan, int on) {
   DRS_REQUIRE(plan, DRS_ERR_ARG, "vgg_profile_enable: null plan");
   plan->prof = on != 0;

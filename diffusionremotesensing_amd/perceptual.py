@@ -106,6 +106,21 @@ class _Plan:
                                                  C.c_void_p(self.workspace.data_ptr()), self.ws_bytes,
                                                  _stream(self.device)), "drs_vgg_backward")
 
+    def tensor_names(self):
+        """Names of the tensors the last forward left in the workspace: x0, conv1 .. conv16 (save=True only), features."""
+        return [self.lib.drs_vgg_tensor_name(self.handle, i).decode() for i in range(self.lib.drs_vgg_num_tensors(self.handle))]
+
+    def read_tensor(self, name):
+        """One workspace tensor of the last forward as an NCHW fp32 device tensor (include/drs_hip.h drs_vgg_read_tensor)."""
+        i = self.tensor_names().index(name)
+        dims = [C.c_int() for _ in range(4)]
+        _lib.check(self.lib.drs_vgg_tensor_shape(self.handle, i, *[C.byref(d) for d in dims]), "drs_vgg_tensor_shape")
+        dst = torch.empty([d.value for d in dims], dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.drs_vgg_read_tensor(self.handle, i, C.c_void_p(self.workspace.data_ptr()),
+                                                    C.c_void_p(dst.data_ptr()), _stream(self.device)), "drs_vgg_read_tensor")
+        return dst
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h is not None and h.value:

@@ -61,7 +61,7 @@ enum {
  * Human-readable message for the last non-zero status returned on this thread. */
 DRS_API const char* drs_last_error(void);
 /* ABI version of this header; bumped on any signature change. */
-DRS_API int drs_abi_version(void);  /* 7 */
+DRS_API int drs_abi_version(void);  /* 8 */
 
 /* ------------------------------------------------------------------------------------------
  * Diffusion arithmetic
@@ -565,6 +565,16 @@ DRS_API int drs_vgg_backward(drs_vgg_plan* plan, const void* packed, const float
 DRS_API int drs_vgg_profile_enable(drs_vgg_plan* plan, int on);
 DRS_API int drs_vgg_profile_num_ops(const drs_vgg_plan* plan);
 DRS_API int drs_vgg_profile_read(drs_vgg_plan* plan, int i, char* name, int name_len, float* ms, double* flops);
+/* Read-out of the tensors a forward leaves in the workspace (ABI 8; the per-layer parity tests), as drs_unet_*_tensor:
+ *   "x0"                   (2 batch, 4, H0, W0)  the prep output, channel 3 = the zero pad channel
+ *   "conv1" .. "conv16"    (batch, C, h, w)      the saved prediction-half ReLU outputs, i.e. what drs_vgg_backward reads;
+ *                                                valid only after a forward with save = 1, else DRS_ERR_STATE
+ *   "features"             (2 batch, 512, h5, w5)
+ * drs_vgg_read_tensor copies tensor i out of `workspace` (NHWC) into dst_nchw (device, n * c * h * w floats). */
+DRS_API int drs_vgg_num_tensors(const drs_vgg_plan* plan);
+DRS_API const char* drs_vgg_tensor_name(const drs_vgg_plan* plan, int i);
+DRS_API int drs_vgg_tensor_shape(const drs_vgg_plan* plan, int i, int* n, int* c, int* h, int* w);
+DRS_API int drs_vgg_read_tensor(const drs_vgg_plan* plan, int i, const void* workspace, float* dst_nchw, drs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ def test_every_declared_symbol_is_exported_and_bound():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in drs_hip.h but not exported"
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
-    assert lib.drs_abi_version() == 7
+    assert lib.drs_abi_version() == 8
 
 
 def test_the_library_exports_nothing_but_the_declared_symbols():

@@ -82,7 +82,7 @@ def test_argument_validation_without_gpu():
     assert lib.drs_colorfix_adain_workspace_bytes(0, 3, 16, 16) == 0
     sizes = [lib.drs_colorfix_adain_workspace_bytes(b, 3, 40, 52) for b in (1, 2, 3, 16)]
     assert sizes == sorted(sizes) and len(set(sizes)) == 4
-    assert lib.drs_abi_version() == 7
+    assert lib.drs_abi_version() == 8
 
 
 def test_wrappers_have_no_cpu_path():

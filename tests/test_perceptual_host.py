@@ -117,3 +117,36 @@ def test_plan_shapes(H, W, ok):
             assert lib.drs_vgg_packed_bytes(h) > 20e6 * 4
             lib.drs_vgg_plan_destroy(h)
     assert lib.drs_vgg_plan_create(C.byref(h), 2, 64, 64, _lib.IMPL_DIRECT) == 1  # no direct-kernel VGG
+
+
+def test_plan_tensor_table():
+    """drs_vgg_num_tensors / _tensor_name / _tensor_shape: x0 with its pad channel, the 16 saved prediction-half ReLU outputs
+    at their (floor-halved) level sizes, the features of both halves; the saved tensors are refused before a forward with
+    save = 1, and a bad index or null pointer before anything runs."""
+    import ctypes as C
+    from diffusionremotesensing_amd import _lib
+    from diffusionremotesensing_amd.perceptual import FEATURE_CHANNELS
+    lib = _lib.load()
+    h = C.c_void_p()
+    assert lib.drs_vgg_num_tensors(None) == 0 and lib.drs_vgg_tensor_name(None, 0) is None
+    assert lib.drs_vgg_plan_create(C.byref(h), 3, 72, 224, _lib.IMPL_MFMA_F32) == 0, lib.drs_last_error()
+    names = [lib.drs_vgg_tensor_name(h, i).decode() for i in range(lib.drs_vgg_num_tensors(h))]
+    assert names == ["x0"] + [f"conv{l}" for l in range(1, 17)] + ["features"]
+    assert lib.drs_vgg_tensor_name(h, 18) is None and lib.drs_vgg_tensor_name(h, -1) is None
+
+    def shape(i):
+        d = [C.c_int() for _ in range(4)]
+        assert lib.drs_vgg_tensor_shape(h, i, *[C.byref(v) for v in d]) == 0
+        return tuple(v.value for v in d)
+    level = (0, 0, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4)
+    assert shape(0) == (6, 4, 72, 224)
+    assert [shape(1 + l) for l in range(16)] == [(3, FEATURE_CHANNELS[l], 72 >> level[l], 224 >> level[l]) for l in range(16)]
+    assert shape(9) == (3, 512, 9, 28) and shape(17) == (6, 512, 2, 7)
+    d = C.c_int()
+    assert lib.drs_vgg_tensor_shape(h, 18, *[C.byref(d)] * 4) == 1 and lib.drs_vgg_tensor_shape(h, 0, None, None, None, None) == 1
+    fake = C.c_void_p(256)  # never dereferenced: every call below is refused first
+    assert lib.drs_vgg_read_tensor(h, 18, fake, fake, None) == 1
+    assert lib.drs_vgg_read_tensor(h, 0, None, fake, None) == 1 and lib.drs_vgg_read_tensor(h, 0, fake, None, None) == 1
+    for i in range(1, 17):
+        assert lib.drs_vgg_read_tensor(h, i, fake, fake, None) == 5 and b"save = 1" in lib.drs_last_error()
+    lib.drs_vgg_plan_destroy(h)
