@@ -10,6 +10,7 @@ from .train_diffusion_superres import Diffusion, launch  # noqa: F401
 from .ensemble import ensemble_scores, ensemble_statistics  # noqa: F401
 from . import colorfix  # noqa: F401
 from .colorfix import color_fix  # noqa: F401
+from . import bsr  # noqa: F401
 
 __all__ = ["EMA", "Residual_Attention_UNet_superres", "Diffusion", "launch", "ensemble_scores", "ensemble_statistics",
-           "colorfix", "color_fix"]
+           "colorfix", "color_fix", "bsr"]

@@ -61,6 +61,13 @@ SIGNATURES = {
     "drs_colorfix_wavelet": (_I, [_P, _P, _P] + [_I] * 5 + [_P]),
     "drs_colorfix_adain_workspace_bytes": (_Z, [_I] * 4),
     "drs_colorfix_adain": (_I, [_P, _P, _P] + [_I] * 4 + [_P, _Z, _P]),
+    "drs_bsr_blur": (_I, [_P, _P, _P, _P] + [_I] * 5 + [_P]),
+    "drs_bsr_blur_sep": (_I, [_P, _P, C.POINTER(_F)] + [_I] * 5 + [_P]),
+    "drs_bsr_sharpen": (_I, [_P, _P, _P, C.POINTER(_F), _I, _F, _F] + [_I] * 4 + [_P]),
+    "drs_bsr_resize": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
+    "drs_bsr_noise": (_I, [_P] * 5 + [_I] * 4 + [_P]),
+    "drs_bsr_jpeg_scratch_bytes": (_Z, [_I] * 3),
+    "drs_bsr_jpeg": (_I, [_P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "drs_conv2d_workspace_bytes": (_Z, [_I] * 11),
     "drs_conv2d_nchw": (_I, [_P, _P, _P, _P] + [_I] * 12 + [_P, _Z, _I, _P]),
     "drs_upconv_fused_workspace_bytes": (_Z, [_I] * 5),

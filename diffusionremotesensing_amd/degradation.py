@@ -13,7 +13,7 @@ reference uses (Python `random` for the level, numpy's global generator for ever
 item (`reference_noise`); the add and the clip run on the device (`drs_add_noise_clip_f32`).  Seeded alike, the feed
 reproduces the reference's items bit for bit (tests/test_gpu_degradation.py, fixtures from the reference function itself).
 `load_image_folder_u8` fills the cache from an image folder (decode + the launch transform's resize with Pillow, once).
-Not covered: the BSRGAN degradation.
+The BSRGAN degradation is the second device feed, over the same uint8 cache: `bsr.DeviceBSRFeed` (bsr.py).
 """
 import ctypes as C
 import random

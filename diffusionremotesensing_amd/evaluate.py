@@ -30,7 +30,7 @@ import torch
 
 from .colorfix import add_color_fix_args, cli_color_fix
 from .sampling import plan_of
-from .train_diffusion_superres import (METRIC_FORMATS, Diffusion, add_solver_args, build_arg_parser, cli_sampling_steps,
+from .train_diffusion_superres import (METRIC_FORMATS, Diffusion, add_bsr_args, add_solver_args, build_arg_parser, cli_sampling_steps,
                                        launch_device, make_superres_feeds)
 from .UNet_model_superres import Residual_Attention_UNet_superres
 
@@ -151,9 +151,9 @@ def sampling_line(sampling_steps, eta):
 
 def cli_arg_parser(task="superres"):
     """The whole command line of `main` for `task`: `evaluate_arg_parser` with the known-pixel, ensemble and solver flags and,
-    for superres (the task with an LR guide), --color_fix / --color_fix_levels."""
+    for superres (the task with an LR guide), --color_fix / --color_fix_levels and the BSRGAN feed's --bsr_kind / --bsr_seed."""
     p = add_solver_args(add_ensemble_args(add_known_args(evaluate_arg_parser(task))))
-    return add_color_fix_args(p) if task == "superres" else p
+    return add_bsr_args(add_color_fix_args(p)) if task == "superres" else p
 
 
 def main(argv=None):

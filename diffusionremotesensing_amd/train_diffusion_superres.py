@@ -569,15 +569,27 @@ def make_superres_feeds(args, device):
         # Pillow on the host) from a uint8 HR cache on the device, bit-exact (degradation.py); rank r owns every
         # world-th image like DistributedSampler
         from .degradation import DeviceSuperresFeed, load_image_folder_u8
-        if args.Degradation_type.lower() not in ("downblur", "downblurnoise"):
-            raise NotImplementedError("the on-device feed implements Degradation_type=DownBlur and DownBlurNoise "
-                                      "(the BSRGAN degradation is outside the hot path)")
-        gauss_noise = args.Degradation_type.lower() == "downblurnoise"  # (reference :612-616: Gauss_noise=True)
-        radius = args.Blur_radius if args.Blur_radius == "random" else float(args.Blur_radius)
+        deg = args.Degradation_type.lower()
+        gauss_noise = deg == "downblurnoise"  # (reference :612-616: Gauss_noise=True)
+        if deg == "bsrgan":
+            # the blind degradation, fresh for every batch on the device (bsr.py); rank r draws its own recipes; the validation
+            # feed starts from its seed at every epoch (the reference's frozen validation set)
+            from .bsr import DeviceBSRFeed
+            kind, seed = getattr(args, "bsr_kind", "plus"), getattr(args, "bsr_seed", 0)
 
-        def make_feed(u8):
-            return DeviceSuperresFeed(u8.to(device), args.magnification_factor, radius, args.batch_size, shuffle=True,
-                                      Gauss_noise=gauss_noise)
+            def make_feed(u8, fixed=False):
+                return DeviceBSRFeed(u8.to(device), args.magnification_factor, args.batch_size, shuffle=not fixed, kind=kind,
+                                     seed=seed + (1 if fixed else 2 + r), fixed=fixed)
+
+            def first_items(u8):  # the LR images of the final sampling: the first five training images under the fixed seed
+                feed = DeviceBSRFeed(u8.to(device), args.magnification_factor, 1, shuffle=False, kind=kind, seed=seed, fixed=True)
+                return [feed.item(i)[0] for i in range(u8.shape[0])]
+        else:
+            radius = args.Blur_radius if args.Blur_radius == "random" else float(args.Blur_radius)
+
+            def make_feed(u8, fixed=False):
+                return DeviceSuperresFeed(u8.to(device), args.magnification_factor, radius, args.batch_size, shuffle=True,
+                                          Gauss_noise=gauss_noise)
     if not spec.startswith("synthetic"):
         # an image folder, laid out as the reference expects it (:597-598): <dataset_path>/train_original, /val_original.
         # Decoded once with Pillow into the uint8 cache (this rank's shard only); resize / blur / noise per batch on the device
@@ -585,32 +597,40 @@ def make_superres_feeds(args, device):
             raise FileNotFoundError(f"--dataset_path {spec!r}: expected the folders train_original/ and val_original/ "
                                     "(or synthetic[:N] / synthetic_u8[:N])")
         train_loader = make_feed(load_image_folder_u8(os.path.join(spec, "train_original"), args.image_size, r, wsz))
-        val_loader = make_feed(load_image_folder_u8(os.path.join(spec, "val_original"), args.image_size, r, wsz))
+        val_loader = make_feed(load_image_folder_u8(os.path.join(spec, "val_original"), args.image_size, r, wsz), fixed=True)
         for what, feed in (("train_original", train_loader), ("val_original", val_loader)):
             if feed.hr.shape[1] != ch:
                 raise ValueError(f"the images of {what} have {feed.hr.shape[1]} channels, --inp_out_channels is {ch}")
         # the final sampling conditions on train_dataset[0..4] of the WHOLE sorted folder (reference :678-680), whatever this
         # rank's shard holds; with Gauss_noise the dataset item carries its noise (utils.py:126-138)
         first = load_image_folder_u8(os.path.join(spec, "train_original"), args.image_size, limit=5).to(device)
-        from .degradation import add_reference_noise, downblur
-        final_x = downblur(first, args.magnification_factor, train_loader.blur_radius)[0]
-        if gauss_noise:
-            add_reference_noise(final_x, noise_level1=2, noise_level2=10)
-        final_lr = [final_x[i] for i in range(final_x.shape[0])]
+        if deg == "bsrgan":
+            final_lr = first_items(first)
+        else:
+            from .degradation import add_reference_noise, downblur
+            final_x = downblur(first, args.magnification_factor, train_loader.blur_radius)[0]
+            if gauss_noise:
+                add_reference_noise(final_x, noise_level1=2, noise_level2=10)
+            final_lr = [final_x[i] for i in range(final_x.shape[0])]
     else:
         length = int(spec.split(":")[1]) if ":" in spec else 4 * args.batch_size
         train_dataset = SyntheticSuperresDataset(length, ch, args.image_size, args.magnification_factor, seed=1)
         val_dataset = SyntheticSuperresDataset(max(length // 4, 1), ch, args.image_size, args.magnification_factor, seed=2)
         final_lr = [train_dataset[i][0] for i in range(min(5, len(train_dataset)))]
         if device_feed:
-            def feed(ds):
+            def to_u8(hr):
+                return (hr * 255).round().clamp(0, 255).to(torch.uint8)
+
+            def feed(ds, fixed=False):
                 # equal shard sizes on every rank (DistributedSampler pads; here the remainder is dropped): ranks must run
                 # the same number of steps, or the per-step all-reduce of the longer shard never completes
                 per_rank = len(ds) // wsz
                 if per_rank == 0:
                     raise ValueError(f"dataset of {len(ds)} images cannot be sharded over {wsz} ranks")
-                return make_feed((ds.hr[r::wsz][:per_rank] * 255).round().clamp(0, 255).to(torch.uint8))
-            train_loader, val_loader = feed(train_dataset), feed(val_dataset)
+                return make_feed(to_u8(ds.hr[r::wsz][:per_rank]), fixed)
+            train_loader, val_loader = feed(train_dataset), feed(val_dataset, fixed=True)
+            if deg == "bsrgan":
+                final_lr = first_items(to_u8(train_dataset.hr[:5]))
         else:
             train_loader, val_loader = make_loaders(args, train_dataset, val_dataset)
     return train_loader, val_loader, final_lr
@@ -683,8 +703,19 @@ def build_arg_parser():
     p.add_argument("--inp_out_channels", type=int, default=3)
     p.add_argument("--magnification_factor", type=int)
     p.add_argument("--Degradation_type", type=str, default="DownBlur")
-    p.add_argument("--num_crops", type=int, default=1)
+    p.add_argument("--num_crops", type=int, default=1,
+                   help="parsed for the reference's command lines and unused: the BSRGAN feed degrades every batch afresh on the "
+                        "device instead of keeping num_crops frozen copies per image")
     p.add_argument("--Blur_radius", type=str, default="random")
+    return p
+
+
+def add_bsr_args(p):
+    """--bsr_kind / --bsr_seed of the command lines that build the BSRGAN feed (not in the reference; `make_superres_feeds`)."""
+    p.add_argument("--bsr_kind", type=str, choices=("plus", "soft"), default="plus",
+                   help="with --Degradation_type BSRGAN: plus (degradation_bsrgan_plus: USM, two rounds of blur / resize / noise, "
+                        "JPEG) or soft (blur, resize, noise once)")
+    p.add_argument("--bsr_seed", type=int, default=0, help="with --Degradation_type BSRGAN: seed of the recipes and the noise")
     return p
 
 
@@ -713,9 +744,9 @@ def add_sampling_args(p):
 
 
 def parse_train_args(argv=None):
-    """The trainer's command line: `build_arg_parser` and `--eval_metrics`, which one process evaluates (no distributed
-    evaluation: rejected together with --multiple_gpus)."""
-    p = build_arg_parser()
+    """The trainer's command line: `build_arg_parser`, the BSRGAN feed's flags and `--eval_metrics`, which one process evaluates
+    (no distributed evaluation: rejected together with --multiple_gpus)."""
+    p = add_bsr_args(build_arg_parser())
     p.add_argument("--eval_metrics", type=int, default=0,
                    help="score the network on the first N validation images (PSNR / SSIM / SAM / ERGAS against the bicubic "
                         "baseline) at every epoch with epoch %% check_preds_epoch == 0; 0 = off")

@@ -379,6 +379,53 @@ DRS_API int drs_gather_pairs_f32(const float* sar_cache, const float* ndvi_cache
 DRS_API int drs_gather_u8_f32(const uint8_t* cache_u8, const int64_t* labels, const int64_t* idx, int n, int64_t L, int row,
                               float* img_out, int64_t* labels_out, drs_stream_t stream);
 
+/* The ops of the blind (BSRGAN-plus) degradation feed (csrc/bsr_degrade.hip; recipe and feed in diffusionremotesensing_amd/bsr.py,
+ * definitions in DESIGN.md section 19).  Every op is one launch (sharpen and jpeg: two) over a dense (N,C,H,W) fp32 batch, 1 <= C
+ * <= 16; per-image parameters are device arrays, so a batch's whole recipe is one upload.  Nothing draws random numbers.
+ * DRS_ERR_ARG: null pointer, overlapping tensors, unknown mode; DRS_ERR_SHAPE: sizes; DRS_ERR_WORKSPACE: scratch too small.
+ *
+ * drs_bsr_blur: out[n][c] = kernel_n (*) x[n][c], a TRUE convolution (scipy.ndimage.convolve: the kernel is flipped) with the
+ *   border continued by reflection about the edge pixels' centres (cv2 BORDER_REFLECT_101, scipy "mirror"), repeated as often as
+ *   the image's size asks.  kernels: (N,K,K) fp32 on the device, K odd, 1 <= K <= 25; ksizes: N int32 on the device or NULL -
+ *   image n's kernel is the centred ksizes[n] x ksizes[n] part of its table (the rest is not read; anything but an odd size in
+ *   1 .. K means K).  `out` must not overlap `x`.
+ * drs_bsr_blur_sep: out = g (*) g^T (*) x for ONE 1-D kernel g of k taps (HOST pointer; k odd, 1 <= k <= 51), all planes alike;
+ *   same border.  The USM's Gaussian is k = 51, sigma = 0.3 ((k - 1) / 2 - 1) + 0.8 = 8 (cv2.GaussianBlur's rule for sigma 0).
+ * drs_bsr_sharpen: unsharp masking, blur = drs_bsr_blur_sep(x):
+ *     mask = |x - blur| * 255 > threshold,  soft = drs_bsr_blur_sep(mask),  out = soft clip(x + weight (x - blur), 0, 1) + (1 - soft) x
+ *   scratch: N C H W floats (holds blur).  x, out and scratch must not overlap.
+ * drs_bsr_resize: (N,C,H,W) -> (N,C,H2,W2), clipped to [0, 1].  Output sample o of an axis sits at (o + 1/2) in / out - 1/2; taps
+ *   outside the image take the border pixel.  mode 1: bilinear.  mode 2: bicubic, the 4-tap cubic convolution kernel with a =
+ *   -0.75, no antialiasing.  mode 3: area - per axis, where it shrinks, the mean over [o in / out, (o + 1) in / out) with
+ *   fractional end pixels, and bilinear where it does not.  These are the project's definitions of cv2.resize's interpolation
+ *   flags 1 / 2 / 3; no parity with cv2 is claimed.  in == out is the identity.  out_q (or NULL): a second output,
+ *   rint(out * 255) / 255.
+ * drs_bsr_noise: in place, per image n with mode[n] = (kind, branch) int32 and par[n] = (sigma, A[3][3]) - 10 floats - on the
+ *   device, z (N,C,H,W) the given draws:
+ *     noise   branch 0: nv[c] = sigma z[c];  1: nv[c] = sigma z[0];  2 (C == 3, else taken as 0): nv = A (z[0], z[1], z[2])
+ *     kind 0  the image is not written;  1  x = clip(x + nv);  2  x = clip(clip(x) + clip(x) nv)   (speckle)
+ *     kind 3  x[c] = clip(z[c] / sigma)   (z: Poisson draws at rate q(x) sigma, q(x) = rint(clip(x) 255) / 255)
+ *     kind 4  x[c] = clip(q(x[c]) + (z[0] - aux) / sigma)   (aux (N,H,W): the rate gray(q(x)) sigma of the draw z[0]; without
+ *             aux the image is not written)
+ * drs_bsr_jpeg: C = 3; out = the baseline-JPEG round trip of x at quality[n] (N int32 on the device, clamped to 1 .. 100),
+ *   4:2:0, in integer arithmetic throughout: bytes rint(clip(x) 255), libjpeg's 16-bit fixed-point YCbCr,
+ *   2 x 2 chroma means with the alternating bias, the edge pixel repeated up to a multiple of 16, Annex K tables under
+ *   libjpeg's quality rule, a 14-bit fixed-point 8 x 8 DCT, quantisation to the nearest integer with halves away from zero,
+ *   triangle chroma up-sampling, bytes / 255.  One work-group per 16 x 16 MCU writes the decoded planes to `scratch`
+ *   (drs_bsr_jpeg_scratch_bytes(N, H, W) bytes); a second launch up-samples across MCU borders and converts.  out may be x. */
+DRS_API int drs_bsr_blur(const float* x, float* out, const float* kernels, const int* ksizes, int N, int C, int H, int W, int K,
+                         drs_stream_t stream);
+DRS_API int drs_bsr_blur_sep(const float* x, float* out, const float* taps, int k, int N, int C, int H, int W, drs_stream_t stream);
+DRS_API int drs_bsr_sharpen(const float* x, float* out, float* scratch, const float* taps, int k, float weight, float threshold,
+                            int N, int C, int H, int W, drs_stream_t stream);
+DRS_API int drs_bsr_resize(const float* x, float* out, float* out_q, int N, int C, int H, int W, int H2, int W2, int mode,
+                           drs_stream_t stream);
+DRS_API int drs_bsr_noise(float* x, const float* z, const float* aux, const int* mode, const float* par, int N, int C, int H, int W,
+                          drs_stream_t stream);
+DRS_API size_t drs_bsr_jpeg_scratch_bytes(int N, int H, int W);
+DRS_API int drs_bsr_jpeg(const float* x, float* out, const int* quality, int N, int H, int W, void* scratch, size_t scratch_bytes,
+                         drs_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Operator-level entry points (used by the parity tests for every convolution flavour
  * the UNet contains, at arbitrary/ragged shapes)
