@@ -45,6 +45,9 @@ SIGNATURES = {
     "drs_add_noise_clip_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "drs_gather_pairs_f32": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _P]),
     "drs_gather_u8_f32": (_I, [_P, _P, _P, _I, _L, _I, _P, _P, _P]),
+    "drs_crop_d4_u8": (_I, [_P, _P, _I, _L] + [_I] * 4 + [_P, _P]),
+    "drs_crop_d4_u8_f32": (_I, [_P, _P, _P, _I, _L] + [_I] * 4 + [_P, _P, _P]),
+    "drs_crop_d4_pairs_f32": (_I, [_P, _P, _P, _I, _L] + [_I] * 5 + [_P, _P, _P]),
     "drs_aggregate_tiles": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "drs_aggregate_tiles_known": (_I, [_P] * 7 + [_I] * 7 + [_F, _F, _P]),
     "drs_gather_tiles": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -17,9 +17,11 @@ degradation on the device, from the uint8 HR cache `DeviceSuperresFeed` keeps th
              for kind "plus", as the reference's `hq` is), LR is image_size // m on a side and lies on the k / 255 grid like the
              reference's stored dataset.
 
-Dropped from the reference: `random_crop` (the cache already holds crops) and its BSRGAN-mode meaning of `image_size` (the LR
-size).  With c != 3 bands JPEG is skipped, the correlated-noise branch falls to per-band noise and the gray Poisson branch to the
-per-band one: those need 3 bands in the reference as well.  The ISP slots are no-ops (`isp_model` is always None there).
+`random_crop` and `num_crops` of the reference's dataset are the feed's `crop_size` / `num_crops` arguments (augment.py: fresh
+windows per batch, cut on the device); without them the cache already holds the training images.  Dropped from the reference: its
+BSRGAN-mode meaning of `image_size` (the LR size).  With c != 3 bands JPEG is skipped, the correlated-noise branch falls to
+per-band noise and the gray Poisson branch to the per-band one: those need 3 bands in the reference as well.  The ISP slots are
+no-ops (`isp_model` is always None there).
 """
 import ctypes as C
 import math
@@ -457,9 +459,16 @@ class DeviceBSRFeed:
     uint8 on the device, LR S // m on a side.  Every batch draws a fresh recipe (`draw_recipe`, kind "plus" or "soft") and fresh
     noise from generators seeded with `seed`: two feeds with one seed yield the same batches; the epochs of one feed differ,
     unless it is `fixed` - then every `__iter__` starts from the seed again (the validation feed: the reference's frozen
-    validation set, so validation losses compare across epochs)."""
+    validation set, so validation losses compare across epochs).
 
-    def __init__(self, hr_u8, magnification_factor, batch_size=16, shuffle=True, kind="plus", seed=0, fixed=False):
+    `crop_size` / `augment` ("none", "flip", "d4") make the feed active (augment.py): every item is a
+    crop_size window of its cache image (default: the whole, square image) under a symmetry of the mode, drawn from the feed's own
+    `np.random.default_rng([augment_seed, augment_rank])` - not from the recipe or noise generators; the recipe is drawn for the
+    window's size; an epoch is `num_crops` passes over the cache; `fixed_crop`: the centre window, no symmetry, one pass.
+    `last_items`: the last batch's (n, 4) host items (src, y0, x0, code)."""
+
+    def __init__(self, hr_u8, magnification_factor, batch_size=16, shuffle=True, kind="plus", seed=0, fixed=False, crop_size=None,
+                 augment="none", num_crops=1, augment_seed=0, augment_rank=0, fixed_crop=False):
         if kind not in KINDS:
             raise ValueError(f"kind={kind!r} must be one of {KINDS}")
         if not isinstance(hr_u8, torch.Tensor) or not hr_u8.is_cuda or hr_u8.dtype != torch.uint8 or hr_u8.dim() != 4:
@@ -475,6 +484,14 @@ class DeviceBSRFeed:
         self.seed = int(seed)
         self.fixed = fixed
         self._labels = torch.zeros(self.hr.shape[0], dtype=torch.int64, device=self.hr.device)
+        self._aug = None
+        if crop_size is not None or augment != "none":
+            from .augment import FeedAugment
+            self._aug = FeedAugment(self.hr.shape[2], self.hr.shape[3], crop_size, augment, num_crops, augment_seed, augment_rank,
+                                    fixed_crop)
+            if self._aug.size // m < 1:
+                raise RuntimeError(f"DeviceBSRFeed: windows of {self._aug.size} are too small for magnification {m}")
+        self.last_items = None
         self._seed_generators()
 
     def _seed_generators(self):
@@ -482,11 +499,21 @@ class DeviceBSRFeed:
         self._gen = torch.Generator(device=self.hr.device).manual_seed(self.seed)
 
     def __len__(self):
+        if self._aug is not None:
+            return self._aug.num_batches(self.hr.shape[0], self.batch_size)
         return (self.hr.shape[0] + self.batch_size - 1) // self.batch_size
 
     def _batch(self, idx, rng, gen):
         from .feeds import gather_u8
         hr = gather_u8(self.hr, self._labels, idx)[0]
+        n, c, h, w = hr.shape
+        return degrade(hr, draw_recipe(rng, n, c, h, w, self.magnification_factor, self.kind), generator=gen)
+
+    def _batch_items(self, items, rng, gen):
+        """`_batch` of an active feed: the windows of `items` as float(b) / 255 (what `gather_u8` makes of whole images), degraded
+        under a recipe for the window's size."""
+        from .augment import crop_d4_u8_f32, upload_items
+        hr = crop_d4_u8_f32(self.hr, self._labels, upload_items(items, self.hr.device), self._aug.size)[0]
         n, c, h, w = hr.shape
         return degrade(hr, draw_recipe(rng, n, c, h, w, self.magnification_factor, self.kind), generator=gen)
 
@@ -496,12 +523,28 @@ class DeviceBSRFeed:
         idx = int(idx)
         rng = np.random.default_rng([self.seed, idx])
         gen = torch.Generator(device=self.hr.device).manual_seed(self.seed * 1000003 + idx)
+        if self._aug is not None:  # the centre window, no symmetry
+            if not 0 <= idx < self.hr.shape[0]:
+                raise IndexError(f"item {idx} of a dataset of {self.hr.shape[0]}")
+            x, y = self._batch_items(self._aug.centre(idx), rng, gen)
+            return x[0], y[0]
         x, y = self._batch(torch.tensor([idx], dtype=torch.int64, device=self.hr.device), rng, gen)
         return x[0], y[0]
+
+    def epoch_order(self):
+        """The index vector of one epoch of an active feed, on the host: `num_crops` orders drawn as one is drawn today."""
+        n = self.hr.shape[0]
+        return self._aug.epoch_order(lambda: torch.from_numpy(self._rng.permutation(n) if self.shuffle else np.arange(n)))
 
     def __iter__(self):
         if self.fixed:
             self._seed_generators()
+        if self._aug is not None:
+            order = self.epoch_order().numpy()
+            for i in range(0, order.shape[0], self.batch_size):
+                self.last_items = self._aug.items(order[i:i + self.batch_size])
+                yield self._batch_items(self.last_items, self._rng, self._gen)
+            return
         n = self.hr.shape[0]
         order = torch.from_numpy(self._rng.permutation(n) if self.shuffle else np.arange(n)).to(self.hr.device)
         for i in range(0, n, self.batch_size):

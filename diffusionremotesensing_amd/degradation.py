@@ -238,11 +238,23 @@ def load_image_folder_u8(root_dir, image_size=None, rank=0, world_size=1, limit=
 class DeviceSuperresFeed:
     """Iterable of (lr, hr) float batches drawn from a uint8 HR cache on the device: what
     `DataLoader(get_data_superres(root, magnification_factor, blur_radius), batch_size, shuffle)` yields, without
-    the per-item PIL work.  `hr_u8`: (L, C, H, W) uint8 on the device (the decoded dataset)."""
+    the per-item PIL work.  `hr_u8`: (L, C, H, W) uint8 on the device (the decoded dataset).
+
+    `crop_size` / `augment` ("none", "flip", "d4") make the feed active (augment.py): every batch is first
+    cut out of the cache - a crop_size window per item (default: the whole, square image) under a symmetry of the mode, drawn
+    from the feed's own `np.random.default_rng([augment_seed, augment_rank])` - and the degradation runs on those bytes as it
+    does on `hr[idx]`; an epoch is `num_crops` passes over the cache; `fixed_crop`: the centre window, no symmetry, one pass.
+    `last_items`: the last batch's (n, 4) host items (src, y0, x0, code)."""
 
     def __init__(self, hr_u8, magnification_factor, blur_radius=0.5, batch_size=16, shuffle=True, generator=None,
-                 Gauss_noise=False):
+                 Gauss_noise=False, crop_size=None, augment="none", num_crops=1, augment_seed=0, augment_rank=0, fixed_crop=False):
         self.hr = hr_u8
+        self._aug = None
+        if crop_size is not None or augment != "none":
+            from .augment import FeedAugment
+            self._aug = FeedAugment(hr_u8.shape[2], hr_u8.shape[3], crop_size, augment, num_crops, augment_seed, augment_rank,
+                                    fixed_crop)
+        self.last_items = None
         self.magnification_factor = magnification_factor
         if blur_radius == "random":  # drawn once per dataset object, like the reference
             blur_radius = random.triangular(0.5, 1.5, 1)
@@ -253,15 +265,54 @@ class DeviceSuperresFeed:
         self.Gauss_noise = Gauss_noise  # reference get_data_superres(..., Gauss_noise): levels 2 .. 10 per item
 
     def __len__(self):
+        if self._aug is not None:
+            return self._aug.num_batches(self.hr.shape[0], self.batch_size)
         return (self.hr.shape[0] + self.batch_size - 1) // self.batch_size
+
+    def _crop(self, items):
+        from .augment import crop_d4_u8, upload_items
+        return crop_d4_u8(self.hr, upload_items(items, self.hr.device), self._aug.size)
 
     def item(self, idx):
         """(x, y) of one dataset item, (C, h, w) / (C, H, W): `dataset[idx]` of the reference's Dataset (no noise draw is
-        consumed for Gauss_noise feeds: previews and the final sampling only need the degraded image's shape and content)."""
+        consumed for Gauss_noise feeds: previews and the final sampling only need the degraded image's shape and content).
+        An active feed: the centre window, no symmetry."""
+        if self._aug is not None:
+            if not 0 <= idx < self.hr.shape[0]:
+                raise IndexError(f"item {idx} of a dataset of {self.hr.shape[0]}")
+            x, y = downblur(self._crop(self._aug.centre(idx)), self.magnification_factor, self.blur_radius)
+            return x[0], y[0]
         x, y = downblur(self.hr[idx:idx + 1], self.magnification_factor, self.blur_radius)
         return x[0], y[0]
 
+    def epoch_order(self):
+        """The index vector of one epoch of an active feed, on the host: `num_crops` orders drawn as one is drawn today."""
+        n = self.hr.shape[0]
+        return self._aug.epoch_order(lambda: torch.randperm(n, generator=self.generator) if self.shuffle else torch.arange(n))
+
+    def _iter_active(self):
+        order = self.epoch_order().numpy()
+        n, size = order.shape[0], self._aug.size
+        noise = None
+        if self.Gauss_noise and n:
+            m = int(self.magnification_factor)
+            noise = NoisePrefetcher([min(self.batch_size, n - i) for i in range(0, n, self.batch_size)], self.hr.shape[1],
+                                    size // m, size // m, 2, 10)
+        try:
+            for i in range(0, n, self.batch_size):
+                self.last_items = self._aug.items(order[i:i + self.batch_size])
+                x, y = downblur(self._crop(self.last_items), self.magnification_factor, self.blur_radius)
+                if noise is not None:
+                    add_noise_clip_(x, noise.next())
+                yield x, y
+        finally:
+            if noise is not None:
+                noise.close()
+
     def __iter__(self):
+        if self._aug is not None:
+            yield from self._iter_active()
+            return
         n = self.hr.shape[0]
         order = torch.randperm(n, generator=self.generator) if self.shuffle else torch.arange(n)
         order = order.to(self.hr.device)

@@ -162,6 +162,10 @@ def main(argv=None):
     pre.add_argument("--task", type=str, default="superres", choices=TASKS)
     task = pre.parse_known_args(argv)[0].task
     p = cli_arg_parser(task)
+    # a model trained on windows of P x P scenes is scored on the validation scenes' centre windows (augment.py)
+    p.add_argument("--scene_size", type=int, default=None,
+                   help="the dataset holds P x P scenes (P >= --image_size), as in the training run: score the centre "
+                        "--image_size windows of the validation scenes")
     args = p.parse_args(argv)
     if args.multiple_gpus:
         p.error("evaluate runs in one process: --multiple_gpus is not supported")

@@ -139,12 +139,27 @@ def _epoch_order(length, shuffle, generator, device):
     return order.to(device)
 
 
+def _feed_augment(H, W, crop_size, augment, num_crops, augment_seed, augment_rank, fixed_crop):
+    """The FeedAugment of a feed's crop / augmentation arguments, or None where they are the defaults: the feed then imports and
+    calls nothing of augment.py."""
+    if crop_size is None and augment == "none":
+        return None
+    from .augment import FeedAugment
+    return FeedAugment(H, W, crop_size, augment, num_crops, augment_seed, augment_rank, fixed_crop)
+
+
 class DeviceSarNdviFeed:
     """Iterable of (SAR, NDVI) fp32 batches in [0, 1] drawn from the two caches on the device: what
     `DataLoader(get_data_SAR_TO_NDVI(root), batch_size, shuffle)` yields.  `sar`, `ndvi`: (L, C, H, W) fp32 on the device, the
-    values of the files (load_sar_ndvi_folder)."""
+    values of the files (load_sar_ndvi_folder).
 
-    def __init__(self, sar, ndvi, batch_size=16, shuffle=True, generator=None):
+    `crop_size` / `augment` ("none", "flip", "d4") make the feed active (augment.py): every item is a
+    crop_size window of its image (default: the whole, square image) under a symmetry of the mode, the same for both tensors of
+    the pair, drawn from the feed's own `np.random.default_rng([augment_seed, augment_rank])`; an epoch is `num_crops` passes
+    over the cache; `fixed_crop`: the centre window, no symmetry, one pass.  `last_items`: the last batch's (n, 4) host items."""
+
+    def __init__(self, sar, ndvi, batch_size=16, shuffle=True, generator=None, crop_size=None, augment="none", num_crops=1,
+                 augment_seed=0, augment_rank=0, fixed_crop=False):
         # (the device is checked where a batch is made: gather_pairs)
         self.sar, self.ndvi = _check_cache("sar", sar, torch.float32, False), _check_cache("ndvi", ndvi, torch.float32, False)
         if self.ndvi.shape[0] != self.sar.shape[0]:
@@ -152,19 +167,43 @@ class DeviceSarNdviFeed:
         self.batch_size = batch_size
         self.shuffle = shuffle
         self.generator = generator
+        self._aug = _feed_augment(self.sar.shape[2], self.sar.shape[3], crop_size, augment, num_crops, augment_seed, augment_rank,
+                                  fixed_crop)
+        self.last_items = None
 
     def __len__(self):
+        if self._aug is not None:
+            return self._aug.num_batches(self.sar.shape[0], self.batch_size)
         return (self.sar.shape[0] + self.batch_size - 1) // self.batch_size
 
+    def _crop(self, items):
+        from .augment import crop_d4_pairs, upload_items
+        return crop_d4_pairs(self.sar, self.ndvi, upload_items(items, self.sar.device), self._aug.size)
+
     def item(self, idx):
-        """(SAR, NDVI) of one dataset item, (C, H, W) each: `dataset[idx]` of the reference's Dataset."""
+        """(SAR, NDVI) of one dataset item, (C, H, W) each: `dataset[idx]` of the reference's Dataset (an active feed: the centre
+        window, no symmetry)."""
         if not 0 <= idx < self.sar.shape[0]:
             raise IndexError(f"item {idx} of a dataset of {self.sar.shape[0]}")
+        if self._aug is not None:
+            x, y = self._crop(self._aug.centre(idx))
+            return x[0], y[0]
         x, y = gather_pairs(self.sar, self.ndvi, torch.tensor([idx], dtype=torch.int64).to(self.sar.device))
         return x[0], y[0]
 
+    def epoch_order(self):
+        """The index vector of one epoch of an active feed, on the host: `num_crops` orders drawn as one is drawn today."""
+        n = self.sar.shape[0]
+        return self._aug.epoch_order(lambda: _epoch_order(n, self.shuffle, self.generator, "cpu"))
+
     def __iter__(self):
         n = self.sar.shape[0]
+        if self._aug is not None:
+            order = self.epoch_order().numpy()
+            for i in range(0, order.shape[0], self.batch_size):
+                self.last_items = self._aug.items(order[i:i + self.batch_size])
+                yield self._crop(self.last_items)
+            return
         order = _epoch_order(n, self.shuffle, self.generator, self.sar.device)
         for i in range(0, n, self.batch_size):
             yield gather_pairs(self.sar, self.ndvi, order[i:i + self.batch_size])
@@ -229,6 +268,9 @@ class _ClassItems:
     def __getitem__(self, idx):
         if not 0 <= idx < len(self):
             raise IndexError(f"item {idx} of a dataset of {len(self)}")
+        if self._feed._aug is not None:  # an active feed: the centre window, no symmetry
+            img, label = self._feed._crop(self._feed._aug.centre(idx))
+            return img[0], int(label[0])
         img, label = gather_u8(self._feed.u8, self._feed.labels, torch.tensor([idx], dtype=torch.int64).to(self._feed.u8.device))
         return img[0], int(label[0])
 
@@ -236,9 +278,11 @@ class _ClassItems:
 class DeviceClassFeed:
     """Iterable of (img fp32 in [0, 1], label int64) device batches drawn from a uint8 cache on the device: what
     `DataLoader(ImageFolder(root, transform), batch_size, shuffle)` yields.  `u8`: (L, C, S, S) uint8, `labels`: (L,) int64, both
-    on the device (load_class_folder_u8)."""
+    on the device (load_class_folder_u8).  `crop_size`, `augment`, `num_crops`, `augment_seed`, `augment_rank`, `fixed_crop`,
+    `last_items`: as in DeviceSarNdviFeed."""
 
-    def __init__(self, u8, labels, classes, batch_size=16, shuffle=True, generator=None):
+    def __init__(self, u8, labels, classes, batch_size=16, shuffle=True, generator=None, crop_size=None, augment="none",
+                 num_crops=1, augment_seed=0, augment_rank=0, fixed_crop=False):
         self.u8 = _check_cache("u8", u8, torch.uint8, False)  # (the device is checked where a batch is made: gather_u8)
         if not isinstance(labels, torch.Tensor) or labels.device != self.u8.device or labels.dtype != torch.int64 or \
                 tuple(labels.shape) != (self.u8.shape[0],):
@@ -248,13 +292,33 @@ class DeviceClassFeed:
         self.batch_size = batch_size
         self.shuffle = shuffle
         self.generator = generator
+        self._aug = _feed_augment(self.u8.shape[2], self.u8.shape[3], crop_size, augment, num_crops, augment_seed, augment_rank,
+                                  fixed_crop)
+        self.last_items = None
         self.dataset = _ClassItems(self)
 
     def __len__(self):
+        if self._aug is not None:
+            return self._aug.num_batches(self.u8.shape[0], self.batch_size)
         return (self.u8.shape[0] + self.batch_size - 1) // self.batch_size
+
+    def _crop(self, items):
+        from .augment import crop_d4_u8_f32, upload_items
+        return crop_d4_u8_f32(self.u8, self.labels, upload_items(items, self.u8.device), self._aug.size)
+
+    def epoch_order(self):
+        """The index vector of one epoch of an active feed, on the host: `num_crops` orders drawn as one is drawn today."""
+        n = self.u8.shape[0]
+        return self._aug.epoch_order(lambda: _epoch_order(n, self.shuffle, self.generator, "cpu"))
 
     def __iter__(self):
         n = self.u8.shape[0]
+        if self._aug is not None:
+            order = self.epoch_order().numpy()
+            for i in range(0, order.shape[0], self.batch_size):
+                self.last_items = self._aug.items(order[i:i + self.batch_size])
+                yield self._crop(self.last_items)
+            return
         order = _epoch_order(n, self.shuffle, self.generator, self.u8.device)
         for i in range(0, n, self.batch_size):
             yield gather_u8(self.u8, self.labels, order[i:i + self.batch_size])

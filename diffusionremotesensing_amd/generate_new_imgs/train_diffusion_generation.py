@@ -121,15 +121,17 @@ class SyntheticClassDataset(torch.utils.data.Dataset):
 
 def class_folder_feed(args, device, rank=0, world_size=1):
     """The device feed of the class-folder tree `--dataset_path` (reference :573-584: ImageFolder + Resize((S, S)) + ToTensor; the
-    path is used as given, the reference's `../` prefix belongs to its working directory)."""
+    path is used as given, the reference's `../` prefix belongs to its working directory).  With --scene_size P the images are
+    decoded at P x P and the items are --image_size windows (augment.py)."""
+    from ..augment import feed_kwargs, scene_size
     from ..feeds import DeviceClassFeed, load_class_folder_u8
     if not os.path.isdir(args.dataset_path):
         raise FileNotFoundError(f"--dataset_path {args.dataset_path!r}: expected a folder with one sub-folder of images per "
                                 "class (or synthetic[:N[:classes]])")
-    u8, labels, classes = load_class_folder_u8(args.dataset_path, args.image_size, rank, world_size)
+    u8, labels, classes = load_class_folder_u8(args.dataset_path, scene_size(args), rank, world_size)
     if u8.shape[1] != args.inp_out_channels:
         raise ValueError(f"the images of {args.dataset_path} have {u8.shape[1]} bands, --inp_out_channels is {args.inp_out_channels}")
-    return DeviceClassFeed(u8.to(device), labels.to(device), classes, args.batch_size, shuffle=True)
+    return DeviceClassFeed(u8.to(device), labels.to(device), classes, args.batch_size, shuffle=True, **feed_kwargs(args, rank))
 
 
 def launch(args):
@@ -174,8 +176,14 @@ def build_arg_parser():
     return p
 
 
+def train_main_parser():
+    """`build_arg_parser` and the crop / augmentation flags (augment.add_augment_args): what `main` parses."""
+    from ..augment import add_augment_args
+    return add_augment_args(build_arg_parser())
+
+
 def main(argv=None):
-    args = build_arg_parser().parse_args(argv)
+    args = train_main_parser().parse_args(argv)
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     launch(args)
 

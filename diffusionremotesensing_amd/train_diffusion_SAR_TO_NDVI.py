@@ -111,22 +111,30 @@ def synthetic_datasets(args):
             SyntheticSarNdviDataset(max(length // 4, 1), args.SAR_channels, args.NDVI_channels, args.image_size, seed=2))
 
 
-def folder_feed(args, device, split, rank=0, world_size=1, limit=None):
+def folder_feed(args, device, split, rank=0, world_size=1, limit=None, fixed=None):
     """The device feed of `<dataset_path>/<split>/{sar,opt}` (reference :567-571: split 'train' or 'test'), checked against the
-    flags: the reference resizes nothing here, so the files must have --image_size and the models' band counts."""
+    flags: the reference resizes nothing here, so the files must have --image_size and the models' band counts.  With
+    --scene_size P the files must be P x P and the items are --image_size windows (augment.py); `fixed` (default: every split but
+    'train', and the `limit` feed of the final sampling): the centre windows, no augmentation."""
+    from .augment import feed_kwargs, scene_size
     from .feeds import DeviceSarNdviFeed, load_sar_ndvi_folder
+    size = scene_size(args)
+    flag = "--scene_size" if getattr(args, "scene_size", None) is not None else "--image_size"
+    if fixed is None:
+        fixed = split != "train" or limit is not None
     root = os.path.join(args.dataset_path, split)
     if not os.path.isdir(os.path.join(root, "sar")) or not os.path.isdir(os.path.join(root, "opt")):
         raise FileNotFoundError(f"--dataset_path {args.dataset_path!r}: expected the folders train/sar, train/opt, test/sar and "
                                 f"test/opt (or synthetic[:N]); {root} lacks sar/ or opt/")
     sar, ndvi = load_sar_ndvi_folder(root, getattr(args, "data_format", "torch"), rank, world_size, limit)
-    for what, t, flag, want in (("sar", sar, "--SAR_channels", args.SAR_channels), ("opt", ndvi, "--NDVI_channels", args.NDVI_channels)):
+    for what, t, bands_flag, want in (("sar", sar, "--SAR_channels", args.SAR_channels),
+                                      ("opt", ndvi, "--NDVI_channels", args.NDVI_channels)):
         if t.shape[1] != want:
-            raise ValueError(f"the images of {root}/{what} have {t.shape[1]} bands, {flag} is {want}")
-        if tuple(t.shape[2:]) != (args.image_size, args.image_size):
-            raise ValueError(f"the images of {root}/{what} are {t.shape[2]} x {t.shape[3]}, --image_size is {args.image_size} "
+            raise ValueError(f"the images of {root}/{what} have {t.shape[1]} bands, {bands_flag} is {want}")
+        if tuple(t.shape[2:]) != (size, size):
+            raise ValueError(f"the images of {root}/{what} are {t.shape[2]} x {t.shape[3]}, {flag} is {size} "
                              "(this dataset is not resized)")
-    return DeviceSarNdviFeed(sar.to(device), ndvi.to(device), args.batch_size, shuffle=True)
+    return DeviceSarNdviFeed(sar.to(device), ndvi.to(device), args.batch_size, shuffle=True, **feed_kwargs(args, rank, fixed))
 
 
 def launch(args):
@@ -178,8 +186,14 @@ def train_arg_parser():
     return p
 
 
+def train_main_parser():
+    """`train_arg_parser` and the crop / augmentation flags (augment.add_augment_args): what `main` parses."""
+    from .augment import add_augment_args
+    return add_augment_args(train_arg_parser())
+
+
 def main(argv=None):
-    args = train_arg_parser().parse_args(argv)
+    args = train_main_parser().parse_args(argv)
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     launch(args)
 

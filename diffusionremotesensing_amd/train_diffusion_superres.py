@@ -569,6 +569,10 @@ def make_superres_feeds(args, device):
         # Pillow on the host) from a uint8 HR cache on the device, bit-exact (degradation.py); rank r owns every
         # world-th image like DistributedSampler
         from .degradation import DeviceSuperresFeed, load_image_folder_u8
+        # --scene_size P: the cache holds P x P scenes and every item is an --image_size window of one, cut on the device
+        # (augment.py); train feeds draw window and symmetry, validation feeds and the final sampling take the centre window
+        from .augment import feed_kwargs, scene_size
+        cache_size = scene_size(args)
         deg = args.Degradation_type.lower()
         gauss_noise = deg == "downblurnoise"  # (reference :612-616: Gauss_noise=True)
         if deg == "bsrgan":
@@ -579,43 +583,49 @@ def make_superres_feeds(args, device):
 
             def make_feed(u8, fixed=False):
                 return DeviceBSRFeed(u8.to(device), args.magnification_factor, args.batch_size, shuffle=not fixed, kind=kind,
-                                     seed=seed + (1 if fixed else 2 + r), fixed=fixed)
+                                     seed=seed + (1 if fixed else 2 + r), fixed=fixed, **feed_kwargs(args, r, fixed))
 
             def first_items(u8):  # the LR images of the final sampling: the first five training images under the fixed seed
-                feed = DeviceBSRFeed(u8.to(device), args.magnification_factor, 1, shuffle=False, kind=kind, seed=seed, fixed=True)
+                feed = DeviceBSRFeed(u8.to(device), args.magnification_factor, 1, shuffle=False, kind=kind, seed=seed, fixed=True,
+                                     **feed_kwargs(args, fixed=True))
                 return [feed.item(i)[0] for i in range(u8.shape[0])]
         else:
             radius = args.Blur_radius if args.Blur_radius == "random" else float(args.Blur_radius)
 
             def make_feed(u8, fixed=False):
                 return DeviceSuperresFeed(u8.to(device), args.magnification_factor, radius, args.batch_size, shuffle=True,
-                                          Gauss_noise=gauss_noise)
+                                          Gauss_noise=gauss_noise, **feed_kwargs(args, r, fixed))
+
+            def first_items(u8, blur_radius):  # the LR images of the final sampling: the first training images' centre windows
+                from .degradation import add_reference_noise, downblur
+                if cache_size != args.image_size:
+                    from .augment import centre_items, crop_d4_u8, upload_items
+                    items = centre_items(range(u8.shape[0]), cache_size, cache_size, args.image_size)
+                    u8 = crop_d4_u8(u8.to(device), upload_items(items, device), args.image_size)
+                final_x = downblur(u8.to(device), args.magnification_factor, blur_radius)[0]
+                if gauss_noise:
+                    add_reference_noise(final_x, noise_level1=2, noise_level2=10)
+                return [final_x[i] for i in range(final_x.shape[0])]
     if not spec.startswith("synthetic"):
         # an image folder, laid out as the reference expects it (:597-598): <dataset_path>/train_original, /val_original.
         # Decoded once with Pillow into the uint8 cache (this rank's shard only); resize / blur / noise per batch on the device
         if not os.path.isdir(os.path.join(spec, "train_original")) or not os.path.isdir(os.path.join(spec, "val_original")):
             raise FileNotFoundError(f"--dataset_path {spec!r}: expected the folders train_original/ and val_original/ "
                                     "(or synthetic[:N] / synthetic_u8[:N])")
-        train_loader = make_feed(load_image_folder_u8(os.path.join(spec, "train_original"), args.image_size, r, wsz))
-        val_loader = make_feed(load_image_folder_u8(os.path.join(spec, "val_original"), args.image_size, r, wsz), fixed=True)
+        train_loader = make_feed(load_image_folder_u8(os.path.join(spec, "train_original"), cache_size, r, wsz))
+        val_loader = make_feed(load_image_folder_u8(os.path.join(spec, "val_original"), cache_size, r, wsz), fixed=True)
         for what, feed in (("train_original", train_loader), ("val_original", val_loader)):
             if feed.hr.shape[1] != ch:
                 raise ValueError(f"the images of {what} have {feed.hr.shape[1]} channels, --inp_out_channels is {ch}")
         # the final sampling conditions on train_dataset[0..4] of the WHOLE sorted folder (reference :678-680), whatever this
         # rank's shard holds; with Gauss_noise the dataset item carries its noise (utils.py:126-138)
-        first = load_image_folder_u8(os.path.join(spec, "train_original"), args.image_size, limit=5).to(device)
-        if deg == "bsrgan":
-            final_lr = first_items(first)
-        else:
-            from .degradation import add_reference_noise, downblur
-            final_x = downblur(first, args.magnification_factor, train_loader.blur_radius)[0]
-            if gauss_noise:
-                add_reference_noise(final_x, noise_level1=2, noise_level2=10)
-            final_lr = [final_x[i] for i in range(final_x.shape[0])]
+        first = load_image_folder_u8(os.path.join(spec, "train_original"), cache_size, limit=5).to(device)
+        final_lr = first_items(first) if deg == "bsrgan" else first_items(first, train_loader.blur_radius)
     else:
         length = int(spec.split(":")[1]) if ":" in spec else 4 * args.batch_size
-        train_dataset = SyntheticSuperresDataset(length, ch, args.image_size, args.magnification_factor, seed=1)
-        val_dataset = SyntheticSuperresDataset(max(length // 4, 1), ch, args.image_size, args.magnification_factor, seed=2)
+        size = cache_size if device_feed else args.image_size  # (the float DataLoader path has no windows)
+        train_dataset = SyntheticSuperresDataset(length, ch, size, args.magnification_factor, seed=1)
+        val_dataset = SyntheticSuperresDataset(max(length // 4, 1), ch, size, args.magnification_factor, seed=2)
         final_lr = [train_dataset[i][0] for i in range(min(5, len(train_dataset)))]
         if device_feed:
             def to_u8(hr):
@@ -631,6 +641,8 @@ def make_superres_feeds(args, device):
             train_loader, val_loader = feed(train_dataset), feed(val_dataset, fixed=True)
             if deg == "bsrgan":
                 final_lr = first_items(to_u8(train_dataset.hr[:5]))
+            elif cache_size != args.image_size:
+                final_lr = first_items(to_u8(train_dataset.hr[:5]), train_loader.blur_radius)
         else:
             train_loader, val_loader = make_loaders(args, train_dataset, val_dataset)
     return train_loader, val_loader, final_lr
@@ -704,8 +716,7 @@ def build_arg_parser():
     p.add_argument("--magnification_factor", type=int)
     p.add_argument("--Degradation_type", type=str, default="DownBlur")
     p.add_argument("--num_crops", type=int, default=1,
-                   help="parsed for the reference's command lines and unused: the BSRGAN feed degrades every batch afresh on the "
-                        "device instead of keeping num_crops frozen copies per image")
+                   help="the reference's patches per scene; this trainer's command line (parse_train_args) says what it does here")
     p.add_argument("--Blur_radius", type=str, default="random")
     return p
 
@@ -744,9 +755,11 @@ def add_sampling_args(p):
 
 
 def parse_train_args(argv=None):
-    """The trainer's command line: `build_arg_parser`, the BSRGAN feed's flags and `--eval_metrics`, which one process evaluates
-    (no distributed evaluation: rejected together with --multiple_gpus)."""
-    p = add_bsr_args(build_arg_parser())
+    """The trainer's command line: `build_arg_parser`, the BSRGAN feed's flags, the crop / augmentation flags (`add_augment_args`:
+    --num_crops gets its meaning there) and `--eval_metrics`, which one process evaluates (no distributed evaluation: rejected
+    together with --multiple_gpus)."""
+    from .augment import add_augment_args
+    p = add_augment_args(add_bsr_args(build_arg_parser()))
     p.add_argument("--eval_metrics", type=int, default=0,
                    help="score the network on the first N validation images (PSNR / SSIM / SAM / ERGAS against the bicubic "
                         "baseline) at every epoch with epoch %% check_preds_epoch == 0; 0 = off")

@@ -379,6 +379,28 @@ DRS_API int drs_gather_pairs_f32(const float* sar_cache, const float* ndvi_cache
 DRS_API int drs_gather_u8_f32(const uint8_t* cache_u8, const int64_t* labels, const int64_t* idx, int n, int64_t L, int row,
                               float* img_out, int64_t* labels_out, drs_stream_t stream);
 
+/* Random crops and dihedral augmentation of the device feeds (csrc/augment.hip, diffusionremotesensing_amd/augment.py; DESIGN.md
+ * section 20): one launch writes a batch of n windows.  items: (n, 4) int32 on the device, items[i] = (src, y0, x0, code): the
+ * S x S window of cache image src with top-left corner (y0, x0) under dihedral code 0..7 -
+ *   if code & 4: w = w.swapaxes(-1, -2);  if code & 1: w = w[..., ::-1];  if code & 2: w = w[..., ::-1, :]   (in this order)
+ * i.e. out[i, c, y, x] = cache[src, c, y0 + y', x0 + x'] with (u, v) = (code & 2 ? S-1-y : y, code & 1 ? S-1-x : x) and
+ * (y', x') = code & 4 ? (v, u) : (u, v).  All bands of an item, and both tensors of a pair, share window and code.  An item with
+ * src outside [0, L), a window that does not lie inside H x W or a code outside 0..7 reads nothing: zeros, label -1.
+ *   drs_crop_d4_u8:        cache (L, C, H, W) uint8 -> out (n, C, S, S) uint8, the bytes themselves
+ *   drs_crop_d4_u8_f32:    the same cache -> img_out (n, C, S, S) fp32 = float(b) / 255 (a true division, as drs_gather_u8_f32),
+ *                          labels_out[i] = labels[src]  (labels: L int64, labels_out: n int64)
+ *   drs_crop_d4_pairs_f32: sar_cache (L, Cs, H, W), ndvi_cache (L, Cn, H, W) fp32 -> sar_out (n, Cs, S, S), ndvi_out (n, Cn, S, S)
+ *                          = (v + 1) * 0.5, as drs_gather_pairs_f32
+ * H != W is allowed, the window is square.  No workspace, no atomics.  DRS_ERR_ARG: null pointer; DRS_ERR_SHAPE: n, L, a band
+ * count, H, W or S < 1, S > H or S > W.  Not in the reference's device path: its BSRGAN dataset cut `num_crops` random patches on
+ * the host (utils.py:205-210, degradation_from_BSRGAN.py:584), its other datasets do not augment. */
+DRS_API int drs_crop_d4_u8(const uint8_t* cache_u8, const int32_t* items, int n, int64_t L, int C, int H, int W, int S,
+                           uint8_t* out, drs_stream_t stream);
+DRS_API int drs_crop_d4_u8_f32(const uint8_t* cache_u8, const int64_t* labels, const int32_t* items, int n, int64_t L, int C,
+                               int H, int W, int S, float* img_out, int64_t* labels_out, drs_stream_t stream);
+DRS_API int drs_crop_d4_pairs_f32(const float* sar_cache, const float* ndvi_cache, const int32_t* items, int n, int64_t L,
+                                  int Cs, int Cn, int H, int W, int S, float* sar_out, float* ndvi_out, drs_stream_t stream);
+
 /* The ops of the blind (BSRGAN-plus) degradation feed (csrc/bsr_degrade.hip; recipe and feed in diffusionremotesensing_amd/bsr.py,
  * definitions in DESIGN.md section 19).  Every op is one launch (sharpen and jpeg: two) over a dense (N,C,H,W) fp32 batch, 1 <= C
  * <= 16; per-image parameters are device arrays, so a batch's whole recipe is one upload.  Nothing draws random numbers.
