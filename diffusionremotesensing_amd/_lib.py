@@ -39,6 +39,8 @@ SIGNATURES = {
     "drs_inpaint_step": (_I, [_P, _P, _P, _F, _P, _P, _P] + [_I] * 8 + [_F, _P, _P, _P, _I, _P]),
     "drs_renoise": (_I, [_P, _P, _I, _I, _P, _I, _L, _P]),
     "drs_adam_multi": (_I, [_P, _I, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
+    "drs_grad_sumsq_partials": (_I, [_P, _I, _L, _P, _P]),
+    "drs_adamw_clip_multi": (_I, [_P, _I, _L] + [C.c_double] * 6 + [_I, _P, _I, _P, _P]),
     "drs_ema_multi": (_I, [_P, _I, C.c_int64, C.c_double, _I, _P]),
     "drs_downblur_scratch_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "drs_downblur_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _P, _Z, _P]),

@@ -14,13 +14,14 @@ Deliberately different (documented in DESIGN.md):
 """
 import copy
 import os
+import types
 
 import torch
 import torch.nn as nn
 
 from . import dist as drs_dist
 from . import hip_ops
-from .optim import FusedAdam
+from .optim import FusedAdam, FusedAdamW, WarmupCosine
 from .sampling import (CHAIN_CHECK_EVERY, _is_int, _repeat_members, asks_for_known_pixels,  # noqa: F401 - re-exported
                        check_ensemble_args, check_inpaint_args, check_sampling_args, check_solver_known, ddim_chain_noise,
                        ddim_timesteps, ensemble_chunks, inpaint_schedule, known_tensors, run_reverse_chain, sample_chain,
@@ -357,6 +358,44 @@ class Diffusion:
         self.epochs_run = snapshot["EPOCHS_RUN"]
         print(f"Resuming training from snapshot at Epoch {self.epochs_run}")
 
+    # -- the rest of a run's state (not in the reference, which marks the gap: LR_SCHEDULER is commented out at :275) --------
+    def train_state_path(self):
+        return os.path.join(os.path.dirname(self.snapshot_path), "train_state.pt")
+
+    def _save_train_state(self, epoch, model, state):
+        """`train_state.pt` beside the snapshot (whose two keys stay what they are): everything else `train` needs to go on at
+        epoch + 1 as if it had not stopped.  With EMA the snapshot holds the averaged copy, so the raw weights are here.  Not
+        saved: the private generators of the crop / BSRGAN feeds.  One file, written by rank 0 and read by every rank."""
+        net = model.module if self.multiple_gpus and hasattr(model, "module") else model
+        torch.save({"OPTIMIZER_STATE": state.optimizer.state_dict(),
+                    "RAW_MODEL_STATE": net.state_dict() if state.ema is not None else None,
+                    "EMA_STEP": state.ema.step if state.ema is not None else None,
+                    "LR_SCHEDULE": state.scheduler.state_dict() if state.scheduler is not None else None,
+                    "BEST_LOSS": state.best_loss, "EPOCHS_WITHOUT_IMPROVING": state.epochs_without_improving,
+                    "NEXT_EPOCH": epoch + 1, "CPU_RNG_STATE": torch.get_rng_state(),
+                    "DEVICE_RNG_STATE": torch.cuda.get_rng_state(self.device)}, self.train_state_path())
+
+    def _load_train_state(self, model, state):
+        """Restores `_save_train_state`'s file into a run that `__init__` has already given the snapshot's weights: those stay
+        in the EMA copy, the raw weights go into `model`, and `epochs_run` becomes NEXT_EPOCH.  A file that does not fit this
+        model or this run's options raises ValueError."""
+        ts = torch.load(self.train_state_path(), map_location="cpu")
+        if (ts["RAW_MODEL_STATE"] is None) != (state.ema is None) or (ts["LR_SCHEDULE"] is None) != (state.scheduler is None):
+            raise ValueError(f"{self.train_state_path()} was written with other --ema_smoothing / --lr_schedule options")
+        net = model.module if self.multiple_gpus and hasattr(model, "module") else model
+        # (another parameter count or other shapes: ValueError from FusedAdamW.load_state_dict, the first thing loaded)
+        state.optimizer.load_state_dict(ts["OPTIMIZER_STATE"])
+        if state.ema is not None:
+            net.load_state_dict(ts["RAW_MODEL_STATE"])
+            state.ema.step = ts["EMA_STEP"]
+        if state.scheduler is not None:
+            state.scheduler.load_state_dict(ts["LR_SCHEDULE"])
+        state.best_loss, state.epochs_without_improving = ts["BEST_LOSS"], ts["EPOCHS_WITHOUT_IMPROVING"]
+        self.epochs_run = ts["NEXT_EPOCH"]
+        torch.set_rng_state(ts["CPU_RNG_STATE"])
+        torch.cuda.set_rng_state(ts["DEVICE_RNG_STATE"], self.device)
+        print(f"Resuming the training state of {self.train_state_path()} at Epoch {self.epochs_run}")
+
     def early_stopping(self, patience, epochs_without_improving):
         if epochs_without_improving >= patience:
             print("Early stopping! Training stopped")
@@ -388,8 +427,9 @@ class Diffusion:
         """(conditioning, clean image) of one loader item: (lr_img, hr_img) here (:379)."""
         return batch[0].to(self.device), batch[1].to(self.device)
 
-    def train_step(self, model, optimizer, loss_function, lr_img, hr_img, ema=None, ema_model=None):
-        """Loop body of reference :379-396 (called `train_step` in BASELINE.json's north_star)."""
+    def train_step(self, model, optimizer, loss_function, lr_img, hr_img, ema=None, ema_model=None, lr_scheduler=None):
+        """Loop body of reference :379-396 (called `train_step` in BASELINE.json's north_star).  `lr_scheduler`
+        (optim.WarmupCosine; not in the reference) sets this step's learning rate right before the update."""
         lr_img, hr_img = self._split_batch((lr_img, hr_img))
         # same CPU-generator draw as the reference (:384); pinned + non_blocking so that the copy does not make the host
         # wait for the previous step's kernels (a pageable .to(device) is a full synchronisation point)
@@ -400,6 +440,8 @@ class Diffusion:
         predicted_noise = self._predict(model, x_t, t, self._train_cond(lr_img))
         train_loss = loss_function(predicted_noise, noise)
         train_loss.backward()
+        if lr_scheduler is not None:
+            lr_scheduler.step(optimizer)
         if self.multiple_gpus:
             # ONE in-place all-reduce of the backward's flat gradient buffer on RCCL's stream, overlapped with the
             # optimizer's host-side table build; the update kernel is enqueued behind it
@@ -421,11 +463,25 @@ class Diffusion:
         return cond
 
     def train(self, lr, epochs, check_preds_epoch, train_loader, val_loader, patience, loss, verbose, eval_metrics=0,
-              sampling_steps=None, eta=0.0):
+              sampling_steps=None, eta=0.0, weight_decay=0.0, max_grad_norm=None, lr_schedule="constant", warmup_steps=0,
+              lr_min=0.0, save_train_state=False):
         """`eval_metrics=N` (not in the reference; 0 = off): at every epoch with epoch % check_preds_epoch == 0 the network that
-        would be saved is scored on the first N validation images (`evaluate` with `sampling_steps` / `eta`), one line."""
+        would be saved is scored on the first N validation images (`evaluate` with `sampling_steps` / `eta`), one line.
+        Not in the reference either, all off by default (then this is its loop: Adam at a fixed rate): `weight_decay` and
+        `max_grad_norm` (decoupled decay, clipping of the global gradient norm, and a guard that skips a step whose gradients
+        are not finite: `optim.FusedAdamW`); `lr_schedule` "constant" | "cosine" with `warmup_steps` and `lr_min`
+        (`optim.WarmupCosine` over len(train_loader) * epochs steps); `save_train_state`: every snapshot gets a
+        `train_state.pt` beside it and a run that finds both continues exactly where that one stood (`_save_train_state`)."""
         model = self.model
-        optimizer = FusedAdam(model.parameters(), lr=lr)  # torch.optim.Adam's math, one launch (optim.py)
+        if lr_schedule not in ("constant", "cosine"):
+            raise ValueError("lr_schedule must be constant or cosine")
+        if weight_decay or max_grad_norm is not None or save_train_state:
+            optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        else:
+            optimizer = FusedAdam(model.parameters(), lr=lr)  # torch.optim.Adam's math, one launch (optim.py)
+        scheduler = None
+        if lr_schedule == "cosine" or warmup_steps:
+            scheduler = WarmupCosine(lr, warmup_steps, max(len(train_loader), 1) * epochs, lr_min, lr_schedule)
         ema = ema_model = None
         if self.ema_smoothing:
             ema = EMA(beta=0.995)
@@ -434,25 +490,50 @@ class Diffusion:
         epochs_without_improving = 0
         best_loss = float("inf")
         saved = ema_model if self.ema_smoothing else model
+        # what a run holds besides the weights; `save` keeps best_loss / epochs_without_improving current
+        state = self.train_state = types.SimpleNamespace(optimizer=optimizer, scheduler=scheduler, ema=ema, ema_model=ema_model,
+                                                         best_loss=best_loss, epochs_without_improving=0)
+        if save_train_state and os.path.exists(self.snapshot_path) and os.path.exists(self.train_state_path()):
+            self._load_train_state(model, state)
+            best_loss, epochs_without_improving = state.best_loss, state.epochs_without_improving
+        clipping = max_grad_norm is not None
+        skipped_before = optimizer.skipped_steps() if isinstance(optimizer, FusedAdamW) else 0
+
+        def save(epoch):
+            self._save_snapshot(epoch, saved)
+            if save_train_state:
+                state.best_loss, state.epochs_without_improving = best_loss, epochs_without_improving
+                self._save_train_state(epoch, model, state)
 
         for epoch in range(self.epochs_run, epochs):
             if self.multiple_gpus and hasattr(train_loader, "sampler") and hasattr(train_loader.sampler, "set_epoch"):
                 train_loader.sampler.set_epoch(epoch)
             running_train_loss = torch.zeros((), device=self.device)  # accumulated on device: no per-step sync
+            running_norm = torch.zeros((), device=self.device)  # (pre-clip gradient norms of the steps that were not skipped)
             model.train()
             for lr_img, hr_img in train_loader:
                 running_train_loss += self.train_step(model, optimizer, loss_function, lr_img, hr_img, ema,
-                                                      ema_model).detach()
+                                                      ema_model, scheduler).detach()
+                if clipping:
+                    running_norm += torch.nan_to_num(optimizer.last_grad_norm(), nan=0.0, posinf=0.0, neginf=0.0)
             running_train_loss = running_train_loss.item() / max(len(train_loader), 1)
             # (the .item() above is the epoch's synchronisation point: a wave of the wave-specialised kernels that gave up on a
             #  counter during this epoch's forwards or backwards - csrc/sp_sync.h - is reported here, not trained on)
             net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
             if hasattr(net, "hip_engine"):
                 net.hip_engine().check_faults()
-            print(f"Epoch {epoch}: Running Train ({loss}) {running_train_loss}")
+            more = ""
+            if isinstance(optimizer, FusedAdamW):
+                skipped = optimizer.skipped_steps() - skipped_before
+                skipped_before += skipped
+                if clipping:
+                    more += f" | mean grad norm {running_norm.item() / max(len(train_loader) - skipped, 1)}"
+                if skipped:
+                    more += f" | skipped steps {skipped}"
+            print(f"Epoch {epoch}: Running Train ({loss}) {running_train_loss}" + more)
 
             if self._is_rank0() and epoch % check_preds_epoch == 0 and val_loader is None:
-                self._save_snapshot(epoch, saved)
+                save(epoch)
 
             if val_loader is not None:
                 running_val_loss = torch.zeros((), device=self.device)
@@ -477,12 +558,13 @@ class Diffusion:
                     best_loss = running_val_loss
                     epochs_without_improving = 0
                     if self._is_rank0():
-                        self._save_snapshot(epoch, saved)
+                        save(epoch)
                 else:
                     epochs_without_improving += 1
                 if self.early_stopping(patience, epochs_without_improving):
                     break
             print("Epochs without improving: ", epochs_without_improving)
+        state.best_loss, state.epochs_without_improving = best_loss, epochs_without_improving
 
 
 class SyntheticSuperresDataset(torch.utils.data.Dataset):
@@ -543,7 +625,7 @@ def train_model(args, diffusion_class, model, device, train_loader, val_loader, 
                                 ema_smoothing=args.ema_smoothing, **diffusion_kwargs)
     diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
                     train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
-                    verbose=True, **(train_kwargs or {}))
+                    verbose=True, **optim_train_kwargs(args), **(train_kwargs or {}))
     if args.multiple_gpus:
         drs_dist.destroy_process_group()
     return diffusion
@@ -747,6 +829,39 @@ def cli_sampling_steps(args):
     return steps if solver == "ddim" and spacing is None else sampling_plan(steps, solver, spacing)
 
 
+OPTIM_DEFAULTS = {"weight_decay": 0.0, "max_grad_norm": None, "lr_schedule": "constant", "warmup_steps": 0, "lr_min": 0.0,
+                  "save_train_state": False}
+
+
+def add_optim_args(p):
+    """The optimizer / schedule / resume flags of the three trainers' command lines (not in the reference; `Diffusion.train`)."""
+    p.add_argument("--weight_decay", type=float, default=0.0, help="decoupled (AdamW) weight decay; 0 = the reference's Adam")
+    p.add_argument("--max_grad_norm", type=float, default=None,
+                   help="clip the global gradient norm to this value; steps with non-finite gradients are skipped")
+    p.add_argument("--lr_schedule", type=str, choices=("constant", "cosine"), default="constant",
+                   help="after --warmup_steps: stay at --lr, or half a cosine down to --lr_min at the last step")
+    p.add_argument("--warmup_steps", type=int, default=0, help="optimizer steps of linear learning-rate warm-up")
+    p.add_argument("--lr_min", type=float, default=0.0, help="final learning rate of --lr_schedule cosine")
+    p.add_argument("--save_train_state", type=str2bool, nargs="?", const=True, default=False,
+                   help="write train_state.pt (optimizer, raw weights under EMA, schedule, early-stopping and RNG state) beside "
+                        "every snapshot, and continue from both when they exist.  Not built: gradient accumulation, loss scaling, "
+                        "the crop / BSRGAN feeds' own generators, per-rank files (rank 0 writes, every rank reads)")
+    return p
+
+
+def check_optim_args(p, args):
+    if args.weight_decay < 0 or args.lr_min < 0 or args.warmup_steps < 0:
+        p.error("--weight_decay, --lr_min and --warmup_steps must be >= 0")
+    if args.max_grad_norm is not None and not args.max_grad_norm > 0:
+        p.error("--max_grad_norm must be > 0")
+    return args
+
+
+def optim_train_kwargs(args):
+    """`add_optim_args`' flags as keyword arguments of `Diffusion.train` (a namespace without them: the defaults)."""
+    return {k: getattr(args, k, v) for k, v in OPTIM_DEFAULTS.items()}
+
+
 def add_sampling_args(p):
     """The DDIM flags of the final sampling (not in the reference): none = the reference's ancestral chain."""
     p.add_argument("--sampling_steps", type=int, default=None,
@@ -759,7 +874,7 @@ def parse_train_args(argv=None):
     --num_crops gets its meaning there) and `--eval_metrics`, which one process evaluates (no distributed evaluation: rejected
     together with --multiple_gpus)."""
     from .augment import add_augment_args
-    p = add_augment_args(add_bsr_args(build_arg_parser()))
+    p = add_optim_args(add_augment_args(add_bsr_args(build_arg_parser())))
     p.add_argument("--eval_metrics", type=int, default=0,
                    help="score the network on the first N validation images (PSNR / SSIM / SAM / ERGAS against the bicubic "
                         "baseline) at every epoch with epoch %% check_preds_epoch == 0; 0 = off")
@@ -768,6 +883,7 @@ def parse_train_args(argv=None):
         p.error("--eval_metrics must be >= 0")
     if args.eval_metrics and args.multiple_gpus:
         p.error("--eval_metrics runs in one process: it cannot be combined with --multiple_gpus")
+    check_optim_args(p, args)
     return args
 
 

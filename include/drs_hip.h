@@ -163,6 +163,52 @@ typedef struct drs_adam_tensor {
 DRS_API int drs_adam_multi(const drs_adam_tensor* table, int ntensors, int64_t max_numel, double lr, double beta1, double beta2,
                    double eps, drs_stream_t stream);
 
+/* AdamW with global-norm gradient clipping and a non-finite guard, as TWO launches on one stream and no host
+ * synchronisation (torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW, which the reference leaves commented out next to
+ * Adam, train_diffusion_superres.py:337-338).  Both use the grid of drs_adam_multi: (chunks of 4096 elements, tensors).
+ *
+ * `table` (device): ntensors x drs_adamw_tensor = drs_adam_tensor's fields + `part0`, the index of the tensor's first chunk
+ * in `partials` (chunk c of the tensor owns partials[part0 + c]; the caller lays the tensors out back to back, so
+ * npartials = sum over tensors of ceil(n / 4096)).
+ *
+ * drs_grad_sumsq_partials: every chunk writes ONE double, the sum of (double)g * (double)g over the chunk, added in a fixed
+ * order (per thread in element order, a shuffle tree over the wave, the four waves in order): two calls give the same bits.
+ * Chunks of tensors with g == NULL write 0.
+ *
+ * drs_adamw_clip_multi: every block first adds partials[0 .. npartials) in index order (so all blocks hold the same S; no
+ * atomics, no fence, no ticket), then with norm = sqrt(S) in double:
+ *   skip:  if skip_nonfinite != 0 and S is not finite, p, m and v of EVERY tensor are left untouched;
+ *   coef = max_norm > 0 ? (float)min(1.0, max_norm / (norm + 1e-6)) : 1.0f        (clip_grad_norm_; a NaN stays NaN)
+ *   g'   = g * coef                                                               (rounded once; exact at coef == 1)
+ *   p    = p * (float)(1.0 - lr * weight_decay)                                   (AdamW's param.mul_, before the update)
+ *   then drs_adam_multi's update of m, v and p with g' in place of g, operation for operation.
+ * With max_norm <= 0, weight_decay == 0 and finite gradients the result is bit-identical to drs_adam_multi's.
+ * npartials == 0 (partials may be NULL) means S = 0: no clipping and no guard, one launch (max_norm > 0 is DRS_ERR_ARG then).
+ * `stats` (device, may be NULL) is written by block (0,0): the pre-clip norm, coef, whether this step was skipped, and a
+ * count of skipped steps that the kernel increments (zero it once).  The caller's per-tensor `step` counts attempted steps: after
+ * a skip the bias correction is one step ahead (documented deviation; it costs no synchronisation). */
+typedef struct drs_adamw_tensor {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  int64_t n;
+  int64_t step;
+  int64_t part0;
+} drs_adamw_tensor;
+typedef struct drs_adamw_stats {
+  float norm;
+  float coef;
+  int32_t skipped;
+  int32_t reserved;
+  int64_t skipped_total;
+} drs_adamw_stats;
+DRS_API int drs_grad_sumsq_partials(const drs_adamw_tensor* table, int ntensors, int64_t max_numel, double* partials,
+                                    drs_stream_t stream);
+DRS_API int drs_adamw_clip_multi(const drs_adamw_tensor* table, int ntensors, int64_t max_numel, double lr, double beta1,
+                                 double beta2, double eps, double weight_decay, double max_norm, int skip_nonfinite,
+                                 const double* partials, int npartials, drs_adamw_stats* stats, drs_stream_t stream);
+
 /* Multi-tensor exponential moving average of the parameters, ONE launch for all tensors:
  *   mode 0:  ema[i] = ema[i] * beta + (1 - beta) * cur[i]   (fp32; `1 - beta` is formed in double and rounded to fp32, the
  *            two products and the sum are rounded separately - reference EMA.update_average, UNet_model_superres.py:25-30,
