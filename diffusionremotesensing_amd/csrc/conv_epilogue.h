@@ -3,33 +3,10 @@
 #pragma once
 #include "mfma_policy.h"
 
-// 16-byte activation store.  DRS_WT_STORES=1 makes it WRITE-THROUGH (`sc1`): the idea was that a kernel which leaves its
-// output dirty in the XCDs' L2s pays for the write-back at the kernel boundary (MI355X_MICROARCH.md, row "boundary").
-// Measured A/B on one box (tools/build_variant.sh, round 3): 681.5 steps/s written through against 686.3 with plain stores
-// - the dropped L2 lines cost the next kernel more than the boundary saves - so plain stores are the default.  (An asm
-// store is invisible to hipcc's vmcnt bookkeeping and ends with s_nop 1 so that its data registers are read before the
-// next instruction may overwrite them: cdna_hip_programming.md 5.7.)
-#ifndef DRS_WT_STORES
-#define DRS_WT_STORES 0
-#endif
-// Experiment switches (tools/build_variant.sh NAME "-DDRS_X_...=1"; never defined in the shipped build): what an item
-// epilogue costs without its stores / bias-ReLU-add arithmetic / hi | lo split / lane swap.  Compile-time on purpose: a
-// run-time switch read from memory inside the epilogue costs more than what it switches off.
-__device__ __forceinline__ void drs_store16(void* p, const u32x4& v) {
-#ifdef DRS_X_NOSTORE
-  asm volatile("" :: "v"(v), "v"(p));
-  return;
-#endif
-#if DRS_WT_STORES == 2  // experiment: non-temporal
-  asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-#elif DRS_WT_STORES == 3  // experiment: system-coherent write-through
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-#elif DRS_WT_STORES
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-#else
-  *reinterpret_cast<u32x4*>(p) = v;
-#endif
-}
+// 16-byte activation store.  A plain store on purpose: written through (`sc1`, so that the output is not left dirty in the
+// XCDs' L2s for the kernel boundary to write back) measured 681.5 steps/s against 686.3 - the dropped L2 lines cost the
+// next kernel more than the boundary saves.
+__device__ __forceinline__ void drs_store16(void* p, const u32x4& v) { *reinterpret_cast<u32x4*>(p) = v; }
 
 // ---- epilogue of RPW rows x NT channel tiles held in MFMA layout ---------------------------------------------------
 // Lane (lr, kg) holds channels t*16 + kg*4 .. +3 of pixel lr for every n-tile t.  Pairs of n-tiles are exchanged
@@ -339,23 +316,10 @@ __device__ __forceinline__ void tile_epilogue_sp_pre(const TapConv& d, f32x4 (&a
 #pragma unroll
         for (int p = 0; p < 4; ++p) v[p] = drs_f32x2{drs_maxf(v[p][0], 0.f), drs_maxf(v[p][1], 0.f)};
       }
-#ifdef DRS_X_NOAFFINE
-#pragma unroll
-      for (int p = 0; p < 4; ++p) v[p] = drs_f32x2{acc[r][p >> 1][2 * (p & 1)], acc[r][p >> 1][2 * (p & 1) + 1]};
-#endif
       auto put = [&](char* g, int hb, const drs_f32x2 (&w2)[4]) __attribute__((always_inline)) {
         const float w8[8] = {w2[0][0], w2[0][1], w2[1][0], w2[1][1], w2[2][0], w2[2][1], w2[3][0], w2[3][1]};
         u32x4 H, L;
-#ifdef DRS_X_NOSPLIT
-        H = u32x4{__float_as_uint(w8[0]), __float_as_uint(w8[1]), __float_as_uint(w8[2]), __float_as_uint(w8[3])};
-        L = u32x4{__float_as_uint(w8[4]), __float_as_uint(w8[5]), __float_as_uint(w8[6]), __float_as_uint(w8[7])};
-#else
         drs_sp_split8(w8, H, L);
-#endif
-#ifdef DRS_X_NOSWAP
-        if (ok0) drs_store16(g, H);
-        if (ok1) drs_store16(g + hb, L);
-#else
         // first store: lanes lr < 8 their own hi, lanes lr >= 8 the lo of the lane 8 below; second store: lanes lr < 8 the hi of
         // the lane 8 above, lanes lr >= 8 their own lo.  row_ror:8 = the lane lr ^ 8 of the 16-lane row; bank mask 0xc writes
         // lanes 8 - 15 only, 0x3 lanes 0 - 7 only; the rest keeps `old`.
@@ -367,7 +331,6 @@ __device__ __forceinline__ void tile_epilogue_sp_pre(const TapConv& d, f32x4 (&a
         }
         if (ok0) drs_store16(g, a);
         if (ok1) drs_store16(g + hb, b);
-#endif
       };
       if (o1) put(o1 + r * row1, h1, v);
       if constexpr (OUT2) {

@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256 * NWG, NWG == 1 ? 2 : 1) void tapconv_mfma_kern
     return P::load(sW, g.w_image, ((size_t)(tap * 4 + kg) * BNB + (ng * NT + t) * 16 + lr) * 16);
   };
 
-  if (!(g.debug & 4)) load_step(0);
+  load_step(0);
   int n = 0, ty0 = 0, tx0 = 0, n0 = 0;
   for (int k = 0; k < S; ++k) {
     const int c = k % nck;
@@ -289,10 +289,9 @@ __global__ __launch_bounds__(256 * NWG, NWG == 1 ? 2 : 1) void tapconv_mfma_kern
           for (int t = 0; t < NT; ++t) acc[a][r][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     if (k) __syncthreads();  // everyone finished reading the previous step's LDS image
-    if (!(g.debug & 2)) store_chunk(c);
+    store_chunk(c);
     __syncthreads();
-    if (k + 1 < S && !(g.debug & 4)) load_step(k + 1);  // next step's loads fly while this one is multiplied / written
-    if (!(g.debug & 1)) {
+    if (k + 1 < S) load_step(k + 1);  // next step's loads fly while this one is multiplied / written
     if (HAS2 && c >= g.nchunks) {  // second input: one tap, stride 1, window origin
       typename P::Frag wf[NT];
 #pragma unroll
@@ -365,9 +364,8 @@ __global__ __launch_bounds__(256 * NWG, NWG == 1 ? 2 : 1) void tapconv_mfma_kern
             }
         }
     }
-    }  // !(debug & 1)
 
-    if (c == nck - 1 && !(g.debug & 8)) {  // item complete
+    if (c == nck - 1) {  // item complete
       if constexpr (MODE == MODE_CONVT) {
 #pragma unroll
         for (int ph = 0; ph < 4; ++ph) {
@@ -399,9 +397,8 @@ static bool is_std3x3(const TapConv& d) {
   return true;
 }
 
-static int nwg_of(const TapConv& d, int mode) {
-  static const int env = getenv("DRS_NWG") ? atoi(getenv("DRS_NWG")) : 2;
-  return (env == 2 && mode == MODE_CONV3X3 && d.Cout % 64 == 0 && !d.shared_cu) ? 2 : 1;
+static int nwg_of(const TapConv& d, int mode) {  // channel groups per block: 2 (512 threads) where the layer has them
+  return (mode == MODE_CONV3X3 && d.Cout % 64 == 0 && !d.shared_cu) ? 2 : 1;
 }
 
 static bool geom(const TapConv& d, int impl, MfmaGeom* g, int* bn, int* rpw, int* mode, size_t* lds) {
@@ -443,8 +440,6 @@ static bool geom(const TapConv& d, int impl, MfmaGeom* g, int* bn, int* rpw, int
   g->nchunks2 = d.in2 ? drs_cdiv(d.Cin2, KC) : 0;
   g->iw_magic = (65536 + g->IW - 1) / g->IW;
   g->w2_gimage = g->nchunks2 * 4 * d.Cout * 16;
-  static const int dbg = getenv("DRS_DEBUG_FLAGS") ? atoi(getenv("DRS_DEBUG_FLAGS")) : 0;
-  g->debug = dbg;
   *lds = (size_t)images(impl) * ((size_t)g->a_image + g->w_image) + 128;  // + tap tables
   return *lds <= (size_t)kLdsLimit;
 }
@@ -494,8 +489,7 @@ static int launch_t(const TapConv& d, const MfmaGeom& g, size_t lds, hipStream_t
   }
   // persistent grid: 2 blocks per CU (what the LDS footprint admits), a multiple of the 8 XCDs, never more than items
   const long long nitems = (long long)d.N * g.tiles_x * g.tiles_y * (d.Cout / (BN * NWG));
-  static const int per_cu_env = getenv("DRS_BLOCKS_PER_CU") ? atoi(getenv("DRS_BLOCKS_PER_CU")) : 2;
-  const int per_cu = NWG == 2 ? 1 : (d.shared_cu ? (d.shared_cu == 2 ? 2 : 1) : per_cu_env);
+  const int per_cu = NWG == 2 ? 1 : (d.shared_cu ? (d.shared_cu == 2 ? 2 : 1) : 2);
   long long blocks = (long long)num_cu * per_cu;
   if (blocks > nitems) blocks = nitems;
   blocks = (blocks + 7) / 8 * 8;
@@ -536,10 +530,7 @@ int drs_launch_tapconv_mfma(const TapConv& d, int impl, hipStream_t s) {
   if ((mode == MODE_CONV3X3 || mode == MODE_CONV3X3_FUSE) && drs_conv3x3_direct_sp_supported(d, impl))
     return drs_launch_conv3x3_direct_sp(d, s);
   if ((mode == MODE_CONV3X3 || mode == MODE_CONV3X3_FUSE) && drs_tapconv_sp_supported(d, impl)) {
-    if (drs_tapconv_fl_supported(d, impl)) {
-      const int rc = drs_launch_tapconv_fl(d, g, s);
-      if (rc != DRS_FL_DECLINED) return rc;
-    }
+    if (drs_tapconv_fl_supported(d, impl)) return drs_launch_tapconv_fl(d, g, s);
     return drs_launch_tapconv_sp(d, g, s);
   }
   if (mode == MODE_CONV3X3 && drs_tapconv_sp_f32out_supported(d, impl)) return drs_launch_tapconv_sp(d, g, s);

@@ -58,14 +58,6 @@ __device__ unsigned long long drs_fl_tl[64];
 #define FL_STAMP(i) do { } while (0)
 #endif
 
-// The movers' polls: LDS counters guarding LDS slots - the relaxed form (sp_sync.h).  The acquire form also drains the wave's
-// vector-memory counter: a mover would wait at every poll for the global loads it has just issued for LATER use.
-#ifdef DRS_FL_ACQPOLL
-#define FL_MPOLL sp_poll
-#else
-#define FL_MPOLL sp_poll_lds
-#endif
-
 struct FlGeom {
   static constexpr int IW = 18;
   static constexpr int WBUF = 41 * 1024;                     // one window buffer (328 lines of 128 bytes)
@@ -78,13 +70,9 @@ struct FlGeom {
 __device__ __forceinline__ void fl_bump_prio(sp_flag_ptr f, unsigned step_base, int lane) {  // (sp_bump_prio of conv_mfma_sp.hip)
   unsigned old = 0;
   if (lane == 0) old = __hip_atomic_fetch_add(f, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifndef DRS_FL_NO_PRIO
   const unsigned rank = (unsigned)__builtin_amdgcn_readfirstlane((int)old) - step_base;
   if (rank >= 4) __builtin_amdgcn_s_setprio(2);
   else __builtin_amdgcn_s_setprio(0);
-#else
-  (void)old; (void)step_base;
-#endif
 }
 
 // ---- SP -> FL for HALF a pixel (16 channels of one 32-channel block) -------------------------------------------------------
@@ -131,16 +119,10 @@ __device__ __forceinline__ void fl_convert_half(const u32x4& h0, const u32x4& h1
     r[d] = lp - t;
   }
   o.sm = fl_block_exp(m, o.over);
-  // The remainders' scale from their own maximum.  (|r| <= 2^-11 |m| element by element, so 2^-11 of the main scale would hold
-  // them too, ~25 instructions cheaper per half pixel: measured on the trained-like fixture of tests/test_gpu_fl.py it costs
-  // accuracy - forward max-rel 7.8e-5 -> 1.05e-4, the largest remainder is on average well under its bound - and buys
-  // nothing measurable: DRS_FL_RSCALE_BOUND.)
-#ifdef DRS_FL_RSCALE_BOUND
-  o.sr = o.sm > 12u ? o.sm - 11u : 1u;
-#else
+  // The remainders' scale from their own maximum, not from the bound 2^-11 of the main scale: the largest remainder is on
+  // average well under that bound, and the bound measured less accurate (forward max-rel 7.8e-5 -> 1.05e-4) and no faster.
   bool over_r;
   o.sr = fl_block_exp(r, over_r);
-#endif
   const u32x6 cm = fl_codes16(m, o.sm), cr = fl_codes16(r, o.sr);
 #pragma unroll
   for (int j = 0; j < 3; ++j) { o.qm[j] = cm[j]; o.qr[j] = cr[j]; }
@@ -326,15 +308,8 @@ __global__ __launch_bounds__(768, 1) void tapconv_fl_kernel(TapConv d, MfmaGeom 
 #pragma unroll
       for (int i = 0; i < NR; ++i) {
         FlHalf f;
-#ifdef DRS_FL_COPYMOVER  // speed experiment (wrong numbers): what the kernel does when its movers only copy
-        f.m0 = ww[i][0]; f.m1 = ww[i][1];
-        f.qm[0] = ww[i][2][0]; f.qm[1] = ww[i][2][1]; f.qm[2] = ww[i][2][2]; f.qr[0] = ww[i][3][0]; f.qr[1] = ww[i][3][1]; f.qr[2] = ww[i][3][2];
-        f.sm = 120u; f.sr = 110u;
-#else
         fl_convert_half(ww[i][0], ww[i][1], ww[i][2], ww[i][3], f);
-#endif
         if ((keep >> i) & 1u) fl_store_half(buf + (pw + 4 * i) * 4096, f, hh != 0, a_m0, a_m1, a_w4, a_p46, a_w5, a_p57);
-#ifndef DRS_FL_COPYMOVER
         if (f.over && d.fault) {  // (never in a healthy network: reported by drs_unet_check_faults as DRS_ERR_RANGE, with the place)
           atomicOr(d.fault, 2u);
           d.fault[1] = ((unsigned)d.Cin << 16) | (unsigned)d.Cout;
@@ -342,7 +317,6 @@ __global__ __launch_bounds__(768, 1) void tapconv_fl_kernel(TapConv d, MfmaGeom 
           d.fault[3] = ((unsigned)blockIdx.x << 16) | ((unsigned)(pw + 4 * i) << 8) | (unsigned)lane;
           d.fault[4] = f.sm;
         }
-#endif
         __builtin_amdgcn_sched_barrier(0);  // one round's temporaries at a time
       }
     };
@@ -404,7 +378,9 @@ __global__ __launch_bounds__(768, 1) void tapconv_fl_kernel(TapConv d, MfmaGeom 
         }
       }
       FL_STAMP(0);
-      if (k >= 1) FL_MPOLL(sCR, 8u * (unsigned)k, d.fault);  // every consumer holds column 0 of step k - 1 in registers
+      // (the movers poll in the relaxed form of sp_sync.h: the acquire form also drains the vector-memory counter, so a mover
+      //  would wait at every poll for the global loads it has just issued for LATER use)
+      if (k >= 1) sp_poll_lds(sCR, 8u * (unsigned)k, d.fault);  // every consumer holds column 0 of step k - 1 in registers
       FL_STAMP(1);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // column 0, the window (requested a step ago) and the constants have landed
       FL_STAMP(2);
@@ -437,7 +413,7 @@ __global__ __launch_bounds__(768, 1) void tapconv_fl_kernel(TapConv d, MfmaGeom 
         for (int j = 0; j < 3; ++j) wrA[3 + j] = *reinterpret_cast<const u32x4*>(cb2 + vo_c[j]);
       }
       FL_STAMP(3);
-      if (k >= 2) FL_MPOLL(sWR + (k & 1), 8u * (unsigned)(k >> 1), d.fault);  // the consumers left the buffer in step k - 2
+      if (k >= 2) sp_poll_lds(sWR + (k & 1), 8u * (unsigned)(k >> 1), d.fault);  // the consumers left the buffer in step k - 2
       FL_STAMP(4);
       store_window(second, sWin + (k & 1) * WBUF);
       sp_wait_lds();
@@ -451,7 +427,7 @@ __global__ __launch_bounds__(768, 1) void tapconv_fl_kernel(TapConv d, MfmaGeom 
       // (the rule behind a filling step: conv_sp_movers.inc)
       const bool after_fill = prev_fill;
       prev_fill = w3;
-      if (k >= 1 && (w3 || after_fill)) FL_MPOLL(sCR + 1, 8u * (unsigned)k, d.fault);
+      if (k >= 1 && (w3 || after_fill)) sp_poll_lds(sCR + 1, 8u * (unsigned)k, d.fault);
       if (w3) {
         asm volatile("s_waitcnt vmcnt(18)" ::: "memory");  // column 1 has landed (behind it: 6 pieces of column 2, 12 window loads)
 #pragma unroll
@@ -460,7 +436,7 @@ __global__ __launch_bounds__(768, 1) void tapconv_fl_kernel(TapConv d, MfmaGeom 
       sp_wait_lds();
       if (lane == 0) sp_bump(sCL + 1);
       FL_STAMP(7);
-      if (k >= 1 && (w3 || after_fill)) FL_MPOLL(sCR + 2, 8u * (unsigned)k, d.fault);
+      if (k >= 1 && (w3 || after_fill)) sp_poll_lds(sCR + 2, 8u * (unsigned)k, d.fault);
       if (w3) {
         asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
 #pragma unroll
@@ -539,11 +515,6 @@ __global__ __launch_bounds__(768, 1) void tapconv_fl_kernel(TapConv d, MfmaGeom 
     // (Releasing a ring slot behind a COUNTED wait - only the reads issued before the release, with the next fragment already
     //  requested - was measured: no gain, and the fragment held across the release cost registers the step loop does not have.)
 #define FL_CROSS(XQ, W) { const i32x8 x0_ = XQ(0); FL_CROSS_P(XQ, W, x0_) }
-#ifdef DRS_FL_X_NOCROSS  // speed experiment (wrong numbers): no cross-term fragments / instructions
-#undef FL_CROSS
-#define FL_CROSS(XQ, W) { }
-#define FL_CROSS_P(XQ, W, X0) { (void)X0; }
-#else
 #define FL_CROSS_P(XQ, W, X0)                                                  \
     {                                                                          \
       i32x8 xq_ = X0;                                                          \
@@ -555,7 +526,6 @@ __global__ __launch_bounds__(768, 1) void tapconv_fl_kernel(TapConv d, MfmaGeom 
         xq_ = xn_;                                                             \
       }                                                                        \
     }
-#endif
     // fp16 products of kernel column `col` (weights wm[ky]); PRE: the main weight fragments of the next column (ring offset
     // `next`) replace wm[ky] as soon as the last window row that needs the old ones has been issued
     auto main_col = [&](const char* buf, int col, bool pre, int next, unsigned ltarget) __attribute__((always_inline)) {
@@ -570,11 +540,7 @@ __global__ __launch_bounds__(768, 1) void tapconv_fl_kernel(TapConv d, MfmaGeom 
           const int r = wr - ky;
           if (r >= 0 && r < RPW) {
 #pragma unroll
-#ifndef DRS_FL_X_NOMAIN  // speed experiment (wrong numbers): no fp16 instructions (their fragments are still read)
             for (int t = 0; t < NT; ++t) acc[r][t] = mm16(wm[ky][t], af, acc[r][t]);
-#else
-            for (int t = 0; t < NT; ++t) acc[r][t][0] += __uint_as_float(wm[ky][t][0] ^ af[t]);
-#endif
           }
         }
         if (pre) {
@@ -687,11 +653,7 @@ __global__ __launch_bounds__(768, 1) void tapconv_fl_kernel(TapConv d, MfmaGeom 
         if (lane == 0) sp_bump(sWR + (k & 1));
         FL_STAMP(8);
       }
-#ifdef DRS_FL_X_NOEPI  // speed experiment (wrong numbers): what the item epilogues cost
-      if (c == nck - 1 && k + 1 == S) {
-#else
       if (c == nck - 1) {
-#endif
         int lr_e = lr, kg_e = kg;  // (opaque copies: conv_mfma_sp.hip)
         asm volatile("" : "+v"(lr_e), "+v"(kg_e));
         const float* ek = sEpi + (ord & 1) * (G::EPI / 4);

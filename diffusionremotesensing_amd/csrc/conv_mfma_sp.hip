@@ -142,16 +142,6 @@ __global__ __launch_bounds__(768, 1) void tapconv_sp_kernel(TapConv d, MfmaGeom 
   if (tid < 10) __hip_atomic_store(sCR + tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   sp_wait_lds();
   sp_barrier();
-  // Experiment (DRS_DEBUG_FLAGS bits 8-11 = unit u): block b starts (b >> 3 & 7) * u * ~0.25 us late, so the CUs of an XCD
-  // reach their item epilogues - 64 KB of stores per CU, issued by all CUs of the chip within the same microsecond - at
-  // eight different times.
-  {
-    const int u = (g.debug >> 8) & 15;
-    if (u) {
-      const int ph = (blockIdx.x >> 3) & 7;
-      for (int i = 0; i < ph * u; ++i) __builtin_amdgcn_s_sleep(8);
-    }
-  }
   int c = -1, ord = -1, n = 0, ty0 = 0, tx0 = 0, n0 = 0;  // current step: chunk, item ordinal, item coordinates
 
   if (mover) {
@@ -200,9 +190,6 @@ __global__ __launch_bounds__(768, 1) void tapconv_sp_kernel(TapConv d, MfmaGeom 
         for (int ky = 0; ky < 3; ++ky) {
           const int r = wr - ky;
           if (r >= 0 && r < RPW) {
-#ifdef DRS_SP_TIMELINE
-            if (g.debug & 4) continue;
-#endif
 #pragma unroll
             for (int t = 0; t < NT; ++t) acc[r][t] = P::mma(wf[ky][t], af, acc[r][t]);
           }
@@ -270,9 +257,6 @@ __global__ __launch_bounds__(768, 1) void tapconv_sp_kernel(TapConv d, MfmaGeom 
         if (lane == 0) sp_bump(sWR + (k & 1));
         SP_STAMP(6);
       }
-#ifdef DRS_SP_TIMELINE
-      if (c == nck - 1 && (g.debug & 64)) continue;  // timing experiment: no epilogue
-#endif
       if (c == nck - 1) {
         // opaque copies of the lane coordinates: everything the epilogue derives from them is computed here, not hoisted
         // out of the step loop (where it would be spilled and reloaded between the stores)
@@ -311,9 +295,6 @@ int sp_launch(const TapConv& d, const MfmaGeom& g, hipStream_t s) {
   }
   const long long nitems = (long long)d.N * g.tiles_x * g.tiles_y * (DUAL ? 1 : d.Cout / BNB);
   long long blocks = num_cu;  // one 12-wave block per CU
-#ifdef DRS_SP_TIMELINE
-  if (getenv("DRS_SP_MAXBLOCKS")) blocks = atoi(getenv("DRS_SP_MAXBLOCKS"));  // experiment: fewer CUs
-#endif
   if (blocks > nitems) blocks = nitems;
   blocks = (blocks + 7) / 8 * 8;
   DRS_LAUNCH(kern, dim3((unsigned)blocks), dim3(768), kLds, s, d, g);

@@ -88,9 +88,6 @@
       for (int col = 0; col < 3; ++col) {
         np[col] = second ? (col == 0 ? (BNB == 64 ? 2 : 1) : 0) : WPC;
         if (ring_hit) np[col] = 0;
-#ifdef DRS_SP_TIMELINE
-        if (g.debug & 2) np[col] = 0;
-#endif
       }
       auto load_col = [&](int col) __attribute__((always_inline)) {
 #pragma unroll
@@ -139,13 +136,7 @@
       }
       load_col(0);
       // ---- window loads ----
-#ifdef DRS_SP_TIMELINE
-      const bool skip_win = (g.debug & 1) != 0;
-#else
-      const bool skip_win = false;
-#endif
-      if (skip_win) {
-      } else if (!second && ty0 >= 1 && ty0 + TH + 1 <= d.H && tx0 >= 1 && tx0 + TW + 1 <= d.W && cc * KC + KC <= d.Cin) {
+      if (!second && ty0 >= 1 && ty0 + TH + 1 <= d.H && tx0 >= 1 && tx0 + TW + 1 <= d.W && cc * KC + KC <= d.Cin) {
         // fast path: every window pixel inside the image, every k-group inside the channel count
         const char* base = reinterpret_cast<const char*>(d.in) +
                            ((((long long)n * d.H + (ty0 - 1)) * d.W + (tx0 - 1)) * d.in_cs + d.in_co) * 4 + cc * 128;
@@ -236,7 +227,7 @@
         char* buf = sWin + (k & 1) * WBUF + lane * 16;
 #pragma unroll
         for (int i = 0; i < NPW; ++i)
-          if (i < nwin && !skip_win) *reinterpret_cast<u32x4*>(buf + (pw + 4 * i) * 1024) = ww[i];
+          if (i < nwin) *reinterpret_cast<u32x4*>(buf + (pw + 4 * i) * 1024) = ww[i];
         sp_wait_lds();
         if (lane == 0) sp_bump(sWL + (k & 1));
       }

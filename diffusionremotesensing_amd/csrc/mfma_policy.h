@@ -53,9 +53,7 @@ struct PolicyBF16X3 {  // x = hi + lo (both bf16, 16 mantissa bits together): w*
     return Frag{*reinterpret_cast<const bf16x8*>(base + off), *reinterpret_cast<const bf16x8*>(base + img_stride + off)};
   }
   __device__ static f32x4 mma(const Frag& w, const Frag& a, f32x4 c) {
-#ifndef DRS_EXPERIMENT_2MFMA  // (experiment, never shipped: tools/experiment_2mfma.sh drops the w_lo * a_hi product - DESIGN.md section 7)
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.lo, a.hi, c, 0, 0, 0);
-#endif
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.hi, a.lo, c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.hi, a.hi, c, 0, 0, 0);
   }
@@ -73,7 +71,6 @@ struct MfmaGeom {
   int nchunks2;          // K-chunks of the second input (0 = none)
   int iw_magic;          // ceil(65536 / IW): p / IW == (p * iw_magic) >> 16 for p < 1024
   int w2_gimage;         // bytes of one weight image of the second input in global memory
-  int debug;             // ablation switches (DRS_DEBUG_FLAGS): 1 skip MFMA phase, 2 skip LDS staging stores, 4 skip global loads, 8 skip epilogue
 };
 
 
@@ -85,8 +82,7 @@ int drs_launch_tapconv_ws(const TapConv& d, const MfmaGeom& g, int impl, hipStre
 int drs_launch_tapconv_sp(const TapConv& d, const MfmaGeom& g, hipStream_t s);
 bool drs_tapconv_sp_f32out_supported(const TapConv& d, int impl);  // the same kernel with the fp32 channels-last epilogue
 // the same item / step protocol in the FL arithmetic (conv_mfma_fl.hip: fp16 main product + block-scaled fp6 cross terms of
-// tap pairs); DRS_FL_DECLINED: the launch prefers the split-bf16 kernel's 32-channel groups (fewer 64-channel items than half the CUs)
-#define DRS_FL_DECLINED (-1000)
+// tap pairs)
 bool drs_tapconv_fl_supported(const TapConv& d, int impl);
 int drs_launch_tapconv_fl(const TapConv& d, const MfmaGeom& g, hipStream_t s);
 // the same structure for 8 x 8 images, four images per item (conv_mfma_sp8.hip): the bottleneck level of 64 x 64 models

@@ -45,7 +45,7 @@ __device__ unsigned long long drs_rb0_tl[32];
 #endif
 
 __global__ __launch_bounds__(512, 1) void resblock0_kernel(ResBlock0Desc d, unsigned w1_gimage, unsigned w2_gimage,
-                                                           unsigned ws_gimage, int debug) {
+                                                           unsigned ws_gimage) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using P = PolicyBF16X3;
   using Frag = typename P::Frag;
@@ -193,7 +193,6 @@ __global__ __launch_bounds__(512, 1) void resblock0_kernel(ResBlock0Desc d, unsi
   unsigned long long tl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const unsigned long long tl_begin = __builtin_amdgcn_s_memtime();
   unsigned long long tl_last = tl_begin, tl_n = 0;
-  if ((debug & 1) && grp == 1) return;  // one group alone: uncontended phase times (the output is incomplete)
 #endif
   if (q0 < t_hi) {
     place_first(q0);
@@ -450,17 +449,16 @@ int drs_launch_resblock0(const ResBlock0Desc& d, hipStream_t s) {
   // global operand images (drs_launch_pack_conv_mfma): [chunk 1][tap][k-group 4][channels] slots, one image per bf16 half
   const unsigned w1_gimage = 9u * 4u * 64u * 16u, w2_gimage = 9u * 4u * 32u * 16u, ws_gimage = 4u * 32u * 16u;
   const int blocks = num_cu / 8 * 8;  // one block per CU
-  DRS_LAUNCH(resblock0_kernel, dim3((unsigned)blocks), dim3(512), resblock0_lds(d.N), s, d, w1_gimage, w2_gimage, ws_gimage, 0);
+  DRS_LAUNCH(resblock0_kernel, dim3((unsigned)blocks), dim3(512), resblock0_lds(d.N), s, d, w1_gimage, w2_gimage, ws_gimage);
   DRS_CHECK_HIP(hipGetLastError());
 #ifdef DRS_SP_TIMELINE
   {
     unsigned long long h[32];
-    const int dbg = getenv("DRS_RB0_DEBUG") ? atoi(getenv("DRS_RB0_DEBUG")) : 0;
     hipEvent_t e0, e1;
     float ms = 0.f;
     DRS_CHECK_HIP(hipEventCreate(&e0)); DRS_CHECK_HIP(hipEventCreate(&e1));
     DRS_CHECK_HIP(hipEventRecord(e0, s));
-    DRS_LAUNCH(resblock0_kernel, dim3((unsigned)blocks), dim3(512), resblock0_lds(d.N), s, d, w1_gimage, w2_gimage, ws_gimage, dbg);  // timed repeat
+    DRS_LAUNCH(resblock0_kernel, dim3((unsigned)blocks), dim3(512), resblock0_lds(d.N), s, d, w1_gimage, w2_gimage, ws_gimage);  // timed repeat
     DRS_CHECK_HIP(hipEventRecord(e1, s));
     DRS_CHECK_HIP(hipStreamSynchronize(s));
     DRS_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));

@@ -236,17 +236,14 @@ int drs_launch_conv3x3_planar(const float* in, const float* w, const float* b, c
 // lo) and its 64 residual bytes cross a 4 KB per-wave LDS image, so every global load / store instruction of the
 // channels-last tensors covers 1 KB of CONSECUTIVE bytes (16 bytes per lane at a 64-byte stride touches each line four
 // times).
-#ifndef DRS_STEM_ROWS
-#define DRS_STEM_ROWS 4
-#define DRS_STEM_BPC 2
-#endif
-constexpr int kStemRows = DRS_STEM_ROWS;  // rows per lane
+constexpr int kStemRows = 4;  // rows per lane
+constexpr int kStemBpc = 2;   // blocks per CU the register budget is set for
 __device__ __attribute__((aligned(16))) float stem_zero_line[4];  // (zero-initialised, never written)
 template <int COUT>
-__global__ __launch_bounds__(256, DRS_STEM_BPC) void stem_kernel(const float* __restrict__ in, const float* __restrict__ w,
-                                                   const float* __restrict__ b, const float* __restrict__ res,
-                                                   int res_batch, float* __restrict__ out, int N, int Cin, int H,
-                                                   int W, int out_sp) {
+__global__ __launch_bounds__(256, kStemBpc) void stem_kernel(const float* __restrict__ in, const float* __restrict__ w,
+                                                             const float* __restrict__ b, const float* __restrict__ res,
+                                                             int res_batch, float* __restrict__ out, int N, int Cin, int H,
+                                                             int W, int out_sp) {
   static_assert(COUT == 16, "a pixel is 64 bytes in both output formats");
   constexpr int R = kStemRows;
   constexpr int kB = COUT * kMaxBands * 9;                                     // bias offset

@@ -69,7 +69,7 @@ __host__ __device__ constexpr bool uf_pair(int p, int t, int kv, int kw) { retur
 __host__ __device__ constexpr int uf_perm(int nn) { return ((nn & 15) >> 2) * 8 + (nn >> 4) * 4 + (nn & 3); }
 
 template <bool FUSE>
-__global__ __launch_bounds__(768, 1) void upfuse_sp_kernel(UpFuseDesc d, int tiles_y, int tiles_x, int nck, int debug) {
+__global__ __launch_bounds__(768, 1) void upfuse_sp_kernel(UpFuseDesc d, int tiles_y, int tiles_x, int nck) {
   constexpr int NT = 2;  // channel tiles a consumer multiplies
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using P = PolicyBF16X3;
@@ -380,11 +380,7 @@ __global__ __launch_bounds__(768, 1) void upfuse_sp_kernel(UpFuseDesc d, int til
         // in-order counter for loads and stores: a load issued behind a store is complete only once that store is).  All
         // sixteen loads are in flight together (the fragment registers of the step loop are free by now): left to itself the
         // compiler issues them pair by pair with a full wait after each, eight memory round trips per item.
-#ifdef DRS_SP_TIMELINE
-        if (d.res && !(debug & 2)) {
-#else
         if (d.res) {
-#endif
           u32x4 rh[RPW][2], rl[RPW][2];
 #pragma unroll
           for (int r = 0; r < RPW; ++r)
@@ -514,9 +510,6 @@ __global__ __launch_bounds__(768, 1) void upfuse_sp_kernel(UpFuseDesc d, int til
                 drs_sp_split8(v, h, l);
                 const typename P::Frag vf{__builtin_bit_cast(bf16x8, h), __builtin_bit_cast(bf16x8, l)};
                 const f32x4 y = P::mma(wfr, vf, f32x4{0.f, 0.f, 0.f, 0.f});  // register 0 of the lane of k-group j: output j of pixel lr
-#ifdef DRS_SP_TIMELINE
-                if (debug & 1) { asm volatile("" :: "v"(y)); } else
-#endif
                 if (own_ok && kg_e < d.fuse_dim) {
                   const size_t plane = (size_t)OH * OW;
                   d.fuse_out[((size_t)n * d.fuse_dim + kg_e) * plane + (size_t)oy * OW + ox_own] = y[0] + fbk + prev[r][py];
@@ -529,9 +522,6 @@ __global__ __launch_bounds__(768, 1) void upfuse_sp_kernel(UpFuseDesc d, int til
                   drs_sp_split8(w8, H, L);
                   const u32x4 got = drs_dpp_swap8(lo ? L : H);  // lr < 8 receives the partner's hi, lr >= 8 the partner's lo
                   char* g = reinterpret_cast<char*>(base) + (pix0 * cs + co + n0) * 4 + lane_b;
-#ifdef DRS_SP_TIMELINE
-                  if (debug & 1) { asm volatile("" :: "v"(H), "v"(L), "v"(got)); return; }
-#endif
                   if (ok0) drs_store16(g, lo ? H : got);
                   if (ok1) drs_store16(g + (size_t)16 * cs * 4, lo ? got : L);
                 };
@@ -932,11 +922,10 @@ int drs_launch_upfuse(const UpFuseDesc& d, hipStream_t s) {
   long long blocks = num_cu;  // one 12-wave block per CU
   if (blocks > nitems) blocks = nitems;
   blocks = (blocks + 7) / 8 * 8;
-  static const int dbg = getenv("DRS_DEBUG_FLAGS") ? atoi(getenv("DRS_DEBUG_FLAGS")) : 0;  // timeline builds: 1 no stores, 2 no residual loads
   if (d.fuse_out)
-    DRS_LAUNCH(upfuse_sp_kernel<true>, dim3((unsigned)blocks), dim3(768), UfGeom::LDS, s, d, tiles_y, tiles_x, nck, dbg);
+    DRS_LAUNCH(upfuse_sp_kernel<true>, dim3((unsigned)blocks), dim3(768), UfGeom::LDS, s, d, tiles_y, tiles_x, nck);
   else
-    DRS_LAUNCH(upfuse_sp_kernel<false>, dim3((unsigned)blocks), dim3(768), UfGeom::LDS, s, d, tiles_y, tiles_x, nck, dbg);
+    DRS_LAUNCH(upfuse_sp_kernel<false>, dim3((unsigned)blocks), dim3(768), UfGeom::LDS, s, d, tiles_y, tiles_x, nck);
   DRS_CHECK_HIP(hipGetLastError());
 #ifdef DRS_SP_TIMELINE
   {
@@ -946,9 +935,9 @@ int drs_launch_upfuse(const UpFuseDesc& d, hipStream_t s) {
     DRS_CHECK_HIP(hipEventCreate(&e0)); DRS_CHECK_HIP(hipEventCreate(&e1));
     DRS_CHECK_HIP(hipEventRecord(e0, s));
     if (d.fuse_out)  // timed repeat (same result)
-      DRS_LAUNCH(upfuse_sp_kernel<true>, dim3((unsigned)blocks), dim3(768), UfGeom::LDS, s, d, tiles_y, tiles_x, nck, dbg);
+      DRS_LAUNCH(upfuse_sp_kernel<true>, dim3((unsigned)blocks), dim3(768), UfGeom::LDS, s, d, tiles_y, tiles_x, nck);
     else
-      DRS_LAUNCH(upfuse_sp_kernel<false>, dim3((unsigned)blocks), dim3(768), UfGeom::LDS, s, d, tiles_y, tiles_x, nck, dbg);
+      DRS_LAUNCH(upfuse_sp_kernel<false>, dim3((unsigned)blocks), dim3(768), UfGeom::LDS, s, d, tiles_y, tiles_x, nck);
     DRS_CHECK_HIP(hipEventRecord(e1, s));
     DRS_CHECK_HIP(hipStreamSynchronize(s));
     DRS_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));

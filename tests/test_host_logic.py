@@ -254,8 +254,7 @@ def test_every_environment_switch_the_library_reads_is_documented():
     for path in glob.glob(os.path.join(root, "diffusionremotesensing_amd", "csrc", "*.*")):
         if path.endswith((".hip", ".h", ".inc")):
             names |= set(re.findall(r'getenv\("(DRS_[A-Z0-9_]+)"\)', open(path).read()))
-    experiment_builds_only = {"DRS_SP_MAXBLOCKS", "DRS_RB0_DEBUG",  # behind #ifdef DRS_SP_TIMELINE
-                              "DRS_X_NUM_CU"}  # behind #ifdef DRS_X_NUM_CU (tools/two_stream_probe.py)
+    experiment_builds_only = set()  # (the timeline builds read no name of their own any more)
     shipped = names - experiment_builds_only
     assert len(shipped) >= 15
     integration = open(os.path.join(root, "INTEGRATION.md")).read()
@@ -267,3 +266,27 @@ def test_every_environment_switch_the_library_reads_is_documented():
         assert n in header, f"{n} is read by the library but missing from include/drs_hip.h"
     listed = set(re.findall(r"`(DRS_[A-Z0-9_]+)`", integration[integration.index("kernel-family switches"):integration.index("A plan is driven")]))
     assert listed - experiment_builds_only <= names, f"INTEGRATION.md lists switches the library no longer reads: {sorted(listed - names)}"
+
+
+def test_the_shipped_sources_have_no_compile_time_switches_but_the_timeline_builds():
+    """A conditional in csrc is an arm that nothing builds or tests: experiments live in variants/ or tools/micro/, and the
+    only conditionals of the product are the three in-kernel timeline builds and the host / device split of drs_common.h."""
+    import glob
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    allowed = {"DRS_SP_TIMELINE", "DRS_WS_TIMELINE", "DRS_FL_TIMELINE", "__HIPCC__"}
+    found = {}
+    for path in sorted(glob.glob(os.path.join(root, "diffusionremotesensing_amd", "csrc", "*.*"))):
+        if not path.endswith((".hip", ".h", ".inc")):
+            continue
+        text = open(path).read()
+        # a directive's logical line: backslash continuations joined; a trailing // comment dropped (it may quote other names)
+        for m in re.finditer(r"^[ \t]*#[ \t]*(if|ifdef|ifndef|elif)\b((?:\\\n|[^\n])*)", text, re.M):
+            expr = m.group(2).replace("\\\n", " ").split("//")[0]
+            for name in re.findall(r"[A-Za-z_]\w*", expr):
+                if name != "defined":
+                    found.setdefault(name, os.path.basename(path))
+        for name in re.findall(r"\bdefined\s*\(\s*([A-Za-z_]\w*)\s*\)", text):
+            found.setdefault(name, os.path.basename(path))
+    assert len(found) >= 4, found  # the scan sees the conditionals that are there
+    assert set(found) <= allowed, {n: f for n, f in found.items() if n not in allowed}
