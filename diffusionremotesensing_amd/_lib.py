@@ -41,7 +41,9 @@ SIGNATURES = {
     "drs_adam_multi": (_I, [_P, _I, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     "drs_grad_sumsq_partials": (_I, [_P, _I, _L, _P, _P]),
     "drs_adamw_clip_multi": (_I, [_P, _I, _L] + [C.c_double] * 6 + [_I, _P, _I, _P, _P]),
-    "drs_ema_multi": (_I, [_P, _I, C.c_int64, C.c_double, _I, _P]),
+    "drs_diffusion_loss": (_I, [_P, _P, _P, _I, _L, _P, _I, _P, _I, C.c_double] + [_P] * 5 + [_I, _I, _I, _P, _P]),
+    "drs_timestep_draw": (_I, [_P, _I, _I, _P, _P, _I, _I, C.c_double, _P, _P, _P]),
+    "drs_ema_multi":(_I, [_P, _I, C.c_int64, C.c_double, _I, _P]),
     "drs_downblur_scratch_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "drs_downblur_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _P, _Z, _P]),
     "drs_add_noise_clip_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),

@@ -15,7 +15,8 @@ import torch.nn as nn
 
 from .. import dist as drs_dist
 from ..sampling import _repeat_members, asks_for_known_pixels, check_inpaint_args, check_sampling_args
-from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, add_optim_args, base_arg_parser, check_optim_args, launch_device, make_loaders,
+from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, add_objective_args, add_optim_args, base_arg_parser,
+                                        check_objective_args, check_optim_args, launch_device, make_loaders,
                                         save_final_samples, train_model)
 from .UNet_model_generation import Residual_Attention_UNet_generation
 
@@ -178,14 +179,14 @@ def build_arg_parser():
 
 def train_main_parser():
     """`build_arg_parser` and the crop / augmentation flags (augment.add_augment_args) and the
-    optimizer / resume flags (add_optim_args): what `main` parses."""
+    optimizer / resume flags (add_optim_args) and the objective flags (add_objective_args): what `main` parses."""
     from ..augment import add_augment_args
-    return add_optim_args(add_augment_args(build_arg_parser()))
+    return add_objective_args(add_optim_args(add_augment_args(build_arg_parser())))
 
 
 def main(argv=None):
     parser = train_main_parser()
-    args = check_optim_args(parser, parser.parse_args(argv))
+    args = check_objective_args(parser, check_optim_args(parser, parser.parse_args(argv)))
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     launch(args)
 

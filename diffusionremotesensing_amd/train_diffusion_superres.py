@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import dist as drs_dist
 from . import hip_ops
+from .losses import DiffusionLoss, LossAwareSampler, LossBins, min_snr_weights
 from .optim import FusedAdam, FusedAdamW, WarmupCosine
 from .sampling import (CHAIN_CHECK_EVERY, _is_int, _repeat_members, asks_for_known_pixels,  # noqa: F401 - re-exported
                        check_ensemble_args, check_inpaint_args, check_sampling_args, check_solver_known, ddim_chain_noise,
@@ -62,6 +63,7 @@ class Diffusion:
         self.ema_smoothing = ema_smoothing
         self.model = model.to(self.device)
         self.epochs_run = 0
+        self.timestep_sampler = None  # `train(timestep_sampling="loss_aware")` puts a losses.LossAwareSampler here
         if os.path.exists(snapshot_path):
             print("Loading snapshot")
             self._load_snapshot()
@@ -367,13 +369,16 @@ class Diffusion:
         epoch + 1 as if it had not stopped.  With EMA the snapshot holds the averaged copy, so the raw weights are here.  Not
         saved: the private generators of the crop / BSRGAN feeds.  One file, written by rank 0 and read by every rank."""
         net = model.module if self.multiple_gpus and hasattr(model, "module") else model
-        torch.save({"OPTIMIZER_STATE": state.optimizer.state_dict(),
-                    "RAW_MODEL_STATE": net.state_dict() if state.ema is not None else None,
-                    "EMA_STEP": state.ema.step if state.ema is not None else None,
-                    "LR_SCHEDULE": state.scheduler.state_dict() if state.scheduler is not None else None,
-                    "BEST_LOSS": state.best_loss, "EPOCHS_WITHOUT_IMPROVING": state.epochs_without_improving,
-                    "NEXT_EPOCH": epoch + 1, "CPU_RNG_STATE": torch.get_rng_state(),
-                    "DEVICE_RNG_STATE": torch.cuda.get_rng_state(self.device)}, self.train_state_path())
+        ts = {"OPTIMIZER_STATE": state.optimizer.state_dict(),
+              "RAW_MODEL_STATE": net.state_dict() if state.ema is not None else None,
+              "EMA_STEP": state.ema.step if state.ema is not None else None,
+              "LR_SCHEDULE": state.scheduler.state_dict() if state.scheduler is not None else None,
+              "BEST_LOSS": state.best_loss, "EPOCHS_WITHOUT_IMPROVING": state.epochs_without_improving,
+              "NEXT_EPOCH": epoch + 1, "CPU_RNG_STATE": torch.get_rng_state(),
+              "DEVICE_RNG_STATE": torch.cuda.get_rng_state(self.device)}
+        if getattr(state, "loss_bins", None) is not None:  # (a run without --loss_bins / loss_aware writes the file it always wrote)
+            ts["LOSS_BINS"] = state.loss_bins.state_dict()
+        torch.save(ts, self.train_state_path())
 
     def _load_train_state(self, model, state):
         """Restores `_save_train_state`'s file into a run that `__init__` has already given the snapshot's weights: those stay
@@ -382,6 +387,11 @@ class Diffusion:
         ts = torch.load(self.train_state_path(), map_location="cpu")
         if (ts["RAW_MODEL_STATE"] is None) != (state.ema is None) or (ts["LR_SCHEDULE"] is None) != (state.scheduler is None):
             raise ValueError(f"{self.train_state_path()} was written with other --ema_smoothing / --lr_schedule options")
+        bins = getattr(state, "loss_bins", None)
+        if ("LOSS_BINS" in ts) != (bins is not None):
+            raise ValueError(f"{self.train_state_path()} was written with other --loss_bins / --timestep_sampling options")
+        if bins is not None:
+            bins.load_state_dict(ts["LOSS_BINS"])  # (other T / bin count: ValueError)
         net = model.module if self.multiple_gpus and hasattr(model, "module") else model
         # (another parameter count or other shapes: ValueError from FusedAdamW.load_state_dict, the first thing loaded)
         state.optimizer.load_state_dict(ts["OPTIMIZER_STATE"])
@@ -416,6 +426,35 @@ class Diffusion:
             return mse_perceptual_noise(device)
         raise ValueError("The Loss must be either MSE or MAE or Huber or MSE+Perceptual_noise")
 
+    def _objective(self, loss, loss_weighting, min_snr_gamma, timestep_sampling, loss_bins):
+        """None for a default run; otherwise what `train` swaps in for the loss module (losses.py): `train` / `val`
+        (`DiffusionLoss` with the same table, bins of their own), `bins` / `val_bins` (`LossBins` or None) and `sampler`
+        (`LossAwareSampler` or None).  Under --multiple_gpus every rank has its own."""
+        if loss_weighting not in ("none", "min_snr") or timestep_sampling not in ("uniform", "loss_aware"):
+            raise ValueError("loss_weighting must be none or min_snr, timestep_sampling uniform or loss_aware")
+        if loss_bins < 0 or not min_snr_gamma > 0:
+            raise ValueError("loss_bins must be >= 0 and min_snr_gamma > 0")
+        if loss_weighting == "none" and timestep_sampling == "uniform" and not loss_bins:
+            return None
+        if loss == "MSE+Perceptual_noise":
+            raise ValueError("--loss MSE+Perceptual_noise cannot be combined with --loss_weighting / --timestep_sampling / "
+                             "--loss_bins: the VGG term has no per-image split")
+        if loss not in ("MSE", "MAE", "Huber"):
+            raise ValueError("The Loss must be either MSE or MAE or Huber or MSE+Perceptual_noise")
+        nbins = loss_bins or (16 if timestep_sampling == "loss_aware" else 0)
+        table = min_snr_weights(self.alpha_hat, min_snr_gamma).to(self.device) if loss_weighting == "min_snr" else None
+        bins = LossBins(self.noise_steps, nbins, self.device) if nbins else None
+        val_bins = LossBins(self.noise_steps, nbins, self.device) if nbins else None
+        return types.SimpleNamespace(train=DiffusionLoss(loss, table, bins), val=DiffusionLoss(loss, table, val_bins),
+                                     bins=bins, val_bins=val_bins,
+                                     sampler=LossAwareSampler(bins) if timestep_sampling == "loss_aware" else None)
+
+    @staticmethod
+    def _bins_line(stats):
+        """The mean loss per timestep bin, lowest-noise bin first, `-` for a bin nothing fell into."""
+        line = " ".join("-" if m is None else f"{m:.4g}" for m in stats["mean"])
+        return line + (f" | non-finite images {stats['nonfinite']}" if stats["nonfinite"] else "")
+
     def _is_rank0(self):
         return (not self.multiple_gpus) or self.device == 0 or drs_dist.rank() == 0
 
@@ -433,13 +472,23 @@ class Diffusion:
         lr_img, hr_img = self._split_batch((lr_img, hr_img))
         # same CPU-generator draw as the reference (:384); pinned + non_blocking so that the copy does not make the host
         # wait for the previous step's kernels (a pageable .to(device) is a full synchronisation point)
-        t = self.sample_timesteps(hr_img.shape[0])
-        t = (t.pin_memory() if not t.is_cuda else t).to(self.device, non_blocking=True)
+        sample_w = None
+        if self.timestep_sampler is not None:
+            # loss-aware draw on the device (losses.LossAwareSampler): consumes the DEVICE generator, not the CPU one
+            t, sample_w = self.timestep_sampler.draw(hr_img.shape[0])
+        else:
+            t = self.sample_timesteps(hr_img.shape[0])
+            t = (t.pin_memory() if not t.is_cuda else t).to(self.device, non_blocking=True)
         x_t, noise = self.noise_images(hr_img, t)
         optimizer.zero_grad()
         predicted_noise = self._predict(model, x_t, t, self._train_cond(lr_img))
-        train_loss = loss_function(predicted_noise, noise)
-        train_loss.backward()
+        if isinstance(loss_function, DiffusionLoss):
+            # loss and d loss / d prediction from one launch: no second pass for autograd's grad_output
+            train_loss, grad = loss_function.loss_and_grad(predicted_noise, noise, t, sample_w)
+            predicted_noise.backward(grad)
+        else:
+            train_loss = loss_function(predicted_noise, noise)
+            train_loss.backward()
         if lr_scheduler is not None:
             lr_scheduler.step(optimizer)
         if self.multiple_gpus:
@@ -464,17 +513,25 @@ class Diffusion:
 
     def train(self, lr, epochs, check_preds_epoch, train_loader, val_loader, patience, loss, verbose, eval_metrics=0,
               sampling_steps=None, eta=0.0, weight_decay=0.0, max_grad_norm=None, lr_schedule="constant", warmup_steps=0,
-              lr_min=0.0, save_train_state=False):
+              lr_min=0.0, save_train_state=False, loss_weighting="none", min_snr_gamma=5.0, timestep_sampling="uniform",
+              loss_bins=0):
         """`eval_metrics=N` (not in the reference; 0 = off): at every epoch with epoch % check_preds_epoch == 0 the network that
         would be saved is scored on the first N validation images (`evaluate` with `sampling_steps` / `eta`), one line.
         Not in the reference either, all off by default (then this is its loop: Adam at a fixed rate): `weight_decay` and
         `max_grad_norm` (decoupled decay, clipping of the global gradient norm, and a guard that skips a step whose gradients
         are not finite: `optim.FusedAdamW`); `lr_schedule` "constant" | "cosine" with `warmup_steps` and `lr_min`
         (`optim.WarmupCosine` over len(train_loader) * epochs steps); `save_train_state`: every snapshot gets a
-        `train_state.pt` beside it and a run that finds both continues exactly where that one stood (`_save_train_state`)."""
+        `train_state.pt` beside it and a run that finds both continues exactly where that one stood (`_save_train_state`).
+        The objective (losses.py; all off by default, then the loss is torch's module and t the CPU
+        generator's uniform draw): `loss_weighting="min_snr"` weights every image's loss with min(1, `min_snr_gamma` / SNR_t);
+        `loss_bins=N` keeps the mean loss per timestep bin and prints it, lowest-noise bin first, one more line per phase;
+        `timestep_sampling="loss_aware"` draws t on the device from those bins' recent losses (16 bins when `loss_bins` is 0)
+        and so consumes the DEVICE generator instead of the CPU one.  Any of them routes `train_step` and the validation loop
+        through `losses.DiffusionLoss`; validation keeps its uniform CPU draw of t and has bins of its own."""
         model = self.model
         if lr_schedule not in ("constant", "cosine"):
             raise ValueError("lr_schedule must be constant or cosine")
+        objective = self._objective(loss, loss_weighting, min_snr_gamma, timestep_sampling, loss_bins)
         if weight_decay or max_grad_norm is not None or save_train_state:
             optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         else:
@@ -486,13 +543,16 @@ class Diffusion:
         if self.ema_smoothing:
             ema = EMA(beta=0.995)
             ema_model = copy.deepcopy(model).eval().requires_grad_(False)
-        loss_function = self._loss_function(loss, self.device)
+        loss_function = objective.train if objective is not None else self._loss_function(loss, self.device)
+        self.timestep_sampler = objective.sampler if objective is not None else None
+        bins = objective.bins if objective is not None else None
         epochs_without_improving = 0
         best_loss = float("inf")
         saved = ema_model if self.ema_smoothing else model
         # what a run holds besides the weights; `save` keeps best_loss / epochs_without_improving current
         state = self.train_state = types.SimpleNamespace(optimizer=optimizer, scheduler=scheduler, ema=ema, ema_model=ema_model,
-                                                         best_loss=best_loss, epochs_without_improving=0)
+                                                         best_loss=best_loss, epochs_without_improving=0, loss_function=loss_function,
+                                                         loss_bins=bins)
         if save_train_state and os.path.exists(self.snapshot_path) and os.path.exists(self.train_state_path()):
             self._load_train_state(model, state)
             best_loss, epochs_without_improving = state.best_loss, state.epochs_without_improving
@@ -531,6 +591,10 @@ class Diffusion:
                 if skipped:
                     more += f" | skipped steps {skipped}"
             print(f"Epoch {epoch}: Running Train ({loss}) {running_train_loss}" + more)
+            if objective is not None:
+                objective.train.check_faults()
+            if bins is not None:
+                print(f"Epoch {epoch}: Train loss by timestep bin (low noise first) " + self._bins_line(bins.read_and_reset()))
 
             if self._is_rank0() and epoch % check_preds_epoch == 0 and val_loader is None:
                 save(epoch)
@@ -544,13 +608,20 @@ class Diffusion:
                         t = self.sample_timesteps(hr_img.shape[0]).to(self.device)
                         x_t, noise = self.noise_images(hr_img, t)
                         net = ema_model if self.ema_smoothing else model
-                        running_val_loss += loss_function(self._predict(net, x_t, t, self._train_cond(lr_img)), noise)
+                        predicted_noise = self._predict(net, x_t, t, self._train_cond(lr_img))
+                        if objective is not None:  # the same table through the no-grad path; uniform t, bins of its own
+                            running_val_loss += objective.val(predicted_noise, noise, t)
+                        else:
+                            running_val_loss += loss_function(predicted_noise, noise)
                 running_val_loss = running_val_loss.item() / max(len(val_loader), 1)
                 if self.multiple_gpus:
                     # the reference decides per rank on its own validation shard (:492-510, quirk Q9); with a collective in
                     # every training step the ranks must leave the loop together: one mean over ranks, same branch everywhere
                     running_val_loss = drs_dist.allreduce_mean_scalar(running_val_loss)
                 print(f"Epoch {epoch}: Running Val loss ({loss}){running_val_loss}")
+                if bins is not None:
+                    print(f"Epoch {epoch}: Val loss by timestep bin (low noise first) "
+                          + self._bins_line(objective.val_bins.read_and_reset()))
                 if eval_metrics and epoch % check_preds_epoch == 0:
                     scores = self.evaluate(saved, val_loader, n_images=eval_metrics, sampling_steps=sampling_steps, eta=eta)
                     print(f"Epoch {epoch}: Val metrics on {scores['n']} images | " + format_scores(scores))
@@ -625,7 +696,7 @@ def train_model(args, diffusion_class, model, device, train_loader, val_loader, 
                                 ema_smoothing=args.ema_smoothing, **diffusion_kwargs)
     diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
                     train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
-                    verbose=True, **optim_train_kwargs(args), **(train_kwargs or {}))
+                    verbose=True, **optim_train_kwargs(args), **objective_train_kwargs(args), **(train_kwargs or {}))
     if args.multiple_gpus:
         drs_dist.destroy_process_group()
     return diffusion
@@ -862,6 +933,36 @@ def optim_train_kwargs(args):
     return {k: getattr(args, k, v) for k, v in OPTIM_DEFAULTS.items()}
 
 
+OBJECTIVE_DEFAULTS = {"loss_weighting": "none", "min_snr_gamma": 5.0, "timestep_sampling": "uniform", "loss_bins": 0}
+
+
+def add_objective_args(p):
+    """The training-objective flags of the three trainers' command lines (not in the reference; `Diffusion.train`, losses.py)."""
+    p.add_argument("--loss_weighting", type=str, choices=("none", "min_snr"), default="none",
+                   help="min_snr: weight every image's loss with min(1, --min_snr_gamma / SNR_t); none = the reference's loss")
+    p.add_argument("--min_snr_gamma", type=float, default=5.0, help="gamma of --loss_weighting min_snr")
+    p.add_argument("--timestep_sampling", type=str, choices=("uniform", "loss_aware"), default="uniform",
+                   help="loss_aware: draw t on the device in proportion to the recent losses of its timestep bin, with the "
+                        "importance weight that keeps the loss an estimate of the uniform mean; uses 16 bins when --loss_bins "
+                        "is 0 and consumes the device generator instead of the CPU one")
+    p.add_argument("--loss_bins", type=int, default=0,
+                   help="keep and print the mean loss per timestep bin (N bins, 2 .. 64 and at most noise_steps / 2; lowest-noise "
+                        "bin first), one more line per phase and epoch; 0 = off.  Not built: bins shared across ranks, "
+                        "weighting of the perceptual loss")
+    return p
+
+
+def check_objective_args(p, args):
+    if args.loss_bins < 0 or not args.min_snr_gamma > 0:
+        p.error("--loss_bins must be >= 0 and --min_snr_gamma > 0")
+    return args
+
+
+def objective_train_kwargs(args):
+    """`add_objective_args`' flags as keyword arguments of `Diffusion.train` (a namespace without them: the defaults)."""
+    return {k: getattr(args, k, v) for k, v in OBJECTIVE_DEFAULTS.items()}
+
+
 def add_sampling_args(p):
     """The DDIM flags of the final sampling (not in the reference): none = the reference's ancestral chain."""
     p.add_argument("--sampling_steps", type=int, default=None,
@@ -874,7 +975,7 @@ def parse_train_args(argv=None):
     --num_crops gets its meaning there) and `--eval_metrics`, which one process evaluates (no distributed evaluation: rejected
     together with --multiple_gpus)."""
     from .augment import add_augment_args
-    p = add_optim_args(add_augment_args(add_bsr_args(build_arg_parser())))
+    p = add_objective_args(add_optim_args(add_augment_args(add_bsr_args(build_arg_parser()))))
     p.add_argument("--eval_metrics", type=int, default=0,
                    help="score the network on the first N validation images (PSNR / SSIM / SAM / ERGAS against the bicubic "
                         "baseline) at every epoch with epoch %% check_preds_epoch == 0; 0 = off")
@@ -884,6 +985,7 @@ def parse_train_args(argv=None):
     if args.eval_metrics and args.multiple_gpus:
         p.error("--eval_metrics runs in one process: it cannot be combined with --multiple_gpus")
     check_optim_args(p, args)
+    check_objective_args(p, args)
     return args
 
 

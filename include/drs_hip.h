@@ -209,6 +209,45 @@ DRS_API int drs_adamw_clip_multi(const drs_adamw_tensor* table, int ntensors, in
                                  double beta2, double eps, double weight_decay, double max_norm, int skip_nonfinite,
                                  const double* partials, int npartials, drs_adamw_stats* stats, drs_stream_t stream);
 
+/* The training objective: loss value, gradient and per-image losses from ONE pass over the data, plus a small ordered finish
+ * launched behind it on the same stream (no atomics, no host synchronisation; two calls on the same inputs give the same bits
+ * in every output).  pred, target: (B, n) fp32 contiguous; with d = pred - target formed in fp32 and l = torch's mse_loss /
+ * l1_loss / huber_loss(delta) element function,
+ *   per_image[b] = (1/n) sum_i l(d[b,i])                     double, summed in double in a fixed order
+ *   w_b          = table[t[b]] * sample_w[b]                 double; a NULL table or sample_w is a factor 1
+ *   loss         = (1/B) sum_b w_b * per_image[b]            out[0] as double, and as fp32 in the 4 bytes at out + 1
+ *   grad[b,i]    = (float)(w_b c / (B n)) * l'(d[b,i])       c = 2, l' = d for MSE; c = 1, l' = sign(d) (0 at 0) for MAE; Huber:
+ *                                                            l' = d for |d| <= delta, else (float)(w_b delta / (B n)) * sign(d)
+ * `grad` may be NULL (validation: nothing is written).  `table` holds T floats and is indexed by t (B int64, device); `t` may be
+ * NULL when neither a table nor bins are given.  `partials`: workspace of B * ((n + 3) / 4096 + 1) doubles.
+ *
+ * `bins` (may be NULL): 3 nbins + 1 + nbins history 8-byte words on the device, zeroed once by the caller -
+ *   double sum[nbins]; int64 count[nbins]; int64 appended[nbins]; int64 nonfinite; double ring[nbins][history]
+ * - with bin(t) = t nbins / T (integer division).  In batch order every finite per_image[b] is added to sum / count of its bin and,
+ * when update_ring != 0, written to ring[bin][appended % history] (appended counts them: the ring holds the last `history`
+ * losses of the bin); a non-finite one only raises `nonfinite`.  `loss` carries it all the same.
+ * A t[b] outside [0, T), with a table or bins: nothing is read or binned for that image, its weight is NaN (so `loss` and its
+ * gradient row are) and *bad_t (device int64, may be NULL, never reset here) grows by one: the caller reads it where it
+ * synchronises anyway.
+ * DRS_ERR_ARG: null pointer, unknown kind, Huber with delta <= 0, a table or bins without t or T, nbins outside 2 .. min(64, T / 2),
+ * history outside 1 .. 32; DRS_ERR_SHAPE: B outside 1 .. 65535, n < 1.  All are reported before anything is launched. */
+enum { DRS_LOSS_MSE = 0, DRS_LOSS_MAE = 1, DRS_LOSS_HUBER = 2 };
+DRS_API int drs_diffusion_loss(const float* pred, const float* target, const int64_t* t, int B, int64_t n, const float* table,
+                               int T, const float* sample_w, int kind, double delta, float* grad, double* per_image,
+                               double* partials, double* out, double* bins, int nbins, int history, int update_ring,
+                               int64_t* bad_t, drs_stream_t stream);
+
+/* Loss-aware timesteps (the loss-second-moment resampler of Nichol & Dhariwal 2021, per bin) from the ring of `bins` (layout
+ * above) and two uniforms per sample, u1, u2 in [0, 1) (B floats each): t (B int64, in 1 .. T - 1) and sample_w (B floats).
+ * With cnt_k the number of timesteps 1 .. T - 1 in bin k: while any bin has appended < history,
+ *   t = 1 + min(T - 2, floor(u1 (T - 1))), sample_w = 1;
+ * afterwards r_k = sqrt(mean of ring[k]^2), p_k = (1 - eps) r_k / sum r + eps / nbins (p_k = 1 / nbins when sum r == 0), k = the
+ * first bin whose cumulative p exceeds u1 (the last bin if none does), t = the floor(u2 cnt_k)-th of bin k's timesteps and
+ * sample_w = cnt_k / ((T - 1) p_k), the ratio uniform / proposal.  p and its cumulative sums are formed in double, in index
+ * order.  DRS_ERR_ARG: null pointer, eps outside [0, 1], nbins / history as above; DRS_ERR_SHAPE: B < 1. */
+DRS_API int drs_timestep_draw(const double* bins, int nbins, int history, const float* u1, const float* u2, int B, int T,
+                              double eps_uniform, int64_t* t, float* sample_w, drs_stream_t stream);
+
 /* Multi-tensor exponential moving average of the parameters, ONE launch for all tensors:
  *   mode 0:  ema[i] = ema[i] * beta + (1 - beta) * cur[i]   (fp32; `1 - beta` is formed in double and rounded to fp32, the
  *            two products and the sum are rounded separately - reference EMA.update_average, UNet_model_superres.py:25-30,
