@@ -329,7 +329,7 @@ def launch(args):
     import os
 
     from .colorfix import cli_color_fix
-    from .train_diffusion_superres import cli_sampling_steps
+    from .cli import cli_sampling_steps
     device = args.device
     task = getattr(args, "task", "superres")
     if args.UNet_type.lower() != "residual attention unet":
@@ -387,7 +387,7 @@ def build_arg_parser():
     import argparse
 
     from .colorfix import add_color_fix_args
-    from .train_diffusion_superres import add_sampling_args, add_solver_args
+    from .cli import add_sampling_args, add_solver_args
     p = argparse.ArgumentParser(description=" ")
     p.add_argument("--noise_schedule", type=str, default="cosine")
     p.add_argument("--snapshot_name", type=str, default="snapshot.pt")

@@ -1,0 +1,158 @@
+"""The command-line pieces that the three trainers, `evaluate` and the aggregation tiler share: the reference's common flags,
+the sampling flags, and the flags of `Diffusion.train` that are not in the reference (`TRAIN_FLAGS`: one table, from which the
+parsers, the defaults and the keyword arguments of `train` are all read)."""
+import argparse
+
+from .sampling import sampling_plan
+
+
+def str2bool(v):
+    return v.lower() in ("yes", "true", "t", "1")
+
+
+def base_arg_parser():
+    """The reference's flags that all three trainers have, verbatim (:703-724), and the DDIM flags (`add_sampling_args`)."""
+    p = argparse.ArgumentParser(description=" ")
+    p.add_argument("--epochs", type=int, default=501)
+    p.add_argument("--batch_size", type=int, default=32)
+    p.add_argument("--image_size", type=int)
+    p.add_argument("--lr", type=float, default=3e-4)
+    p.add_argument("--check_preds_epoch", type=int, default=20)
+    p.add_argument("--noise_schedule", type=str, default="cosine")
+    p.add_argument("--snapshot_name", type=str, default="snapshot.pt")
+    p.add_argument("--model_name", type=str)
+    p.add_argument("--noise_steps", type=int, default=200)
+    p.add_argument("--patience", type=int, default=10)
+    p.add_argument("--dataset_path", type=str, default=None)
+    p.add_argument("--generate_video", type=str2bool, nargs="?", const=True, default=False)
+    p.add_argument("--loss", type=str)
+    p.add_argument("--UNet_type", type=str, default="Residual Attention UNet")
+    p.add_argument("--multiple_gpus", type=str2bool, nargs="?", const=True, default=False)
+    p.add_argument("--ema_smoothing", type=str2bool, nargs="?", const=True, default=False)
+    add_sampling_args(p)
+    return p
+
+
+def add_sampling_args(p):
+    """The DDIM flags of the final sampling (not in the reference): none = the reference's ancestral chain."""
+    p.add_argument("--sampling_steps", type=int, default=None,
+                   help="sample with DDIM over this many timesteps (1 .. noise_steps - 1); default: the full ancestral chain")
+    p.add_argument("--eta", type=float, default=0.0, help="DDIM eta: 0 deterministic, 1 DDPM-like (with --sampling_steps)")
+
+
+def add_solver_args(p):
+    """--solver / --spacing for the command lines that take them next to --sampling_steps (`cli_sampling_steps`)."""
+    p.add_argument("--solver", type=str, choices=("ddim", "dpmpp_2m"), default="ddim",
+                   help="how the --sampling_steps steps are taken: ddim, or dpmpp_2m (DPM-Solver++(2M): second order, eta 0)")
+    p.add_argument("--spacing", type=str, choices=("uniform", "logsnr"), default=None,
+                   help="where the --sampling_steps levels lie: uniform in t or uniform in logSNR; default: uniform for ddim, "
+                        "logsnr for dpmpp_2m")
+    return p
+
+
+def cli_sampling_steps(args):
+    """The `sampling_steps` argument of a command line: --sampling_steps, as a `sampling_plan` when --solver / --spacing say more."""
+    solver, spacing = getattr(args, "solver", "ddim"), getattr(args, "spacing", None)
+    steps = getattr(args, "sampling_steps", None)
+    return steps if solver == "ddim" and spacing is None else sampling_plan(steps, solver, spacing)
+
+
+def add_bsr_args(p):
+    """--bsr_kind / --bsr_seed of the command lines that build the BSRGAN feed (not in the reference; `make_superres_feeds`)."""
+    p.add_argument("--bsr_kind", type=str, choices=("plus", "soft"), default="plus",
+                   help="with --Degradation_type BSRGAN: plus (degradation_bsrgan_plus: USM, two rounds of blur / resize / noise, "
+                        "JPEG) or soft (blur, resize, noise once)")
+    p.add_argument("--bsr_seed", type=int, default=0, help="with --Degradation_type BSRGAN: seed of the recipes and the noise")
+    return p
+
+
+# -- the flags of `Diffusion.train` that are not in the reference ----------------------------------------------------------------
+# {group: {keyword of `train`: the `add_argument` keywords of --<keyword>}}, in the order --help lists them.  A new group is a new
+# entry here and, if its values need checking, in `check_train_args`.
+TRAIN_FLAGS = {
+    "optim": {  # optimizer / schedule / resume (optim.py)
+        "weight_decay": dict(type=float, default=0.0, help="decoupled (AdamW) weight decay; 0 = the reference's Adam"),
+        "max_grad_norm": dict(type=float, default=None,
+                              help="clip the global gradient norm to this value; steps with non-finite gradients are skipped"),
+        "lr_schedule": dict(type=str, choices=("constant", "cosine"), default="constant",
+                            help="after --warmup_steps: stay at --lr, or half a cosine down to --lr_min at the last step"),
+        "warmup_steps": dict(type=int, default=0, help="optimizer steps of linear learning-rate warm-up"),
+        "lr_min": dict(type=float, default=0.0, help="final learning rate of --lr_schedule cosine"),
+        "save_train_state": dict(
+            type=str2bool, nargs="?", const=True, default=False,
+            help="write train_state.pt (optimizer, raw weights under EMA, schedule, early-stopping and RNG state) beside "
+                 "every snapshot, and continue from both when they exist.  Not built: gradient accumulation, loss scaling, "
+                 "the crop / BSRGAN feeds' own generators, per-rank files (rank 0 writes, every rank reads)"),
+    },
+    "objective": {  # the training objective (losses.py)
+        "loss_weighting": dict(type=str, choices=("none", "min_snr"), default="none",
+                               help="min_snr: weight every image's loss with min(1, --min_snr_gamma / SNR_t); none = the "
+                                    "reference's loss"),
+        "min_snr_gamma": dict(type=float, default=5.0, help="gamma of --loss_weighting min_snr"),
+        "timestep_sampling": dict(
+            type=str, choices=("uniform", "loss_aware"), default="uniform",
+            help="loss_aware: draw t on the device in proportion to the recent losses of its timestep bin, with the "
+                 "importance weight that keeps the loss an estimate of the uniform mean; uses 16 bins when --loss_bins "
+                 "is 0 and consumes the device generator instead of the CPU one"),
+        "loss_bins": dict(type=int, default=0,
+                          help="keep and print the mean loss per timestep bin (N bins, 2 .. 64 and at most noise_steps / 2; "
+                               "lowest-noise bin first), one more line per phase and epoch; 0 = off.  Not built: bins shared "
+                               "across ranks, weighting of the perceptual loss"),
+    },
+}
+OPTIM_DEFAULTS = {k: kw["default"] for k, kw in TRAIN_FLAGS["optim"].items()}
+OBJECTIVE_DEFAULTS = {k: kw["default"] for k, kw in TRAIN_FLAGS["objective"].items()}
+
+
+def _add_group(p, group):
+    for name, kw in TRAIN_FLAGS[group].items():
+        p.add_argument("--" + name, **kw)
+    return p
+
+
+def add_optim_args(p):
+    return _add_group(p, "optim")
+
+
+def add_objective_args(p):
+    return _add_group(p, "objective")
+
+
+def add_train_args(p):
+    """Every group of `TRAIN_FLAGS` on the parser of a trainer's command line."""
+    for group in TRAIN_FLAGS:
+        _add_group(p, group)
+    return p
+
+
+def check_optim_args(p, args):
+    if args.weight_decay < 0 or args.lr_min < 0 or args.warmup_steps < 0:
+        p.error("--weight_decay, --lr_min and --warmup_steps must be >= 0")
+    if args.max_grad_norm is not None and not args.max_grad_norm > 0:
+        p.error("--max_grad_norm must be > 0")
+    return args
+
+
+def check_objective_args(p, args):
+    if args.loss_bins < 0 or not args.min_snr_gamma > 0:
+        p.error("--loss_bins must be >= 0 and --min_snr_gamma > 0")
+    return args
+
+
+def check_train_args(p, args):
+    """`p.error` for a value of `add_train_args`' flags that no run takes; returns `args`."""
+    check_optim_args(p, args)
+    return check_objective_args(p, args)
+
+
+def optim_train_kwargs(args):
+    return {k: getattr(args, k, v) for k, v in OPTIM_DEFAULTS.items()}
+
+
+def objective_train_kwargs(args):
+    return {k: getattr(args, k, v) for k, v in OBJECTIVE_DEFAULTS.items()}
+
+
+def train_kwargs(args):
+    """`add_train_args`' flags as keyword arguments of `Diffusion.train` (a namespace without them: the defaults)."""
+    return {**optim_train_kwargs(args), **objective_train_kwargs(args)}

@@ -28,10 +28,12 @@ import os
 
 import torch
 
+from .cli import add_bsr_args, add_solver_args, cli_sampling_steps
 from .colorfix import add_color_fix_args, cli_color_fix
+from .launcher import launch_device
 from .sampling import plan_of
-from .train_diffusion_superres import (METRIC_FORMATS, Diffusion, add_bsr_args, add_solver_args, build_arg_parser, cli_sampling_steps,
-                                       launch_device, make_superres_feeds)
+from .superres_feeds import make_superres_feeds
+from .train_diffusion_superres import METRIC_FORMATS, Diffusion, build_arg_parser
 from .UNet_model_superres import Residual_Attention_UNet_superres
 
 

@@ -4,8 +4,8 @@ kernels: class-conditional DDPM with classifier-free guidance.
 Overrides what differs from the super-resolution Diffusion it derives from: no conditioning image, the loader yields
 (img, label), 10% of the training steps drop the label (:393-394), and the model call of `sample` is a conditional and
 (for cfg_scale > 0) an unconditional prediction per step, combined with torch.lerp (:236-239) by the base class's reverse
-chain.  `launch` and the CLI are that module's launcher pieces and parser base around this file's datasets (the reference's
-class-folder tree through the device feed of feeds.py, or seeded images), model and flag.
+chain.  `launch` and the CLI are the shared launcher pieces (launcher.py) and parser base and train flags (cli.py) around this
+file's datasets (the reference's class-folder tree through the device feed of feeds.py, or seeded images), model and flag.
 """
 import os
 
@@ -14,10 +14,11 @@ import torch
 import torch.nn as nn
 
 from .. import dist as drs_dist
+from ..augment import add_augment_args
+from ..cli import add_train_args, base_arg_parser, check_objective_args, check_train_args  # noqa: F401 - re-exported
+from ..launcher import launch_device, make_loaders, save_final_samples, train_model
 from ..sampling import _repeat_members, asks_for_known_pixels, check_inpaint_args, check_sampling_args
-from ..train_diffusion_superres import (Diffusion as _SuperresDiffusion, add_objective_args, add_optim_args, base_arg_parser,
-                                        check_objective_args, check_optim_args, launch_device, make_loaders,
-                                        save_final_samples, train_model)
+from ..train_diffusion_superres import Diffusion as _SuperresDiffusion
 from .UNet_model_generation import Residual_Attention_UNet_generation
 
 
@@ -76,9 +77,8 @@ class Diffusion(_SuperresDiffusion):
                 known=None, known_mask=None, resample=1, jump=1):
         check_sampling_args(self.noise_steps, sampling_steps, eta)
         check_inpaint_args((n, input_channels, self.image_size, self.image_size), known, known_mask, resample, jump)
-        net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
         if target_class is not None:
-            ncls = getattr(net, "num_classes", None)
+            ncls = getattr(self._engine_net(model), "num_classes", None)
             if not target_class.is_cuda and ncls and target_class.numel() and int(target_class.max()) >= int(ncls):
                 raise IndexError(f"target_class {int(target_class.max())} out of range for num_classes={ncls}")
             target_class = target_class.to(self.device)
@@ -178,15 +178,16 @@ def build_arg_parser():
 
 
 def train_main_parser():
-    """`build_arg_parser` and the crop / augmentation flags (augment.add_augment_args) and the
-    optimizer / resume flags (add_optim_args) and the objective flags (add_objective_args): what `main` parses."""
-    from ..augment import add_augment_args
-    return add_objective_args(add_optim_args(add_augment_args(build_arg_parser())))
+    """`build_arg_parser`, the crop / augmentation flags (augment.add_augment_args) and the optimizer / resume and objective
+    flags (cli.add_train_args): what `main` parses."""
+    p = build_arg_parser()
+    add_augment_args(p)
+    return add_train_args(p)
 
 
 def main(argv=None):
     parser = train_main_parser()
-    args = check_objective_args(parser, check_optim_args(parser, parser.parse_args(argv)))
+    args = check_train_args(parser, parser.parse_args(argv))
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     launch(args)
 

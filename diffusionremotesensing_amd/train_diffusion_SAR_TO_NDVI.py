@@ -4,8 +4,8 @@ Same arithmetic as the super-resolution Diffusion (the reference's two files dif
 `model(x_t, t, SAR_img)`, and in the absence of magnification / degradation arguments), so this class reuses the
 schedules, q-sample, reverse chain, snapshots and training loop of `train_diffusion_superres.Diffusion` and overrides what
 differs: constructor (:80-123), the conditioning image and model call of `sample` (:204-249) and the model call of the loop
-bodies (:373-388, :455-470).  `launch` and the CLI are that module's launcher pieces and parser base around this file's
-dataset, model and two flags.
+bodies (:373-388, :455-470).  `launch` and the CLI are the shared launcher pieces (launcher.py) and parser base and train flags
+(cli.py) around this file's dataset, model and two flags.
 """
 import os
 
@@ -13,10 +13,11 @@ import torch
 import torch.nn as nn
 
 from . import dist as drs_dist
+from .augment import add_augment_args
+from .cli import add_train_args, base_arg_parser, check_objective_args, check_train_args  # noqa: F401 - re-exported
+from .launcher import launch_device, make_loaders, save_final_samples, train_model
 from .sampling import _repeat_members, asks_for_known_pixels, check_inpaint_args, check_sampling_args
-from .train_diffusion_superres import (Diffusion as _SuperresDiffusion, add_objective_args, add_optim_args, base_arg_parser,
-                                       check_objective_args, check_optim_args, launch_device, make_loaders,
-                                       save_final_samples, train_model)
+from .train_diffusion_superres import Diffusion as _SuperresDiffusion
 from .UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
 
 
@@ -188,15 +189,16 @@ def train_arg_parser():
 
 
 def train_main_parser():
-    """`train_arg_parser` and the crop / augmentation flags (augment.add_augment_args) and the
-    optimizer / resume flags (add_optim_args) and the objective flags (add_objective_args): what `main` parses."""
-    from .augment import add_augment_args
-    return add_objective_args(add_optim_args(add_augment_args(train_arg_parser())))
+    """`train_arg_parser`, the crop / augmentation flags (augment.add_augment_args) and the optimizer / resume and objective
+    flags (cli.add_train_args): what `main` parses."""
+    p = train_arg_parser()
+    add_augment_args(p)
+    return add_train_args(p)
 
 
 def main(argv=None):
     parser = train_main_parser()
-    args = check_objective_args(parser, check_optim_args(parser, parser.parse_args(argv)))
+    args = check_train_args(parser, parser.parse_args(argv))
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     launch(args)
 

@@ -11,6 +11,10 @@ Deliberately different (documented in DESIGN.md):
     the per-step timestep tensor lives on the device instead of being rebuilt on the host (:235);
   * multi-GPU uses one flat-buffer RCCL all-reduce per step (`dist.allreduce_gradients`) instead of
     DistributedDataParallel(find_unused_parameters=True) (:658).
+
+`Diffusion.train` is an epoch loop over named steps that share one `TrainRun` (`Diffusion.train_state`).  What the reference
+keeps in this file besides the class lives next to it and is re-exported here under its old names: the flag helpers in cli.py,
+the launcher pieces the three trainers share in launcher.py, the dataset and the feeds in superres_feeds.py.
 """
 import copy
 import os
@@ -21,12 +25,19 @@ import torch.nn as nn
 
 from . import dist as drs_dist
 from . import hip_ops
+from .augment import add_augment_args
+# (the names this module does not use itself are re-exported: they lived here before cli.py, launcher.py and superres_feeds.py)
+from .cli import (OBJECTIVE_DEFAULTS, OPTIM_DEFAULTS, add_bsr_args, add_objective_args, add_optim_args,  # noqa: F401
+                  add_sampling_args, add_solver_args, add_train_args, base_arg_parser, check_objective_args, check_optim_args,
+                  check_train_args, cli_sampling_steps, objective_train_kwargs, optim_train_kwargs, str2bool)
+from .launcher import launch_device, make_loaders, save_final_samples, train_model  # noqa: F401
 from .losses import DiffusionLoss, LossAwareSampler, LossBins, min_snr_weights
 from .optim import FusedAdam, FusedAdamW, WarmupCosine
 from .sampling import (CHAIN_CHECK_EVERY, _is_int, _repeat_members, asks_for_known_pixels,  # noqa: F401 - re-exported
                        check_ensemble_args, check_inpaint_args, check_sampling_args, check_solver_known, ddim_chain_noise,
                        ddim_timesteps, ensemble_chunks, inpaint_schedule, known_tensors, run_reverse_chain, sample_chain,
                        sampling_plan)
+from .superres_feeds import SyntheticSuperresDataset, make_superres_feeds  # noqa: F401
 from .UNet_model_superres import EMA, Residual_Attention_UNet_superres
 
 _DEGRADATIONS = ("downblur", "bsrgan", "downblurnoise")
@@ -44,6 +55,23 @@ def format_scores(scores):
             parts.append(name + " " + " ".join(f"{METRIC_FORMATS[k][0]} {METRIC_FORMATS[k][1].format(v)}"
                                                for k, v in scores[name].items()))
     return " | ".join(parts)
+
+
+class TrainRun:
+    """What one `Diffusion.train` call holds besides the weights, kept as `Diffusion.train_state` (`Diffusion._begin_run` makes
+    it): the parts `train_step` is called with, the objective behind `loss_function` (None for a default run: then it is torch's
+    module), the flags that steer the loop, and early stopping's two counters - the only copy of them, which `train_state.pt`
+    is written from and read into."""
+
+    def __init__(self, model, loss, optimizer, scheduler, ema, ema_model, objective, loss_function, clipping, save_train_state):
+        self.model, self.loss = model, loss  # the network that is trained; the loss's name in the report lines
+        self.optimizer, self.scheduler, self.ema, self.ema_model = optimizer, scheduler, ema, ema_model
+        self.saved = ema_model if ema_model is not None else model  # the network that is validated, scored and snapshotted
+        self.objective, self.loss_function = objective, loss_function
+        self.loss_bins = objective.bins if objective is not None else None
+        self.clipping, self.save_train_state = clipping, save_train_state
+        self.best_loss, self.epochs_without_improving = float("inf"), 0
+        self.skipped_before = 0  # the optimizer's count of skipped steps at the end of the last epoch (it is new: none yet)
 
 
 class Diffusion:
@@ -193,10 +221,9 @@ class Diffusion:
         `hist=` and `t_q=`, as `sampling.sample_chain` says.  The chain is `sampling.sample_chain`; this method adds the eval
         mode around it and the video."""
         check_solver_known(sampling_steps, known, known_mask)
-        net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
         model.eval()
         frames = [] if generate_video else None
-        x = sample_chain(self, net.hip_engine(), shape, predict, table_rows=table_rows, noise_source=noise_source,
+        x = sample_chain(self, self._engine_net(model).hip_engine(), shape, predict, table_rows=table_rows, noise_source=noise_source,
                          sampling_steps=sampling_steps, eta=eta, cfg_scale=cfg_scale, update=update, known=known,
                          known_mask=known_mask, resample=resample, jump=jump, frames=frames)
         if generate_video:
@@ -340,9 +367,17 @@ class Diffusion:
         return out
 
     # -- snapshots (reference :257-308) -----------------------------------------------------------
+    def _unwrapped(self, model):
+        """The network whose state_dict is saved and loaded: under --multiple_gpus a wrapper's `.module`."""
+        return model.module if self.multiple_gpus and hasattr(model, "module") else model
+
+    @staticmethod
+    def _engine_net(model):
+        """The network that owns the HIP engine: a wrapper's `.module`, unless the wrapper answers `hip_engine` itself."""
+        return model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
+
     def _save_snapshot(self, epoch, model):
-        net = model.module if self.multiple_gpus and hasattr(model, "module") else model
-        snapshot = {"MODEL_STATE": net.state_dict(), "EPOCHS_RUN": epoch}
+        snapshot = {"MODEL_STATE": self._unwrapped(model).state_dict(), "EPOCHS_RUN": epoch}
         torch.save(snapshot, self.snapshot_path)
         print(f"Epoch {epoch} | Training snapshot saved at {self.snapshot_path}")
 
@@ -351,7 +386,7 @@ class Diffusion:
             from collections import OrderedDict
             snapshot = torch.load(self.snapshot_path, map_location="cpu")
             state = OrderedDict((k.replace("module.", ""), v) for k, v in snapshot["MODEL_STATE"].items())
-            net = self.model.module if hasattr(self.model, "module") else self.model
+            net = self._unwrapped(self.model)
             net.load_state_dict(state)
             net.to(self.device)
         else:
@@ -364,43 +399,40 @@ class Diffusion:
     def train_state_path(self):
         return os.path.join(os.path.dirname(self.snapshot_path), "train_state.pt")
 
-    def _save_train_state(self, epoch, model, state):
+    def _save_train_state(self, epoch, run):
         """`train_state.pt` beside the snapshot (whose two keys stay what they are): everything else `train` needs to go on at
         epoch + 1 as if it had not stopped.  With EMA the snapshot holds the averaged copy, so the raw weights are here.  Not
         saved: the private generators of the crop / BSRGAN feeds.  One file, written by rank 0 and read by every rank."""
-        net = model.module if self.multiple_gpus and hasattr(model, "module") else model
-        ts = {"OPTIMIZER_STATE": state.optimizer.state_dict(),
-              "RAW_MODEL_STATE": net.state_dict() if state.ema is not None else None,
-              "EMA_STEP": state.ema.step if state.ema is not None else None,
-              "LR_SCHEDULE": state.scheduler.state_dict() if state.scheduler is not None else None,
-              "BEST_LOSS": state.best_loss, "EPOCHS_WITHOUT_IMPROVING": state.epochs_without_improving,
+        ts = {"OPTIMIZER_STATE": run.optimizer.state_dict(),
+              "RAW_MODEL_STATE": self._unwrapped(run.model).state_dict() if run.ema is not None else None,
+              "EMA_STEP": run.ema.step if run.ema is not None else None,
+              "LR_SCHEDULE": run.scheduler.state_dict() if run.scheduler is not None else None,
+              "BEST_LOSS": run.best_loss, "EPOCHS_WITHOUT_IMPROVING": run.epochs_without_improving,
               "NEXT_EPOCH": epoch + 1, "CPU_RNG_STATE": torch.get_rng_state(),
               "DEVICE_RNG_STATE": torch.cuda.get_rng_state(self.device)}
-        if getattr(state, "loss_bins", None) is not None:  # (a run without --loss_bins / loss_aware writes the file it always wrote)
-            ts["LOSS_BINS"] = state.loss_bins.state_dict()
+        if run.loss_bins is not None:  # (a run without --loss_bins / loss_aware writes the file it always wrote)
+            ts["LOSS_BINS"] = run.loss_bins.state_dict()
         torch.save(ts, self.train_state_path())
 
-    def _load_train_state(self, model, state):
+    def _load_train_state(self, run):
         """Restores `_save_train_state`'s file into a run that `__init__` has already given the snapshot's weights: those stay
-        in the EMA copy, the raw weights go into `model`, and `epochs_run` becomes NEXT_EPOCH.  A file that does not fit this
-        model or this run's options raises ValueError."""
+        in the EMA copy, the raw weights go into `run.model`, and `epochs_run` becomes NEXT_EPOCH.  A file that does not fit
+        this model or this run's options raises ValueError."""
         ts = torch.load(self.train_state_path(), map_location="cpu")
-        if (ts["RAW_MODEL_STATE"] is None) != (state.ema is None) or (ts["LR_SCHEDULE"] is None) != (state.scheduler is None):
+        if (ts["RAW_MODEL_STATE"] is None) != (run.ema is None) or (ts["LR_SCHEDULE"] is None) != (run.scheduler is None):
             raise ValueError(f"{self.train_state_path()} was written with other --ema_smoothing / --lr_schedule options")
-        bins = getattr(state, "loss_bins", None)
-        if ("LOSS_BINS" in ts) != (bins is not None):
+        if ("LOSS_BINS" in ts) != (run.loss_bins is not None):
             raise ValueError(f"{self.train_state_path()} was written with other --loss_bins / --timestep_sampling options")
-        if bins is not None:
-            bins.load_state_dict(ts["LOSS_BINS"])  # (other T / bin count: ValueError)
-        net = model.module if self.multiple_gpus and hasattr(model, "module") else model
+        if run.loss_bins is not None:
+            run.loss_bins.load_state_dict(ts["LOSS_BINS"])  # (other T / bin count: ValueError)
         # (another parameter count or other shapes: ValueError from FusedAdamW.load_state_dict, the first thing loaded)
-        state.optimizer.load_state_dict(ts["OPTIMIZER_STATE"])
-        if state.ema is not None:
-            net.load_state_dict(ts["RAW_MODEL_STATE"])
-            state.ema.step = ts["EMA_STEP"]
-        if state.scheduler is not None:
-            state.scheduler.load_state_dict(ts["LR_SCHEDULE"])
-        state.best_loss, state.epochs_without_improving = ts["BEST_LOSS"], ts["EPOCHS_WITHOUT_IMPROVING"]
+        run.optimizer.load_state_dict(ts["OPTIMIZER_STATE"])
+        if run.ema is not None:
+            self._unwrapped(run.model).load_state_dict(ts["RAW_MODEL_STATE"])
+            run.ema.step = ts["EMA_STEP"]
+        if run.scheduler is not None:
+            run.scheduler.load_state_dict(ts["LR_SCHEDULE"])
+        run.best_loss, run.epochs_without_improving = ts["BEST_LOSS"], ts["EPOCHS_WITHOUT_IMPROVING"]
         self.epochs_run = ts["NEXT_EPOCH"]
         torch.set_rng_state(ts["CPU_RNG_STATE"])
         torch.cuda.set_rng_state(ts["DEVICE_RNG_STATE"], self.device)
@@ -528,6 +560,31 @@ class Diffusion:
         `timestep_sampling="loss_aware"` draws t on the device from those bins' recent losses (16 bins when `loss_bins` is 0)
         and so consumes the DEVICE generator instead of the CPU one.  Any of them routes `train_step` and the validation loop
         through `losses.DiffusionLoss`; validation keeps its uniform CPU draw of t and has bins of its own."""
+        run = self._begin_run(
+            loss, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule,
+            warmup_steps=warmup_steps, lr_min=lr_min, total_steps=max(len(train_loader), 1) * epochs,
+            save_train_state=save_train_state, loss_weighting=loss_weighting, min_snr_gamma=min_snr_gamma,
+            timestep_sampling=timestep_sampling, loss_bins=loss_bins)
+        eval_args = {"n_images": eval_metrics, "sampling_steps": sampling_steps, "eta": eta} if eval_metrics else None
+        for epoch in range(self.epochs_run, epochs):
+            checking = epoch % check_preds_epoch == 0
+            train_loss, norm_sum = self._train_epoch(run, epoch, train_loader)
+            self._report_train_epoch(run, epoch, train_loss, norm_sum, len(train_loader))
+            if val_loader is None:
+                if checking and self._is_rank0():
+                    self._save(run, epoch)
+            else:
+                val_loss = self._validation_epoch(run, val_loader)
+                self._report_validation(run, epoch, val_loss, val_loader, eval_args if checking else None)
+                self._keep_if_best(run, epoch, val_loss)
+                if self.early_stopping(patience, run.epochs_without_improving):
+                    break
+            print("Epochs without improving: ", run.epochs_without_improving)
+
+    def _begin_run(self, loss, *, lr, weight_decay, max_grad_norm, lr_schedule, warmup_steps, lr_min, total_steps,
+                   save_train_state, loss_weighting, min_snr_gamma, timestep_sampling, loss_bins):
+        """The `TrainRun` of one `train` call, kept as `self.train_state`: optimizer, schedule, EMA copy and objective from its
+        arguments (and `self.timestep_sampler`), continued from `train_state.pt` when `save_train_state` finds one."""
         model = self.model
         if lr_schedule not in ("constant", "cosine"):
             raise ValueError("lr_schedule must be constant or cosine")
@@ -538,267 +595,104 @@ class Diffusion:
             optimizer = FusedAdam(model.parameters(), lr=lr)  # torch.optim.Adam's math, one launch (optim.py)
         scheduler = None
         if lr_schedule == "cosine" or warmup_steps:
-            scheduler = WarmupCosine(lr, warmup_steps, max(len(train_loader), 1) * epochs, lr_min, lr_schedule)
+            scheduler = WarmupCosine(lr, warmup_steps, total_steps, lr_min, lr_schedule)
         ema = ema_model = None
         if self.ema_smoothing:
             ema = EMA(beta=0.995)
             ema_model = copy.deepcopy(model).eval().requires_grad_(False)
         loss_function = objective.train if objective is not None else self._loss_function(loss, self.device)
         self.timestep_sampler = objective.sampler if objective is not None else None
-        bins = objective.bins if objective is not None else None
-        epochs_without_improving = 0
-        best_loss = float("inf")
-        saved = ema_model if self.ema_smoothing else model
-        # what a run holds besides the weights; `save` keeps best_loss / epochs_without_improving current
-        state = self.train_state = types.SimpleNamespace(optimizer=optimizer, scheduler=scheduler, ema=ema, ema_model=ema_model,
-                                                         best_loss=best_loss, epochs_without_improving=0, loss_function=loss_function,
-                                                         loss_bins=bins)
+        run = self.train_state = TrainRun(model, loss, optimizer, scheduler, ema, ema_model, objective, loss_function,
+                                          clipping=max_grad_norm is not None, save_train_state=save_train_state)
         if save_train_state and os.path.exists(self.snapshot_path) and os.path.exists(self.train_state_path()):
-            self._load_train_state(model, state)
-            best_loss, epochs_without_improving = state.best_loss, state.epochs_without_improving
-        clipping = max_grad_norm is not None
-        skipped_before = optimizer.skipped_steps() if isinstance(optimizer, FusedAdamW) else 0
+            self._load_train_state(run)
+        return run
 
-        def save(epoch):
-            self._save_snapshot(epoch, saved)
-            if save_train_state:
-                state.best_loss, state.epochs_without_improving = best_loss, epochs_without_improving
-                self._save_train_state(epoch, model, state)
+    def _save(self, run, epoch):
+        self._save_snapshot(epoch, run.saved)
+        if run.save_train_state:
+            self._save_train_state(epoch, run)
 
-        for epoch in range(self.epochs_run, epochs):
-            if self.multiple_gpus and hasattr(train_loader, "sampler") and hasattr(train_loader.sampler, "set_epoch"):
-                train_loader.sampler.set_epoch(epoch)
-            running_train_loss = torch.zeros((), device=self.device)  # accumulated on device: no per-step sync
-            running_norm = torch.zeros((), device=self.device)  # (pre-clip gradient norms of the steps that were not skipped)
-            model.train()
-            for lr_img, hr_img in train_loader:
-                running_train_loss += self.train_step(model, optimizer, loss_function, lr_img, hr_img, ema,
-                                                      ema_model, scheduler).detach()
-                if clipping:
-                    running_norm += torch.nan_to_num(optimizer.last_grad_norm(), nan=0.0, posinf=0.0, neginf=0.0)
-            running_train_loss = running_train_loss.item() / max(len(train_loader), 1)
-            # (the .item() above is the epoch's synchronisation point: a wave of the wave-specialised kernels that gave up on a
-            #  counter during this epoch's forwards or backwards - csrc/sp_sync.h - is reported here, not trained on)
-            net = model.module if hasattr(model, "module") and not hasattr(model, "hip_engine") else model
-            if hasattr(net, "hip_engine"):
-                net.hip_engine().check_faults()
-            more = ""
-            if isinstance(optimizer, FusedAdamW):
-                skipped = optimizer.skipped_steps() - skipped_before
-                skipped_before += skipped
-                if clipping:
-                    more += f" | mean grad norm {running_norm.item() / max(len(train_loader) - skipped, 1)}"
-                if skipped:
-                    more += f" | skipped steps {skipped}"
-            print(f"Epoch {epoch}: Running Train ({loss}) {running_train_loss}" + more)
-            if objective is not None:
-                objective.train.check_faults()
-            if bins is not None:
-                print(f"Epoch {epoch}: Train loss by timestep bin (low noise first) " + self._bins_line(bins.read_and_reset()))
+    def _train_epoch(self, run, epoch, train_loader):
+        """One pass over `train_loader` through `train_step`: (mean loss, the sum of the pre-clip gradient norms of the steps
+        that were not skipped - a device tensor, zero without clipping)."""
+        if self.multiple_gpus and hasattr(train_loader, "sampler") and hasattr(train_loader.sampler, "set_epoch"):
+            train_loader.sampler.set_epoch(epoch)
+        running_train_loss = torch.zeros((), device=self.device)  # accumulated on device: no per-step sync
+        running_norm = torch.zeros((), device=self.device)
+        run.model.train()
+        for lr_img, hr_img in train_loader:
+            running_train_loss += self.train_step(run.model, run.optimizer, run.loss_function, lr_img, hr_img, run.ema,
+                                                  run.ema_model, run.scheduler).detach()
+            if run.clipping:
+                running_norm += torch.nan_to_num(run.optimizer.last_grad_norm(), nan=0.0, posinf=0.0, neginf=0.0)
+        # (this .item() is the epoch's synchronisation point: a wave of the wave-specialised kernels that gave up on a counter
+        #  during this epoch's forwards or backwards - csrc/sp_sync.h - is reported right after it, not trained on)
+        return running_train_loss.item() / max(len(train_loader), 1), running_norm
 
-            if self._is_rank0() and epoch % check_preds_epoch == 0 and val_loader is None:
-                save(epoch)
+    def _report_train_epoch(self, run, epoch, train_loss, norm_sum, steps):
+        """The engine's fault check, then the epoch's train lines: the loss (with the clipping figures), the fused loss's own
+        fault check, the loss bins."""
+        net = self._engine_net(run.model)
+        if hasattr(net, "hip_engine"):
+            net.hip_engine().check_faults()
+        print(f"Epoch {epoch}: Running Train ({run.loss}) {train_loss}" + self._clipping_report(run, norm_sum, steps))
+        if run.objective is not None:
+            run.objective.train.check_faults()
+        if run.loss_bins is not None:
+            print(f"Epoch {epoch}: Train loss by timestep bin (low noise first) "
+                  + self._bins_line(run.loss_bins.read_and_reset()))
 
-            if val_loader is not None:
-                running_val_loss = torch.zeros((), device=self.device)
-                with torch.no_grad():
-                    model.eval()
-                    for batch in val_loader:
-                        lr_img, hr_img = self._split_batch(batch)
-                        t = self.sample_timesteps(hr_img.shape[0]).to(self.device)
-                        x_t, noise = self.noise_images(hr_img, t)
-                        net = ema_model if self.ema_smoothing else model
-                        predicted_noise = self._predict(net, x_t, t, self._train_cond(lr_img))
-                        if objective is not None:  # the same table through the no-grad path; uniform t, bins of its own
-                            running_val_loss += objective.val(predicted_noise, noise, t)
-                        else:
-                            running_val_loss += loss_function(predicted_noise, noise)
-                running_val_loss = running_val_loss.item() / max(len(val_loader), 1)
-                if self.multiple_gpus:
-                    # the reference decides per rank on its own validation shard (:492-510, quirk Q9); with a collective in
-                    # every training step the ranks must leave the loop together: one mean over ranks, same branch everywhere
-                    running_val_loss = drs_dist.allreduce_mean_scalar(running_val_loss)
-                print(f"Epoch {epoch}: Running Val loss ({loss}){running_val_loss}")
-                if bins is not None:
-                    print(f"Epoch {epoch}: Val loss by timestep bin (low noise first) "
-                          + self._bins_line(objective.val_bins.read_and_reset()))
-                if eval_metrics and epoch % check_preds_epoch == 0:
-                    scores = self.evaluate(saved, val_loader, n_images=eval_metrics, sampling_steps=sampling_steps, eta=eta)
-                    print(f"Epoch {epoch}: Val metrics on {scores['n']} images | " + format_scores(scores))
-                if running_val_loss < best_loss:
-                    best_loss = running_val_loss
-                    epochs_without_improving = 0
-                    if self._is_rank0():
-                        save(epoch)
+    @staticmethod
+    def _clipping_report(run, norm_sum, steps):
+        """` | mean grad norm ... | skipped steps ...` of an epoch of `steps` steps, as far as the run has them."""
+        if not isinstance(run.optimizer, FusedAdamW):
+            return ""
+        skipped = run.optimizer.skipped_steps() - run.skipped_before
+        run.skipped_before += skipped
+        more = f" | mean grad norm {norm_sum.item() / max(steps - skipped, 1)}" if run.clipping else ""
+        return more + (f" | skipped steps {skipped}" if skipped else "")
+
+    def _validation_epoch(self, run, val_loader):
+        """The mean loss of the network that would be saved over `val_loader`, with t from the uniform CPU draw; under
+        --multiple_gpus the mean over the ranks' means."""
+        running_val_loss = torch.zeros((), device=self.device)
+        with torch.no_grad():
+            run.model.eval()
+            for batch in val_loader:
+                lr_img, hr_img = self._split_batch(batch)
+                t = self.sample_timesteps(hr_img.shape[0]).to(self.device)
+                x_t, noise = self.noise_images(hr_img, t)
+                predicted_noise = self._predict(run.saved, x_t, t, self._train_cond(lr_img))
+                if run.objective is not None:  # the same table through the no-grad path; uniform t, bins of its own
+                    running_val_loss += run.objective.val(predicted_noise, noise, t)
                 else:
-                    epochs_without_improving += 1
-                if self.early_stopping(patience, epochs_without_improving):
-                    break
-            print("Epochs without improving: ", epochs_without_improving)
-        state.best_loss, state.epochs_without_improving = best_loss, epochs_without_improving
+                    running_val_loss += run.loss_function(predicted_noise, noise)
+        val_loss = running_val_loss.item() / max(len(val_loader), 1)
+        if self.multiple_gpus:
+            # the reference decides per rank on its own validation shard (:492-510, quirk Q9); with a collective in
+            # every training step the ranks must leave the loop together: one mean over ranks, same branch everywhere
+            val_loss = drs_dist.allreduce_mean_scalar(val_loss)
+        return val_loss
 
+    def _report_validation(self, run, epoch, val_loss, val_loader, eval_args):
+        """The epoch's validation lines: the loss, the loss bins, and - with `eval_args` - the image scores of `run.saved`."""
+        print(f"Epoch {epoch}: Running Val loss ({run.loss}){val_loss}")
+        if run.loss_bins is not None:
+            print(f"Epoch {epoch}: Val loss by timestep bin (low noise first) "
+                  + self._bins_line(run.objective.val_bins.read_and_reset()))
+        if eval_args is not None:
+            scores = self.evaluate(run.saved, val_loader, **eval_args)
+            print(f"Epoch {epoch}: Val metrics on {scores['n']} images | " + format_scores(scores))
 
-class SyntheticSuperresDataset(torch.utils.data.Dataset):
-    """Seeded Gaussian/uniform (lr, hr) patches with the shapes `get_data_superres` yields (reference
-    utils.py:93-166): the reference's image-folder datasets (PIL / torchvision) are outside the hot path and
-    BASELINE.json's configs are all "synthetic"."""
-
-    def __init__(self, length, channels, image_size, magnification_factor, seed=0):
-        from . import synthetic
-        s = image_size // magnification_factor
-        self.hr = synthetic.tensor_uniform("synthetic.hr", (length, channels, image_size, image_size), seed)
-        self.lr = synthetic.tensor_uniform("synthetic.lr", (length, channels, s, s), seed)
-
-    def __len__(self):
-        return self.hr.shape[0]
-
-    def __getitem__(self, i):
-        return self.lr[i], self.hr[i]
-
-
-def launch_device(args):
-    """The run directories and the device of a `launch`: RCCL process group + this rank's GPU with --multiple_gpus
-    (reference :586-590), the visible one otherwise."""
-    os.makedirs(args.snapshot_folder_path, exist_ok=True)
-    os.makedirs(os.path.join(os.curdir, "models_run", args.model_name, "results"), exist_ok=True)
-    if args.multiple_gpus:
-        drs_dist.init_process_group()  # RCCL ("nccl" backend on ROCm), env:// rendezvous like reference :586
-        gpu_id = int(os.environ["LOCAL_RANK"])
-        torch.cuda.set_device(gpu_id)
-        return gpu_id
-    if not torch.cuda.is_available():
-        raise RuntimeError("no ROCm device visible: this implementation has no CPU path")
-    return torch.device("cuda")
-
-
-def make_loaders(args, train_dataset, val_dataset):
-    """(train, val) DataLoaders of a dataset pair: one shard per rank with --multiple_gpus, shuffled otherwise."""
-    from torch.utils.data import DataLoader
-    from torch.utils.data.distributed import DistributedSampler
-
-    def loader(ds):
-        if args.multiple_gpus:
-            return DataLoader(ds, batch_size=args.batch_size, shuffle=False, sampler=DistributedSampler(ds))
-        return DataLoader(ds, batch_size=args.batch_size, shuffle=True)
-    return loader(train_dataset), loader(val_dataset)
-
-
-def train_model(args, diffusion_class, model, device, train_loader, val_loader, train_kwargs=None, **diffusion_kwargs):
-    """Same weights on every rank, `diffusion_class(...)` from the flags (a snapshot, if there is one, is loaded here),
-    the training run, and the end of the process group.  Returns the Diffusion."""
-    print("Num params: ", sum(p.numel() for p in model.parameters()))
-    if args.multiple_gpus:
-        drs_dist.broadcast_module(model)  # what the DDP constructor does in the reference (:658)
-    diffusion = diffusion_class(noise_schedule=args.noise_schedule, model=model,
-                                snapshot_path=os.path.join(args.snapshot_folder_path, args.snapshot_name),
-                                noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02, device=device,
-                                image_size=args.image_size, model_name=args.model_name, multiple_gpus=args.multiple_gpus,
-                                ema_smoothing=args.ema_smoothing, **diffusion_kwargs)
-    diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
-                    train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
-                    verbose=True, **optim_train_kwargs(args), **objective_train_kwargs(args), **(train_kwargs or {}))
-    if args.multiple_gpus:
-        drs_dist.destroy_process_group()
-    return diffusion
-
-
-def save_final_samples(args, sample, conditions, file_name):
-    """The final sampling of a `launch`: `sample(c, sampling_steps=, eta=)` for every c of `conditions` (the DDIM flags, or
-    the ancestral chain), concatenated into models_run/<model_name>/results/<file_name>."""
-    ddim = {"sampling_steps": getattr(args, "sampling_steps", None), "eta": getattr(args, "eta", 0.0)}
-    outs = [sample(c, **ddim) for c in conditions]
-    torch.save(torch.cat(outs).cpu(), os.path.join(os.getcwd(), "models_run", args.model_name, "results", file_name))
-
-
-def make_superres_feeds(args, device):
-    """(train feed, validation feed, the LR images the final sampling conditions on) of `--dataset_path`: the reference's
-    image folder or `synthetic[:N]` / `synthetic_u8[:N]` (see `launch`)."""
-    spec = str(args.dataset_path or "")
-    ch = args.inp_out_channels
-    r, wsz = (drs_dist.rank(), drs_dist.world_size()) if args.multiple_gpus else (0, 1)
-    device_feed = not spec.startswith("synthetic") or spec.startswith("synthetic_u8")
-    if device_feed:
-        # the reference's DownBlur feed (utils.get_data_superres: bicubic down-sampling + Gaussian blur per item with
-        # Pillow on the host) from a uint8 HR cache on the device, bit-exact (degradation.py); rank r owns every
-        # world-th image like DistributedSampler
-        from .degradation import DeviceSuperresFeed, load_image_folder_u8
-        # --scene_size P: the cache holds P x P scenes and every item is an --image_size window of one, cut on the device
-        # (augment.py); train feeds draw window and symmetry, validation feeds and the final sampling take the centre window
-        from .augment import feed_kwargs, scene_size
-        cache_size = scene_size(args)
-        deg = args.Degradation_type.lower()
-        gauss_noise = deg == "downblurnoise"  # (reference :612-616: Gauss_noise=True)
-        if deg == "bsrgan":
-            # the blind degradation, fresh for every batch on the device (bsr.py); rank r draws its own recipes; the validation
-            # feed starts from its seed at every epoch (the reference's frozen validation set)
-            from .bsr import DeviceBSRFeed
-            kind, seed = getattr(args, "bsr_kind", "plus"), getattr(args, "bsr_seed", 0)
-
-            def make_feed(u8, fixed=False):
-                return DeviceBSRFeed(u8.to(device), args.magnification_factor, args.batch_size, shuffle=not fixed, kind=kind,
-                                     seed=seed + (1 if fixed else 2 + r), fixed=fixed, **feed_kwargs(args, r, fixed))
-
-            def first_items(u8):  # the LR images of the final sampling: the first five training images under the fixed seed
-                feed = DeviceBSRFeed(u8.to(device), args.magnification_factor, 1, shuffle=False, kind=kind, seed=seed, fixed=True,
-                                     **feed_kwargs(args, fixed=True))
-                return [feed.item(i)[0] for i in range(u8.shape[0])]
+    def _keep_if_best(self, run, epoch, val_loss):
+        """Early stopping's bookkeeping, the one place that moves it: a new best validation loss is saved (by rank 0)."""
+        if val_loss < run.best_loss:
+            run.best_loss, run.epochs_without_improving = val_loss, 0
+            if self._is_rank0():
+                self._save(run, epoch)
         else:
-            radius = args.Blur_radius if args.Blur_radius == "random" else float(args.Blur_radius)
-
-            def make_feed(u8, fixed=False):
-                return DeviceSuperresFeed(u8.to(device), args.magnification_factor, radius, args.batch_size, shuffle=True,
-                                          Gauss_noise=gauss_noise, **feed_kwargs(args, r, fixed))
-
-            def first_items(u8, blur_radius):  # the LR images of the final sampling: the first training images' centre windows
-                from .degradation import add_reference_noise, downblur
-                if cache_size != args.image_size:
-                    from .augment import centre_items, crop_d4_u8, upload_items
-                    items = centre_items(range(u8.shape[0]), cache_size, cache_size, args.image_size)
-                    u8 = crop_d4_u8(u8.to(device), upload_items(items, device), args.image_size)
-                final_x = downblur(u8.to(device), args.magnification_factor, blur_radius)[0]
-                if gauss_noise:
-                    add_reference_noise(final_x, noise_level1=2, noise_level2=10)
-                return [final_x[i] for i in range(final_x.shape[0])]
-    if not spec.startswith("synthetic"):
-        # an image folder, laid out as the reference expects it (:597-598): <dataset_path>/train_original, /val_original.
-        # Decoded once with Pillow into the uint8 cache (this rank's shard only); resize / blur / noise per batch on the device
-        if not os.path.isdir(os.path.join(spec, "train_original")) or not os.path.isdir(os.path.join(spec, "val_original")):
-            raise FileNotFoundError(f"--dataset_path {spec!r}: expected the folders train_original/ and val_original/ "
-                                    "(or synthetic[:N] / synthetic_u8[:N])")
-        train_loader = make_feed(load_image_folder_u8(os.path.join(spec, "train_original"), cache_size, r, wsz))
-        val_loader = make_feed(load_image_folder_u8(os.path.join(spec, "val_original"), cache_size, r, wsz), fixed=True)
-        for what, feed in (("train_original", train_loader), ("val_original", val_loader)):
-            if feed.hr.shape[1] != ch:
-                raise ValueError(f"the images of {what} have {feed.hr.shape[1]} channels, --inp_out_channels is {ch}")
-        # the final sampling conditions on train_dataset[0..4] of the WHOLE sorted folder (reference :678-680), whatever this
-        # rank's shard holds; with Gauss_noise the dataset item carries its noise (utils.py:126-138)
-        first = load_image_folder_u8(os.path.join(spec, "train_original"), cache_size, limit=5).to(device)
-        final_lr = first_items(first) if deg == "bsrgan" else first_items(first, train_loader.blur_radius)
-    else:
-        length = int(spec.split(":")[1]) if ":" in spec else 4 * args.batch_size
-        size = cache_size if device_feed else args.image_size  # (the float DataLoader path has no windows)
-        train_dataset = SyntheticSuperresDataset(length, ch, size, args.magnification_factor, seed=1)
-        val_dataset = SyntheticSuperresDataset(max(length // 4, 1), ch, size, args.magnification_factor, seed=2)
-        final_lr = [train_dataset[i][0] for i in range(min(5, len(train_dataset)))]
-        if device_feed:
-            def to_u8(hr):
-                return (hr * 255).round().clamp(0, 255).to(torch.uint8)
-
-            def feed(ds, fixed=False):
-                # equal shard sizes on every rank (DistributedSampler pads; here the remainder is dropped): ranks must run
-                # the same number of steps, or the per-step all-reduce of the longer shard never completes
-                per_rank = len(ds) // wsz
-                if per_rank == 0:
-                    raise ValueError(f"dataset of {len(ds)} images cannot be sharded over {wsz} ranks")
-                return make_feed(to_u8(ds.hr[r::wsz][:per_rank]), fixed)
-            train_loader, val_loader = feed(train_dataset), feed(val_dataset, fixed=True)
-            if deg == "bsrgan":
-                final_lr = first_items(to_u8(train_dataset.hr[:5]))
-            elif cache_size != args.image_size:
-                final_lr = first_items(to_u8(train_dataset.hr[:5]), train_loader.blur_radius)
-        else:
-            train_loader, val_loader = make_loaders(args, train_dataset, val_dataset)
-    return train_loader, val_loader, final_lr
+            run.epochs_without_improving += 1
 
 
 def launch(args):
@@ -834,34 +728,6 @@ def launch(args):
     save_final_samples(args, sample, final_lr, "superres_results.pt")
 
 
-def str2bool(v):
-    return v.lower() in ("yes", "true", "t", "1")
-
-
-def base_arg_parser():
-    """The reference's flags that all three trainers have, verbatim (:703-724), and the DDIM flags (`add_sampling_args`)."""
-    import argparse
-    p = argparse.ArgumentParser(description=" ")
-    p.add_argument("--epochs", type=int, default=501)
-    p.add_argument("--batch_size", type=int, default=32)
-    p.add_argument("--image_size", type=int)
-    p.add_argument("--lr", type=float, default=3e-4)
-    p.add_argument("--check_preds_epoch", type=int, default=20)
-    p.add_argument("--noise_schedule", type=str, default="cosine")
-    p.add_argument("--snapshot_name", type=str, default="snapshot.pt")
-    p.add_argument("--model_name", type=str)
-    p.add_argument("--noise_steps", type=int, default=200)
-    p.add_argument("--patience", type=int, default=10)
-    p.add_argument("--dataset_path", type=str, default=None)
-    p.add_argument("--generate_video", type=str2bool, nargs="?", const=True, default=False)
-    p.add_argument("--loss", type=str)
-    p.add_argument("--UNet_type", type=str, default="Residual Attention UNet")
-    p.add_argument("--multiple_gpus", type=str2bool, nargs="?", const=True, default=False)
-    p.add_argument("--ema_smoothing", type=str2bool, nargs="?", const=True, default=False)
-    add_sampling_args(p)
-    return p
-
-
 def build_arg_parser():
     """`base_arg_parser` and the super-resolution flags of the reference (:703-724)."""
     p = base_arg_parser()
@@ -874,108 +740,14 @@ def build_arg_parser():
     return p
 
 
-def add_bsr_args(p):
-    """--bsr_kind / --bsr_seed of the command lines that build the BSRGAN feed (not in the reference; `make_superres_feeds`)."""
-    p.add_argument("--bsr_kind", type=str, choices=("plus", "soft"), default="plus",
-                   help="with --Degradation_type BSRGAN: plus (degradation_bsrgan_plus: USM, two rounds of blur / resize / noise, "
-                        "JPEG) or soft (blur, resize, noise once)")
-    p.add_argument("--bsr_seed", type=int, default=0, help="with --Degradation_type BSRGAN: seed of the recipes and the noise")
-    return p
-
-
-def add_solver_args(p):
-    """--solver / --spacing for the command lines that take them next to --sampling_steps (`cli_sampling_steps`)."""
-    p.add_argument("--solver", type=str, choices=("ddim", "dpmpp_2m"), default="ddim",
-                   help="how the --sampling_steps steps are taken: ddim, or dpmpp_2m (DPM-Solver++(2M): second order, eta 0)")
-    p.add_argument("--spacing", type=str, choices=("uniform", "logsnr"), default=None,
-                   help="where the --sampling_steps levels lie: uniform in t or uniform in logSNR; default: uniform for ddim, "
-                        "logsnr for dpmpp_2m")
-    return p
-
-
-def cli_sampling_steps(args):
-    """The `sampling_steps` argument of a command line: --sampling_steps, as a `sampling_plan` when --solver / --spacing say more."""
-    solver, spacing = getattr(args, "solver", "ddim"), getattr(args, "spacing", None)
-    steps = getattr(args, "sampling_steps", None)
-    return steps if solver == "ddim" and spacing is None else sampling_plan(steps, solver, spacing)
-
-
-OPTIM_DEFAULTS = {"weight_decay": 0.0, "max_grad_norm": None, "lr_schedule": "constant", "warmup_steps": 0, "lr_min": 0.0,
-                  "save_train_state": False}
-
-
-def add_optim_args(p):
-    """The optimizer / schedule / resume flags of the three trainers' command lines (not in the reference; `Diffusion.train`)."""
-    p.add_argument("--weight_decay", type=float, default=0.0, help="decoupled (AdamW) weight decay; 0 = the reference's Adam")
-    p.add_argument("--max_grad_norm", type=float, default=None,
-                   help="clip the global gradient norm to this value; steps with non-finite gradients are skipped")
-    p.add_argument("--lr_schedule", type=str, choices=("constant", "cosine"), default="constant",
-                   help="after --warmup_steps: stay at --lr, or half a cosine down to --lr_min at the last step")
-    p.add_argument("--warmup_steps", type=int, default=0, help="optimizer steps of linear learning-rate warm-up")
-    p.add_argument("--lr_min", type=float, default=0.0, help="final learning rate of --lr_schedule cosine")
-    p.add_argument("--save_train_state", type=str2bool, nargs="?", const=True, default=False,
-                   help="write train_state.pt (optimizer, raw weights under EMA, schedule, early-stopping and RNG state) beside "
-                        "every snapshot, and continue from both when they exist.  Not built: gradient accumulation, loss scaling, "
-                        "the crop / BSRGAN feeds' own generators, per-rank files (rank 0 writes, every rank reads)")
-    return p
-
-
-def check_optim_args(p, args):
-    if args.weight_decay < 0 or args.lr_min < 0 or args.warmup_steps < 0:
-        p.error("--weight_decay, --lr_min and --warmup_steps must be >= 0")
-    if args.max_grad_norm is not None and not args.max_grad_norm > 0:
-        p.error("--max_grad_norm must be > 0")
-    return args
-
-
-def optim_train_kwargs(args):
-    """`add_optim_args`' flags as keyword arguments of `Diffusion.train` (a namespace without them: the defaults)."""
-    return {k: getattr(args, k, v) for k, v in OPTIM_DEFAULTS.items()}
-
-
-OBJECTIVE_DEFAULTS = {"loss_weighting": "none", "min_snr_gamma": 5.0, "timestep_sampling": "uniform", "loss_bins": 0}
-
-
-def add_objective_args(p):
-    """The training-objective flags of the three trainers' command lines (not in the reference; `Diffusion.train`, losses.py)."""
-    p.add_argument("--loss_weighting", type=str, choices=("none", "min_snr"), default="none",
-                   help="min_snr: weight every image's loss with min(1, --min_snr_gamma / SNR_t); none = the reference's loss")
-    p.add_argument("--min_snr_gamma", type=float, default=5.0, help="gamma of --loss_weighting min_snr")
-    p.add_argument("--timestep_sampling", type=str, choices=("uniform", "loss_aware"), default="uniform",
-                   help="loss_aware: draw t on the device in proportion to the recent losses of its timestep bin, with the "
-                        "importance weight that keeps the loss an estimate of the uniform mean; uses 16 bins when --loss_bins "
-                        "is 0 and consumes the device generator instead of the CPU one")
-    p.add_argument("--loss_bins", type=int, default=0,
-                   help="keep and print the mean loss per timestep bin (N bins, 2 .. 64 and at most noise_steps / 2; lowest-noise "
-                        "bin first), one more line per phase and epoch; 0 = off.  Not built: bins shared across ranks, "
-                        "weighting of the perceptual loss")
-    return p
-
-
-def check_objective_args(p, args):
-    if args.loss_bins < 0 or not args.min_snr_gamma > 0:
-        p.error("--loss_bins must be >= 0 and --min_snr_gamma > 0")
-    return args
-
-
-def objective_train_kwargs(args):
-    """`add_objective_args`' flags as keyword arguments of `Diffusion.train` (a namespace without them: the defaults)."""
-    return {k: getattr(args, k, v) for k, v in OBJECTIVE_DEFAULTS.items()}
-
-
-def add_sampling_args(p):
-    """The DDIM flags of the final sampling (not in the reference): none = the reference's ancestral chain."""
-    p.add_argument("--sampling_steps", type=int, default=None,
-                   help="sample with DDIM over this many timesteps (1 .. noise_steps - 1); default: the full ancestral chain")
-    p.add_argument("--eta", type=float, default=0.0, help="DDIM eta: 0 deterministic, 1 DDPM-like (with --sampling_steps)")
-
-
 def parse_train_args(argv=None):
     """The trainer's command line: `build_arg_parser`, the BSRGAN feed's flags, the crop / augmentation flags (`add_augment_args`:
     --num_crops gets its meaning there) and `--eval_metrics`, which one process evaluates (no distributed evaluation: rejected
     together with --multiple_gpus)."""
-    from .augment import add_augment_args
-    p = add_objective_args(add_optim_args(add_augment_args(add_bsr_args(build_arg_parser()))))
+    p = build_arg_parser()
+    add_bsr_args(p)
+    add_augment_args(p)
+    add_train_args(p)
     p.add_argument("--eval_metrics", type=int, default=0,
                    help="score the network on the first N validation images (PSNR / SSIM / SAM / ERGAS against the bicubic "
                         "baseline) at every epoch with epoch %% check_preds_epoch == 0; 0 = off")
@@ -984,9 +756,7 @@ def parse_train_args(argv=None):
         p.error("--eval_metrics must be >= 0")
     if args.eval_metrics and args.multiple_gpus:
         p.error("--eval_metrics runs in one process: it cannot be combined with --multiple_gpus")
-    check_optim_args(p, args)
-    check_objective_args(p, args)
-    return args
+    return check_train_args(p, args)
 
 
 def main(argv=None):
