@@ -229,13 +229,22 @@ class split_aggregation_sampling:
         x_tiles = torch.empty((size, channels, S, S), dtype=torch.float32, device=dev)
         uncovered = torch.zeros(1, dtype=torch.int32, device=dev)
         single = len(starts) == 1
+        # what the network predicts (`Diffusion(prediction=, x0_clip=)`): its output becomes eps here, chunk by chunk against the
+        # tiles it saw, since the chain's state is the scene; with "eps" and no clip nothing is launched
+        from .sampling import check_prediction, converts_prediction
+        prediction, x0_clip = check_prediction(getattr(d, "prediction", "eps"), getattr(d, "x0_clip", None))
+        convert = prediction != "eps" or x0_clip is not None
 
         def predict(engine, x, t, first):
             for j, c0 in enumerate(starts):
                 hip_ops.gather_tiles(x[0], origins, S, out=x_tiles, first=c0, count=size)
                 engine.forward(x_tiles, t, lr_chunks[j], m, reuse_cond=single and not first,
                                check_weights=first and j == 0, out=eps_buf[c0:c0 + size])
+                if convert:
+                    hip_ops.pred_to_eps_(eps_buf[c0:c0 + size], x_tiles, t, d.alpha_hat, prediction, x0_clip)
             return eps_buf
+        if convert:
+            converts_prediction(predict)
 
         def update(x, eps, noise, i, i_prev, hist=None, t_q=-1, known=None, known_mask=None):
             kept = {"known": known[0], "known_mask": known_mask[0]} if known is not None else {}
@@ -329,7 +338,7 @@ def launch(args):
     import os
 
     from .colorfix import cli_color_fix
-    from .cli import cli_sampling_steps
+    from .cli import cli_prediction, cli_sampling_steps
     device = args.device
     task = getattr(args, "task", "superres")
     if args.UNet_type.lower() != "residual attention unet":
@@ -345,7 +354,7 @@ def launch(args):
         diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot_path,
                               noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02, device=device,
                               image_size=args.model_input_size, model_name=args.model_name, multiple_gpus=False,
-                              ema_smoothing=False)
+                              ema_smoothing=False, **cli_prediction(args))
         out_channels = args.NDVI_channels
     elif task == "superres":
         from .train_diffusion_superres import Diffusion
@@ -355,7 +364,8 @@ def launch(args):
                               noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02,
                               magnification_factor=args.magnification_factor, device=device,
                               image_size=args.model_input_size, model_name=args.model_name,
-                              Degradation_type=args.Degradation_type, multiple_gpus=False, ema_smoothing=False)
+                              Degradation_type=args.Degradation_type, multiple_gpus=False, ema_smoothing=False,
+                              **cli_prediction(args))
         out_channels = None
     else:
         raise ValueError(f"--task {task!r} must be 'superres' or 'sar_to_ndvi'")
@@ -383,11 +393,11 @@ def launch(args):
 
 def build_arg_parser():
     """The reference's flags, verbatim (:217-231), the DDIM flags, --aggregation, the colour-correction flags, the known-pixel
-    flags and --task / --clamp."""
+    flags, --task / --clamp and --prediction / --x0_clip (the snapshot's prediction; the clip of the x0 implied at every step)."""
     import argparse
 
     from .colorfix import add_color_fix_args
-    from .cli import add_sampling_args, add_solver_args
+    from .cli import add_prediction_args, add_sampling_args, add_solver_args
     p = argparse.ArgumentParser(description=" ")
     p.add_argument("--noise_schedule", type=str, default="cosine")
     p.add_argument("--snapshot_name", type=str, default="snapshot.pt")
@@ -405,6 +415,7 @@ def build_arg_parser():
     p.add_argument("--img_lr_path", type=str)
     add_sampling_args(p)
     add_solver_args(p)
+    add_prediction_args(p)
     p.add_argument("--aggregation", type=str, choices=("final", "per_step"), default="final",
                    help="final: independent tile chains blended once (the reference); per_step: one joint chain of the "
                         "whole scene, the tiles' noise predictions blended at every reverse step")

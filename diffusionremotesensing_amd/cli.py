@@ -57,6 +57,39 @@ def cli_sampling_steps(args):
     return steps if solver == "ddim" and spacing is None else sampling_plan(steps, solver, spacing)
 
 
+def add_prediction_args(p, in_help=True):
+    """--prediction / --x0_clip of the outer command lines (the trainers' `main` parsers, `evaluate`, the tiler): the
+    `prediction` / `x0_clip` of `Diffusion` (`cli_prediction`).  `in_help` False registers them without a --help entry: the
+    trainers' help texts are recorded (tests/golden/train_loop_transcripts.json), README.md describes the flags."""
+    p.add_argument("--prediction", type=str, choices=("eps", "v", "x0"), default="eps",
+                   help="what the network predicts: the noise eps (the reference), v = sqrt(ah) eps - sqrt(1 - ah) x0, or the "
+                        "clean image x0; training writes it into the snapshot, which refuses to load as another"
+                        if in_help else argparse.SUPPRESS)
+    p.add_argument("--x0_clip", type=cli_x0_clip, default=None,
+                   help="'none' or 'LO,HI' (--x0_clip=-1,1 for a negative bound): clamp the clean image every reverse step "
+                        "implies to this range while sampling; default none" if in_help else argparse.SUPPRESS)
+    return p
+
+
+def cli_x0_clip(text):
+    """The value of --x0_clip as `Diffusion`'s `x0_clip`: None for 'none', (LO, HI) for 'LO,HI' - the words of the tiler's
+    --clamp (`Aggregation_Sampling.cli_clamp`), read while the command line is parsed, so that a bad value ends every parser."""
+    if text.strip().lower() == "none":
+        return None
+    try:
+        lo, hi = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} must be 'none' or 'LO,HI'") from None
+    if not lo < hi:
+        raise argparse.ArgumentTypeError(f"{text!r} needs LO < HI")
+    return lo, hi
+
+
+def cli_prediction(args):
+    """`add_prediction_args`' flags as keyword arguments of a `Diffusion` (a namespace without them: the defaults)."""
+    return {"prediction": getattr(args, "prediction", "eps"), "x0_clip": getattr(args, "x0_clip", None)}
+
+
 def add_bsr_args(p):
     """--bsr_kind / --bsr_seed of the command lines that build the BSRGAN feed (not in the reference; `make_superres_feeds`)."""
     p.add_argument("--bsr_kind", type=str, choices=("plus", "soft"), default="plus",

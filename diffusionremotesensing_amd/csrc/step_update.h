@@ -4,6 +4,7 @@
 // drs_blend_step_ddim), the DPM-Solver++(2M) move of both (drs_dpm_step, drs_blend_step_dpm), and the forward-noised known
 // element of the moves with known pixels (drs_inpaint_step, drs_blend_step_known).
 // One definition, so that a scene state and a tile state that see the same eps move by the same bits.
+// At the end: the forward process with its v target, and the conversion of a v / x0 prediction into that eps (prediction.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -134,3 +135,85 @@ struct DrsKnownCoef {
     return p + q;
   }
 };
+
+// The forward process of one training element and its v target (prediction.hip: drs_noise_v_target), a = sqrtf(ah) and
+// b = sqrtf(1 - ah) in fp32 as drs_noise_images forms them: fl(a x0) + fl(b eps) and fl(a eps) - fl(b x0), no contraction.
+// Plain operators under contract(off), as above: HIP's __fmul_rn / __fadd_rn are inline functions of a header compiled with
+// contraction on, and once inlined into an unrolled group the compiler fuses them (v_pk_fma_f32) whatever this file says.
+__device__ __forceinline__ float drs_forward_noise(float a, float b, float x0, float eps) {
+#pragma clang fp contract(off)
+  const float p = a * x0, q = b * eps;
+  return p + q;
+}
+__device__ __forceinline__ float drs_v_target(float a, float b, float x0, float eps) {
+#pragma clang fp contract(off)
+  const float p = a * eps, q = b * x0;
+  return p - q;
+}
+
+// A prediction p of the network - eps, v = a eps - s x0 or x0 (`kind`: DRS_PRED_EPS / _V / _X0 = 0 / 1 / 2 of include/drs_hip.h)
+// - as the eps every update above takes, against the x the network saw at the level of table entry `ah`; with `clip` the
+// implied x0 is first clamped to [lo, hi] (prediction.hip: drs_pred_to_eps).  a = sqrt(ah), s = sqrt(1 - ah) in fp64 from the
+// fp32 entry, each coefficient rounded once (as drs_ddim_coef), products and sums rounded one by one:
+//   no clip   eps: p          v: s x + a p            x0: (1/s) x + (-a/s) p
+//   clip      x0 = eps: (1/a) x + (-s/a) p   v: a x + (-s) p   x0: p;   eps = (1/s) x + (-a/s) clamp(x0)
+// Where s == 0 (ah == 1, level 0 of the cosine table) the forms that divide by s give 0; where a == 0 an eps prediction is
+// passed through unclipped; `bad` (a level outside the table) gives NaN.  No chain predicts at those levels.
+struct DrsPredCoef {
+  enum Form { PASS, LINEAR, CLIP_LINEAR, CLIP_PRED, ZERO, BAD };
+  Form form;
+  float xa, xb;  // CLIP_LINEAR: x0 = xa x + xb p
+  float ea, eb;  // eps = ea x + eb q, q = p (LINEAR) or the clamped x0
+  float lo, hi;
+};
+__device__ __forceinline__ DrsPredCoef drs_pred_coef(float ah, int kind, bool clip, float lo, float hi, bool bad) {
+  const double a = sqrt((double)ah), s = sqrt(fmax(1.0 - (double)ah, 0.0));
+  DrsPredCoef k;
+  k.xa = k.xb = k.ea = k.eb = 0.f;
+  k.lo = lo;
+  k.hi = hi;
+  const bool is_eps = kind == 0, is_v = kind == 1;
+  if (bad) {
+    k.form = DrsPredCoef::BAD;
+  } else if (is_eps && (!clip || a == 0.0)) {
+    k.form = DrsPredCoef::PASS;
+  } else if (is_v && !clip) {
+    k.form = DrsPredCoef::LINEAR;
+    k.ea = (float)s;
+    k.eb = (float)a;
+  } else if (s == 0.0) {
+    k.form = DrsPredCoef::ZERO;
+  } else {
+    k.ea = (float)(1.0 / s);
+    k.eb = (float)(-a / s);
+    if (!clip) {
+      k.form = DrsPredCoef::LINEAR;
+    } else if (is_eps) {
+      k.form = DrsPredCoef::CLIP_LINEAR;
+      k.xa = (float)(1.0 / a);
+      k.xb = (float)(-s / a);
+    } else if (is_v) {
+      k.form = DrsPredCoef::CLIP_LINEAR;
+      k.xa = (float)a;
+      k.xb = (float)(-s);
+    } else {
+      k.form = DrsPredCoef::CLIP_PRED;
+    }
+  }
+  return k;
+}
+__device__ __forceinline__ float drs_pred_eps(const DrsPredCoef& k, float x, float p) {
+#pragma clang fp contract(off)
+  if (k.form == DrsPredCoef::PASS) return p;
+  if (k.form == DrsPredCoef::ZERO) return 0.f;
+  if (k.form == DrsPredCoef::BAD) return __builtin_nanf("");
+  float q = p;
+  if (k.form == DrsPredCoef::CLIP_LINEAR) {
+    const float u = k.xa * x, w = k.xb * p;
+    q = u + w;
+  }
+  if (k.form != DrsPredCoef::LINEAR && fabsf(q) < __builtin_huge_valf())  // a NaN or an infinity stays what it is (no fminf / fmaxf)
+    q = q < k.lo ? k.lo : (q > k.hi ? k.hi : q);
+  const float u = k.ea * x, w = k.eb * q;
+  return u + w;
+}

@@ -28,7 +28,7 @@ import os
 
 import torch
 
-from .cli import add_bsr_args, add_solver_args, cli_sampling_steps
+from .cli import add_bsr_args, add_prediction_args, add_solver_args, cli_prediction, cli_sampling_steps
 from .colorfix import add_color_fix_args, cli_color_fix
 from .launcher import launch_device
 from .sampling import plan_of
@@ -126,7 +126,8 @@ def _superres_setup(args, device, snapshot):
     model = Residual_Attention_UNet_superres(ch, ch, device).to(device)
     diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot,
                           noise_steps=args.noise_steps, device=device, magnification_factor=args.magnification_factor,
-                          image_size=args.image_size, model_name=args.model_name, Degradation_type=args.Degradation_type)
+                          image_size=args.image_size, model_name=args.model_name, Degradation_type=args.Degradation_type,
+                          **cli_prediction(args))
     return model, diffusion, val_loader
 
 
@@ -139,7 +140,7 @@ def _sar_setup(args, device, snapshot):
         val_loader = S.folder_feed(args, device, "test")
     model = Residual_Attention_UNet_SAR_TO_NDVI(args.SAR_channels, args.NDVI_channels, device).to(device)
     diffusion = S.Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot, noise_steps=args.noise_steps,
-                            device=device, image_size=args.image_size, model_name=args.model_name)
+                            device=device, image_size=args.image_size, model_name=args.model_name, **cli_prediction(args))
     return model, diffusion, val_loader
 
 
@@ -152,9 +153,10 @@ def sampling_line(sampling_steps, eta):
 
 
 def cli_arg_parser(task="superres"):
-    """The whole command line of `main` for `task`: `evaluate_arg_parser` with the known-pixel, ensemble and solver flags and,
-    for superres (the task with an LR guide), --color_fix / --color_fix_levels and the BSRGAN feed's --bsr_kind / --bsr_seed."""
-    p = add_solver_args(add_ensemble_args(add_known_args(evaluate_arg_parser(task))))
+    """The whole command line of `main` for `task`: `evaluate_arg_parser` with the known-pixel, ensemble, solver and prediction
+    flags (--prediction must be the snapshot's; --x0_clip) and, for superres (the task with an LR guide), --color_fix /
+    --color_fix_levels and the BSRGAN feed's --bsr_kind / --bsr_seed."""
+    p = add_prediction_args(add_solver_args(add_ensemble_args(add_known_args(evaluate_arg_parser(task)))))
     return add_bsr_args(add_color_fix_args(p)) if task == "superres" else p
 
 

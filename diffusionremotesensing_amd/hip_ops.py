@@ -149,6 +149,58 @@ def noise_images(x0, eps, t, alpha_hat):
     return out
 
 
+PREDICTIONS = {"eps": 0, "v": 1, "x0": 2}  # include/drs_hip.h: DRS_PRED_*
+
+
+def noise_v_target(x0, eps, t, alpha_hat):
+    """(x_t, v) of a training batch from one launch (include/drs_hip.h: drs_noise_v_target): `noise_images`' x_t and the
+    v-prediction target sqrt(alpha_hat[t]) eps - sqrt(1 - alpha_hat[t]) x0.  A t outside the table gives that image NaN."""
+    lib = _lib.load()
+    x0 = _req(x0, "x0"); eps = _req(eps, "eps"); t = _req(t, "t", torch.int64); alpha_hat = _req(alpha_hat, "alpha_hat")
+    _req_numel("noise_v_target", x0, (("eps", eps),), "x0")
+    n = x0.shape[0] if x0.dim() else 0
+    if t.numel() != n:
+        raise RuntimeError(f"noise_v_target: t has {t.numel()} elements, x0 has {n} images")
+    x_t, v = torch.empty_like(x0), torch.empty_like(x0)
+    chw = x0.numel() // n if n else 0
+    with torch.cuda.device(x0.device):
+        st = lib.drs_noise_v_target(_ptr(x0), _ptr(eps), _ptr(t), _ptr(alpha_hat), alpha_hat.numel(), _ptr(x_t), _ptr(v), n,
+                                    chw, _stream(x0.device))
+    _lib.check(st, "drs_noise_v_target")
+    return x_t, v
+
+
+def pred_to_eps_(pred, x, t, alpha_hat, prediction="eps", x0_clip=None, pred_uncond=None, cfg_scale=0.0, out=None):
+    """The network's `pred` (n, ...) - of kind `prediction`: "eps", "v" or "x0" - as the eps the reverse-step wrappers take, in
+    place (or into `out`), against the state `x` the network saw at the levels `t` (n int64 values on the device); include/
+    drs_hip.h: drs_pred_to_eps.  With `pred_uncond` the prediction is torch.lerp(pred_uncond, pred, cfg_scale) first; with
+    `x0_clip=(lo, hi)` the x0 the prediction implies is clamped to that range before eps is formed from it.  Returns eps."""
+    lib = _lib.load()
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"prediction={prediction!r} must be one of {tuple(PREDICTIONS)}")
+    _req_state(pred, "pred_to_eps_", "pred")
+    x = _req(x, "x"); t = _req(t, "t", torch.int64); alpha_hat = _req(alpha_hat, "alpha_hat")
+    pred_uncond = _req(pred_uncond, "pred_uncond") if pred_uncond is not None else None
+    if out is None:
+        out = pred
+    else:
+        _req_state(out, "pred_to_eps_", "out")
+    _req_numel("pred_to_eps_", pred, (("x", x), ("pred_uncond", pred_uncond), ("out", out)), "pred")
+    n = pred.shape[0] if pred.dim() else 0
+    if t.numel() != n:
+        raise RuntimeError(f"pred_to_eps_: t has {t.numel()} elements, pred has {n} images")
+    flag, lo, hi = _clamp_args(x0_clip, "pred_to_eps_")
+    if flag and not lo < hi:
+        raise ValueError(f"pred_to_eps_: x0_clip=({lo}, {hi}) needs lo < hi")
+    chw = pred.numel() // n if n else 0
+    with torch.cuda.device(pred.device):
+        st = lib.drs_pred_to_eps(_ptr(pred), _ptr(pred_uncond), float(cfg_scale), _ptr(x), _ptr(t), _ptr(alpha_hat),
+                                 alpha_hat.numel(), PREDICTIONS[prediction], flag, lo, hi, _ptr(out), n, chw,
+                                 _stream(pred.device))
+    _lib.check(st, "drs_pred_to_eps")
+    return out
+
+
 def timestep_table(noise_steps, n, device):
     """(noise_steps, n) int64: row i is the reference's `t = (torch.ones(n) * i).long()` of sampling step i
     (train_diffusion_superres.py:237) for every step of a chain, built once: a row view per step instead of a fill kernel

@@ -23,11 +23,18 @@ def snr(alpha_hat):
     return (a / (1.0 - a)).to(torch.float32)
 
 
-def min_snr_weights(alpha_hat, gamma=5.0):
-    """Min-SNR-gamma weights of the eps-prediction loss, w_t = min(1, gamma / SNR_t): (T,) fp32 computed in float64.
-    gamma / inf = 0 where alpha_hat == 1, never NaN."""
+def min_snr_weights(alpha_hat, gamma=5.0, prediction="eps"):
+    """Min-SNR-gamma weights of the loss on what the network predicts, (T,) fp32 computed in float64: min(SNR_t, gamma) over
+    SNR_t for "eps" (= min(1, gamma / SNR_t)), over SNR_t + 1 for "v", over 1 for "x0" - one weighting of the x0 error, stated
+    for each target (Hang et al. 2023, section 3.4).  Where alpha_hat == 1 (SNR = inf) they are 0, 0 and gamma, never NaN."""
     a = alpha_hat.detach().to("cpu", torch.float64)
-    return torch.clamp(float(gamma) / (a / (1.0 - a)), max=1.0).to(torch.float32)
+    if prediction == "eps":
+        return torch.clamp(float(gamma) / (a / (1.0 - a)), max=1.0).to(torch.float32)
+    if prediction not in ("v", "x0"):
+        raise ValueError(f"prediction={prediction!r} must be one of ('eps', 'v', 'x0')")
+    capped = torch.clamp(a / (1.0 - a), max=float(gamma))
+    # v: min(SNR, gamma) / (SNR + 1), and SNR + 1 = 1 / (1 - alpha_hat): no inf / inf where alpha_hat == 1
+    return (capped * (1.0 - a) if prediction == "v" else capped).to(torch.float32)
 
 
 def _ptr(t):

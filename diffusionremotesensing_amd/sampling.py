@@ -22,6 +22,33 @@ def ddim_timesteps(noise_steps, sampling_steps):
     return [1 + (k * (T - 2)) // (S - 1) for k in reversed(range(S))]
 
 
+PREDICTIONS = ("eps", "v", "x0")
+
+
+def check_prediction(prediction="eps", x0_clip=None):
+    """ValueError for a `prediction` / `x0_clip` no `Diffusion` takes: what the network predicts - "eps", "v" (v = sqrt(ah) eps -
+    sqrt(1 - ah) x0) or "x0" - and None or the (lo, hi), lo < hi, the x0 every reverse step implies is clamped to.  Returns
+    (prediction, x0_clip as a pair of floats or None)."""
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"prediction={prediction!r} must be one of {PREDICTIONS}")
+    if x0_clip is None:
+        return prediction, None
+    try:
+        lo, hi = (float(v) for v in x0_clip)
+    except (TypeError, ValueError):
+        raise ValueError(f"x0_clip={x0_clip!r} must be None or (lo, hi)") from None
+    if not lo < hi:
+        raise ValueError(f"x0_clip=({lo}, {hi}) needs lo < hi")
+    return prediction, (lo, hi)
+
+
+def converts_prediction(predict):
+    """Marks a `predict` of `sample_chain` whose result is eps already: it has converted the network's output itself, against
+    the x the network saw (the tiler's per-step `predict`, whose network sees tiles and not the chain's scene state)."""
+    predict.converts_prediction = True
+    return predict
+
+
 SOLVERS = ("ddim", "dpmpp_2m")
 SPACINGS = ("uniform", "logsnr")
 
@@ -283,10 +310,17 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
     The chain owns the history `hist` (state shape, allocated once: the x0 prediction of the move that wrote it last) and
     `hist_level`, that move's t.  A move is second order iff `hist_level` is the level before its t in the level list and it does
     not end at level 0; so the first move is first order, and so is the move a roll-back of `run_reverse_chain` resumes at
-    (the history then holds the x0 of a later move).  Its spacing places the levels (`plan_of`)."""
+    (the history then holds the x0 of a later move).  Its spacing places the levels (`plan_of`).
+    `schedule.prediction` ("eps" when it has none) says what `predict` returns and `schedule.x0_clip` (None or (lo, hi)) what the
+    x0 it implies is clamped to.  With anything but "eps" / None the result of `predict` is turned into eps right after the
+    call, in place, against the x it was called with (one `hip_ops.pred_to_eps_`, which also forms the guided prediction: the
+    update then gets one eps and cfg_scale 0), so every move above takes what it always took; a `predict` marked by
+    `converts_prediction` has done so itself.  With "eps" and None nothing is launched."""
     ddim = sampling_steps is not None
     solver, spacing = plan_of(sampling_steps)
     dpm = solver == "dpmpp_2m"
+    prediction, x0_clip = check_prediction(getattr(schedule, "prediction", "eps"), getattr(schedule, "x0_clip", None))
+    convert = (prediction != "eps" or x0_clip is not None) and not getattr(predict, "converts_prediction", False)
     moves = chain_moves(schedule.noise_steps, sampling_steps, resample, jump, spacing, schedule.alpha_hat if ddim else None)
     with torch.no_grad():
         x = noise_source(schedule.noise_steps, shape) if noise_source is not None else torch.randn(shape)  # (CPU generator, :230)
@@ -309,6 +343,11 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
                 eps = predict(engine, x, t_rows[t], state["first"])
                 state["first"] = False
                 eps, eps_uncond = eps if isinstance(eps, tuple) else (eps, None)
+                guide = cfg_scale
+                if convert:  # (the generation sampler's rows are 2n wide: conditional | unconditional)
+                    eps = hip_ops.pred_to_eps_(eps, x, t_rows[t][:shape[0]], schedule.alpha_hat, prediction, x0_clip,
+                                               pred_uncond=eps_uncond, cfg_scale=cfg_scale)
+                    eps_uncond, guide = None, 0.0
                 noise = draw(t) if t_to > 0 and (known is not None or not ddim or eta > 0) else None
                 if dpm:
                     second = t_to > 0 and state["hist_level"] is not None and state["hist_level"] == level_before.get(t)
@@ -318,13 +357,13 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
                         update(x, eps, None, t, t_to, **order)
                     else:
                         hip_ops.reverse_step_(x, eps, None, t, t_to, alpha=schedule.alpha, alpha_hat=schedule.alpha_hat,
-                                              beta=schedule.beta, ddim=True, eps_uncond=eps_uncond, cfg_scale=cfg_scale, **order)
+                                              beta=schedule.beta, ddim=True, eps_uncond=eps_uncond, cfg_scale=guide, **order)
                 elif update is not None:
                     kept = {"known": known, "known_mask": known_mask} if known is not None else {}
                     update(x, eps, noise, t, t_to if ddim else None, **kept)
                 else:
                     hip_ops.reverse_step_(x, eps, noise, t, t_to, alpha=schedule.alpha, alpha_hat=schedule.alpha_hat,
-                                          beta=schedule.beta, ddim=ddim, eta=eta, eps_uncond=eps_uncond, cfg_scale=cfg_scale,
+                                          beta=schedule.beta, ddim=ddim, eta=eta, eps_uncond=eps_uncond, cfg_scale=guide,
                                           known=known, known_mask=known_mask)
             if frames is not None:
                 frames.append(x.clone())

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import dist as drs_dist
 from .augment import add_augment_args
-from .cli import add_train_args, base_arg_parser, check_objective_args, check_train_args  # noqa: F401 - re-exported
+from .cli import add_prediction_args, add_train_args, base_arg_parser, check_objective_args, check_train_args  # noqa: F401 - re-exported
 from .launcher import launch_device, make_loaders, save_final_samples, train_model
 from .sampling import _repeat_members, asks_for_known_pixels, check_inpaint_args, check_sampling_args
 from .train_diffusion_superres import Diffusion as _SuperresDiffusion
@@ -24,11 +24,11 @@ from .UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
 class Diffusion(_SuperresDiffusion):
     def __init__(self, noise_schedule: str, model: nn.Module, snapshot_path: str, noise_steps=1000, beta_start=1e-4,
                  beta_end=0.02, device="cuda", image_size=224, model_name="SAR_TO_NDVI", multiple_gpus=False,
-                 ema_smoothing=False):
+                 ema_smoothing=False, prediction="eps", x0_clip=None):
         super().__init__(noise_schedule, model, snapshot_path, noise_steps=noise_steps, beta_start=beta_start,
                          beta_end=beta_end, device=device, magnification_factor=1, image_size=image_size,
                          model_name=model_name, Degradation_type="DownBlur", multiple_gpus=multiple_gpus,
-                         ema_smoothing=ema_smoothing)
+                         ema_smoothing=ema_smoothing, prediction=prediction, x0_clip=x0_clip)
         del self.magnification_factor, self.Degradation_type  # attributes the reference's SAR Diffusion does not have
 
     def _predict(self, net, x_t, t, cond):
@@ -193,7 +193,7 @@ def train_main_parser():
     flags (cli.add_train_args): what `main` parses."""
     p = train_arg_parser()
     add_augment_args(p)
-    return add_train_args(p)
+    return add_prediction_args(add_train_args(p), in_help=False)
 
 
 def main(argv=None):

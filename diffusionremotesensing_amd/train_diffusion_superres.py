@@ -28,13 +28,14 @@ from . import hip_ops
 from .augment import add_augment_args
 # (the names this module does not use itself are re-exported: they lived here before cli.py, launcher.py and superres_feeds.py)
 from .cli import (OBJECTIVE_DEFAULTS, OPTIM_DEFAULTS, add_bsr_args, add_objective_args, add_optim_args,  # noqa: F401
-                  add_sampling_args, add_solver_args, add_train_args, base_arg_parser, check_objective_args, check_optim_args,
+                  add_prediction_args, add_sampling_args, add_solver_args, add_train_args, base_arg_parser, check_objective_args, check_optim_args,
                   check_train_args, cli_sampling_steps, objective_train_kwargs, optim_train_kwargs, str2bool)
 from .launcher import launch_device, make_loaders, save_final_samples, train_model  # noqa: F401
 from .losses import DiffusionLoss, LossAwareSampler, LossBins, min_snr_weights
 from .optim import FusedAdam, FusedAdamW, WarmupCosine
 from .sampling import (CHAIN_CHECK_EVERY, _is_int, _repeat_members, asks_for_known_pixels,  # noqa: F401 - re-exported
-                       check_ensemble_args, check_inpaint_args, check_sampling_args, check_solver_known, ddim_chain_noise,
+                       check_ensemble_args, check_inpaint_args, check_prediction, check_sampling_args, check_solver_known,
+                       ddim_chain_noise,
                        ddim_timesteps, ensemble_chunks, inpaint_schedule, known_tensors, run_reverse_chain, sample_chain,
                        sampling_plan)
 from .superres_feeds import SyntheticSuperresDataset, make_superres_feeds  # noqa: F401
@@ -77,7 +78,11 @@ class TrainRun:
 class Diffusion:
     def __init__(self, noise_schedule: str, model: nn.Module, snapshot_path: str, noise_steps=1000, beta_start=1e-4,
                  beta_end=0.02, device="cuda", magnification_factor=4, image_size=224, model_name="superres",
-                 Degradation_type="BSRGAN", multiple_gpus=False, ema_smoothing=False):
+                 Degradation_type="BSRGAN", multiple_gpus=False, ema_smoothing=False, prediction="eps", x0_clip=None):
+        # not in the reference, whose networks predict the noise: what this one predicts ("eps", "v" or "x0": the training
+        # target, and what sampling converts to eps before every update) and the range the x0 implied at every reverse step
+        # is clamped to (None or (lo, hi); a plain attribute, read at the start of every chain).  DESIGN.md section 23.
+        self.prediction, self.x0_clip = check_prediction(prediction, x0_clip)
         self.noise_steps = noise_steps
         self.beta_start = beta_start
         self.beta_end = beta_end
@@ -130,6 +135,16 @@ class Diffusion:
 
     def sample_timesteps(self, n):
         return torch.randint(low=1, high=self.noise_steps, size=(n,))
+
+    def _noised_target(self, x0, t):
+        """(x_t, what the network is trained to return for it) of a clean batch at the levels t, for the training and the
+        validation loop alike: `noise_images`' pair for "eps"; its x_t and the clean batch for "x0"; for "v" the same draw
+        of eps, x_t and v from one launch (`hip_ops.noise_v_target`: that x_t is `noise_images`')."""
+        if self.prediction == "v":
+            epsilon = torch.randn_like(x0, dtype=torch.float32)
+            return hip_ops.noise_v_target(x0, epsilon, t, self.alpha_hat)
+        x_t, noise = self.noise_images(x0, t)
+        return x_t, (x0 if self.prediction == "x0" else noise)
 
     # -- reverse process (reference :207-255) ---------------------------------------------------
     def sample(self, n, model, lr_img, input_channels=3, generate_video=False, noise_source=None, sampling_steps=None,
@@ -378,6 +393,8 @@ class Diffusion:
 
     def _save_snapshot(self, epoch, model):
         snapshot = {"MODEL_STATE": self._unwrapped(model).state_dict(), "EPOCHS_RUN": epoch}
+        if self.prediction != "eps":  # (an eps network's file stays the reference's two keys)
+            snapshot["PREDICTION"] = self.prediction
         torch.save(snapshot, self.snapshot_path)
         print(f"Epoch {epoch} | Training snapshot saved at {self.snapshot_path}")
 
@@ -385,15 +402,25 @@ class Diffusion:
         if self.multiple_gpus:
             from collections import OrderedDict
             snapshot = torch.load(self.snapshot_path, map_location="cpu")
+            self._check_snapshot_prediction(snapshot)
             state = OrderedDict((k.replace("module.", ""), v) for k, v in snapshot["MODEL_STATE"].items())
             net = self._unwrapped(self.model)
             net.load_state_dict(state)
             net.to(self.device)
         else:
             snapshot = torch.load(self.snapshot_path, map_location=self.device)
+            self._check_snapshot_prediction(snapshot)
             self.model.load_state_dict(snapshot["MODEL_STATE"])
         self.epochs_run = snapshot["EPOCHS_RUN"]
         print(f"Resuming training from snapshot at Epoch {self.epochs_run}")
+
+    def _check_snapshot_prediction(self, snapshot):
+        """ValueError for a snapshot of a network that predicts something else than this `Diffusion` was told (a file without
+        the key: eps): its weights would be sampled and trained as what they are not."""
+        saved = snapshot.get("PREDICTION", "eps")
+        if saved != self.prediction:
+            raise ValueError(f"{self.snapshot_path} holds a network that predicts {saved!r}, this Diffusion was built with "
+                             f"prediction={self.prediction!r} (--prediction {saved})")
 
     # -- the rest of a run's state (not in the reference, which marks the gap: LR_SCHEDULER is commented out at :275) --------
     def train_state_path(self):
@@ -474,7 +501,8 @@ class Diffusion:
         if loss not in ("MSE", "MAE", "Huber"):
             raise ValueError("The Loss must be either MSE or MAE or Huber or MSE+Perceptual_noise")
         nbins = loss_bins or (16 if timestep_sampling == "loss_aware" else 0)
-        table = min_snr_weights(self.alpha_hat, min_snr_gamma).to(self.device) if loss_weighting == "min_snr" else None
+        table = (min_snr_weights(self.alpha_hat, min_snr_gamma, self.prediction).to(self.device)
+                 if loss_weighting == "min_snr" else None)
         bins = LossBins(self.noise_steps, nbins, self.device) if nbins else None
         val_bins = LossBins(self.noise_steps, nbins, self.device) if nbins else None
         return types.SimpleNamespace(train=DiffusionLoss(loss, table, bins), val=DiffusionLoss(loss, table, val_bins),
@@ -511,7 +539,7 @@ class Diffusion:
         else:
             t = self.sample_timesteps(hr_img.shape[0])
             t = (t.pin_memory() if not t.is_cuda else t).to(self.device, non_blocking=True)
-        x_t, noise = self.noise_images(hr_img, t)
+        x_t, noise = self._noised_target(hr_img, t)  # (`noise`: the target - eps, v or x0 - of `self.prediction`)
         optimizer.zero_grad()
         predicted_noise = self._predict(model, x_t, t, self._train_cond(lr_img))
         if isinstance(loss_function, DiffusionLoss):
@@ -559,7 +587,9 @@ class Diffusion:
         `loss_bins=N` keeps the mean loss per timestep bin and prints it, lowest-noise bin first, one more line per phase;
         `timestep_sampling="loss_aware"` draws t on the device from those bins' recent losses (16 bins when `loss_bins` is 0)
         and so consumes the DEVICE generator instead of the CPU one.  Any of them routes `train_step` and the validation loop
-        through `losses.DiffusionLoss`; validation keeps its uniform CPU draw of t and has bins of its own."""
+        through `losses.DiffusionLoss`; validation keeps its uniform CPU draw of t and has bins of its own.
+        The regression target of both loops is what the constructor's `prediction` names (`_noised_target`: eps, v or x0; Min-SNR
+        weights that target); `loss="MSE+Perceptual_noise"` needs an eps network (ValueError otherwise)."""
         run = self._begin_run(
             loss, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule,
             warmup_steps=warmup_steps, lr_min=lr_min, total_steps=max(len(train_loader), 1) * epochs,
@@ -588,6 +618,9 @@ class Diffusion:
         model = self.model
         if lr_schedule not in ("constant", "cosine"):
             raise ValueError("lr_schedule must be constant or cosine")
+        if loss == "MSE+Perceptual_noise" and self.prediction != "eps":
+            raise ValueError(f"--loss MSE+Perceptual_noise cannot be combined with prediction={self.prediction!r}: its VGG term "
+                             "compares the predicted noise with the true noise")
         objective = self._objective(loss, loss_weighting, min_snr_gamma, timestep_sampling, loss_bins)
         if weight_decay or max_grad_norm is not None or save_train_state:
             optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
@@ -662,7 +695,7 @@ class Diffusion:
             for batch in val_loader:
                 lr_img, hr_img = self._split_batch(batch)
                 t = self.sample_timesteps(hr_img.shape[0]).to(self.device)
-                x_t, noise = self.noise_images(hr_img, t)
+                x_t, noise = self._noised_target(hr_img, t)
                 predicted_noise = self._predict(run.saved, x_t, t, self._train_cond(lr_img))
                 if run.objective is not None:  # the same table through the no-grad path; uniform t, bins of its own
                     running_val_loss += run.objective.val(predicted_noise, noise, t)
@@ -748,6 +781,7 @@ def parse_train_args(argv=None):
     add_bsr_args(p)
     add_augment_args(p)
     add_train_args(p)
+    add_prediction_args(p, in_help=False)
     p.add_argument("--eval_metrics", type=int, default=0,
                    help="score the network on the first N validation images (PSNR / SSIM / SAM / ERGAS against the bicubic "
                         "baseline) at every epoch with epoch %% check_preds_epoch == 0; 0 = off")

@@ -146,6 +146,41 @@ DRS_API int drs_inpaint_step(float* x, const float* eps_cond, const float* eps_u
 DRS_API int drs_renoise(float* x, const float* noise, int s, int t, const float* alpha_hat, int noise_steps, int64_t numel,
                         drs_stream_t stream);
 
+/* What the network predicts (csrc/prediction.hip; not in the reference, whose networks all predict the noise). */
+enum {
+  DRS_PRED_EPS = 0, /* the noise eps */
+  DRS_PRED_V = 1,   /* v = sqrt(alpha_hat) eps - sqrt(1 - alpha_hat) x0 */
+  DRS_PRED_X0 = 2   /* the clean image x0 */
+};
+
+/* The forward process and the v target of a training batch in one pass: per image i of `chw` elements, with
+ * a = sqrtf(alpha_hat[t[i]]) and b = sqrtf(1 - alpha_hat[t[i]]) in fp32,
+ *   x_t = fl(a x0) + fl(b eps)          v = fl(a eps) - fl(b x0)
+ * every product and sum rounded on its own (no fused multiply-add): x_t is the documented value of the entry above.
+ * A t[i] outside [0, noise_steps) does not index the table: x_t and v of that image are NaN, the other images are untouched
+ * by it.  x_t and v must be two buffers.  16-byte accesses when x0, eps, x_t and v start at the same place of a 16-byte line
+ * (chw need not be a multiple of 4: each image then has a scalar head and tail), element by element otherwise.
+ * DRS_ERR_ARG: null pointer, x_t == v; DRS_ERR_SHAPE: n < 0, chw < 0, noise_steps <= 0. */
+DRS_API int drs_noise_v_target(const float* x0, const float* eps, const int64_t* t, const float* alpha_hat, int noise_steps,
+                               float* x_t, float* v, int n, int64_t chw, drs_stream_t stream);
+
+/* A prediction of `kind` (DRS_PRED_*) as the eps the reverse-step entries take, against the x the network saw; n images of
+ * `chw` elements, t: n int64 levels on the device.  Per image a = sqrt(ah), s = sqrt(1 - ah) are formed in fp64 from the fp32
+ * table entry ah = alpha_hat[t[i]]; every coefficient below is rounded to fp32 once, products and sums are fp32 and rounded one
+ * by one.  First p = pred_uncond ? lerp(pred_uncond, pred, cfg_scale) : pred   (torch.lerp, as the guided step entries).
+ *   clip == 0:   EPS: eps = p      V: eps = s x + a p      X0: eps = (1/s) x + (-a/s) p
+ *   clip != 0:   x0 = EPS: (1/a) x + (-s/a) p    V: a x + (-s) p    X0: p
+ *                x0c = min(max(x0, lo), hi) for a finite x0, x0 itself otherwise (a NaN or an infinity of the network is
+ *                never clamped into range);     eps = (1/s) x + (-a/s) x0c
+ * Where s == 0 (ah == 1: level 0 of the cosine table) the forms that divide by s give eps = 0; where a == 0 an EPS prediction
+ * is passed through unclipped.  A t[i] outside [0, noise_steps) does not index the table: that image's eps is NaN.
+ * `out` may be `pred` (in place); `pred_uncond` may be NULL.  Accesses as drs_noise_v_target (pred, pred_uncond, x, out).
+ * DRS_ERR_ARG: null pointer, unknown kind, clip with lo >= hi, pred_uncond with a cfg_scale that is not finite;
+ * DRS_ERR_SHAPE: n < 0, chw < 0, noise_steps <= 0. */
+DRS_API int drs_pred_to_eps(const float* pred, const float* pred_uncond, float cfg_scale, const float* x, const int64_t* t,
+                            const float* alpha_hat, int noise_steps, int kind, int clip, float lo, float hi, float* out, int n,
+                            int64_t chw, drs_stream_t stream);
+
 /* One Adam step over many tensors in ONE launch (torch.optim.Adam defaults: no weight decay, no amsgrad):
  *   m = lerp(m, g, 1-beta1); v = v*beta2 + (1-beta2)*g*g; p -= lr/(1-beta1^step) * m / (sqrt(v)/sqrt(1-beta2^step) + eps)
  * `table` (device): ntensors x drs_adam_tensor {p, g, m, v, n, step}; entries with g == NULL are skipped (parameters
