@@ -391,7 +391,7 @@ int drs_launch_bn_train(const float* z, int z_cs, int z_co, long long npix, long
                         int post_cs, const float* res, int res_cs, int res_co, float* out, int out_cs, int out_co,
                         int relu_pre, int relu_post, hipStream_t s);
 
-// ---- training backward (train_kernels.hip) ------------------------------------------------------------------------
+// ---- training backward (wgrad_direct.hip, colsum.hip, bn_train.hip, attn_bwd.hip, time_mlp_bwd.hip, stem_bwd.hip) ----
 struct WgradDesc {
   const float* A; int a_cs, a_co, Ca, AH, AW, sa;
   const float* B; int b_cs, b_co, Cb, BH, BW, sb;
@@ -412,8 +412,9 @@ int drs_launch_wgrad_mfma_bf16(const WgradDesc& d, float* partial, size_t partia
 // `partials`: optional DRS_RED_BLOCKS x C floats of scratch (stream-ordered use): whole-tensor sums then run without atomics
 int drs_launch_colsum(const float* t, int cs, int co, int C, long long npix, long long pix_per_image, int per_image,
                       int out_stride, float* out, hipStream_t s, float* partials = nullptr);
-int drs_launch_relu_mask(float* g, int g_cs, int g_co, const float* y, int y_cs, int y_co, int C, long long npix,
-                         hipStream_t s);
+// adds `nrows` per-block partial rows of `ncol` floats in a fixed order: dst_a[c] += column c for c < nW, dst_b[c - nW] += the
+// rest (either destination may be null); the finish step of the colsum, psi, stem and few-channel launchers (colsum.hip)
+int drs_launch_rows_finish(const float* partials, int nrows, int ncol, int nW, float* dst_a, float* dst_b, hipStream_t s);
 int drs_launch_bn_bwd(const float* g, int g_cs, int g_co, float* z, const float* mean, const float* rstd,
                       const float* gamma, const float* beta, int relu_pre, int C, long long npix, double* partials,
                       double* sums, float* dgamma, float* dbeta, hipStream_t s, float* z_sp = nullptr,

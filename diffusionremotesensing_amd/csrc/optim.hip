@@ -1,7 +1,7 @@
 // Clipped, decayed, guarded Adam (include/drs_hip.h: drs_grad_sumsq_partials, drs_adamw_clip_multi): the global gradient
 // norm and the update that consumes it, two launches on one stream and no host synchronisation between them.  Both run on
-// the (chunk of 4096, tensor) grid of adam_multi_kernel (train_kernels.hip); the update's per-element arithmetic IS that
-// kernel's, on the scaled gradient and the decayed parameter.
+// the (chunk of kChunk, tensor) grid of adam_multi_kernel (below); the update's per-element arithmetic IS that kernel's,
+// on the scaled gradient and the decayed parameter.  The plain multi-tensor Adam and the parameter EMA close the file.
 //
 // Reduction order (the only thing here that could make two runs differ): thread t of a chunk adds the squares of elements
 // t, t + 256, ... in that order; 64 lanes are combined by a shuffle tree (offsets 32, 16, .. 1); the four wave sums are added
@@ -9,7 +9,7 @@
 // block holds the same bits, and neither the dispatch order nor the grid's extent enters.  No atomics, no fences.
 #include "drs_common.h"
 
-constexpr int kChunk = 4096;            // elements per block, as in adam_multi_kernel
+constexpr int kChunk = 4096;            // elements per block of every kernel here
 constexpr int kPerThread = kChunk / 256;
 constexpr int kPartialTile = 2048;      // partials staged in LDS at a time (16 KiB)
 
@@ -133,6 +133,75 @@ extern "C" int drs_adamw_clip_multi(const drs_adamw_tensor* table, int ntensors,
   const unsigned gx = (unsigned)((max_numel + kChunk - 1) / kChunk);
   DRS_LAUNCH(adamw_clip_multi_kernel, dim3(gx, ntensors), dim3(256), 0, (hipStream_t)stream, table, lr, beta1, beta2,
              (float)eps, weight_decay, max_norm, skip_nonfinite, partials, npartials, stats);
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Multi-tensor Adam (torch.optim.Adam defaults), one launch for all parameters: grid = (chunks of the largest tensor,
+// tensors); blocks beyond a tensor's length exit.  Same operation order as torch's single-tensor implementation.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void adam_multi_kernel(const drs_adam_tensor* __restrict__ table, double lr, double b1d,
+                                                         double b2d, float eps) {
+  const drs_adam_tensor t = table[blockIdx.y];
+  if (!t.g) return;  // no gradient this step: torch skips the parameter (state untouched)
+  // torch forms 1 - beta in Python doubles and rounds the result to fp32 inside the kernels
+  const float beta2 = (float)b2d, w1 = (float)(1.0 - b1d), w2 = (float)(1.0 - b2d);
+  const long long lo = (long long)blockIdx.x * kChunk;
+  if (lo >= t.n) return;
+  const long long hi = min(t.n, lo + kChunk);
+  // bias corrections in double like torch's Python-side scalars (step_size = lr / bc1, bias_correction2_sqrt)
+  const double bc1 = 1.0 - pow(b1d, (double)t.step), bc2 = 1.0 - pow(b2d, (double)t.step);
+  const float lr_over_bc1 = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+  for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+    const float g = t.g[i];
+    float m = t.m[i], v = t.v[i];
+    m = w1 < 0.5f ? fmaf(w1, __fsub_rn(g, m), m) : __fsub_rn(g, __fmul_rn(__fsub_rn(g, m), __fsub_rn(1.f, w1)));  // lerp_
+    v = __fadd_rn(__fmul_rn(v, beta2), __fmul_rn(__fmul_rn(w2, g), g));                                          // mul_, addcmul_
+    const float denom = __fadd_rn(__fdiv_rn(sqrtf(v), bc2_sqrt), eps);
+    t.m[i] = m;
+    t.v[i] = v;
+    t.p[i] = __fadd_rn(t.p[i], __fmul_rn(-lr_over_bc1, __fdiv_rn(m, denom)));                                    // addcdiv_
+  }
+}
+extern "C" int drs_adam_multi(const drs_adam_tensor* table, int ntensors, int64_t max_numel, double lr, double beta1,
+                              double beta2, double eps, drs_stream_t stream) {
+  DRS_REQUIRE(table && ntensors >= 0, DRS_ERR_ARG, "adam_multi: bad arguments");
+  if (ntensors == 0 || max_numel <= 0) return DRS_OK;
+  const unsigned gx = (unsigned)((max_numel + kChunk - 1) / kChunk);
+  DRS_LAUNCH(adam_multi_kernel, dim3(gx, ntensors), dim3(256), 0, (hipStream_t)stream, table, lr, beta1, beta2,
+                     (float)eps);
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Multi-tensor EMA of the parameters (include/drs_hip.h: drs_ema_multi; reference EMA, UNet_model_superres.py:12-55):
+// grid = (chunks of the largest tensor, tensors).  mode 0: old * beta + (1 - beta) * new with torch's rounding (scalar
+// operands rounded to fp32, two products and one sum, no fused multiply-add); mode 1: word copy (warm-up).
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ema_multi_kernel(const drs_ema_tensor* __restrict__ table, float beta, float w, int mode) {
+  const drs_ema_tensor t = table[blockIdx.y];
+  const long long lo = (long long)blockIdx.x * kChunk;
+  if (lo >= t.n) return;
+  const long long hi = min((long long)t.n, lo + kChunk);
+  if (mode == 1) {
+    unsigned* dst = (unsigned*)t.ema;
+    const unsigned* src = (const unsigned*)t.cur;
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) dst[i] = src[i];
+  } else {
+    float* e = (float*)t.ema;
+    const float* c = (const float*)t.cur;
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) e[i] = __fadd_rn(__fmul_rn(e[i], beta), __fmul_rn(w, c[i]));
+  }
+}
+extern "C" int drs_ema_multi(const drs_ema_tensor* table, int ntensors, int64_t max_numel, double beta, int mode,
+                             drs_stream_t stream) {
+  DRS_REQUIRE(table && ntensors >= 0 && (mode == 0 || mode == 1), DRS_ERR_ARG, "ema_multi: bad arguments");
+  if (ntensors == 0 || max_numel <= 0) return DRS_OK;
+  const unsigned gx = (unsigned)((max_numel + kChunk - 1) / kChunk);
+  DRS_LAUNCH(ema_multi_kernel, dim3(gx, ntensors), dim3(256), 0, (hipStream_t)stream, table, (float)beta,
+                     (float)(1.0 - beta), mode);
   DRS_CHECK_HIP(hipGetLastError());
   return DRS_OK;
 }

@@ -263,7 +263,7 @@ static int wgrad(BwdCtx& c, WgradDesc d, float* dW, float* db) {
   return drs_launch_wgrad(d, wgrad_stream(c));
 }
 static int wgrad(BwdCtx& c, const ConvLayer& L, const WgradDesc& d) { return wgrad(c, d, c.G(L.w), c.G(L.b)); }
-// few-channel stem layers (image -> 16 channels): their own kernel (stem_wgrad_kernel, train_kernels.hip), on the side stream
+// few-channel stem layers (image -> 16 channels): their own kernel (stem_wgrad_kernel, stem_bwd.hip), on the side stream
 // like every weight gradient (operands x.nhwc / upsampled_lr_img.nhwc / grad.x0 are not rewritten below; the partial
 // rows share the side stream's slice workspace, whose users are stream-ordered).  Direct (VALU) plans keep wgrad_kernel.
 static int stem_wgrad(BwdCtx& c, const PlanarConv& L, const WgradDesc& d) {
@@ -272,7 +272,7 @@ static int stem_wgrad(BwdCtx& c, const PlanarConv& L, const WgradDesc& d) {
                                  kWgradPartialBytes, c.G(L.w), c.G(L.b), wgrad_stream(c));
   return wgrad(c, d, c.G(L.w), c.G(L.b));
 }
-// one launch per RRDB layer on the main stream: weight + bias gradient, data gradient, the ReLU mask on it (train_kernels.hip)
+// one launch per RRDB layer on the main stream: weight + bias gradient, data gradient, the ReLU mask on it (stem_bwd.hip)
 static int small_bwd(BwdCtx& c, const PlanarConv& L, const float* in_nhwc, const float* gout, float* gin, bool accumulate,
                      const float* mask_y) {
   return drs_launch_small_conv_bwd(in_nhwc, gout, c.PARAM(L.w), gin, accumulate ? 1 : 0, mask_y, c.B, c.cfg.cond_channels,
@@ -431,7 +431,7 @@ static int bwd_lr_branch(BwdCtx& c) {
   RUN(drs_launch_nchw_to_nhwc(c.TP(plan->t_up), upn, B, CC, H, W, CC, 0, c.s));
   RUN(stem_wgrad(c, plan->stemc, wgrad_conv(upn, CC, 0, CC, H, W, gx0, kGx0Stride, 0, kDown[0], H, W, B, 3, 1, 1)));
   float* gup = c.TP(plan->g_upn);
-  // dgrad of the CC -> 16 conditioning convolution (its own LDS-tiled kernel: train_kernels.hip)
+  // dgrad of the CC -> 16 conditioning convolution (its own LDS-tiled kernel: stem_bwd.hip)
   RUN(drs_launch_stem_dgrad(gx0, kGx0Stride, c.PARAM(plan->stemc.w), gup, B, H, W, CC, c.s));
   float* genc = c.TP(plan->g_lr[3]);  // gradient w.r.t. the LR encoding (h x w)
   RUN(drs_launch_bicubic_bwd(gup, genc, B, CC, c.h, c.w, c.cfg.magnification, c.s));  // (gather form: writes every element)

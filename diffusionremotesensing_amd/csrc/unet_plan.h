@@ -149,7 +149,7 @@ struct drs_plan {
   // stream (BatchNorm statistics, BatchNorm backward, bias-gradient column sums: kRedBlocks x 2 x 1024 doubles).  Partials +
   // a small finishing kernel replaced per-block atomics onto the same 2 x Cout addresses: 512 blocks x 90 ns per serialised
   // atomic = a 46 us floor under every one of those launches, whatever the tensor size (round 3: 63 of them per step).
-  // (also the partial rows of the few-channel LR / SAR encoder backward: 1024 x (9 CC^2 + CC) floats, train_kernels.hip)
+  // (also the partial rows of the few-channel LR / SAR encoder backward: 1024 x (9 CC^2 + CC) floats, stem_bwd.hip)
   size_t o_bn_sums = 0, bn_sums_bytes = 0, o_red = 0, red_bytes = 0;
   // FL arithmetic (conv_mfma_fl.hip) for the layers the wave-specialised SP kernel takes at 64 channels per item; per-layer range
   // flags (device words, one per FL image: bit 0 = a folded weight outside what fp16 holds) are read back at pack time
