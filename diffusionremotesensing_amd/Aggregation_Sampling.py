@@ -231,8 +231,11 @@ class split_aggregation_sampling:
         single = len(starts) == 1
         # what the network predicts (`Diffusion(prediction=, x0_clip=)`): its output becomes eps here, chunk by chunk against the
         # tiles it saw, since the chain's state is the scene; with "eps" and no clip nothing is launched
-        from .sampling import check_prediction, converts_prediction
+        # with `x0_threshold` the clamp is dynamic thresholding, per tile: the image the network saw
+        from .sampling import check_prediction, check_threshold, converts_prediction
         prediction, x0_clip = check_prediction(getattr(d, "prediction", "eps"), getattr(d, "x0_clip", None))
+        x0_threshold = check_threshold(getattr(d, "x0_threshold", None), x0_clip)
+        dynamic = {"x0_threshold": x0_threshold} if x0_threshold is not None else {}
         convert = prediction != "eps" or x0_clip is not None
 
         def predict(engine, x, t, first):
@@ -241,7 +244,7 @@ class split_aggregation_sampling:
                 engine.forward(x_tiles, t, lr_chunks[j], m, reuse_cond=single and not first,
                                check_weights=first and j == 0, out=eps_buf[c0:c0 + size])
                 if convert:
-                    hip_ops.pred_to_eps_(eps_buf[c0:c0 + size], x_tiles, t, d.alpha_hat, prediction, x0_clip)
+                    hip_ops.pred_to_eps_(eps_buf[c0:c0 + size], x_tiles, t, d.alpha_hat, prediction, x0_clip, **dynamic)
             return eps_buf
         if convert:
             converts_prediction(predict)
@@ -338,7 +341,7 @@ def launch(args):
     import os
 
     from .colorfix import cli_color_fix
-    from .cli import cli_prediction, cli_sampling_steps
+    from .cli import cli_prediction, cli_sampling_steps, cli_threshold
     device = args.device
     task = getattr(args, "task", "superres")
     if args.UNet_type.lower() != "residual attention unet":
@@ -354,7 +357,7 @@ def launch(args):
         diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot_path,
                               noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02, device=device,
                               image_size=args.model_input_size, model_name=args.model_name, multiple_gpus=False,
-                              ema_smoothing=False, **cli_prediction(args))
+                              ema_smoothing=False, **cli_prediction(args), **cli_threshold(args))
         out_channels = args.NDVI_channels
     elif task == "superres":
         from .train_diffusion_superres import Diffusion
@@ -365,7 +368,7 @@ def launch(args):
                               magnification_factor=args.magnification_factor, device=device,
                               image_size=args.model_input_size, model_name=args.model_name,
                               Degradation_type=args.Degradation_type, multiple_gpus=False, ema_smoothing=False,
-                              **cli_prediction(args))
+                              **cli_prediction(args), **cli_threshold(args))
         out_channels = None
     else:
         raise ValueError(f"--task {task!r} must be 'superres' or 'sar_to_ndvi'")

@@ -58,8 +58,8 @@ def cli_sampling_steps(args):
 
 
 def add_prediction_args(p, in_help=True):
-    """--prediction / --x0_clip of the outer command lines (the trainers' `main` parsers, `evaluate`, the tiler): the
-    `prediction` / `x0_clip` of `Diffusion` (`cli_prediction`).  `in_help` False registers them without a --help entry: the
+    """--prediction / --x0_clip / --x0_threshold of the outer command lines (the trainers' `main` parsers, `evaluate`, the
+    tiler): the `prediction` / `x0_clip` of `Diffusion` (`cli_prediction`) and its `x0_threshold` (`cli_threshold`).  `in_help` False registers them without a --help entry: the
     trainers' help texts are recorded (tests/golden/train_loop_transcripts.json), README.md describes the flags."""
     p.add_argument("--prediction", type=str, choices=("eps", "v", "x0"), default="eps",
                    help="what the network predicts: the noise eps (the reference), v = sqrt(ah) eps - sqrt(1 - ah) x0, or the "
@@ -68,6 +68,21 @@ def add_prediction_args(p, in_help=True):
     p.add_argument("--x0_clip", type=cli_x0_clip, default=None,
                    help="'none' or 'LO,HI' (--x0_clip=-1,1 for a negative bound): clamp the clean image every reverse step "
                         "implies to this range while sampling; default none" if in_help else argparse.SUPPRESS)
+    p.add_argument("--x0_threshold", type=cli_x0_threshold, default=None,
+                   help="P, 0 < P <= 1, with --x0_clip: dynamic thresholding (Imagen) - per image, where the P-quantile of "
+                        "|x0 - centre| exceeds the half-range, the clean image is compressed into the range instead of clamped; "
+                        "default none" if in_help else argparse.SUPPRESS)
+    return p
+
+
+def cli_x0_threshold(text):
+    """The value of --x0_threshold as `Diffusion`'s `x0_threshold`: a P in (0, 1], read while the command line is parsed."""
+    try:
+        p = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} must be a number in (0, 1]") from None
+    if not 0.0 < p <= 1.0:
+        raise argparse.ArgumentTypeError(f"{text!r} must lie in (0, 1]")
     return p
 
 
@@ -88,6 +103,12 @@ def cli_x0_clip(text):
 def cli_prediction(args):
     """`add_prediction_args`' flags as keyword arguments of a `Diffusion` (a namespace without them: the defaults)."""
     return {"prediction": getattr(args, "prediction", "eps"), "x0_clip": getattr(args, "x0_clip", None)}
+
+
+def cli_threshold(args):
+    """`add_prediction_args`' --x0_threshold as a keyword argument of a `Diffusion` (merged next to `cli_prediction`; a
+    namespace without it: off).  Without --x0_clip the constructor refuses it (`sampling.check_threshold`)."""
+    return {"x0_threshold": getattr(args, "x0_threshold", None)}
 
 
 def add_bsr_args(p):

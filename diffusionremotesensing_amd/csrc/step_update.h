@@ -217,3 +217,49 @@ __device__ __forceinline__ float drs_pred_eps(const DrsPredCoef& k, float x, flo
   const float u = k.ea * x, w = k.eb * q;
   return u + w;
 }
+
+// Dynamic thresholding of the implied x0 (Saharia et al., "Imagen", 2022, section 2.3; x0_threshold.hip: drs_pred_to_eps_dyn,
+// DESIGN.md section 24), element by element.  The x0 is the clip path's `q` before its clamp (forms CLIP_LINEAR / CLIP_PRED of
+// drs_pred_coef); c = (lo + hi) / 2 and r = (hi - lo) / 2 are formed in fp64 and rounded once.  An image is ranked by
+// key = bits(|fl(x0 - c)|) as an unsigned integer, a NaN or an infinity as +inf; its scale s is the key of one rank.
+__device__ __forceinline__ float drs_pred_x0(const DrsPredCoef& k, float x, float p) {
+#pragma clang fp contract(off)
+  if (k.form != DrsPredCoef::CLIP_LINEAR) return p;
+  const float u = k.xa * x, w = k.xb * p;
+  return u + w;
+}
+__device__ __forceinline__ unsigned drs_dyn_key(float x0, float c) {
+  const unsigned key = __float_as_uint(fabsf(x0 - c));
+  return key < 0x7f800000u ? key : 0x7f800000u;
+}
+// s <= r or s not finite: the static clamp of drs_pred_eps; otherwise clamp(c + clamp(x0 - c, -s, s) rho, lo, hi) with
+// rho = (float)((double)r / s), products and sums rounded one by one.  A NaN or an infinity stays what it is.
+struct DrsDynScale {
+  float c, s, rho;
+  bool dynamic;
+  __device__ DrsDynScale(float lo, float hi, float scale) {
+    c = (float)(((double)lo + (double)hi) / 2.0);
+    const float r = (float)(((double)hi - (double)lo) / 2.0);
+    s = scale;
+    dynamic = scale > r && scale < __builtin_huge_valf();
+    rho = dynamic ? (float)((double)r / (double)scale) : 1.f;
+  }
+};
+__device__ __forceinline__ float drs_dyn_q(const DrsPredCoef& k, const DrsDynScale& y, float x0) {
+#pragma clang fp contract(off)
+  if (!(fabsf(x0) < __builtin_huge_valf())) return x0;
+  float q = x0;
+  if (y.dynamic) {
+    const float d = x0 - y.c;
+    const float e = d < -y.s ? -y.s : (d > y.s ? y.s : d);
+    const float m = e * y.rho;
+    q = y.c + m;
+  }
+  return q < k.lo ? k.lo : (q > k.hi ? k.hi : q);
+}
+// eps = fl(ea x) + fl(eb q) of the clip forms, q the clamped or thresholded x0
+__device__ __forceinline__ float drs_eps_of_x0(const DrsPredCoef& k, float x, float q) {
+#pragma clang fp contract(off)
+  const float u = k.ea * x, w = k.eb * q;
+  return u + w;
+}

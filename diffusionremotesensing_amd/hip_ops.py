@@ -4,6 +4,7 @@ PyTorch is used only for device memory and the current stream.  Every wrapper re
 ROCm-device fp32 contiguous tensors and raises otherwise: there is no CPU path.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -170,14 +171,43 @@ def noise_v_target(x0, eps, t, alpha_hat):
     return x_t, v
 
 
-def pred_to_eps_(pred, x, t, alpha_hat, prediction="eps", x0_clip=None, pred_uncond=None, cfg_scale=0.0, out=None):
+def threshold_rank(x0_threshold, chw):
+    """The 0-based rank k = floor(p (chw - 1)) of the order statistic behind `x0_threshold` = p, 0 < p <= 1, among chw values:
+    torch.quantile(..., interpolation="lower")."""
+    p = float(x0_threshold)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"x0_threshold={x0_threshold!r} must lie in (0, 1]")
+    return min(max(int(math.floor(p * (chw - 1))), 0), max(chw - 1, 0))
+
+
+_THRESHOLD_WS = {}  # device index -> uint8 workspace of drs_x0_quantile / drs_pred_to_eps_dyn, grown as needed
+
+
+def _threshold_workspace(lib, n, device):
+    need = lib.drs_x0_threshold_workspace_bytes(n)
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    ws = _THRESHOLD_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _THRESHOLD_WS[key] = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    return ws
+
+
+def pred_to_eps_(pred, x, t, alpha_hat, prediction="eps", x0_clip=None, pred_uncond=None, cfg_scale=0.0, out=None,
+                 x0_threshold=None, scale_out=None):
     """The network's `pred` (n, ...) - of kind `prediction`: "eps", "v" or "x0" - as the eps the reverse-step wrappers take, in
     place (or into `out`), against the state `x` the network saw at the levels `t` (n int64 values on the device); include/
     drs_hip.h: drs_pred_to_eps.  With `pred_uncond` the prediction is torch.lerp(pred_uncond, pred, cfg_scale) first; with
-    `x0_clip=(lo, hi)` the x0 the prediction implies is clamped to that range before eps is formed from it.  Returns eps."""
+    `x0_clip=(lo, hi)` the x0 the prediction implies is clamped to that range before eps is formed from it.  Returns eps.
+    With `x0_threshold=p` (0 < p <= 1; needs `x0_clip`) the clamp is dynamic thresholding instead (drs_pred_to_eps_dyn): per
+    image, s = the floor(p (chw - 1))-th smallest |x0 - centre|; where s exceeds the half-range, x0 is clamped to centre +- s and
+    rescaled into the range.  `scale_out`: (n,) fp32, gets every image's s.  `x` must then not share memory with the result."""
     lib = _lib.load()
     if prediction not in PREDICTIONS:
         raise ValueError(f"prediction={prediction!r} must be one of {tuple(PREDICTIONS)}")
+    if x0_threshold is not None:
+        threshold_rank(x0_threshold, 1)  # (ValueError for a p outside (0, 1])
+        if x0_clip is None:
+            raise ValueError("pred_to_eps_: x0_threshold needs x0_clip=(lo, hi), the range it thresholds to")
     _req_state(pred, "pred_to_eps_", "pred")
     x = _req(x, "x"); t = _req(t, "t", torch.int64); alpha_hat = _req(alpha_hat, "alpha_hat")
     pred_uncond = _req(pred_uncond, "pred_uncond") if pred_uncond is not None else None
@@ -193,12 +223,64 @@ def pred_to_eps_(pred, x, t, alpha_hat, prediction="eps", x0_clip=None, pred_unc
     if flag and not lo < hi:
         raise ValueError(f"pred_to_eps_: x0_clip=({lo}, {hi}) needs lo < hi")
     chw = pred.numel() // n if n else 0
+    if x0_threshold is not None:
+        k = threshold_rank(x0_threshold, chw)
+        if scale_out is not None:
+            _req_state(scale_out, "pred_to_eps_", "scale_out")
+            if scale_out.numel() != n:
+                raise RuntimeError(f"pred_to_eps_: scale_out has {scale_out.numel()} elements, pred has {n} images")
+        if n == 0 or chw == 0:
+            return out
+        if x.data_ptr() == out.data_ptr():
+            raise RuntimeError("pred_to_eps_: with x0_threshold, x and the result must be two buffers")
+        ws = _threshold_workspace(lib, n, pred.device)
+        with torch.cuda.device(pred.device):
+            st = lib.drs_pred_to_eps_dyn(_ptr(pred), _ptr(pred_uncond), float(cfg_scale), _ptr(x), _ptr(t), _ptr(alpha_hat),
+                                         alpha_hat.numel(), PREDICTIONS[prediction], lo, hi, k, _ptr(out), _ptr(scale_out), n,
+                                         chw, _ptr(ws), ws.numel(), _stream(pred.device))
+        _lib.check(st, "drs_pred_to_eps_dyn")
+        return out
+    if scale_out is not None:
+        raise ValueError("pred_to_eps_: scale_out is written with x0_threshold only")
     with torch.cuda.device(pred.device):
         st = lib.drs_pred_to_eps(_ptr(pred), _ptr(pred_uncond), float(cfg_scale), _ptr(x), _ptr(t), _ptr(alpha_hat),
                                  alpha_hat.numel(), PREDICTIONS[prediction], flag, lo, hi, _ptr(out), n, chw,
                                  _stream(pred.device))
     _lib.check(st, "drs_pred_to_eps")
     return out
+
+
+def x0_abs_quantile(pred, x, t, alpha_hat, prediction, x0_clip, q, pred_uncond=None, cfg_scale=0.0):
+    """(n,) fp32: per image of `pred`, the floor(q (chw - 1))-th smallest |x0 - (lo + hi) / 2| of the x0 the (guided) prediction
+    implies - the scale `pred_to_eps_(..., x0_threshold=q)` thresholds with, as found (include/drs_hip.h: drs_x0_quantile).
+    An exact order statistic (torch.quantile's interpolation="lower"), all bands ranked together; `pred` is left as it is."""
+    lib = _lib.load()
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"prediction={prediction!r} must be one of {tuple(PREDICTIONS)}")
+    pred = _req(pred, "pred"); x = _req(x, "x"); t = _req(t, "t", torch.int64); alpha_hat = _req(alpha_hat, "alpha_hat")
+    pred_uncond = _req(pred_uncond, "pred_uncond") if pred_uncond is not None else None
+    _req_numel("x0_abs_quantile", pred, (("x", x), ("pred_uncond", pred_uncond)), "pred")
+    n = pred.shape[0] if pred.dim() else 0
+    if t.numel() != n:
+        raise RuntimeError(f"x0_abs_quantile: t has {t.numel()} elements, pred has {n} images")
+    flag, lo, hi = _clamp_args(x0_clip, "x0_abs_quantile")
+    if not flag:
+        raise ValueError("x0_abs_quantile: x0_clip=(lo, hi) gives the range and is required")
+    if not lo < hi:
+        raise ValueError(f"x0_abs_quantile: x0_clip=({lo}, {hi}) needs lo < hi")
+    chw = pred.numel() // n if n else 0
+    k = threshold_rank(q, chw)
+    x0 = torch.empty_like(pred)
+    scale = torch.zeros(n, dtype=torch.float32, device=pred.device)
+    if n == 0 or chw == 0:
+        return scale
+    ws = _threshold_workspace(lib, n, pred.device)
+    with torch.cuda.device(pred.device):
+        st = lib.drs_x0_quantile(_ptr(pred), _ptr(pred_uncond), float(cfg_scale), _ptr(x), _ptr(t), _ptr(alpha_hat),
+                                 alpha_hat.numel(), PREDICTIONS[prediction], lo, hi, k, _ptr(x0), _ptr(scale), n, chw, _ptr(ws),
+                                 ws.numel(), _stream(pred.device))
+    _lib.check(st, "drs_x0_quantile")
+    return scale
 
 
 def timestep_table(noise_steps, n, device):

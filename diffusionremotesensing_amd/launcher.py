@@ -45,7 +45,8 @@ def train_model(args, diffusion_class, model, device, train_loader, val_loader, 
                                 snapshot_path=os.path.join(args.snapshot_folder_path, args.snapshot_name),
                                 noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02, device=device,
                                 image_size=args.image_size, model_name=args.model_name, multiple_gpus=args.multiple_gpus,
-                                ema_smoothing=args.ema_smoothing, **cli.cli_prediction(args), **diffusion_kwargs)
+                                ema_smoothing=args.ema_smoothing, **cli.cli_prediction(args), **cli.cli_threshold(args),
+                                **diffusion_kwargs)
     diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
                     train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
                     verbose=True, **cli.train_kwargs(args), **(train_kwargs or {}))

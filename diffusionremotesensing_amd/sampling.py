@@ -1,6 +1,7 @@
 """The reverse chain all three samplers and the tiler share: its moves (`chain_moves`), the argument checks, the loop with its
 fault checks and roll-back (`run_reverse_chain`) and the chain itself (`sample_chain`), whose one `step` takes every move."""
 import math
+import numbers
 import sys
 from typing import NamedTuple
 
@@ -40,6 +41,23 @@ def check_prediction(prediction="eps", x0_clip=None):
     if not lo < hi:
         raise ValueError(f"x0_clip=({lo}, {hi}) needs lo < hi")
     return prediction, (lo, hi)
+
+
+def check_threshold(x0_threshold=None, x0_clip=None):
+    """ValueError for an `x0_threshold` no `Diffusion` takes: None (off) or the quantile p, 0 < p <= 1, of dynamic thresholding
+    (Saharia et al. 2022: per image, the p-quantile s of |x0 - centre of x0_clip|; where s exceeds the half-range the implied x0
+    is clamped to centre +- s and rescaled into the range instead of being cut off at it).  A p needs the `x0_clip` that names
+    the range.  Returns p as a float, or None."""
+    if x0_threshold is None:
+        return None
+    if isinstance(x0_threshold, bool) or not isinstance(x0_threshold, numbers.Real):
+        raise ValueError(f"x0_threshold={x0_threshold!r} must be None or a number in (0, 1]")
+    p = float(x0_threshold)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"x0_threshold={x0_threshold!r} must lie in (0, 1]")
+    if x0_clip is None:
+        raise ValueError(f"x0_threshold={p} needs x0_clip=(lo, hi): the range the image is thresholded to")
+    return p
 
 
 def converts_prediction(predict):
@@ -315,11 +333,15 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
     x0 it implies is clamped to.  With anything but "eps" / None the result of `predict` is turned into eps right after the
     call, in place, against the x it was called with (one `hip_ops.pred_to_eps_`, which also forms the guided prediction: the
     update then gets one eps and cfg_scale 0), so every move above takes what it always took; a `predict` marked by
-    `converts_prediction` has done so itself.  With "eps" and None nothing is launched."""
+    `converts_prediction` has done so itself.  With "eps" and None nothing is launched.  `schedule.x0_threshold` (None when
+    it has none; a quantile p needs the clip: `check_threshold`) makes that one call threshold the implied x0 per image instead
+    of clamping it (`pred_to_eps_(..., x0_threshold=p)`); nothing else in the chain changes."""
     ddim = sampling_steps is not None
     solver, spacing = plan_of(sampling_steps)
     dpm = solver == "dpmpp_2m"
     prediction, x0_clip = check_prediction(getattr(schedule, "prediction", "eps"), getattr(schedule, "x0_clip", None))
+    x0_threshold = check_threshold(getattr(schedule, "x0_threshold", None), x0_clip)
+    dynamic = {"x0_threshold": x0_threshold} if x0_threshold is not None else {}
     convert = (prediction != "eps" or x0_clip is not None) and not getattr(predict, "converts_prediction", False)
     moves = chain_moves(schedule.noise_steps, sampling_steps, resample, jump, spacing, schedule.alpha_hat if ddim else None)
     with torch.no_grad():
@@ -346,7 +368,7 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
                 guide = cfg_scale
                 if convert:  # (the generation sampler's rows are 2n wide: conditional | unconditional)
                     eps = hip_ops.pred_to_eps_(eps, x, t_rows[t][:shape[0]], schedule.alpha_hat, prediction, x0_clip,
-                                               pred_uncond=eps_uncond, cfg_scale=cfg_scale)
+                                               pred_uncond=eps_uncond, cfg_scale=cfg_scale, **dynamic)
                     eps_uncond, guide = None, 0.0
                 noise = draw(t) if t_to > 0 and (known is not None or not ddim or eta > 0) else None
                 if dpm:

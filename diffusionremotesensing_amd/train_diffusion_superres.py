@@ -34,7 +34,7 @@ from .launcher import launch_device, make_loaders, save_final_samples, train_mod
 from .losses import DiffusionLoss, LossAwareSampler, LossBins, min_snr_weights
 from .optim import FusedAdam, FusedAdamW, WarmupCosine
 from .sampling import (CHAIN_CHECK_EVERY, _is_int, _repeat_members, asks_for_known_pixels,  # noqa: F401 - re-exported
-                       check_ensemble_args, check_inpaint_args, check_prediction, check_sampling_args, check_solver_known,
+                       check_ensemble_args, check_inpaint_args, check_prediction, check_sampling_args, check_threshold, check_solver_known,
                        ddim_chain_noise,
                        ddim_timesteps, ensemble_chunks, inpaint_schedule, known_tensors, run_reverse_chain, sample_chain,
                        sampling_plan)
@@ -78,11 +78,16 @@ class TrainRun:
 class Diffusion:
     def __init__(self, noise_schedule: str, model: nn.Module, snapshot_path: str, noise_steps=1000, beta_start=1e-4,
                  beta_end=0.02, device="cuda", magnification_factor=4, image_size=224, model_name="superres",
-                 Degradation_type="BSRGAN", multiple_gpus=False, ema_smoothing=False, prediction="eps", x0_clip=None):
+                 Degradation_type="BSRGAN", multiple_gpus=False, ema_smoothing=False, prediction="eps", x0_clip=None,
+                 x0_threshold=None):
         # not in the reference, whose networks predict the noise: what this one predicts ("eps", "v" or "x0": the training
         # target, and what sampling converts to eps before every update) and the range the x0 implied at every reverse step
         # is clamped to (None or (lo, hi); a plain attribute, read at the start of every chain).  DESIGN.md section 23.
         self.prediction, self.x0_clip = check_prediction(prediction, x0_clip)
+        # ... and the quantile of dynamic thresholding (None, or p in (0, 1] with an x0_clip: per image, where the p-quantile of
+        # |x0 - centre| exceeds the half-range, x0 is compressed into the range instead of cut off at it).  A plain attribute
+        # like x0_clip, not written into snapshots.  DESIGN.md section 24.
+        self.x0_threshold = check_threshold(x0_threshold, self.x0_clip)
         self.noise_steps = noise_steps
         self.beta_start = beta_start
         self.beta_end = beta_end

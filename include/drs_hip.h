@@ -181,6 +181,37 @@ DRS_API int drs_pred_to_eps(const float* pred, const float* pred_uncond, float c
                             const float* alpha_hat, int noise_steps, int kind, int clip, float lo, float hi, float* out, int n,
                             int64_t chw, drs_stream_t stream);
 
+/* Dynamic thresholding of the implied x0 (Saharia et al., "Imagen", 2022, section 2.3), per image, in place of the static clip of
+ * drs_pred_to_eps (arguments as there; the clip range [lo, hi] is mandatory).  With c = (float)((lo + hi) / 2) and
+ * r = (float)((hi - lo) / 2), formed in double, and x0 the clip path's value before its clamp:
+ *   d = fl(x0 - c),  key = bits(|d|) as an unsigned integer, a NaN or an infinity ranked as +inf (0x7f800000)
+ *   s = the value whose key is the k-th smallest (0-based) of the image's chw keys, all bands together: an exact order
+ *       statistic, torch.quantile(|d|, p, interpolation="lower") for k = floor(p (chw - 1)); no interpolation
+ *   s <= r, or s not finite:  q = clamp(x0, lo, hi), the bits drs_pred_to_eps gives that image with clip != 0
+ *   otherwise:                q = clamp(c + clamp(d, -s, s) * rho, lo, hi),  rho = (float)((double)r / s)
+ *   eps = fl(ea x) + fl(eb q) with the clip path's coefficients; a non-finite x0 element is never clamped.
+ * Products and sums are fp32 and rounded one by one.  Images at a level where drs_pred_to_eps does not form an x0 (s == 0,
+ * an EPS prediction where a == 0, a t[i] outside the table) get exactly its result and the scale 0: nothing is thresholded.
+ * The selection is a radix select over the 31 key bits (digits of 11, 10 and 10 bits, one streaming pass each, integer
+ * counts only): s and every output are bitwise reproducible.  No allocation, no device-to-host copy, no synchronisation:
+ * `workspace` (device, 4-byte aligned, >= drs_x0_threshold_workspace_bytes(n) bytes) is zeroed on `stream` by the call.
+ *
+ * drs_x0_quantile: the selection alone.  out = the implied x0 (the eps of drs_pred_to_eps for the images named last above),
+ * scale[i] = s of image i as found, before the s <= r rule.
+ * drs_pred_to_eps_dyn: the whole operation; out = eps, scale_out (optional, may be NULL) as `scale` above.
+ * `out` may be `pred`; `x` must not be `out` (x is read again after out has been written).
+ * DRS_ERR_ARG: null pointer (pred, x, t, alpha_hat, out, workspace, scale of drs_x0_quantile), unknown kind, lo >= hi,
+ * pred_uncond with a cfg_scale that is not finite, x == out, k outside [0, chw), workspace_bytes too small;
+ * DRS_ERR_SHAPE: n < 0, chw < 0 or chw >= 2^32, noise_steps <= 0.  n == 0 or chw == 0: DRS_OK, nothing is done. */
+DRS_API size_t drs_x0_threshold_workspace_bytes(int n);
+DRS_API int drs_x0_quantile(const float* pred, const float* pred_uncond, float cfg_scale, const float* x, const int64_t* t,
+                            const float* alpha_hat, int noise_steps, int kind, float lo, float hi, int64_t k, float* out,
+                            float* scale, int n, int64_t chw, void* workspace, size_t workspace_bytes, drs_stream_t stream);
+DRS_API int drs_pred_to_eps_dyn(const float* pred, const float* pred_uncond, float cfg_scale, const float* x, const int64_t* t,
+                                const float* alpha_hat, int noise_steps, int kind, float lo, float hi, int64_t k, float* out,
+                                float* scale_out, int n, int64_t chw, void* workspace, size_t workspace_bytes,
+                                drs_stream_t stream);
+
 /* One Adam step over many tensors in ONE launch (torch.optim.Adam defaults: no weight decay, no amsgrad):
  *   m = lerp(m, g, 1-beta1); v = v*beta2 + (1-beta2)*g*g; p -= lr/(1-beta1^step) * m / (sqrt(v)/sqrt(1-beta2^step) + eps)
  * `table` (device): ntensors x drs_adam_tensor {p, g, m, v, n, step}; entries with g == NULL are skipped (parameters
