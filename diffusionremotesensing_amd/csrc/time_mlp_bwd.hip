@@ -4,7 +4,8 @@
 // ---------------------------------------------------------------------------------------------------------------
 // Time-embedding MLP backward (reference :143-151,:161): out = relu(W2 silu(W1 e + b1) + b2), e = posenc(t) (constant).
 // dim/8 blocks per MLP, each owning 8 rows of every gradient; loops over the batch.  dtemb = gradient w.r.t. out
-// (already summed over pixels by the caller).
+// (already summed over pixels by the caller).  Each of dW1 / db1 / dW2 / db2 of an MLP and dlabel may be null (the caller
+// does not want it): every store tests its own pointer, block-uniformly.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void time_mlp_bwd_kernel(const long long* __restrict__ t,
                                                            const float* __restrict__ inv_freq, DrsMlpBwdTable tab,
@@ -97,12 +98,12 @@ __global__ __launch_bounds__(256) void time_mlp_bwd_kernel(const long long* __re
 #pragma unroll
   for (int r = 0; r < RB; ++r) {
     if (r0 + r >= dim) break;
-    if (tid < dim) dW2[(size_t)(r0 + r) * dim + tid] += acc2[r];
-    if (tid < 100) dW1[(size_t)(r0 + r) * 100 + tid] += acc1[r];
+    if (dW2 && tid < dim) dW2[(size_t)(r0 + r) * dim + tid] += acc2[r];
+    if (dW1 && tid < 100) dW1[(size_t)(r0 + r) * 100 + tid] += acc1[r];
   }
   if (tid >= 128 && tid < 128 + RB && r0 + tid - 128 < dim) {
-    db2[r0 + tid - 128] += accb2;
-    db1[r0 + tid - 128] += accb1;
+    if (db2) db2[r0 + tid - 128] += accb2;
+    if (db1) db1[r0 + tid - 128] += accb1;
   }
 }
 int drs_launch_time_mlp_bwd(const long long* t, const float* inv_freq, const DrsMlpBwdTable& tab, int stride, int B,

@@ -452,15 +452,17 @@ static int bwd_lr_branch(BwdCtx& c) {
 static int bwd_time_mlps(BwdCtx& c, const int64_t* t, const int64_t* labels, int label_batch) {
   const drs_plan* plan = c.plan;
   DrsMlpBwdTable tab = {};
+  float* dlabel = labels ? c.G(plan->label_emb) : nullptr;
   for (Mlp* m : plan->mlps) {
-    if (!c.G(m->w1)) continue;
+    // an MLP takes part when any of its four gradients is wanted, or the label gradient (every MLP adds its share to it)
+    if (!c.G(m->w1) && !c.G(m->b1) && !c.G(m->w2) && !c.G(m->b2) && !dlabel) continue;
     DRS_REQUIRE(tab.n < 8, DRS_ERR_SHAPE, "backward: more than 8 time MLPs");
     tab.m[tab.n++] = DrsMlpBwd{c.PARAM(m->w1), c.PARAM(m->b1), c.PARAM(m->w2), c.temb + m->temb_off, c.dtemb + m->temb_off,
                                c.G(m->w1), c.G(m->b1), c.G(m->w2), c.G(m->b2), m->dim};
   }
   return drs_launch_time_mlp_bwd((const long long*)t, (const float*)(c.pk + plan->o_inv_freq), tab, plan->temb_total, c.B,
                                  labels ? c.PARAM(plan->label_emb) : nullptr, (const long long*)labels, label_batch,
-                                 c.cfg.num_classes, labels ? c.G(plan->label_emb) : nullptr, c.s);
+                                 c.cfg.num_classes, dlabel, c.s);
 }
 
 extern "C" int drs_unet_backward(drs_plan* plan, const void* packed, void* packed_bwd, size_t packed_bwd_bytes,

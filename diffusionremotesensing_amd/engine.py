@@ -126,6 +126,7 @@ class HipUNetEngine:
             self._channels = (cx, cout, cc)
             plan = _Plan(_lib.load(), cfg, device)
             plan.train = train
+            plan.train_serial = 0  # number of the last train-mode forward on this plan (its workspace holds that forward)
             self._plans[key] = plan
             while len(self._plans) > max(self.max_plans, 1):
                 self._plans.popitem(last=False)  # its workspace is freed once no autograd node / caller holds the plan
@@ -245,6 +246,7 @@ class HipUNetEngine:
                 plan.cond_key = (lr_img.data_ptr(), lr_img._version)
             if train:  # the kernels updated running_mean / running_var in place; num_batches_tracked follows here
                 self._bn_epoch += 1
+                plan.train_serial += 1  # autograd nodes of earlier forwards on this plan can no longer run their backward
                 nbt = [b for k, b in m.named_buffers() if k.endswith("num_batches_tracked")]
                 with torch.no_grad():
                     torch._foreach_add_(nbt, 1)
@@ -387,7 +389,9 @@ class HipUNetEngine:
 
 class _UNetTrainFn(torch.autograd.Function):
     """Autograd node of one train-mode UNet forward: forward = drs_unet_forward_labels on the train plan, backward =
-    drs_unet_backward_labels.  No gradient flows to x_t / the conditioning image (data in the reference's loops)."""
+    drs_unet_backward_labels.  No gradient flows to x_t / the conditioning image (data in the reference's loops).
+    The backward reads the plan's workspace as this node's forward left it and consumes it (BatchNorm turns Z into dZ in
+    place): it runs once, and only while no later train-mode forward has used the plan."""
 
     @staticmethod
     def forward(ctx, engine, x, timestep, lr_img, mag, labels, *params):
@@ -397,6 +401,7 @@ class _UNetTrainFn(torch.autograd.Function):
             labels = labels.to(torch.int64).contiguous()
         out = engine.forward(x, timestep, lr_img, mag, _in_autograd_fn=True, labels=labels)
         ctx.engine, ctx.plan = engine, engine._last_plan
+        ctx.serial, ctx.spent = ctx.plan.train_serial, False
         sd = engine._tensors(ctx.plan.param_names)
         ctx.names = [n for n in ctx.plan.param_names if sd[n].requires_grad]
         ctx.labels = labels
@@ -405,6 +410,14 @@ class _UNetTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        if ctx.spent:
+            raise RuntimeError("UNet backward ran twice for one forward: the first backward consumed the activations in the "
+                               "plan's workspace (retain_graph=True cannot keep them); run the forward again")
+        if ctx.plan.train_serial != ctx.serial:
+            raise RuntimeError("UNet backward after a later train-mode forward of the same shape: the plan's workspace holds "
+                               f"forward {ctx.plan.train_serial}, this gradient belongs to forward {ctx.serial}; call "
+                               "backward before the next forward on this plan")
+        ctx.spent = True
         x, timestep = ctx.saved_tensors
         grads = ctx.engine.backward(ctx.plan, x, timestep, dout, ctx.labels)
         if ctx.labels is None:  # unconditional step: autograd leaves label_emb.weight.grad = None (Adam skips it)

@@ -725,7 +725,9 @@ DRS_API int drs_unet_read_tensor(const drs_plan* plan, int i, const void* worksp
  * drs_unet_param_name(): grads[i] = device pointer of drs_unet_param_numel(i) floats, or NULL to skip (BatchNorm
  * running statistics, which receive no gradient, must be NULL).  Gradients are OVERWRITTEN (zeroed first).
  * Requires a DRS_PLAN_TRAIN plan with lr_batch == batch and the workspace exactly as the last drs_unet_forward
- * (train mode) on this plan left it; `packed_bwd` is scratch for the re-packed (transposed) weights.
+ * (train mode) on this plan left it; `packed_bwd` is scratch for the re-packed (transposed) weights.  The call consumes
+ * that workspace (BatchNorm turns Z into dZ in place): one backward per forward.  Any subset of the slots may be NULL,
+ * down to a single wanted gradient; a NULL slot is neither written nor zeroed and costs no other gradient anything.
  * ------------------------------------------------------------------------------------------ */
 DRS_API size_t drs_unet_packed_bwd_bytes(const drs_plan* plan);
 DRS_API int drs_unet_backward(drs_plan* plan, const void* packed, void* packed_bwd, size_t packed_bwd_bytes, const float* x,

@@ -43,13 +43,15 @@ def oracle_leaves(sd, live, dtype=torch.float64):
     return out
 
 
-def oracle_step(variant, sd, live, x, t, cond, noise, mag=1, dtype=torch.float64):
+def oracle_step(variant, sd, live, x, t, cond, noise, mag=1, dtype=torch.float64, dout=None):
     """One training step of the oracle: (prediction, loss, {live name: gradient or None}, {BatchNorm prefix: (running_mean,
-    running_var)}).  `cond` is the LR image (superres), the SAR image (sar) or the labels (generation; None = unconditional)."""
+    running_var)}).  `cond` is the LR image (superres), the SAR image (sar) or the labels (generation; None = unconditional).
+    With `dout` (a tensor of the prediction's shape) the backward is pred.backward(dout) instead of the MSE's: `noise` is
+    not read and the loss returned is sum(pred * dout), the scalar that has this upstream gradient."""
     from oracle import unet_oracle as U
     live = set(live)
     leaves = oracle_leaves(sd, {canonical(n) for n in live}, dtype)
-    x, noise = x.to(dtype), noise.to(dtype)
+    x = x.to(dtype)
     stats = {}
     if variant == "superres":
         pred = U.unet_forward(leaves, x, t, cond.to(dtype), mag, training=True, stats=stats)
@@ -59,8 +61,13 @@ def oracle_step(variant, sd, live, x, t, cond, noise, mag=1, dtype=torch.float64
         pred = U.unet_forward_generation(leaves, x, t, cond, training=True, stats=stats)
     else:
         raise ValueError(variant)
-    loss = F.mse_loss(pred, noise)
-    loss.backward()
+    if dout is None:
+        loss = F.mse_loss(pred, noise.to(dtype))
+        loss.backward()
+    else:
+        dout = dout.to(dtype)
+        loss = (pred.detach() * dout).sum()
+        pred.backward(dout)
     grads = {n: (None if leaves[n].grad is None else leaves[n].grad.detach().clone()) for n in live}
     stats = {k: (rm.detach(), rv.detach()) for k, (rm, rv) in stats.items()}
     return pred.detach(), loss.item(), grads, stats
@@ -71,11 +78,19 @@ def model_grads(model):
     return {n: (None if p.grad is None else p.grad.detach().cpu()) for n, p in model.named_parameters()}
 
 
-def grad_errors(got, ref):
+def grad_scale(ref):
+    """The norm of the largest true gradient: what a structural zero is measured against."""
+    return max(r.norm().item() for r in ref.values() if r is not None)
+
+
+def grad_errors(got, ref, scale=None):
     """{name: (max-rel, rel-L2)} of every parameter with a live, non-negligible true gradient, and the list of problems
-    that no tolerance excuses (a missing or extra gradient, the wrong shape, a structural zero that is not small)."""
+    that no tolerance excuses (a missing or extra gradient, the wrong shape, a structural zero that is not small).
+    `scale`: grad_scale of the FULL gradient set when `ref` is a subset of it (some parameters frozen), so that the same
+    tensors count as structural zeros as in the full comparison; default: grad_scale(ref)."""
     assert set(got) == set(ref), (sorted(set(got) ^ set(ref)))[:8]
-    scale = max(r.norm().item() for r in ref.values() if r is not None)
+    if scale is None:
+        scale = grad_scale(ref)
     errs, hard = {}, []
     for name, r in ref.items():
         g = got[name]
@@ -97,10 +112,10 @@ def grad_errors(got, ref):
     return errs, hard
 
 
-def check_grads(got, ref, rel_l2, max_rel=None, what=""):
+def check_grads(got, ref, rel_l2, max_rel=None, what="", scale=None):
     """Assert every gradient of `got` against `ref` (see grad_errors); returns (worst name, max-rel, rel-L2) by rel-L2 and
     prints it."""
-    errs, hard = grad_errors(got, ref)
+    errs, hard = grad_errors(got, ref, scale)
     bad = [(n, e_max, e_l2) for n, (e_max, e_l2) in errs.items()
            if not (e_l2 <= rel_l2 and (max_rel is None or e_max <= max_rel))]
     worst = max(errs.items(), key=lambda kv: kv[1][1])

@@ -22,10 +22,10 @@ import os
 
 import pytest
 import torch
-import torch.nn.functional as F
 
-from conftest import golden_inputs, rel_errors
-from grad_check import MAX_REL_F32, REL_L2_BF16X3, REL_L2_F32, canonical, check_grads, model_grads, oracle_step
+from conftest import golden_inputs
+from grad_check import MAX_REL_F32, REL_L2_BF16X3, REL_L2_F32, check_grads
+from train_step import build_model as _model, step as _step  # noqa: F401 (_model: used by test_gpu_guard.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,58 +40,6 @@ def dev():
     _lib.load()
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     return torch.device("cuda:0")
-
-
-def _model(dev, variant, sd):
-    if variant == "superres":
-        from diffusionremotesensing_amd.UNet_model_superres import Residual_Attention_UNet_superres
-        m = Residual_Attention_UNet_superres(3, 3, dev)
-    elif variant == "sar":
-        from diffusionremotesensing_amd.UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
-        m = Residual_Attention_UNet_SAR_TO_NDVI(2, 1, dev)
-    else:
-        from diffusionremotesensing_amd.generate_new_imgs.UNet_model_generation import Residual_Attention_UNet_generation
-        m = Residual_Attention_UNet_generation(3, 3, 10, dev)
-    m.load_state_dict(sd)
-    return m.to(dev).train()
-
-
-def _step(dev, variant, sd, x, t, cond, noise, mag=1, train_impl=None):
-    """The HIP training step and the float64 oracle's on the same batch; checks the loss and every BatchNorm's running
-    statistics, returns (HIP gradients, oracle gradients)."""
-    m = _model(dev, variant, sd)
-    eng = m.hip_engine()
-    if train_impl is not None:
-        eng.set_impl(train_impl, train_impl=train_impl)
-    # forward-side bars: the train-mode prediction and the running statistics of the exact-fp32 plans vs those of the
-    # split-bf16 training forward (test_gpu_parity.py's train-mode bars)
-    tol = 1e-3 if train_impl == "mfma_bf16x3" else 1e-4
-    args = (x.to(dev), t.to(dev), None if cond is None else cond.to(dev))
-    if variant == "superres":
-        args = args + (mag,)
-    pred = m(*args)
-    loss = F.mse_loss(pred, noise.to(dev))
-    loss.backward()
-    torch.cuda.synchronize()
-    eng.check_faults()
-    got = model_grads(m)
-    want, ref_loss, ref, stats = oracle_step(variant, sd, list(got), x, t, cond, noise, mag)
-    e_max, e_l2 = rel_errors(pred.detach().cpu(), want)
-    assert e_l2 <= tol and e_max <= tol, ("prediction", e_max, e_l2)
-    assert abs(loss.item() - ref_loss) <= tol * ref_loss, (loss.item(), ref_loss)
-    # running statistics of EVERY BatchNorm (both registered names of a ResConvBlock BatchNorm are one tensor)
-    msd = m.state_dict()
-    bns = {canonical(k)[:-len(".running_mean")] for k in msd if k.endswith(".running_mean")}
-    assert bns == set(stats), sorted(bns ^ set(stats))[:8]
-    worst = (0.0, "")
-    for k, (rm, rv) in stats.items():
-        for what, got_s, want_s in (("running_mean", msd[k + ".running_mean"], rm), ("running_var", msd[k + ".running_var"], rv)):
-            e = max(rel_errors(got_s.cpu(), want_s))
-            worst = max(worst, (e, f"{k}.{what}"))
-            assert e <= tol, (k, what, e)
-        assert int(msd[k + ".num_batches_tracked"]) == int(sd[k + ".num_batches_tracked"]) + 1, k
-    print(f"  prediction max-rel {e_max:.2e} rel-L2 {e_l2:.2e}; running statistics of {len(stats)} BatchNorms: worst {worst[0]:.2e} ({worst[1]})")
-    return got, ref
 
 
 def _bars(impl):

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from conftest import golden_inputs
-from grad_check import MAX_REL_F32, REL_L2_F32, check_grads, grad_errors, oracle_step
+from grad_check import MAX_REL_F32, REL_L2_F32, check_grads, grad_errors, grad_scale, oracle_step
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -194,3 +194,80 @@ def test_check_rules_for_unused_and_structural_zeros(g5_f64):
     got = dict(grads)  # rounding noise on a structural zero is fine
     got[zeros[0]] = torch.full_like(grads[zeros[0]], 1e-7 * scale)
     check_grads(got, grads, REL_L2_F32, MAX_REL_F32)
+
+
+# ---- what the frozen-slot tests (tests/test_gpu_backward_contract.py) rely on ------------------------------------------
+def test_check_fails_on_wanted_gradient_left_at_zero(g5_f64):
+    """A backward that skips a wanted slot leaves the zeros of its clearing pass: that fails, for a large tensor and for the
+    smallest live one alike."""
+    _, _, grads, _ = g5_f64
+    errs, _ = grad_errors(grads, grads)
+    smallest = min(errs, key=lambda n: grads[n].norm().item())
+    for name in ("bottle_neck.time_mlp.2.weight", "conv_blocks.1.time_mlp.0.bias", smallest):
+        got = dict(grads)
+        got[name] = torch.zeros_like(grads[name])
+        e, hard = grad_errors(got, grads)
+        assert not hard and abs(e[name][1] - 1.0) < 1e-12, (name, e[name])
+        with pytest.raises(AssertionError, match=name.replace(".", r"\.")):
+            check_grads(got, grads, REL_L2_F32, MAX_REL_F32, "zeros")
+
+
+def test_check_fails_on_label_gradient_without_one_mlp(seeded_sd_gen):
+    """d(label_emb.weight) is the sum of one share per time MLP (every MLP reads e = posenc(t) + label_emb[y]).  The shares
+    come from the oracle itself: with an MLP's first bias given per sample, its gradient is d(pre1) per sample, and the
+    share is that times W1, added onto the rows of the samples' classes.  Dropping any one share fails the check."""
+    from diffusionremotesensing_amd import synthetic
+    from diffusionremotesensing_amd.generate_new_imgs.UNet_model_generation import Residual_Attention_UNet_generation
+    names = [n for n, _ in Residual_Attention_UNet_generation(3, 3, 10, "cpu").named_parameters()]
+    x = synthetic.tensor_normal("grads.gen.x", (3, 3, 24, 40))
+    noise = synthetic.tensor_normal("grads.gen.noise", (3, 3, 24, 40))
+    t, y = torch.tensor([1, 800, 1499]), torch.tensor([4, 9, 4])
+    b1s = [n for n in names if n.endswith(".time_mlp.0.bias")]
+    assert len(b1s) == 7
+    sd = dict(seeded_sd_gen)
+    for n in b1s:
+        sd[n] = sd[n].expand(3, -1).clone()  # F.linear broadcasts it: same forward, one gradient row per sample
+    _, loss, grads, _ = oracle_step("generation", sd, names, x, t, y, noise)
+    _, loss0, grads0, _ = oracle_step("generation", seeded_sd_gen, names, x, t, y, noise)
+    assert loss == loss0
+    full = grads0["label_emb.weight"]
+    assert torch.equal(grads["label_emb.weight"], full)
+    shares = {}
+    for n in b1s:
+        w1 = seeded_sd_gen[n[:-len("bias")] + "weight"].double()
+        shares[n] = torch.zeros_like(full).index_add_(0, y, grads[n] @ w1)
+        assert ((grads[n].sum(0) - grads0[n]).norm() / grads0[n].norm()).item() < 1e-12
+    assert ((sum(shares.values()) - full).norm() / full.norm()).item() < 1e-12
+    for n, share in shares.items():
+        got = dict(grads0)
+        got["label_emb.weight"] = full - share
+        errs, hard = grad_errors(got, grads0)
+        e_max, e_l2 = errs["label_emb.weight"]
+        print(f"label gradient without the share of {n[:-len('.time_mlp.0.bias')]}: max-rel {e_max:.2e} rel-L2 {e_l2:.2e}")
+        assert not hard and e_l2 >= 5 * REL_L2_F32, (n, e_max, e_l2)
+        with pytest.raises(AssertionError, match=r"label_emb\.weight"):
+            check_grads(got, grads0, REL_L2_F32, MAX_REL_F32, "label share")
+
+
+def test_subset_with_full_scale_keeps_the_structural_zeros(g5_f64):
+    """With some parameters frozen only a subset is compared.  Its structural zeros are those of the full set when the
+    full set's scale is handed in; measured against the subset's own largest gradient they would not be."""
+    _, _, grads, _ = g5_f64
+    scale = grad_scale(grads)
+    full_errs, hard = grad_errors(grads, grads)
+    assert not hard
+    zeros = {n for n, g in grads.items() if g is not None and n not in full_errs}
+    assert len(zeros) >= 8
+    live = sorted(full_errs, key=lambda n: grads[n].norm().item())
+    # (a) the zeros and the three smallest live tensors; (b) the zeros alone; (c) every seventh name
+    for subset in (zeros | set(live[:3]), zeros, set(list(grads)[::7])):
+        sub = {n: grads[n] for n in subset}
+        errs, hard = grad_errors(sub, sub, scale)
+        assert not hard and set(errs) == set(full_errs) & subset, sorted(set(errs) ^ (set(full_errs) & subset))
+        noisy = {n: (g + 1e-3 * scale if n in zeros else g) for n, g in sub.items() if g is not None}
+        noisy.update({n: None for n, g in sub.items() if g is None})
+        _, hard = grad_errors(noisy, sub, scale)
+        assert {h[0] for h in hard} == zeros & subset
+    # without the full scale the largest structural zero of (b) would be held to the relative bars as if it were live
+    own, _ = grad_errors({n: grads[n] for n in zeros}, {n: grads[n] for n in zeros})
+    assert own, "the subset's own scale turns a structural zero into a live tensor"
