@@ -212,6 +212,26 @@ class _HipUNet(nn.Module):
         arg = t.repeat(1, channels // 2) * inv_freq
         return torch.cat([torch.sin(arg), torch.cos(arg)], dim=-1)
 
+    # -- frozen BatchNorm (fine-tuning a snapshot on small batches) ----------------------------
+    def freeze_batchnorm(self, flag=True):
+        """Keep every nn.BatchNorm2d in eval mode: a train-mode forward then normalises with the running statistics and
+        leaves them (and num_batches_tracked) alone - the engine's frozen train plan (DRS_PLAN_FROZEN_BN).  Sticky: a later
+        `train()` (the trainers and `sample` call it) puts the layers back into eval.  `freeze_batchnorm(False)` gives them
+        the model's mode again.  `eval()` and the eval plan are not affected.  Returns self."""
+        self.__dict__["_bn_frozen"] = bool(flag)
+        for m in self.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.train(self.training and not flag)
+        return self
+
+    def train(self, mode=True):
+        super().train(mode)
+        if mode and self.__dict__.get("_bn_frozen"):
+            for m in self.modules():
+                if isinstance(m, nn.BatchNorm2d):
+                    m.train(False)
+        return self
+
     # -- HIP dispatch ---------------------------------------------------------------------
     def hip_engine(self):
         if self.__dict__.get("_hip_engine") is None:

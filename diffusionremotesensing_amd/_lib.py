@@ -16,6 +16,7 @@ IMPL_BY_NAME = {"direct": IMPL_DIRECT, "mfma_f32": IMPL_MFMA_F32, "mfma_bf16x3":
 FWD_REUSE_COND = 1
 PLAN_KEEP_ALL = 1
 PLAN_TRAIN = 2
+PLAN_FROZEN_BN = 4  # with PLAN_TRAIN only: BatchNorm normalises with the running statistics and leaves them alone
 VARIANT_SUPERRES, VARIANT_SAR_TO_NDVI, VARIANT_GENERATION = 0, 1, 2
 
 

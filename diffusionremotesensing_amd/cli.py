@@ -111,6 +111,30 @@ def cli_threshold(args):
     return {"x0_threshold": getattr(args, "x0_threshold", None)}
 
 
+def cli_prefixes(text):
+    """The value of --freeze: 'PREFIX[,PREFIX...]' as a tuple of state_dict-key prefixes (empty pieces: an error)."""
+    parts = tuple(s.strip() for s in text.split(","))
+    if not all(parts):
+        raise argparse.ArgumentTypeError(f"{text!r} must be PREFIX[,PREFIX...] of state_dict keys, e.g. downs.,LR_encoder.")
+    return parts
+
+
+def add_finetune_args(p):
+    """--freeze_bn / --freeze / --init_from of the trainers' `main` parsers: `Diffusion.train`'s `freeze_bn`, `freeze` and
+    `init_from` (`cli_finetune`; finetune.py).  Registered without a --help entry, like
+    `add_prediction_args(in_help=False)`: the trainers' help texts are recorded, README.md describes the flags."""
+    p.add_argument("--freeze_bn", type=str2bool, nargs="?", const=True, default=False, help=argparse.SUPPRESS)
+    p.add_argument("--freeze", type=cli_prefixes, default=(), help=argparse.SUPPRESS)
+    p.add_argument("--init_from", type=str, default=None, help=argparse.SUPPRESS)
+    return p
+
+
+def cli_finetune(args):
+    """`add_finetune_args`' flags as keyword arguments of `Diffusion.train` (a namespace without them: the defaults)."""
+    return {"freeze_bn": bool(getattr(args, "freeze_bn", False)), "freeze": tuple(getattr(args, "freeze", ()) or ()),
+            "init_from": getattr(args, "init_from", None)}
+
+
 def add_bsr_args(p):
     """--bsr_kind / --bsr_seed of the command lines that build the BSRGAN feed (not in the reference; `make_superres_feeds`)."""
     p.add_argument("--bsr_kind", type=str, choices=("plus", "soft"), default="plus",

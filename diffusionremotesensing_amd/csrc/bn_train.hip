@@ -3,6 +3,8 @@
 // In train mode the normalisation cannot be folded into the preceding convolution, so the plan runs
 //   conv (raw weights) -> Z  ->  bn_stats(Z)  ->  bn_finalize  ->  bn_apply(Z) with the block's activation / adds.
 // Its backward (bn_bwd_reduce -> bn_bwd_finish -> bn_bwd_apply) follows below: same partial-row layout, same row buffer.
+// Plans with DRS_PLAN_FROZEN_BN normalise with the running statistics instead and never write them:
+//   conv -> Z  ->  bn_frozen_stats (C threads)  ->  bn_apply(Z),   backward  bn_bwd_frozen (one pass)  ->  bn_bwd_finish.
 #include "conv_epilogue.h"  // drs_sp_split4
 #include "drs_common.h"
 #include "train_reduce.h"
@@ -143,6 +145,34 @@ int drs_launch_bn_train(const float* z, int z_cs, int z_co, long long npix, long
   DRS_LAUNCH(bn_stats_kernel, dim3(blocks), dim3(256), 0, s, z, npix, C, z_cs, z_co, sums_scratch);
   DRS_LAUNCH(bn_finalize_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, sums_scratch, (int)blocks, npix, C, eps, momentum, mean,
                      rstd, running_mean, running_var);
+  DRS_LAUNCH(bn_apply_kernel, dim3(grid1d(npix * (C >> 2), 256, 8192)), dim3(256), 0, s, z, z_cs, z_co, mean, rstd, gamma, beta,
+                     post_add, post_cs, res, res_cs, res_co, out, out_cs, out_co, npix, pix_per_image, C, relu_pre, relu_post);
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
+}
+
+// Frozen statistics (DRS_PLAN_FROZEN_BN: the reference modules under model.train() with every BatchNorm2d in .eval()):
+// y = (z - running_mean) / sqrt(running_var + eps) * gamma + beta.  No pass over Z: one thread per channel copies the
+// running statistics into the layer's mean | rstd slot (rstd rounded like bn_finalize_kernel's), which bn_apply_kernel, the
+// backward and its ReLU-mask recomputation read as they read batch statistics.  The running statistics are only read.
+__global__ __launch_bounds__(256) void bn_frozen_stats_kernel(const float* __restrict__ running_mean,
+                                                              const float* __restrict__ running_var, float eps, int C,
+                                                              float* __restrict__ mean, float* __restrict__ rstd) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  mean[c] = running_mean[c];
+  rstd[c] = (float)(1.0 / sqrt((double)running_var[c] + (double)eps));
+}
+
+int drs_launch_bn_frozen(const float* z, int z_cs, int z_co, long long npix, long long pix_per_image, int C,
+                         const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                         float eps, float* mean, float* rstd, const float* post_add, int post_cs, const float* res,
+                         int res_cs, int res_co, float* out, int out_cs, int out_co, int relu_pre, int relu_post,
+                         hipStream_t s) {
+  DRS_REQUIRE(C % 4 == 0 && C <= 1024, DRS_ERR_SHAPE, "bn_frozen: C=%d", C);
+  DRS_REQUIRE((z_cs & 3) == 0 && (z_co & 3) == 0 && (out_cs & 3) == 0 && (out_co & 3) == 0, DRS_ERR_SHAPE,
+              "bn_frozen: unaligned channel slices");
+  DRS_LAUNCH(bn_frozen_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, s, running_mean, running_var, eps, C, mean, rstd);
   DRS_LAUNCH(bn_apply_kernel, dim3(grid1d(npix * (C >> 2), 256, 8192)), dim3(256), 0, s, z, z_cs, z_co, mean, rstd, gamma, beta,
                      post_add, post_cs, res, res_cs, res_co, out, out_cs, out_co, npix, pix_per_image, C, relu_pre, relu_post);
   DRS_CHECK_HIP(hipGetLastError());
@@ -311,6 +341,113 @@ int drs_launch_bn_bwd(const float* g, int g_cs, int g_co, float* z, const float*
   DRS_LAUNCH(bn_bwd_finish_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, partials, (int)blocks, C, sums, dgamma, dbeta);
   DRS_LAUNCH(bn_bwd_apply_kernel, dim3(grid1d(npix * (C >> 2), 256, 8192)), dim3(256), 0, s, g, g_cs, g_co, z, mean, rstd,
                      gamma, beta, relu_pre, C, npix, sums, reinterpret_cast<char*>(z_sp), mask_y, my_cs, my_co);
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// BatchNorm backward with frozen statistics: mean and rstd are constants of the step, so
+//   dbeta = sum g, dgamma = sum g*zhat, dz = gamma*rstd*g
+// and dz no longer waits for the sums: ONE pass reads g (with its masks) and Z, accumulates the block's row of the two sums
+// in bn_bwd_reduce_kernel's layout (fp32 per thread, fp64 rows, no atomics) and writes dz over Z (and the SP copy);
+// bn_bwd_finish_kernel then adds the rows up as it does for the batch-statistics backward.
+// In place: thread = (pixel row in block, group of 4 channels) and the pixels p = blockIdx.x * rows + row + k * stride
+// of one thread are its own for reading AND for writing (the same map for both): the 16 bytes of Z at (p, channel group)
+// are loaded by exactly one thread of the grid, once, and that thread stores dz there after the load (each round loads its
+// four pixels before it stores any of them).  g and mask_y are other tensors and only read.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void bn_bwd_frozen_kernel(const float* __restrict__ g, int g_cs, int g_co,
+                                                            float* __restrict__ z, const float* __restrict__ mean,
+                                                            const float* __restrict__ rstd,
+                                                            const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, int relu_pre, int C,
+                                                            long long npix, double* __restrict__ partials,
+                                                            char* __restrict__ z_sp, const float* __restrict__ mask_y,
+                                                            int my_cs, int my_co) {
+  __shared__ float red[2][256][4];
+  const int c4n = C >> 2;
+  const int rows = 256 / c4n;
+  const int cg = threadIdx.x % c4n, row = threadIdx.x / c4n;
+  float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+  if (row < rows) {
+    const int c = cg * 4;
+    const float4 m = *reinterpret_cast<const float4*>(mean + c), r = *reinterpret_cast<const float4*>(rstd + c);
+    const float4 ga = *reinterpret_cast<const float4*>(gamma + c), be = *reinterpret_cast<const float4*>(beta + c);
+    const float mm[4] = {m.x, m.y, m.z, m.w}, rr[4] = {r.x, r.y, r.z, r.w}, gg[4] = {ga.x, ga.y, ga.z, ga.w},
+                bb[4] = {be.x, be.y, be.z, be.w};
+    const float gr[4] = {gg[0] * rr[0], gg[1] * rr[1], gg[2] * rr[2], gg[3] * rr[3]};
+    auto one = [&](long long p, const float4& zv, const float4& gv4) __attribute__((always_inline)) {
+      const float zz[4] = {zv.x, zv.y, zv.z, zv.w};
+      float gv[4] = {gv4.x, gv4.y, gv4.z, gv4.w}, o[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float zh = (zz[j] - mm[j]) * rr[j];
+        if (relu_pre && !(zh * gg[j] + bb[j] > 0.f)) gv[j] = 0.f;
+        s1[j] += gv[j];
+        s2[j] += gv[j] * zh;
+        o[j] = gr[j] * gv[j];
+      }
+      *reinterpret_cast<float4*>(z + p * C + c) = make_float4(o[0], o[1], o[2], o[3]);
+      if (z_sp) {  // (bn_bwd_apply_kernel's SP copy)
+        unsigned hi[2], lo[2];
+        drs_sp_split4(o, hi, lo);
+        char* gp = z_sp + ((size_t)p * C + (c & ~31)) * 4 + (c & 31) * 2;
+        *reinterpret_cast<uint2*>(gp) = make_uint2(hi[0], hi[1]);
+        *reinterpret_cast<uint2*>(gp + 64) = make_uint2(lo[0], lo[1]);
+      }
+    };
+    const long long stride = (long long)gridDim.x * rows;
+    long long p = (long long)blockIdx.x * rows + row;
+    // four pixels in flight per thread, as in bn_bwd_reduce_kernel: all of a round's loads are issued before its stores
+    for (; p + 3 * stride < npix; p += 4 * stride) {
+      float4 zv[4], gv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        zv[u] = *reinterpret_cast<const float4*>(z + (p + u * stride) * C + c);
+        gv[u] = *reinterpret_cast<const float4*>(g + (p + u * stride) * g_cs + g_co + c);
+      }
+      if (mask_y) {
+        float4 yv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) yv[u] = *reinterpret_cast<const float4*>(mask_y + (p + u * stride) * my_cs + my_co + c);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) gv[u] = drs_mask4(gv[u], yv[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) one(p + u * stride, zv[u], gv[u]);
+    }
+    for (; p < npix; p += stride) {
+      float4 g0 = *reinterpret_cast<const float4*>(g + p * g_cs + g_co + c);
+      if (mask_y) g0 = drs_mask4(g0, *reinterpret_cast<const float4*>(mask_y + p * my_cs + my_co + c));
+      one(p, *reinterpret_cast<const float4*>(z + p * C + c), g0);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { red[0][threadIdx.x][j] = s1[j]; red[1][threadIdx.x][j] = s2[j]; }
+  __syncthreads();
+  if (threadIdx.x < c4n) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      double d1 = 0, d2 = 0;
+      for (int r = 0; r < rows; ++r) { d1 += (double)red[0][r * c4n + threadIdx.x][j]; d2 += (double)red[1][r * c4n + threadIdx.x][j]; }
+      partials[(size_t)blockIdx.x * 2 * C + threadIdx.x * 4 + j] = d1;
+      partials[(size_t)blockIdx.x * 2 * C + C + threadIdx.x * 4 + j] = d2;
+    }
+  }
+}
+int drs_launch_bn_bwd_frozen(const float* g, int g_cs, int g_co, float* z, const float* mean, const float* rstd,
+                             const float* gamma, const float* beta, int relu_pre, int C, long long npix, double* partials,
+                             double* sums, float* dgamma, float* dbeta, hipStream_t s, float* z_sp, const float* mask_y,
+                             int my_cs, int my_co) {
+  DRS_REQUIRE(!z_sp || C % 32 == 0, DRS_ERR_SHAPE, "bn_bwd_frozen: an SP copy needs C %% 32 == 0 (C=%d)", C);
+  DRS_REQUIRE(!mask_y || ((my_cs & 3) == 0 && (my_co & 3) == 0), DRS_ERR_SHAPE, "bn_bwd_frozen: unaligned mask slice");
+  DRS_REQUIRE(C % 4 == 0 && C <= 1024 && 256 % (C >> 2) == 0 && (g_cs & 3) == 0 && (g_co & 3) == 0, DRS_ERR_SHAPE,
+              "bn_bwd_frozen: C=%d g_cs=%d g_co=%d", C, g_cs, g_co);
+  const int rows = 256 / (C >> 2);
+  const unsigned blocks = grid1d(npix, rows, DRS_RED_BLOCKS);  // one partials row per block: at most DRS_RED_BLOCKS rows
+  DRS_LAUNCH(bn_bwd_frozen_kernel, dim3(blocks), dim3(256), 0, s, g, g_cs, g_co, z, mean, rstd, gamma, beta, relu_pre, C, npix,
+             partials, reinterpret_cast<char*>(z_sp), mask_y, my_cs, my_co);
+  DRS_LAUNCH(bn_bwd_finish_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, partials, (int)blocks, C, sums, dgamma, dbeta);
   DRS_CHECK_HIP(hipGetLastError());
   return DRS_OK;
 }

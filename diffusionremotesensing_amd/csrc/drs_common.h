@@ -390,6 +390,12 @@ int drs_launch_bn_train(const float* z, int z_cs, int z_co, long long npix, long
                         float momentum, double* sums_scratch, float* mean, float* rstd, const float* post_add,
                         int post_cs, const float* res, int res_cs, int res_co, float* out, int out_cs, int out_co,
                         int relu_pre, int relu_post, hipStream_t s);
+// the same with frozen statistics (DRS_PLAN_FROZEN_BN): mean | rstd come from the running statistics, which are only read
+int drs_launch_bn_frozen(const float* z, int z_cs, int z_co, long long npix, long long pix_per_image, int C,
+                         const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                         float eps, float* mean, float* rstd, const float* post_add, int post_cs, const float* res,
+                         int res_cs, int res_co, float* out, int out_cs, int out_co, int relu_pre, int relu_post,
+                         hipStream_t s);
 
 // ---- training backward (wgrad_direct.hip, colsum.hip, bn_train.hip, attn_bwd.hip, time_mlp_bwd.hip, stem_bwd.hip) ----
 struct WgradDesc {
@@ -419,6 +425,11 @@ int drs_launch_bn_bwd(const float* g, int g_cs, int g_co, float* z, const float*
                       const float* gamma, const float* beta, int relu_pre, int C, long long npix, double* partials,
                       double* sums, float* dgamma, float* dbeta, hipStream_t s, float* z_sp = nullptr,
                       const float* mask_y = nullptr, int my_cs = 0, int my_co = 0);
+// frozen statistics: dz = gamma * rstd * g, sums and dz in one pass over g and Z (bn_bwd_frozen_kernel), then the same finish
+int drs_launch_bn_bwd_frozen(const float* g, int g_cs, int g_co, float* z, const float* mean, const float* rstd,
+                             const float* gamma, const float* beta, int relu_pre, int C, long long npix, double* partials,
+                             double* sums, float* dgamma, float* dbeta, hipStream_t s, float* z_sp = nullptr,
+                             const float* mask_y = nullptr, int my_cs = 0, int my_co = 0);
 int drs_launch_gate_bwd(const float* x, const float* E, const float* psi, float* dx, float* dpsi_pre, int N, int LH,
                         int LW, int C, hipStream_t s);
 int drs_launch_psi_bwd(const float* Pm, const float* wpsi, const float* dpsi_pre, float* dP, float* dw, float* db, int C,

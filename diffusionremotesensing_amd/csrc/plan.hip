@@ -317,6 +317,9 @@ extern "C" int drs_unet_plan_create(drs_plan** out, const drs_unet_config* cfg) 
   DRS_REQUIRE(cfg->variant >= DRS_VARIANT_SUPERRES && cfg->variant <= DRS_VARIANT_GENERATION, DRS_ERR_ARG,
               "plan_create: variant=%d", cfg->variant);
   DRS_REQUIRE(cfg->num_classes >= 0, DRS_ERR_ARG, "plan_create: num_classes=%d", cfg->num_classes);
+  DRS_REQUIRE(!(cfg->flags & DRS_PLAN_FROZEN_BN) || (cfg->flags & DRS_PLAN_TRAIN), DRS_ERR_ARG,
+              "plan_create: DRS_PLAN_FROZEN_BN needs DRS_PLAN_TRAIN (flags=%d; an eval plan folds the running statistics)",
+              cfg->flags);
   std::unique_ptr<drs_plan> p(new drs_plan());
   p->cfg = *cfg;
   if (p->cfg.bn_eps <= 0.f) p->cfg.bn_eps = 1e-5f;

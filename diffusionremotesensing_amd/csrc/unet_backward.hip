@@ -3,7 +3,8 @@
 //
 // Mirrors what autograd does for the reference graph (UNet_model_superres.py:337-379 under model.train()), given
 // d(loss)/d(output).  Data gradients are tap-convolutions with re-packed weights (same kernels as the forward);
-// weight gradients use wgrad_kernel; BatchNorm uses the batch statistics saved by the train-mode forward.
+// weight gradients use wgrad_kernel; BatchNorm uses the batch statistics saved by the train-mode forward
+// (a DRS_PLAN_FROZEN_BN plan: the running statistics that forward copied into the same slot, and dZ = gamma * rstd * g).
 // Requires: a train plan (DRS_PLAN_TRAIN), lr_batch == batch, and the workspace exactly as the last
 // drs_unet_forward on this plan left it.
 
@@ -241,9 +242,22 @@ static int bn_bwd(BwdCtx& c, const ConvLayer& L, const float* g, int g_cs, int g
   float* stats = (float*)((char*)c.ws + L.stats_off);
   float* dgam = c.G(L.bn) ? c.G(L.bn) : c.scratch;
   float* dbet = c.G(L.bn + 1) ? c.G(L.bn + 1) : c.scratch + 1024;
-  return drs_launch_bn_bwd(g, g_cs, g_co, c.TP(L.t_Z), stats, stats + L.Cout, c.PARAM(L.bn), c.PARAM(L.bn + 1), relu_pre,
-                           L.Cout, npix, (double*)c.red, (double*)((char*)c.sums_bwd + L.sums_off), dgam, dbet, c.s,
-                           c.ZSP(L), mask_y, my_cs, 0);
+  // With profiling on (drs_unet_profile_enable) every BatchNorm backward is one op appended to the forward's op list
+  // ("<norm>.bwd"; algorithmic bytes: g, Z and the optional mask read once or twice, dZ and its optional SP copy written).
+  std::string name = c.plan->params[L.bn].name;
+  name = name.substr(0, name.size() - 7) + ".bwd";  // strip ".weight"
+  const double tb = 4.0 * npix * L.Cout, reads = (mask_y ? 3.0 : 2.0) * tb, writes = (c.ZSP(L) ? 2.0 : 1.0) * tb;
+  if (c.plan->frozen_bn())  // dZ = gamma * rstd * g: sums and dZ in one pass
+    return prof_op(c.plan, name, 0, reads + writes, c.s, [&] {
+      return drs_launch_bn_bwd_frozen(g, g_cs, g_co, c.TP(L.t_Z), stats, stats + L.Cout, c.PARAM(L.bn), c.PARAM(L.bn + 1),
+                                      relu_pre, L.Cout, npix, (double*)c.red, (double*)((char*)c.sums_bwd + L.sums_off), dgam,
+                                      dbet, c.s, c.ZSP(L), mask_y, my_cs, 0);
+    });
+  return prof_op(c.plan, name, 0, 2.0 * reads + writes, c.s, [&] {
+    return drs_launch_bn_bwd(g, g_cs, g_co, c.TP(L.t_Z), stats, stats + L.Cout, c.PARAM(L.bn), c.PARAM(L.bn + 1), relu_pre,
+                             L.Cout, npix, (double*)c.red, (double*)((char*)c.sums_bwd + L.sums_off), dgam, dbet, c.s,
+                             c.ZSP(L), mask_y, my_cs, 0);
+  });
 }
 static hipStream_t wgrad_stream(BwdCtx& c) {  // stream for a weight-gradient launch whose operands are ready on c.s now
   if (!c.wgrad_side) return c.s;

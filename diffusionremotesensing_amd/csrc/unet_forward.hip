@@ -65,11 +65,25 @@ static int conv_bn(FwdCtx& f, const ConvLayer& L, const TapConv& d) {
   RUN(plan_conv(f.plan, L, zc, f.s));
   float* stats = (float*)((char*)f.ws + L.stats_off);
   const long long ppi = (long long)d.OH * d.OW;
-  return drs_launch_bn_train(zc.out, L.Cout, 0, (long long)d.N * ppi, ppi, L.Cout,
-                             (const float*)f.plan->param_ptrs[L.bn], (const float*)f.plan->param_ptrs[L.bn + 1],
-                             (float*)f.plan->param_ptrs[L.bn + 2], (float*)f.plan->param_ptrs[L.bn + 3], f.cfg.bn_eps,
-                             0.1f, (double*)((char*)f.ws + f.plan->o_red), stats, stats + L.Cout, d.post_add, d.post_cs,
-                             d.res, d.res_cs, d.res_co, d.out, d.out_cs, d.out_co, d.relu_pre, d.relu_post, f.s);
+  std::string name = f.plan->params[L.bn].name;
+  name = name.substr(0, name.size() - 7);  // strip ".weight"
+  // (algorithmic bytes: Z read once for the statistics and once for the normalisation, or only the latter; the output written)
+  const double zbytes = 4.0 * d.N * ppi * L.Cout;
+  if (f.plan->frozen_bn())  // running statistics into the mean | rstd slot (per forward: they may have been loaded since), no pass over Z
+    return prof_op(f.plan, name + ".frozen", 0, 2.0 * zbytes, f.s, [&] {
+      return drs_launch_bn_frozen(zc.out, L.Cout, 0, (long long)d.N * ppi, ppi, L.Cout,
+                                  (const float*)f.plan->param_ptrs[L.bn], (const float*)f.plan->param_ptrs[L.bn + 1],
+                                  (const float*)f.plan->param_ptrs[L.bn + 2], (const float*)f.plan->param_ptrs[L.bn + 3],
+                                  f.cfg.bn_eps, stats, stats + L.Cout, d.post_add, d.post_cs, d.res, d.res_cs, d.res_co,
+                                  d.out, d.out_cs, d.out_co, d.relu_pre, d.relu_post, f.s);
+    });
+  return prof_op(f.plan, name + ".train", 0, 3.0 * zbytes, f.s, [&] {
+    return drs_launch_bn_train(zc.out, L.Cout, 0, (long long)d.N * ppi, ppi, L.Cout,
+                               (const float*)f.plan->param_ptrs[L.bn], (const float*)f.plan->param_ptrs[L.bn + 1],
+                               (float*)f.plan->param_ptrs[L.bn + 2], (float*)f.plan->param_ptrs[L.bn + 3], f.cfg.bn_eps,
+                               0.1f, (double*)((char*)f.ws + f.plan->o_red), stats, stats + L.Cout, d.post_add, d.post_cs,
+                               d.res, d.res_cs, d.res_co, d.out, d.out_cs, d.out_co, d.relu_pre, d.relu_post, f.s);
+  });
 }
 // --- time embeddings for the 7 blocks (reference :338-339 + every time_mlp) and the decoder gates' bias tables ---
 // (eval: on the side stream, next to the conditioning branch / conv0; the first consumer is block 0's conv1)

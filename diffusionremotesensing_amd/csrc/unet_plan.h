@@ -139,6 +139,8 @@ struct drs_plan {
   size_t o_inv_freq = 0, o_mlp_table = 0, o_out_w = 0, o_out_b = 0, o_label = 0, o_zero = 0, o_fault = 0;
   // eval plans of the split-bf16 implementation keep every MFMA-consumed activation in SP format (drs_common.h)
   bool sp = false;
+  // train plans with DRS_PLAN_FROZEN_BN: every BatchNorm normalises with the running statistics (read-only), forward and backward
+  bool frozen_bn() const { return (cfg.flags & DRS_PLAN_FROZEN_BN) != 0; }
   int t_XT[3] = {-1, -1, -1};  // x + relu(time_mlp(t)) of UpConvBlock i (reference :199), second output of its producer
   int label_emb = -1;  // param index of label_emb.weight (generation variant)
   int temb_total = 0;

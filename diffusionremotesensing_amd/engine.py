@@ -51,7 +51,9 @@ class _Plan:
 class HipUNetEngine:
     """Runs reference `Residual_Attention_UNet_superres.forward` (UNet_model_superres.py:337-379)
     on the HIP plan.  Eval mode folds BatchNorm; train mode uses batch statistics and updates the running statistics
-    like nn.BatchNorm2d, and with autograd enabled the call is recorded so that loss.backward() runs
+    like nn.BatchNorm2d - unless every BatchNorm2d of the train-mode module is in eval mode (model.freeze_batchnorm()): then
+    the train plan normalises with the running statistics and writes neither them nor num_batches_tracked.  With autograd
+    enabled the call is recorded so that loss.backward() runs
     drs_unet_backward (weight / bias / BatchNorm-affine gradients of every live parameter)."""
 
     VARIANTS = {"superres": _lib.VARIANT_SUPERRES, "sar_to_ndvi": _lib.VARIANT_SAR_TO_NDVI,
@@ -71,7 +73,7 @@ class HipUNetEngine:
             warnings.warn("DRS_TRAIN_IMPL=mfma_bf16x3: split-bf16 training is outside the gradient bar (worst gradient-norm "
                           "deviation 1.26e-3 on the full-size configs[2] step against 1e-3); the exact-fp32 MFMA kernels are "
                           "the parity-grade training path")
-        # least-recently-used cache of plans: every distinct (batch, lr batch, H, W, mag, impl, train) owns a workspace
+        # least-recently-used cache of plans: every distinct (batch, lr batch, H, W, mag, impl, train, frozen) owns a workspace
         # (~1.6 GB at batch 16, 256x256); train + validation + preview + tiler shapes would otherwise pile up
         self._plans = collections.OrderedDict()
         self.max_plans = int(os.environ.get("DRS_MAX_PLANS", "6"))
@@ -106,9 +108,9 @@ class HipUNetEngine:
         return out
 
     # -- plan / weights -------------------------------------------------------------------
-    def _get_plan(self, B, Bl, H, W, mag, device, train=False):
+    def _get_plan(self, B, Bl, H, W, mag, device, train=False, frozen=False):
         impl = self.train_impl if train else self.impl
-        key = (B, Bl, H, W, mag, device.index, impl, self.keep_intermediates, train)
+        key = (B, Bl, H, W, mag, device.index, impl, self.keep_intermediates, train, frozen)
         plan = self._plans.get(key)
         if plan is not None:
             self._plans.move_to_end(key)
@@ -122,15 +124,32 @@ class HipUNetEngine:
                 cx, cout, cc, ncls = m.image_channels, m.out_dim, m.image_channels, 0
             cfg = _lib.UNetConfig(B, Bl, cx, cout, H, W, mag, impl, 1e-5,
                                   (_lib.PLAN_KEEP_ALL if self.keep_intermediates else 0) |
-                                  (_lib.PLAN_TRAIN if train else 0), self.VARIANTS[self.variant], cc, ncls)
+                                  (_lib.PLAN_TRAIN if train else 0) | (_lib.PLAN_FROZEN_BN if frozen else 0),
+                                  self.VARIANTS[self.variant], cc, ncls)
             self._channels = (cx, cout, cc)
             plan = _Plan(_lib.load(), cfg, device)
             plan.train = train
+            plan.frozen = frozen
             plan.train_serial = 0  # number of the last train-mode forward on this plan (its workspace holds that forward)
             self._plans[key] = plan
             while len(self._plans) > max(self.max_plans, 1):
                 self._plans.popitem(last=False)  # its workspace is freed once no autograd node / caller holds the plan
         return plan
+
+    def _frozen_bn(self, m):
+        """True when every nn.BatchNorm2d of the (train-mode) module is in eval mode: the frozen train plan.  Some in eval and
+        some in train mode is refused: a plan has one BatchNorm regime."""
+        bns = self.__dict__.get("_bn_modules")
+        if bns is None:
+            bns = self.__dict__["_bn_modules"] = [b for b in m.modules() if isinstance(b, torch.nn.BatchNorm2d)]
+        n_eval = sum(1 for b in bns if not b.training)
+        if n_eval == 0:
+            return False
+        if n_eval != len(bns):
+            raise RuntimeError(f"{n_eval} of the model's {len(bns)} BatchNorm2d layers are in eval mode and the others in train "
+                               "mode: the HIP train plan runs all of them on batch statistics or all of them on the running "
+                               "statistics (model.freeze_batchnorm())")
+        return True
 
     def set_impl(self, impl, train_impl=None):
         self.impl = _lib.IMPL_BY_NAME[impl]
@@ -170,6 +189,7 @@ class HipUNetEngine:
         tensor of the output's size to write into instead of a fresh one (a slice of the tiler's per-step eps buffer)."""
         m = self._module()
         train = bool(m.training)
+        frozen = train and self._frozen_bn(m)  # model.train() with every BatchNorm2d in .eval(): running statistics, untouched
         has_cond = self.variant != "generation"
         if not has_cond:
             lr_img, magnification_factor = None, 1
@@ -180,7 +200,7 @@ class HipUNetEngine:
             if out is not None:
                 raise RuntimeError("out= is for forwards outside autograd")
             plan = self._get_plan(x.shape[0], lr_img.shape[0] if has_cond else x.shape[0], x.shape[2], x.shape[3],
-                                  int(magnification_factor), x.device, True)
+                                  int(magnification_factor), x.device, True, frozen)
             sd = self._tensors(plan.param_names)
             params = [sd[n] for n in plan.param_names if sd[n].requires_grad]
             return _UNetTrainFn.apply(self, x, timestep, lr_img, magnification_factor, labels, *params)
@@ -196,7 +216,7 @@ class HipUNetEngine:
         B, Cx, H, W = x.shape
         Bl = lr_img.shape[0] if has_cond else B
         mag = int(magnification_factor)
-        plan = self._get_plan(B, Bl, H, W, mag, x.device, train)
+        plan = self._get_plan(B, Bl, H, W, mag, x.device, train, frozen)
         cx, _, cc = self._channels
         if Cx != cx or (has_cond and lr_img.shape[1] != cc):
             raise RuntimeError(f"expected {cx} image / {cc} conditioning channels, got x {Cx}"
@@ -244,9 +264,10 @@ class HipUNetEngine:
             _lib.check(st, "drs_unet_forward")
             if has_cond:
                 plan.cond_key = (lr_img.data_ptr(), lr_img._version)
-            if train:  # the kernels updated running_mean / running_var in place; num_batches_tracked follows here
-                self._bn_epoch += 1
+            if train:
                 plan.train_serial += 1  # autograd nodes of earlier forwards on this plan can no longer run their backward
+            if train and not frozen:  # the kernels updated running_mean / running_var in place; num_batches_tracked follows here
+                self._bn_epoch += 1
                 nbt = [b for k, b in m.named_buffers() if k.endswith("num_batches_tracked")]
                 with torch.no_grad():
                     torch._foreach_add_(nbt, 1)

@@ -49,7 +49,7 @@ def train_model(args, diffusion_class, model, device, train_loader, val_loader, 
                                 **diffusion_kwargs)
     diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
                     train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
-                    verbose=True, **cli.train_kwargs(args), **(train_kwargs or {}))
+                    verbose=True, **cli.train_kwargs(args), **cli.cli_finetune(args), **(train_kwargs or {}))
     if args.multiple_gpus:
         drs_dist.destroy_process_group()
     return diffusion

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import dist as drs_dist
 from .augment import add_augment_args
-from .cli import add_prediction_args, add_train_args, base_arg_parser, check_objective_args, check_train_args  # noqa: F401 - re-exported
+from .cli import add_finetune_args, add_prediction_args, add_train_args, base_arg_parser, check_objective_args, check_train_args  # noqa: F401 - re-exported
 from .launcher import launch_device, make_loaders, save_final_samples, train_model
 from .sampling import _repeat_members, asks_for_known_pixels, check_inpaint_args, check_sampling_args
 from .train_diffusion_superres import Diffusion as _SuperresDiffusion
@@ -194,7 +194,7 @@ def train_main_parser():
     flags (cli.add_train_args): what `main` parses."""
     p = train_arg_parser()
     add_augment_args(p)
-    return add_prediction_args(add_train_args(p), in_help=False)
+    return add_finetune_args(add_prediction_args(add_train_args(p), in_help=False))
 
 
 def main(argv=None):

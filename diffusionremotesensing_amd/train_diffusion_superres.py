@@ -27,9 +27,10 @@ from . import dist as drs_dist
 from . import hip_ops
 from .augment import add_augment_args
 # (the names this module does not use itself are re-exported: they lived here before cli.py, launcher.py and superres_feeds.py)
-from .cli import (OBJECTIVE_DEFAULTS, OPTIM_DEFAULTS, add_bsr_args, add_objective_args, add_optim_args,  # noqa: F401
+from .cli import (OBJECTIVE_DEFAULTS, OPTIM_DEFAULTS, add_bsr_args, add_finetune_args, add_objective_args, add_optim_args,  # noqa: F401
                   add_prediction_args, add_sampling_args, add_solver_args, add_train_args, base_arg_parser, check_objective_args, check_optim_args,
                   check_train_args, cli_sampling_steps, objective_train_kwargs, optim_train_kwargs, str2bool)
+from .finetune import freeze_parameters, load_init_weights
 from .launcher import launch_device, make_loaders, save_final_samples, train_model  # noqa: F401
 from .losses import DiffusionLoss, LossAwareSampler, LossBins, min_snr_weights
 from .optim import FusedAdam, FusedAdamW, WarmupCosine
@@ -444,6 +445,8 @@ class Diffusion:
               "DEVICE_RNG_STATE": torch.cuda.get_rng_state(self.device)}
         if run.loss_bins is not None:  # (a run without --loss_bins / loss_aware writes the file it always wrote)
             ts["LOSS_BINS"] = run.loss_bins.state_dict()
+        if getattr(run, "freeze_bn", False) or getattr(run, "freeze", ()):  # (likewise)
+            ts["FREEZE_BN"], ts["FREEZE"] = run.freeze_bn, tuple(run.freeze)
         torch.save(ts, self.train_state_path())
 
     def _load_train_state(self, run):
@@ -455,6 +458,10 @@ class Diffusion:
             raise ValueError(f"{self.train_state_path()} was written with other --ema_smoothing / --lr_schedule options")
         if ("LOSS_BINS" in ts) != (run.loss_bins is not None):
             raise ValueError(f"{self.train_state_path()} was written with other --loss_bins / --timestep_sampling options")
+        if (bool(ts.get("FREEZE_BN", False)), tuple(ts.get("FREEZE", ()))) != (getattr(run, "freeze_bn", False),
+                                                                                tuple(getattr(run, "freeze", ()))):
+            raise ValueError(f"{self.train_state_path()} was written with --freeze_bn {bool(ts.get('FREEZE_BN', False))} "
+                             f"--freeze {','.join(ts.get('FREEZE', ())) or '(none)'}: a resumed run must freeze the same")
         if run.loss_bins is not None:
             run.loss_bins.load_state_dict(ts["LOSS_BINS"])  # (other T / bin count: ValueError)
         # (another parameter count or other shapes: ValueError from FusedAdamW.load_state_dict, the first thing loaded)
@@ -579,7 +586,7 @@ class Diffusion:
     def train(self, lr, epochs, check_preds_epoch, train_loader, val_loader, patience, loss, verbose, eval_metrics=0,
               sampling_steps=None, eta=0.0, weight_decay=0.0, max_grad_norm=None, lr_schedule="constant", warmup_steps=0,
               lr_min=0.0, save_train_state=False, loss_weighting="none", min_snr_gamma=5.0, timestep_sampling="uniform",
-              loss_bins=0):
+              loss_bins=0, freeze_bn=False, freeze=(), init_from=None):
         """`eval_metrics=N` (not in the reference; 0 = off): at every epoch with epoch % check_preds_epoch == 0 the network that
         would be saved is scored on the first N validation images (`evaluate` with `sampling_steps` / `eta`), one line.
         Not in the reference either, all off by default (then this is its loop: Adam at a fixed rate): `weight_decay` and
@@ -594,12 +601,17 @@ class Diffusion:
         and so consumes the DEVICE generator instead of the CPU one.  Any of them routes `train_step` and the validation loop
         through `losses.DiffusionLoss`; validation keeps its uniform CPU draw of t and has bins of its own.
         The regression target of both loops is what the constructor's `prediction` names (`_noised_target`: eps, v or x0; Min-SNR
-        weights that target); `loss="MSE+Perceptual_noise"` needs an eps network (ValueError otherwise)."""
+        weights that target); `loss="MSE+Perceptual_noise"` needs an eps network (ValueError otherwise).
+        Fine-tuning a snapshot (finetune.py; all off by default): `init_from=PATH` starts a run whose own
+        snapshot does not exist yet from the MODEL_STATE of that file, at epoch 0; `freeze_bn=True` keeps every BatchNorm2d on
+        its running statistics (`model.freeze_batchnorm()`: the frozen train plan, statistics never written);
+        `freeze=("downs.", "LR_encoder.")` takes the parameters under those state_dict-key prefixes out of training."""
+        self._prepare_finetune(freeze_bn, freeze, init_from)
         run = self._begin_run(
             loss, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule,
             warmup_steps=warmup_steps, lr_min=lr_min, total_steps=max(len(train_loader), 1) * epochs,
             save_train_state=save_train_state, loss_weighting=loss_weighting, min_snr_gamma=min_snr_gamma,
-            timestep_sampling=timestep_sampling, loss_bins=loss_bins)
+            timestep_sampling=timestep_sampling, loss_bins=loss_bins, freeze_bn=freeze_bn, freeze=freeze)
         eval_args = {"n_images": eval_metrics, "sampling_steps": sampling_steps, "eta": eta} if eval_metrics else None
         for epoch in range(self.epochs_run, epochs):
             checking = epoch % check_preds_epoch == 0
@@ -617,7 +629,7 @@ class Diffusion:
             print("Epochs without improving: ", run.epochs_without_improving)
 
     def _begin_run(self, loss, *, lr, weight_decay, max_grad_norm, lr_schedule, warmup_steps, lr_min, total_steps,
-                   save_train_state, loss_weighting, min_snr_gamma, timestep_sampling, loss_bins):
+                   save_train_state, loss_weighting, min_snr_gamma, timestep_sampling, loss_bins, freeze_bn=False, freeze=()):
         """The `TrainRun` of one `train` call, kept as `self.train_state`: optimizer, schedule, EMA copy and objective from its
         arguments (and `self.timestep_sampler`), continued from `train_state.pt` when `save_train_state` finds one."""
         model = self.model
@@ -642,9 +654,31 @@ class Diffusion:
         self.timestep_sampler = objective.sampler if objective is not None else None
         run = self.train_state = TrainRun(model, loss, optimizer, scheduler, ema, ema_model, objective, loss_function,
                                           clipping=max_grad_norm is not None, save_train_state=save_train_state)
+        run.freeze_bn, run.freeze = bool(freeze_bn), tuple(freeze)
         if save_train_state and os.path.exists(self.snapshot_path) and os.path.exists(self.train_state_path()):
             self._load_train_state(run)
         return run
+
+    def _prepare_finetune(self, freeze_bn, freeze, init_from):
+        """What `train`'s `init_from` / `freeze_bn` / `freeze` do to the network before the optimizer and the EMA copy are
+        made (finetune.py).  A default call touches nothing and prints nothing."""
+        if isinstance(freeze, str):
+            raise ValueError("freeze must be a tuple of state_dict-key prefixes, e.g. ('downs.', 'LR_encoder.')")
+        freeze = tuple(freeze)
+        if not (freeze_bn or freeze or init_from):
+            return
+        net = self._unwrapped(self.model)
+        if init_from and not os.path.exists(self.snapshot_path):  # (the run's own snapshot, loaded by __init__, wins)
+            load_init_weights(net, init_from, self.prediction, "cpu" if self.multiple_gpus else self.device)
+            net.to(self.device)
+            print(f"Starting from the weights of {init_from} at Epoch 0")
+        if freeze_bn:
+            if not hasattr(net, "freeze_batchnorm"):
+                raise ValueError("freeze_bn needs one of the three UNet classes (model.freeze_batchnorm())")
+            net.freeze_batchnorm(True)
+        (n_off, n_on), (e_off, e_on) = freeze_parameters(net, freeze)
+        print(f"Fine-tuning: {n_off} parameter tensors frozen ({e_off} values), {n_on} trained ({e_on} values); BatchNorm "
+              f"statistics {'frozen' if freeze_bn else 'updated'}")
 
     def _save(self, run, epoch):
         self._save_snapshot(epoch, run.saved)
@@ -787,6 +821,7 @@ def parse_train_args(argv=None):
     add_augment_args(p)
     add_train_args(p)
     add_prediction_args(p, in_help=False)
+    add_finetune_args(p)
     p.add_argument("--eval_metrics", type=int, default=0,
                    help="score the network on the first N validation images (PSNR / SSIM / SAM / ERGAS against the bicubic "
                         "baseline) at every epoch with epoch %% check_preds_epoch == 0; 0 = off")

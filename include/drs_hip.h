@@ -679,6 +679,13 @@ typedef struct drs_unet_config {
  * parameter pointers given to drs_unet_pack_weights), nothing is folded or fused across a BatchNorm, every
  * pre-normalisation tensor is kept.  Reference: model.train() + nn.BatchNorm2d defaults (eps 1e-5, momentum 0.1). */
 #define DRS_PLAN_TRAIN 2
+/* Frozen BatchNorm statistics, for fine-tuning a snapshot on small batches; valid only together with DRS_PLAN_TRAIN
+ * (plan creation returns DRS_ERR_ARG otherwise).  Reference: model.train() with every nn.BatchNorm2d in .eval():
+ * y = (z - running_mean) / sqrt(running_var + eps) * gamma + beta.  The running statistics are read through the
+ * parameter pointers on every forward and never written.  Everything else is the train plan: nothing folded, every
+ * pre-normalisation tensor kept, the same workspace layout and the same backward contract (its BatchNorm step is
+ * dz = gamma * rstd * g, with dgamma / dbeta as before; a conv bias in front of a BatchNorm now has a real gradient). */
+#define DRS_PLAN_FROZEN_BN 4
 
 DRS_API int drs_unet_plan_create(drs_plan** plan, const drs_unet_config* cfg);
 DRS_API void drs_unet_plan_destroy(drs_plan* plan);
