@@ -200,6 +200,9 @@ class split_aggregation_sampling:
         its uint8 mask, once, at scene size (4 + 1 bytes per element read per move).  ValueError as `check_known`."""
         from .sampling import check_sampling_args
         d = self.diffusion_model
+        if getattr(d, "zero_terminal_snr", False):
+            raise ValueError("aggregation='per_step' cannot run on a zero_terminal_snr schedule: its per-tile conversion of the "
+                             "prediction to eps is 0 / 0 at the terminal level (alpha_hat == 0); use aggregation='final'")
         check_sampling_args(d.noise_steps, sampling_steps, eta)
         self.check_known(sampling_steps, known, known_mask, resample, jump)
         if drs_dist.world_size() > 1:
@@ -341,7 +344,7 @@ def launch(args):
     import os
 
     from .colorfix import cli_color_fix
-    from .cli import cli_prediction, cli_sampling_steps, cli_threshold
+    from .cli import cli_prediction, cli_sampling_steps, cli_threshold, cli_ztsnr, set_guidance_rescale
     device = args.device
     task = getattr(args, "task", "superres")
     if args.UNet_type.lower() != "residual attention unet":
@@ -357,7 +360,7 @@ def launch(args):
         diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot_path,
                               noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02, device=device,
                               image_size=args.model_input_size, model_name=args.model_name, multiple_gpus=False,
-                              ema_smoothing=False, **cli_prediction(args), **cli_threshold(args))
+                              ema_smoothing=False, **cli_prediction(args), **cli_threshold(args), **cli_ztsnr(args))
         out_channels = args.NDVI_channels
     elif task == "superres":
         from .train_diffusion_superres import Diffusion
@@ -368,10 +371,11 @@ def launch(args):
                               magnification_factor=args.magnification_factor, device=device,
                               image_size=args.model_input_size, model_name=args.model_name,
                               Degradation_type=args.Degradation_type, multiple_gpus=False, ema_smoothing=False,
-                              **cli_prediction(args), **cli_threshold(args))
+                              **cli_prediction(args), **cli_threshold(args), **cli_ztsnr(args))
         out_channels = None
     else:
         raise ValueError(f"--task {task!r} must be 'superres' or 'sar_to_ndvi'")
+    set_guidance_rescale(diffusion, args)
     print(f"You are using {args.UNet_type} model")
     img_lr = _load_tensor(args.img_lr_path).float()
     if img_lr.dim() == 3:

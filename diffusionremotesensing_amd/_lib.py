@@ -44,6 +44,9 @@ SIGNATURES = {
     "drs_x0_threshold_workspace_bytes": (_Z, [_I]),
     "drs_x0_quantile": (_I, [_P, _P, _F, _P, _P, _P, _I, _I, _F, _F, _L, _P, _P, _I, _L, _P, _Z, _P]),
     "drs_pred_to_eps_dyn": (_I, [_P, _P, _F, _P, _P, _P, _I, _I, _F, _F, _L, _P, _P, _I, _L, _P, _Z, _P]),
+    "drs_terminal_step": (_I, [_P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P] + [_I] * 6 + [_F, _P, _I, _P]),
+    "drs_cfg_rescale_workspace_bytes": (_Z, [_I, _L]),
+    "drs_cfg_rescale": (_I, [_P, _P, _F, _F, _P, _I, _L, _P, _Z, _P]),
     "drs_adam_multi": (_I, [_P, _I, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     "drs_grad_sumsq_partials": (_I, [_P, _I, _L, _P, _P]),
     "drs_adamw_clip_multi": (_I, [_P, _I, _L] + [C.c_double] * 6 + [_I, _P, _I, _P, _P]),

@@ -72,7 +72,38 @@ def add_prediction_args(p, in_help=True):
                    help="P, 0 < P <= 1, with --x0_clip: dynamic thresholding (Imagen) - per image, where the P-quantile of "
                         "|x0 - centre| exceeds the half-range, the clean image is compressed into the range instead of clamped; "
                         "default none" if in_help else argparse.SUPPRESS)
+    p.add_argument("--zero_terminal_snr", type=str2bool, nargs="?", const=True, default=False,
+                   help="rescale the noise schedule to zero terminal SNR (alpha_hat[T-1] = 0; needs --prediction v or x0); "
+                        "training writes it into the snapshot, which refuses to load under the other schedule"
+                        if in_help else argparse.SUPPRESS)
+    p.add_argument("--guidance_rescale", type=cli_guidance_rescale, default=0.0, metavar="PHI",
+                   help="PHI in [0, 1]: rescale the classifier-free-guided prediction per image towards the standard deviation "
+                        "of the conditional one (acts where a sampler guides with cfg_scale > 0); default 0"
+                        if in_help else argparse.SUPPRESS)
     return p
+
+
+def cli_guidance_rescale(text):
+    """The value of --guidance_rescale: a PHI in [0, 1], read while the command line is parsed."""
+    try:
+        phi = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} must be a number in [0, 1]") from None
+    if not 0.0 <= phi <= 1.0:
+        raise argparse.ArgumentTypeError(f"{text!r} must lie in [0, 1]")
+    return phi
+
+
+def cli_ztsnr(args):
+    """`add_prediction_args`' --zero_terminal_snr as a keyword argument of a `Diffusion` (merged next to `cli_prediction`; a
+    namespace without it: off)."""
+    return {"zero_terminal_snr": bool(getattr(args, "zero_terminal_snr", False))}
+
+
+def set_guidance_rescale(diffusion, args):
+    """`add_prediction_args`' --guidance_rescale onto a `Diffusion` (a plain attribute; a namespace without it: 0); returns it."""
+    diffusion.guidance_rescale = float(getattr(args, "guidance_rescale", 0.0) or 0.0)
+    return diffusion
 
 
 def cli_x0_threshold(text):

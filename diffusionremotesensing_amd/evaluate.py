@@ -28,7 +28,7 @@ import os
 
 import torch
 
-from .cli import add_bsr_args, add_prediction_args, add_solver_args, cli_prediction, cli_sampling_steps, cli_threshold
+from .cli import add_bsr_args, add_prediction_args, add_solver_args, cli_prediction, cli_sampling_steps, cli_threshold, cli_ztsnr, set_guidance_rescale
 from .colorfix import add_color_fix_args, cli_color_fix
 from .launcher import launch_device
 from .sampling import plan_of
@@ -127,8 +127,8 @@ def _superres_setup(args, device, snapshot):
     diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot,
                           noise_steps=args.noise_steps, device=device, magnification_factor=args.magnification_factor,
                           image_size=args.image_size, model_name=args.model_name, Degradation_type=args.Degradation_type,
-                          **cli_prediction(args), **cli_threshold(args))
-    return model, diffusion, val_loader
+                          **cli_prediction(args), **cli_threshold(args), **cli_ztsnr(args))
+    return model, set_guidance_rescale(diffusion, args), val_loader
 
 
 def _sar_setup(args, device, snapshot):
@@ -141,8 +141,8 @@ def _sar_setup(args, device, snapshot):
     model = Residual_Attention_UNet_SAR_TO_NDVI(args.SAR_channels, args.NDVI_channels, device).to(device)
     diffusion = S.Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot, noise_steps=args.noise_steps,
                             device=device, image_size=args.image_size, model_name=args.model_name, **cli_prediction(args),
-                            **cli_threshold(args))
-    return model, diffusion, val_loader
+                            **cli_threshold(args), **cli_ztsnr(args))
+    return model, set_guidance_rescale(diffusion, args), val_loader
 
 
 def sampling_line(sampling_steps, eta):

@@ -411,6 +411,103 @@ def renoise_(x, noise, s, t, alpha_hat):
     return x
 
 
+def terminal_step_(x, pred, noise, t, t_prev, alpha_hat, prediction, *, eta=0.0, x0_clip=None, scale=None, pred_uncond=None,
+                   cfg_scale=0.0, known=None, known_mask=None, hist=None):
+    """The reverse move of x (n, C, H, W) from the terminal level t of a zero-terminal-SNR table (alpha_hat[t] == 0) to t_prev,
+    in place (include/drs_hip.h: drs_terminal_step).  `pred` is the network's raw output of kind `prediction` ("v" or "x0";
+    ValueError for "eps", whose output at that level names no x0), guided with `pred_uncond` / `cfg_scale`; the x0 it names is
+    clamped to `x0_clip`, or thresholded with the per-image `scale` ((n,) fp32: `x0_abs_quantile`); `hist`, when given, receives
+    that x0 (the history of `dpm_step_`).  x = sqrt(ah_p) x0 + sqrt((1 - ah_p)(1 - eta^2)) x + eta sqrt(1 - ah_p) noise; `noise`
+    is needed iff t_prev > 0 and (eta > 0 or there are known pixels).  With `known` / `known_mask` (as `inpaint_step_`) the
+    known pixels get exactly `inpaint_step_`'s value.  A t whose alpha_hat is not 0, or levels outside the table, give NaN."""
+    lib = _lib.load()
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"prediction={prediction!r} must be one of {tuple(PREDICTIONS)}")
+    if prediction == "eps":
+        raise ValueError("terminal_step_: at alpha_hat == 0 an eps prediction is the state itself and names no x0 "
+                         "(prediction must be 'v' or 'x0')")
+    _req_state(x, "terminal_step_")
+    if x.dim() != 4:
+        raise RuntimeError(f"terminal_step_: x must be (n, C, H, W), got {tuple(x.shape)}")
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"terminal_step_: eta={eta} must lie in [0, 1]")
+    pred = _req(pred, "pred")
+    pred_uncond = _req(pred_uncond, "pred_uncond") if pred_uncond is not None else None
+    noise = _req(noise, "noise") if noise is not None else None
+    alpha_hat = _req(alpha_hat, "alpha_hat")
+    if (known is None) != (known_mask is None):
+        raise RuntimeError("terminal_step_: known and known_mask go together")
+    n, C_, H, W = x.shape
+    mask_channels = 1
+    if known is not None:
+        known = _req(known, "known")
+        known_mask = _req(known_mask, "known_mask", torch.uint8)
+        if known_mask.dim() != 4 or known_mask.shape[0] != n or tuple(known_mask.shape[2:]) != (H, W):
+            raise RuntimeError(f"terminal_step_: known_mask {tuple(known_mask.shape)} must be ({n}, 1 or {C_}, {H}, {W})")
+        mask_channels = int(known_mask.shape[1])
+    _req_numel("terminal_step_", x, (("pred", pred), ("pred_uncond", pred_uncond), ("noise", noise), ("known", known)))
+    flag, lo, hi = _clamp_args(x0_clip, "terminal_step_")
+    if flag and not lo < hi:
+        raise ValueError(f"terminal_step_: x0_clip=({lo}, {hi}) needs lo < hi")
+    if scale is not None:
+        if not flag:
+            raise ValueError("terminal_step_: scale needs x0_clip=(lo, hi), the range it thresholds to")
+        scale = _req(scale, "scale")
+        if scale.numel() != n:
+            raise RuntimeError(f"terminal_step_: scale has {scale.numel()} elements, x has {n} images")
+    if hist is not None:
+        _req_history("terminal_step_", x, hist, None)
+    with torch.cuda.device(x.device):
+        st = lib.drs_terminal_step(_ptr(x), _ptr(pred), _ptr(pred_uncond), float(cfg_scale), _ptr(noise), _ptr(known),
+                                   _ptr(known_mask), mask_channels, PREDICTIONS[prediction], flag, lo, hi, _ptr(scale),
+                                   _ptr(hist), n, C_, H, W, int(t), int(t_prev), float(eta), _ptr(alpha_hat), alpha_hat.numel(),
+                                   _stream(x.device))
+    _lib.check(st, "drs_terminal_step")
+    return x
+
+
+_RESCALE_WS = {}  # device index -> uint8 workspace of drs_cfg_rescale, grown as needed
+
+
+def _rescale_workspace(lib, n, chw, device):
+    need = lib.drs_cfg_rescale_workspace_bytes(n, chw)
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    ws = _RESCALE_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _RESCALE_WS[key] = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+    return ws
+
+
+def cfg_rescale(cond, uncond, cfg_scale, guidance_rescale, out=None):
+    """The guided prediction torch.lerp(uncond, cond, cfg_scale) (n, ...) with every image scaled by 1 + phi (std(cond) /
+    std(guided) - 1), phi = `guidance_rescale` in [0, 1] (include/drs_hip.h: drs_cfg_rescale; Lin et al. 2024, section 3.4), into
+    `out` (which may be `cond`) or a new tensor.  phi == 0 launches nothing of it: the result is the plain torch.lerp."""
+    phi = float(guidance_rescale)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"guidance_rescale={guidance_rescale!r} must lie in [0, 1]")
+    cond = _req(cond, "cond"); uncond = _req(uncond, "uncond")
+    _req_numel("cfg_rescale", cond, (("uncond", uncond),), "cond")
+    if out is not None:
+        _req_state(out, "cfg_rescale", "out")
+        _req_numel("cfg_rescale", cond, (("out", out),), "cond")
+    if phi == 0.0:
+        g = torch.lerp(uncond, cond, float(cfg_scale))
+        return g if out is None else out.copy_(g.view_as(out))
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(cond)
+    n = cond.shape[0] if cond.dim() else 0
+    chw = cond.numel() // n if n else 0
+    if n == 0 or chw == 0:
+        return out
+    ws = _rescale_workspace(lib, n, chw, cond.device)
+    with torch.cuda.device(cond.device):
+        st = lib.drs_cfg_rescale(_ptr(cond), _ptr(uncond), float(cfg_scale), phi, _ptr(out), n, chw, _ptr(ws), ws.numel(),
+                                 _stream(cond.device))
+    _lib.check(st, "drs_cfg_rescale")
+    return out
+
+
 def reverse_step_(x, eps, noise, t, t_prev, *, alpha, alpha_hat, beta, ddim=False, eta=0.0, eps_uncond=None, cfg_scale=0.0,
                   known=None, known_mask=None, hist=None, t_q=-1):
     """One reverse move t -> t_prev of x, in place, by the wrapper that takes this kind of move: `dpm_step_` with a history

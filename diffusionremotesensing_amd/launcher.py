@@ -46,7 +46,8 @@ def train_model(args, diffusion_class, model, device, train_loader, val_loader, 
                                 noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02, device=device,
                                 image_size=args.image_size, model_name=args.model_name, multiple_gpus=args.multiple_gpus,
                                 ema_smoothing=args.ema_smoothing, **cli.cli_prediction(args), **cli.cli_threshold(args),
-                                **diffusion_kwargs)
+                                **cli.cli_ztsnr(args), **diffusion_kwargs)
+    cli.set_guidance_rescale(diffusion, args)
     diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
                     train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
                     verbose=True, **cli.train_kwargs(args), **cli.cli_finetune(args), **(train_kwargs or {}))

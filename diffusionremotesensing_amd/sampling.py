@@ -23,6 +23,48 @@ def ddim_timesteps(noise_steps, sampling_steps):
     return [1 + (k * (T - 2)) // (S - 1) for k in reversed(range(S))]
 
 
+def rescale_zero_terminal_snr(alpha_hat):
+    """The alpha_hat table rescaled to zero terminal SNR (Lin et al., "Common Diffusion Noise Schedules and Sample Steps Are
+    Flawed", 2024, Algorithm 1), fp32 on the input's device: with s = sqrt(ah) in float64, s' = (s - s[T-1]) s[0] / (s[0] - s[T-1])
+    and ah' = s'^2 cast to fp32; ah'[T-1] is exactly 0.0 and ah'[0] is the input's ah[0], bit for bit.  At the last level the
+    forward process then returns pure noise, which is what every sampler starts from."""
+    ah = torch.as_tensor(alpha_hat)
+    if ah.dim() != 1 or ah.numel() < 2:
+        raise ValueError("rescale_zero_terminal_snr needs a table of at least 2 levels")
+    s = ah.detach().to("cpu", torch.float64).sqrt()
+    if not s[0] > s[-1]:
+        raise ValueError("rescale_zero_terminal_snr needs alpha_hat[0] > alpha_hat[T - 1]")
+    out = (((s - s[-1]) * s[0] / (s[0] - s[-1])) ** 2).to(torch.float32)
+    out[-1] = 0.0
+    out = out.to(ah.device)
+    out[0] = ah[0].to(torch.float32)
+    return out
+
+
+def check_zero_terminal_snr(zero_terminal_snr, prediction):
+    """ValueError for a zero-terminal-SNR schedule under an eps network: at alpha_hat == 0 the state is the noise, so the eps
+    target is the network's input and its output says nothing about the image."""
+    if zero_terminal_snr and prediction == "eps":
+        raise ValueError("zero_terminal_snr needs prediction='v' or 'x0': at the terminal level (alpha_hat == 0) the eps target "
+                         "is the network's input itself")
+    return bool(zero_terminal_snr)
+
+
+def check_terminal_eta(schedule, eta):
+    """ValueError for eta > 1 on a chain that has a terminal level (sqrt((1 - ah_p)(1 - eta^2)) has no real value there)."""
+    if getattr(schedule, "zero_terminal_snr", False) and eta > 1:
+        raise ValueError(f"eta={eta} > 1 cannot be taken from the terminal level of a zero_terminal_snr schedule: the move's "
+                         "variance eta^2 (1 - alpha_hat) would exceed that of the level it reaches")
+
+
+def check_guidance_rescale(guidance_rescale):
+    """ValueError for a `guidance_rescale` outside [0, 1]; the value as a float."""
+    if isinstance(guidance_rescale, bool) or not isinstance(guidance_rescale, numbers.Real) or \
+            not 0.0 <= float(guidance_rescale) <= 1.0:
+        raise ValueError(f"guidance_rescale={guidance_rescale!r} must be a number in [0, 1]")
+    return float(guidance_rescale)
+
+
 PREDICTIONS = ("eps", "v", "x0")
 
 
@@ -117,11 +159,15 @@ def logsnr_timesteps(alpha_hat, sampling_steps):
     """S levels, descending and distinct, in [1, T - 1], as uniform in lam_t = 0.5 ln(ah_t / (1 - ah_t)) as the table allows
     (float64 arithmetic on the fp32 table, one read-back per chain): for each of linspace(lam_{T-1}, lam_1, S) the nearest t
     (ties: the larger t), then t_k = min(t_k, t_{k-1} - 1) going down the list and t_k = max(t_k, S - k) going back up, so
-    that the last entry is at least 1.  The step after the last entry goes to level 0, as after `ddim_timesteps`."""
+    that the last entry is at least 1.  The step after the last entry goes to level 0, as after `ddim_timesteps`.
+    On a zero-terminal-SNR table (ah_{T-1} == 0: lam_{T-1} = -inf, which never enters the linspace) the list is T - 1 followed by
+    the S - 1 levels this rule gives on the table restricted to the levels 0 .. T - 2."""
     ah = torch.as_tensor(alpha_hat).detach().to("cpu", torch.float64)
     T, S = ah.numel(), int(sampling_steps)
     if not 1 <= S <= T - 1:
         raise ValueError(f"sampling_steps={sampling_steps} outside [1, noise_steps - 1 = {T - 1}]")
+    if float(ah[-1]) == 0.0:
+        return [T - 1] + (logsnr_timesteps(ah[:-1], S - 1) if S > 1 else [])
     ah = ah.numpy()
     lam = 0.5 * np.log(ah[1:] / (1.0 - ah[1:]))  # lam[t - 1] = lam_t, decreasing in t
     targets = np.linspace(lam[-1], lam[0], S)
@@ -164,6 +210,22 @@ def check_solver_known(sampling_steps, known, known_mask):
     if plan_of(sampling_steps)[0] == "dpmpp_2m" and (known is not None or known_mask is not None):
         raise ValueError("solver='dpmpp_2m' cannot keep known pixels: their replacement and the forward jumps of the "
                          "resampling invalidate the multistep history (use solver='ddim' or the ancestral chain)")
+
+
+def check_terminal_chain(schedule, prediction, eta, update=None):
+    """(the terminal level of `schedule` or None, its guidance_rescale) for `sample_chain`; ValueError for a chain on a
+    zero-terminal-SNR schedule that cannot run: an eps network, eta > 1, or the per-step `update` hook of the tiler, whose
+    per-tile conversion to eps is 0 / 0 at the terminal level."""
+    phi = check_guidance_rescale(getattr(schedule, "guidance_rescale", 0.0))
+    if not getattr(schedule, "zero_terminal_snr", False):
+        return None, phi
+    check_zero_terminal_snr(True, prediction)
+    check_terminal_eta(schedule, eta)
+    if update is not None:
+        raise ValueError("zero_terminal_snr cannot be combined with a per-step update hook (the tiler's "
+                         "aggregation='per_step'): its per-tile conversion to eps is 0 / 0 at the terminal level; use "
+                         "aggregation='final'")
+    return int(schedule.noise_steps) - 1, phi
 
 
 def ddim_chain_noise(eta, t, t_prev, shape, x, noise_source):
@@ -335,7 +397,16 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
     update then gets one eps and cfg_scale 0), so every move above takes what it always took; a `predict` marked by
     `converts_prediction` has done so itself.  With "eps" and None nothing is launched.  `schedule.x0_threshold` (None when
     it has none; a quantile p needs the clip: `check_threshold`) makes that one call threshold the implied x0 per image instead
-    of clamping it (`pred_to_eps_(..., x0_threshold=p)`); nothing else in the chain changes."""
+    of clamping it (`pred_to_eps_(..., x0_threshold=p)`); nothing else in the chain changes.
+    `schedule.zero_terminal_snr` (False when it has none; read from the schedule, not from the device table: no synchronisation)
+    makes level noise_steps - 1 the terminal one, where alpha_hat is 0: a reverse move away from it - the first of every chain,
+    and the one after a forward jump back up to it - skips `pred_to_eps_` and the update and is one `hip_ops.terminal_step_`
+    on the raw prediction (with the clip, the per-image `hip_ops.x0_abs_quantile` scales under `x0_threshold`, the move's draw,
+    the known pixels and, under "dpmpp_2m", the history, after which `hist_level` is None: the next move is first order).  On
+    the ancestral chain that move is taken as eta = 1, the true posterior at beta = 1.  The `update` hook cannot take it
+    (ValueError: `check_terminal_chain`).  `schedule.guidance_rescale` = phi in (0, 1] (0 when it has none) acts where `predict`
+    returns a pair and cfg_scale > 0: one `hip_ops.cfg_rescale` forms the rescaled guided prediction first, and everything after
+    it sees a single prediction and cfg_scale 0."""
     ddim = sampling_steps is not None
     solver, spacing = plan_of(sampling_steps)
     dpm = solver == "dpmpp_2m"
@@ -343,6 +414,7 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
     x0_threshold = check_threshold(getattr(schedule, "x0_threshold", None), x0_clip)
     dynamic = {"x0_threshold": x0_threshold} if x0_threshold is not None else {}
     convert = (prediction != "eps" or x0_clip is not None) and not getattr(predict, "converts_prediction", False)
+    terminal_level, phi = check_terminal_chain(schedule, prediction, eta, update)
     moves = chain_moves(schedule.noise_steps, sampling_steps, resample, jump, spacing, schedule.alpha_hat if ddim else None)
     with torch.no_grad():
         x = noise_source(schedule.noise_steps, shape) if noise_source is not None else torch.randn(shape)  # (CPU generator, :230)
@@ -366,6 +438,22 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
                 state["first"] = False
                 eps, eps_uncond = eps if isinstance(eps, tuple) else (eps, None)
                 guide = cfg_scale
+                if phi > 0 and eps_uncond is not None and cfg_scale > 0:  # (one prediction from here on, as after `convert`)
+                    eps = hip_ops.cfg_rescale(eps, eps_uncond, cfg_scale, phi, out=eps)
+                    eps_uncond, guide = None, 0.0
+                if t == terminal_level:
+                    noise = draw(t) if t_to > 0 and (known is not None or not ddim or eta > 0) else None
+                    scale = None
+                    if x0_threshold is not None:
+                        scale = hip_ops.x0_abs_quantile(eps, x, t_rows[t][:shape[0]], schedule.alpha_hat, prediction, x0_clip,
+                                                        x0_threshold, pred_uncond=eps_uncond, cfg_scale=guide)
+                    hip_ops.terminal_step_(x, eps, noise, t, t_to, schedule.alpha_hat, prediction, eta=eta if ddim else 1.0,
+                                           x0_clip=x0_clip, scale=scale, pred_uncond=eps_uncond, cfg_scale=guide, known=known,
+                                           known_mask=known_mask, hist=hist)
+                    state["hist_level"] = None  # (the next DPM-Solver++(2M) move is first order)
+                    if frames is not None:
+                        frames.append(x.clone())
+                    return
                 if convert:  # (the generation sampler's rows are 2n wide: conditional | unconditional)
                     eps = hip_ops.pred_to_eps_(eps, x, t_rows[t][:shape[0]], schedule.alpha_hat, prediction, x0_clip,
                                                pred_uncond=eps_uncond, cfg_scale=cfg_scale, **dynamic)

@@ -24,12 +24,12 @@ from .UNet_model_SAR_TO_NDVI import Residual_Attention_UNet_SAR_TO_NDVI
 class Diffusion(_SuperresDiffusion):
     def __init__(self, noise_schedule: str, model: nn.Module, snapshot_path: str, noise_steps=1000, beta_start=1e-4,
                  beta_end=0.02, device="cuda", image_size=224, model_name="SAR_TO_NDVI", multiple_gpus=False,
-                 ema_smoothing=False, prediction="eps", x0_clip=None, x0_threshold=None):
+                 ema_smoothing=False, prediction="eps", x0_clip=None, x0_threshold=None, zero_terminal_snr=False):
         super().__init__(noise_schedule, model, snapshot_path, noise_steps=noise_steps, beta_start=beta_start,
                          beta_end=beta_end, device=device, magnification_factor=1, image_size=image_size,
                          model_name=model_name, Degradation_type="DownBlur", multiple_gpus=multiple_gpus,
                          ema_smoothing=ema_smoothing, prediction=prediction, x0_clip=x0_clip,
-                         x0_threshold=x0_threshold)
+                         x0_threshold=x0_threshold, zero_terminal_snr=zero_terminal_snr)
         del self.magnification_factor, self.Degradation_type  # attributes the reference's SAR Diffusion does not have
 
     def _predict(self, net, x_t, t, cond):

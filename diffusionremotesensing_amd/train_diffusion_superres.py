@@ -36,8 +36,8 @@ from .losses import DiffusionLoss, LossAwareSampler, LossBins, min_snr_weights
 from .optim import FusedAdam, FusedAdamW, WarmupCosine
 from .sampling import (CHAIN_CHECK_EVERY, _is_int, _repeat_members, asks_for_known_pixels,  # noqa: F401 - re-exported
                        check_ensemble_args, check_inpaint_args, check_prediction, check_sampling_args, check_threshold, check_solver_known,
-                       ddim_chain_noise,
-                       ddim_timesteps, ensemble_chunks, inpaint_schedule, known_tensors, run_reverse_chain, sample_chain,
+                       check_terminal_chain, check_zero_terminal_snr, ddim_chain_noise,
+                       rescale_zero_terminal_snr, ddim_timesteps, ensemble_chunks, inpaint_schedule, known_tensors, run_reverse_chain, sample_chain,
                        sampling_plan)
 from .superres_feeds import SyntheticSuperresDataset, make_superres_feeds  # noqa: F401
 from .UNet_model_superres import EMA, Residual_Attention_UNet_superres
@@ -80,7 +80,7 @@ class Diffusion:
     def __init__(self, noise_schedule: str, model: nn.Module, snapshot_path: str, noise_steps=1000, beta_start=1e-4,
                  beta_end=0.02, device="cuda", magnification_factor=4, image_size=224, model_name="superres",
                  Degradation_type="BSRGAN", multiple_gpus=False, ema_smoothing=False, prediction="eps", x0_clip=None,
-                 x0_threshold=None):
+                 x0_threshold=None, zero_terminal_snr=False):
         # not in the reference, whose networks predict the noise: what this one predicts ("eps", "v" or "x0": the training
         # target, and what sampling converts to eps before every update) and the range the x0 implied at every reverse step
         # is clamped to (None or (lo, hi); a plain attribute, read at the start of every chain).  DESIGN.md section 23.
@@ -89,6 +89,11 @@ class Diffusion:
         # |x0 - centre| exceeds the half-range, x0 is compressed into the range instead of cut off at it).  A plain attribute
         # like x0_clip, not written into snapshots.  DESIGN.md section 24.
         self.x0_threshold = check_threshold(x0_threshold, self.x0_clip)
+        # ... and a schedule rescaled to zero terminal SNR (alpha_hat[T - 1] == 0: the network is trained on pure noise at the
+        # level every sampler starts from; needs a v or x0 network, written into snapshots), with the guidance rescale that goes
+        # with it (phi in [0, 1], a plain attribute; acts where a sampler guides with cfg_scale > 0).  DESIGN.md section 26.
+        self.zero_terminal_snr = check_zero_terminal_snr(zero_terminal_snr, self.prediction)
+        self.guidance_rescale = 0.0
         self.noise_steps = noise_steps
         self.beta_start = beta_start
         self.beta_end = beta_end
@@ -117,6 +122,10 @@ class Diffusion:
             self.beta = self.from_alpha_hat_to_beta()
             self.alpha = 1.0 - self.beta
         # any other name leaves the schedule unset, like the reference (:117-126)
+        if self.zero_terminal_snr and noise_schedule in ("linear", "cosine"):
+            self.alpha_hat = rescale_zero_terminal_snr(self.alpha_hat)
+            self.beta = self.from_alpha_hat_to_beta()  # (beta[T - 1] == 1, alpha[T - 1] == 0)
+            self.alpha = 1.0 - self.beta
 
     # -- schedules (reference :128-169) ---------------------------------------------------------
     def prepare_noise_schedule(self):
@@ -242,6 +251,7 @@ class Diffusion:
         `hist=` and `t_q=`, as `sampling.sample_chain` says.  The chain is `sampling.sample_chain`; this method adds the eval
         mode around it and the video."""
         check_solver_known(sampling_steps, known, known_mask)
+        check_terminal_chain(self, self.prediction, eta, update)
         model.eval()
         frames = [] if generate_video else None
         x = sample_chain(self, self._engine_net(model).hip_engine(), shape, predict, table_rows=table_rows, noise_source=noise_source,
@@ -401,6 +411,8 @@ class Diffusion:
         snapshot = {"MODEL_STATE": self._unwrapped(model).state_dict(), "EPOCHS_RUN": epoch}
         if self.prediction != "eps":  # (an eps network's file stays the reference's two keys)
             snapshot["PREDICTION"] = self.prediction
+        if self.zero_terminal_snr:  # (likewise: an off run writes what it always wrote)
+            snapshot["ZERO_TERMINAL_SNR"] = True
         torch.save(snapshot, self.snapshot_path)
         print(f"Epoch {epoch} | Training snapshot saved at {self.snapshot_path}")
 
@@ -427,6 +439,11 @@ class Diffusion:
         if saved != self.prediction:
             raise ValueError(f"{self.snapshot_path} holds a network that predicts {saved!r}, this Diffusion was built with "
                              f"prediction={self.prediction!r} (--prediction {saved})")
+        saved = bool(snapshot.get("ZERO_TERMINAL_SNR", False))
+        if saved != self.zero_terminal_snr:
+            raise ValueError(f"{self.snapshot_path} holds a network trained with zero_terminal_snr={saved}, this Diffusion was "
+                             f"built with zero_terminal_snr={self.zero_terminal_snr}: the two schedules differ at every level "
+                             f"({'pass' if saved else 'drop'} --zero_terminal_snr)")
 
     # -- the rest of a run's state (not in the reference, which marks the gap: LR_SCHEDULER is commented out at :275) --------
     def train_state_path(self):
@@ -447,6 +464,8 @@ class Diffusion:
             ts["LOSS_BINS"] = run.loss_bins.state_dict()
         if getattr(run, "freeze_bn", False) or getattr(run, "freeze", ()):  # (likewise)
             ts["FREEZE_BN"], ts["FREEZE"] = run.freeze_bn, tuple(run.freeze)
+        if self.zero_terminal_snr:  # (likewise)
+            ts["ZERO_TERMINAL_SNR"] = True
         torch.save(ts, self.train_state_path())
 
     def _load_train_state(self, run):
@@ -462,6 +481,9 @@ class Diffusion:
                                                                                 tuple(getattr(run, "freeze", ()))):
             raise ValueError(f"{self.train_state_path()} was written with --freeze_bn {bool(ts.get('FREEZE_BN', False))} "
                              f"--freeze {','.join(ts.get('FREEZE', ())) or '(none)'}: a resumed run must freeze the same")
+        if bool(ts.get("ZERO_TERMINAL_SNR", False)) != self.zero_terminal_snr:
+            raise ValueError(f"{self.train_state_path()} was written with zero_terminal_snr="
+                             f"{bool(ts.get('ZERO_TERMINAL_SNR', False))}: a resumed run must keep the schedule")
         if run.loss_bins is not None:
             run.loss_bins.load_state_dict(ts["LOSS_BINS"])  # (other T / bin count: ValueError)
         # (another parameter count or other shapes: ValueError from FusedAdamW.load_state_dict, the first thing loaded)
@@ -505,6 +527,10 @@ class Diffusion:
             raise ValueError("loss_weighting must be none or min_snr, timestep_sampling uniform or loss_aware")
         if loss_bins < 0 or not min_snr_gamma > 0:
             raise ValueError("loss_bins must be >= 0 and min_snr_gamma > 0")
+        if loss_weighting == "min_snr" and self.zero_terminal_snr:
+            raise ValueError("loss_weighting='min_snr' cannot be combined with zero_terminal_snr: the Min-SNR weight of a v or "
+                             "x0 target is 0 at SNR 0, so the terminal level - the one the schedule exists for - would not be "
+                             "trained")
         if loss_weighting == "none" and timestep_sampling == "uniform" and not loss_bins:
             return None
         if loss == "MSE+Perceptual_noise":

@@ -212,6 +212,51 @@ DRS_API int drs_pred_to_eps_dyn(const float* pred, const float* pred_uncond, flo
                                 float* scale_out, int n, int64_t chw, void* workspace, size_t workspace_bytes,
                                 drs_stream_t stream);
 
+/* The reverse move away from the terminal level of a zero-terminal-SNR schedule (alpha_hat[t] == 0; Lin et al., "Common
+ * Diffusion Noise Schedules and Sample Steps Are Flawed", 2024; csrc/terminal_step.hip), in place on x (n,C,H,W), one scalar t
+ * and t_prev for all images as in drs_ddim_step.  At that level x is the noise itself and the network names x0 directly, so the
+ * move divides by nothing.  Per element, with ah_p = alpha_hat[t_prev] read on the device (for t_prev == 0 too, as drs_ddim_step):
+ *   p     = pred_uncond ? lerp(pred_uncond, pred, cfg_scale) : pred              (torch.lerp, as the guided step entries)
+ *   x0    = kind == DRS_PRED_V ? -p : p
+ *   x0    = clip, scale == NULL: min(max(x0, lo), hi) for a finite x0, x0 itself otherwise     (as drs_pred_to_eps)
+ *           scale != NULL (needs clip): the rule of drs_pred_to_eps_dyn with s = scale[image] and its fp32 c and r: the static
+ *           clamp (its bits) where s <= r or s is not finite; otherwise clamp(c + (clamp(x0 - c, -s, s) / s) r, lo, hi), which
+ *           is evaluated in fp64 from the fp32 inputs (the guidance lerp included) and rounded to fp32 once - that entry's
+ *           fp32 steps round around c and s, many ulps of a result next to the lower edge of a (0, 1) range; an element
+ *           clamped to c +- s lands on lo / hi exactly
+ *   x0_hist = x0                                                                  (if given: the history of drs_dpm_step)
+ *   sigma = t_prev == 0 ? 0 : eta sqrt(1 - ah_p),   c0 = sqrt(ah_p),   c1 = sqrt(max(0, (1 - ah_p)(1 - eta^2)))
+ *   x     = fl(fl(c0 x0) + fl(c1 x)) + fl(sigma noise)                            (the last term only where sigma != 0)
+ * The coefficients are formed in fp64 from the fp32 table entry and rounded to fp32 once; products and sums are fp32, rounded one
+ * by one.  eta = 1 is the true posterior at beta_t = 1: mean sqrt(ah_p) x0, variance 1 - ah_p.  Where mask != 0 (known, mask as in
+ * drs_inpaint_step; both NULL: no known pixels) the element is exactly drs_inpaint_step's known-pixel value for that t_prev and
+ * noise.  `noise` is required iff t_prev > 0 and (eta > 0 or there are known pixels).
+ * If alpha_hat[t] != 0 on the device, or not 0 <= t_prev < t < noise_steps, every output of the call (x, x0_hist) is NaN and the
+ * table is not indexed outside its bounds: the convention of drs_pred_to_eps.  16-byte accesses when x, pred, pred_uncond, noise,
+ * known and x0_hist start at the same place of a 16-byte line (rows as drs_noise_v_target), element by element otherwise.
+ * DRS_ERR_ARG (x untouched): null x / pred / alpha_hat, kind not DRS_PRED_V or DRS_PRED_X0, known without mask or the reverse,
+ * clip with lo >= hi, scale without clip, a cfg_scale that is not finite, eta outside [0, 1], a missing noise, x0_hist == x;
+ * DRS_ERR_SHAPE: n < 0, C < 1, H < 0, W < 0, noise_steps <= 0, mask_channels neither 1 nor C. */
+DRS_API int drs_terminal_step(float* x, const float* pred, const float* pred_uncond, float cfg_scale, const float* noise,
+                              const float* known, const uint8_t* mask, int mask_channels, int kind, int clip, float lo, float hi,
+                              const float* scale, float* x0_hist, int n, int C, int H, int W, int t, int t_prev, float eta,
+                              const float* alpha_hat, int noise_steps, drs_stream_t stream);
+
+/* Guidance rescale (the same paper, section 3.4), per image of `chw` elements:
+ *   g   = lerp(uncond, cond, cfg_scale)                      (torch.lerp, fp32, as the guided step entries)
+ *   f   = 1 + phi (std(cond) / std(g) - 1)                   fp64, rounded to fp32 once; both stds over the image's chw elements
+ *   out = fl(g f)
+ * std(g) == 0 or a ratio that is not finite gives f = 1.  Two launches on `stream`, no atomics and no host synchronisation:
+ * the first writes, per chunk of 4096 elements, fp64 sums and sums of squares of cond - cond[0] and g - g[0] (added in a fixed
+ * order: per thread in element order, a shuffle tree over the wave, the four waves in order); the second adds an image's
+ * partials in index order in every block and scales.  Two calls give the same bits.  `out` may be `cond`.  `workspace`: device,
+ * 8-byte aligned, >= drs_cfg_rescale_workspace_bytes(n, chw) bytes.
+ * DRS_ERR_ARG: null pointer, cfg_scale not finite, phi outside [0, 1], workspace too small; DRS_ERR_SHAPE: n < 0, chw < 0,
+ * n > 65535. */
+DRS_API size_t drs_cfg_rescale_workspace_bytes(int n, int64_t chw);
+DRS_API int drs_cfg_rescale(const float* cond, const float* uncond, float cfg_scale, float phi, float* out, int n, int64_t chw,
+                            void* workspace, size_t workspace_bytes, drs_stream_t stream);
+
 /* One Adam step over many tensors in ONE launch (torch.optim.Adam defaults: no weight decay, no amsgrad):
  *   m = lerp(m, g, 1-beta1); v = v*beta2 + (1-beta2)*g*g; p -= lr/(1-beta1^step) * m / (sqrt(v)/sqrt(1-beta2^step) + eps)
  * `table` (device): ntensors x drs_adam_tensor {p, g, m, v, n, step}; entries with g == NULL are skipped (parameters
