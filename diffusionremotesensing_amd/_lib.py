@@ -71,6 +71,11 @@ SIGNATURES = {
     "drs_metrics_workspace_bytes": (_Z, [_I] * 4),
     "drs_metrics_pointwise": (_I, [_P, _P, _P] + [_I] * 5 + [_P, _Z, _P]),
     "drs_ssim": (_I, [_P, _P, _P] + [_I] * 5 + [_P, _Z, _P]),
+    "drs_noise_target_nodata": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _I, _I, _L, _P]),
+    "drs_diffusion_loss_masked": (_I, [_P, _P, _P, _P, _I, _I, _L, _P, _I, _P, _I, C.c_double] + [_P] * 6 + [_I, _I, _I, _P, _P]),
+    "drs_metrics_nodata_workspace_bytes": (_Z, [_I] * 4),
+    "drs_metrics_pointwise_nodata": (_I, [_P, _P, _F, _P] + [_I] * 5 + [_P, _Z, _P]),
+    "drs_ssim_nodata": (_I, [_P, _P, _F, _P] + [_I] * 5 + [_P, _Z, _P]),
     "drs_ensemble_workspace_bytes": (_Z, [_I] * 5),
     "drs_ensemble_stats": (_I, [_P] * 5 + [_I] * 7 + [_F, _F, _P]),
     "drs_ensemble_scores": (_I, [_P] * 5 + [_I] * 6 + [_F, _F, _P, _Z, _P]),

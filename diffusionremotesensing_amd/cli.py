@@ -166,6 +166,45 @@ def cli_finetune(args):
             "init_from": getattr(args, "init_from", None)}
 
 
+def cli_nodata(text):
+    """The value of the SAR -> NDVI trainer's and `evaluate`'s --nodata: 'nan' (a pixel with a NaN band is no-data) or the
+    no-data value V (also a pixel whose bands all equal V), read while the command line is parsed."""
+    if text.strip().lower() == "nan":
+        return "nan"
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} must be 'nan' or a number") from None
+    if value != value:
+        return "nan"
+    if value in (float("inf"), float("-inf")):
+        raise argparse.ArgumentTypeError(f"{text!r} must be finite")
+    return value
+
+
+def cli_nodata_u8(text):
+    """The value of the super-resolution trainer's --nodata: an integer K in 0 .. 255, the stored pixel value that marks no-data."""
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} must be an integer in 0 .. 255") from None
+    if not 0 <= k <= 255:
+        raise argparse.ArgumentTypeError(f"{text!r} must lie in 0 .. 255")
+    return k
+
+
+def add_nodata_args(p, in_help=True, u8=False):
+    """--nodata of the two conditional trainers and `evaluate`.  `u8`: the super-resolution form, an
+    integer pixel value K (the rule value is float32(K) / 255, the bits the u8 feeds produce); otherwise 'nan' or a number.
+    `in_help` False registers it without a --help entry, as `add_prediction_args` does for the trainers."""
+    text = ("K in 0 .. 255: HR pixels whose bands all hold K are no-data - left out of the loss and the scores (DownBlur only; "
+            "the LR image is still made from the stored pixels)" if u8 else
+            "'nan' or V: pixels of the truth with a NaN band (and, with V, whose bands all equal V) are no-data - left out of "
+            "the loss and the scores")
+    p.add_argument("--nodata", type=cli_nodata_u8 if u8 else cli_nodata, default=None, help=text if in_help else argparse.SUPPRESS)
+    return p
+
+
 def add_bsr_args(p):
     """--bsr_kind / --bsr_seed of the command lines that build the BSRGAN feed (not in the reference; `make_superres_feeds`)."""
     p.add_argument("--bsr_kind", type=str, choices=("plus", "soft"), default="plus",

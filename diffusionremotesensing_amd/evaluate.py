@@ -22,13 +22,18 @@ line gives CRPS, spread, RMSE of the mean, the spread / skill ratio and the rank
 
 `--color_fix wavelet|adain [--color_fix_levels L]` (superres only: the task with an LR guide) adds a `model_fixed` row: the
 same samples, colour-corrected against the up-sampled LR image (colorfix.py).
+
+`--nodata V` (sar_to_ndvi: 'nan' or the files' no-data value; superres: the stored byte K in 0 .. 255, as on its trainer - the
+rule value is float32(K) / 255, the bits the uint8 feeds give it) scores every row over the valid pixels of the truth alone and adds the `valid` column, the share of valid pixels;
+for sar_to_ndvi the folder is also read with it (a no-data pixel becomes NaN).  Not with --ensemble or --known_fraction.
 """
 import json
 import os
 
 import torch
 
-from .cli import add_bsr_args, add_prediction_args, add_solver_args, cli_prediction, cli_sampling_steps, cli_threshold, cli_ztsnr, set_guidance_rescale
+from .cli import (add_bsr_args, add_nodata_args, add_prediction_args, add_solver_args, cli_prediction, cli_sampling_steps, cli_threshold,
+                  cli_ztsnr, set_guidance_rescale)
 from .colorfix import add_color_fix_args, cli_color_fix
 from .launcher import launch_device
 from .sampling import plan_of
@@ -145,6 +150,17 @@ def _sar_setup(args, device, snapshot):
     return model, set_guidance_rescale(diffusion, args), val_loader
 
 
+def _evaluate_nodata(args, task):
+    """`Diffusion.evaluate`'s `nodata` for --nodata: the SAR -> NDVI folder loader has already turned every no-data pixel into
+    NaN (the synthetic pairs have none: the value rule stays), so the NaN rule scores it; superres takes the stored byte K and
+    compares float32(K) / 255 (`nodata_u8_value`: ValueError under BSRGAN, whose HR image is sharpened)."""
+    if task == "superres":
+        from .train_diffusion_superres import nodata_u8_value
+        return nodata_u8_value(args.nodata, args.Degradation_type)
+    folder = not str(args.dataset_path or "").startswith("synthetic")
+    return True if folder else args.nodata
+
+
 def sampling_line(sampling_steps, eta):
     """The summary line's words for a chain of `sampling_steps` levels: solver, steps, eta and - unless it is plain DDIM on
     uniform levels, whose words stay what they were - the spacing `plan_of` resolves."""
@@ -157,7 +173,8 @@ def cli_arg_parser(task="superres"):
     """The whole command line of `main` for `task`: `evaluate_arg_parser` with the known-pixel, ensemble, solver and prediction
     flags (--prediction must be the snapshot's; --x0_clip) and, for superres (the task with an LR guide), --color_fix /
     --color_fix_levels and the BSRGAN feed's --bsr_kind / --bsr_seed."""
-    p = add_prediction_args(add_solver_args(add_ensemble_args(add_known_args(evaluate_arg_parser(task)))))
+    p = add_nodata_args(add_prediction_args(add_solver_args(add_ensemble_args(add_known_args(evaluate_arg_parser(task))))),
+                        u8=task == "superres")
     return add_bsr_args(add_color_fix_args(p)) if task == "superres" else p
 
 
@@ -186,6 +203,8 @@ def main(argv=None):
         p.error("--member_batch (>= 1) belongs to --ensemble")
     if args.ensemble is not None and args.known_fraction is not None:
         p.error("--ensemble and --known_fraction cannot be combined")
+    if args.nodata is not None and (args.ensemble is not None or args.known_fraction is not None):
+        p.error("--nodata cannot be combined with --ensemble or --known_fraction")
     fix = cli_color_fix(args)
     if fix and (args.ensemble is not None or args.known_fraction is not None):
         p.error("--color_fix cannot be combined with --ensemble or --known_fraction")
@@ -202,7 +221,7 @@ def main(argv=None):
     scores = diffusion.evaluate(model, unshuffled(val_loader), n_images=args.n_images, sampling_steps=cli_sampling_steps(args),
                                 eta=args.eta, known_mask_fn=known_mask_fn(args), resample=args.resample, jump=args.jump,
                                 **({"ensemble": args.ensemble, "member_batch": args.member_batch} if args.ensemble else {}),
-                                **fix)
+                                **({"nodata": _evaluate_nodata(args, task)} if args.nodata is not None else {}), **fix)
     print(f"{scores['n']} validation images, snapshot of epoch {diffusion.epochs_run}, "
           + (sampling_line(cli_sampling_steps(args), args.eta) if args.sampling_steps else f"{args.noise_steps - 1} ancestral steps")
           + (f", {args.known_fraction:.0%} of every image hidden, the rest known (resample {args.resample}, jump {args.jump})"

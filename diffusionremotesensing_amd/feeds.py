@@ -97,12 +97,30 @@ def gather_u8(u8, labels, idx):
     return img, lab
 
 
-def load_sar_ndvi_folder(root_dir, data_format="torch", rank=0, world_size=1, limit=None):
+def nodata_pixels(img, nodata):
+    """(..., 1, H, W) bool: the no-data pixels of fp32 images (..., C, H, W) under the package's rule - any band NaN or, when
+    `nodata` is a number, all bands equal to it as fp32 ("nan" / True: the NaN rule alone)."""
+    out = torch.isnan(img).any(dim=-3, keepdim=True)
+    if nodata is True or (isinstance(nodata, str) and nodata.lower() == "nan"):
+        return out
+    if nodata is None or isinstance(nodata, (str, bool)):
+        raise ValueError(f"nodata={nodata!r} must be 'nan', True or a number")
+    value = torch.tensor(float(nodata), dtype=torch.float32)
+    if torch.isinf(value):
+        raise ValueError("nodata must be finite or NaN")
+    return out if torch.isnan(value) else out | (img == value).all(dim=-3, keepdim=True)
+
+
+def load_sar_ndvi_folder(root_dir, data_format="torch", rank=0, world_size=1, limit=None, nodata=None):
     """Read side of the reference's `get_data_SAR_TO_NDVI(root_dir, data_format=...)` (utils.py:54-85): the files of
     `root_dir/sar` in `sorted(os.listdir(...))` order, each with the file of the same name in `root_dir/opt`, as two fp32 host
     tensors (sar (L, Cs, H, W), ndvi (L, Cn, H, W)) holding the values of the files - the `(img + 1) / 2` of the dataset item
     happens per batch on the device (DeviceSarNdviFeed).  'torch': `.pt` files holding one tensor each; 'numpy': `.npy` files,
-    `torch.tensor(np.load(p)).to(torch.float)`.  `rank` / `world_size` / `limit` as in `degradation.load_image_folder_u8`."""
+    `torch.tensor(np.load(p)).to(torch.float)`.  `rank` / `world_size` / `limit` as in `degradation.load_image_folder_u8`.
+    `nodata` ("nan" or the files' no-data value; None: the files as they are) marks no-data pixels in band, once, here on the
+    host: a no-data NDVI pixel (`nodata_pixels`) becomes NaN in all NDVI bands, and a no-data SAR pixel gets its SAR bands set
+    to 0.0 - the network is never fed a NaN - and its NDVI bands set to NaN.  The gathers and crops carry a NaN untouched, so a
+    `Diffusion` with `nodata = True` finds the mask in every batch."""
     if data_format not in ("torch", "numpy"):
         raise ValueError(f"data_format must be 'torch' or 'numpy', got {data_format!r}")
     sar_dir, opt_dir = os.path.join(root_dir, "sar"), os.path.join(root_dir, "opt")
@@ -131,7 +149,13 @@ def load_sar_ndvi_folder(root_dir, data_format="torch", rank=0, world_size=1, li
             if images and img.shape != images[0].shape:
                 raise ValueError(f"{path}: shape {tuple(img.shape)} differs from the {tuple(images[0].shape)} of the files before it")
             images.append(img)
-    return torch.stack(sar).contiguous(), torch.stack(ndvi).contiguous()
+    sar, ndvi = torch.stack(sar).contiguous(), torch.stack(ndvi).contiguous()
+    if nodata is not None:
+        no_sar = nodata_pixels(sar, nodata)
+        no_ndvi = nodata_pixels(ndvi, nodata) | no_sar
+        sar = torch.where(no_sar, torch.zeros((), dtype=sar.dtype), sar)
+        ndvi = torch.where(no_ndvi, torch.full((), float("nan"), dtype=ndvi.dtype), ndvi)
+    return sar, ndvi
 
 
 def _epoch_order(length, shuffle, generator, device):

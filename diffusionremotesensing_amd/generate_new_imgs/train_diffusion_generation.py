@@ -44,6 +44,11 @@ class Diffusion(_SuperresDiffusion):
     def _predict(self, net, x_t, t, cond):
         return net(x_t, t, cond)
 
+    def _check_nodata(self, loss):
+        """The generation trainer has no no-data pixels: its images are decoded RGB files."""
+        if self.nodata is not None:
+            raise ValueError("the generation Diffusion does not take nodata: set it on the super-resolution or SAR -> NDVI class")
+
     def sample(self, n, model, target_class=None, cfg_scale=3, input_channels=3, generate_video=False,
                noise_source=None, sampling_steps=None, eta=0.0):
         """Reference :206-259.  `sampling_steps` / `eta`: a DDIM chain, as in the super-resolution sampler."""

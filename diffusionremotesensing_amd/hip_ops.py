@@ -171,6 +171,43 @@ def noise_v_target(x0, eps, t, alpha_hat):
     return x_t, v
 
 
+def nodata_rule(nodata):
+    """The `nodata_value` of the C-ABI for the package's `nodata` setting: True or "nan" is the NaN rule alone (a NaN), a
+    number is that value rounded to fp32 (its bands are compared as fp32) on top of the NaN rule."""
+    if nodata is True or (isinstance(nodata, str) and nodata.lower() == "nan"):
+        return math.nan
+    if nodata is None or nodata is False or isinstance(nodata, str):
+        raise ValueError(f"nodata={nodata!r} must be True, 'nan' or a number")
+    value = float(nodata)
+    if math.isinf(value):
+        raise ValueError("nodata must be finite (or NaN / True for the NaN rule alone)")
+    return value
+
+
+def noise_target_nodata(x0, eps, t, alpha_hat, prediction, nodata_value=None, fill=0.5):
+    """(x_t, target, valid) of a training batch x0 (n, C, H, W) whose no-data pixels are NaN in any band or, with a
+    `nodata_value`, equal to it in all bands (include/drs_hip.h: drs_noise_target_nodata).  valid: (n, 1, H, W) uint8.  At valid
+    pixels x_t and target are `noise_images` / `noise_v_target`'s; at no-data pixels x_t is the noised `fill` and target 0."""
+    lib = _lib.load()
+    x0 = _req(x0, "x0"); eps = _req(eps, "eps"); t = _req(t, "t", torch.int64); alpha_hat = _req(alpha_hat, "alpha_hat")
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"noise_target_nodata: prediction={prediction!r} must be one of {tuple(PREDICTIONS)}")
+    if x0.dim() != 4 or eps.shape != x0.shape:
+        raise RuntimeError(f"noise_target_nodata: x0 {tuple(x0.shape)} and eps {tuple(eps.shape)} must be the same (n, C, H, W)")
+    n, C_, H, W = x0.shape
+    if t.numel() != n:
+        raise RuntimeError(f"noise_target_nodata: t has {t.numel()} elements, x0 has {n} images")
+    value = math.nan if nodata_value is None else nodata_rule(nodata_value)
+    x_t, target = torch.empty_like(x0), torch.empty_like(x0)
+    valid = torch.empty((n, 1, H, W), dtype=torch.uint8, device=x0.device)
+    with torch.cuda.device(x0.device):
+        st = lib.drs_noise_target_nodata(_ptr(x0), _ptr(eps), _ptr(t), _ptr(alpha_hat), alpha_hat.numel(), PREDICTIONS[prediction],
+                                         value, float(fill), _ptr(x_t), _ptr(target), _ptr(valid), n, C_, H * W,
+                                         _stream(x0.device))
+    _lib.check(st, "drs_noise_target_nodata")
+    return x_t, target, valid
+
+
 def threshold_rank(x0_threshold, chw):
     """The 0-based rank k = floor(p (chw - 1)) of the order statistic behind `x0_threshold` = p, 0 < p <= 1, among chw values:
     torch.quantile(..., interpolation="lower")."""
@@ -733,6 +770,43 @@ def ssim_mean(sr, hr, clamp=True, workspace=None):
         st = lib.drs_ssim(_ptr(sr), _ptr(hr), _ptr(out), B, C_, H, W, int(bool(clamp)), _ptr(ws), ws.numel(),
                           _stream(sr.device))
     _lib.check(st, "drs_ssim")
+    return out
+
+
+def metrics_nodata_workspace(B, C, H, W, device):
+    """The scratch buffer `metrics_pointwise_nodata` and `ssim_nodata` take (either call, stream-ordered)."""
+    return torch.empty(max(_lib.load().drs_metrics_nodata_workspace_bytes(B, C, H, W), 8), dtype=torch.uint8, device=device)
+
+
+def metrics_pointwise_nodata(sr, hr, nodata, clamp=True, workspace=None):
+    """`metrics_pointwise` over the valid pixels of hr (`nodata`: True / "nan" or the no-data value): a (B, 2 C + 3) float64
+    device tensor, the last column the number of valid pixels (include/drs_hip.h: drs_metrics_pointwise_nodata)."""
+    lib = _lib.load()
+    sr, hr = _req_image_pair(sr, hr, "metrics_pointwise_nodata")
+    value = nodata_rule(nodata)
+    B, C_, H, W = sr.shape
+    ws = metrics_nodata_workspace(B, C_, H, W, sr.device) if workspace is None else _req(workspace, "workspace", torch.uint8)
+    out = torch.empty((B, 2 * C_ + 3), dtype=torch.float64, device=sr.device)
+    with torch.cuda.device(sr.device):
+        st = lib.drs_metrics_pointwise_nodata(_ptr(sr), _ptr(hr), value, _ptr(out), B, C_, H, W, int(bool(clamp)), _ptr(ws),
+                                              ws.numel(), _stream(sr.device))
+    _lib.check(st, "drs_metrics_pointwise_nodata")
+    return out
+
+
+def ssim_nodata(sr, hr, nodata, clamp=True, workspace=None):
+    """Per image (mean SSIM over bands and over the window positions whose 11 x 11 pixels of hr are all valid - NaN when there
+    is none -, number of such positions): a (B, 2) float64 device tensor (include/drs_hip.h: drs_ssim_nodata)."""
+    lib = _lib.load()
+    sr, hr = _req_image_pair(sr, hr, "ssim_nodata")
+    value = nodata_rule(nodata)
+    B, C_, H, W = sr.shape
+    ws = metrics_nodata_workspace(B, C_, H, W, sr.device) if workspace is None else _req(workspace, "workspace", torch.uint8)
+    out = torch.empty((B, 2), dtype=torch.float64, device=sr.device)
+    with torch.cuda.device(sr.device):
+        st = lib.drs_ssim_nodata(_ptr(sr), _ptr(hr), value, _ptr(out), B, C_, H, W, int(bool(clamp)), _ptr(ws), ws.numel(),
+                                 _stream(sr.device))
+    _lib.check(st, "drs_ssim_nodata")
     return out
 
 

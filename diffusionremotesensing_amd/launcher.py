@@ -35,9 +35,11 @@ def make_loaders(args, train_dataset, val_dataset):
     return loader(train_dataset), loader(val_dataset)
 
 
-def train_model(args, diffusion_class, model, device, train_loader, val_loader, train_kwargs=None, **diffusion_kwargs):
+def train_model(args, diffusion_class, model, device, train_loader, val_loader, train_kwargs=None, nodata=None,
+                **diffusion_kwargs):
     """Same weights on every rank, `diffusion_class(...)` from the flags (a snapshot, if there is one, is loaded here),
-    the training run, and the end of the process group.  Returns the Diffusion."""
+    the training run, and the end of the process group.  `nodata`: the Diffusion's attribute of that name (None: left alone).
+    Returns the Diffusion."""
     print("Num params: ", sum(p.numel() for p in model.parameters()))
     if args.multiple_gpus:
         drs_dist.broadcast_module(model)  # what the DDP constructor does in the reference (:658)
@@ -48,6 +50,8 @@ def train_model(args, diffusion_class, model, device, train_loader, val_loader, 
                                 ema_smoothing=args.ema_smoothing, **cli.cli_prediction(args), **cli.cli_threshold(args),
                                 **cli.cli_ztsnr(args), **diffusion_kwargs)
     cli.set_guidance_rescale(diffusion, args)
+    if nodata is not None:
+        diffusion.nodata = nodata
     diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
                     train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
                     verbose=True, **cli.train_kwargs(args), **cli.cli_finetune(args), **(train_kwargs or {}))

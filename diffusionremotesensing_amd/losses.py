@@ -45,6 +45,12 @@ def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def _masked(valid):
+    """The keyword of `DiffusionLoss._launch` for a mask; none without one, so that an unmasked call reaches `_launch` with
+    the five positional arguments it always had - code that wraps or replaces `_launch` with that signature keeps working."""
+    return {} if valid is None else {"valid": valid}
+
+
 class LossBins:
     """Per-timestep-bin statistics of the unweighted per-image losses, bin(t) = t * nbins // T, kept on the device and updated by
     the loss launch itself: per bin a double sum and a count (`read_and_reset`), and a ring of the last `history` losses (what
@@ -111,10 +117,11 @@ class DiffusionLoss:
         self.kind, self.delta, self.bins = kind, float(delta), bins
         self.table = None if table is None else table.detach().to(torch.float32).contiguous()
         self.per_image = None  # the last call's unweighted per-image losses, (B,) float64 on the device
+        self.valid_counts = None  # the last call's valid pixels per image, (B,) int64 on the device; None without a mask
         self.loss_f64 = None   # the last call's loss before its rounding to fp32, 0-dim float64 on the device
         self._partials = self._bad_t = None
 
-    def _launch(self, pred, target, t, sample_w, with_grad):
+    def _launch(self, pred, target, t, sample_w, with_grad, valid=None):
         for name, x in (("pred", pred), ("target", target)):
             if not x.is_cuda or x.dtype != torch.float32:
                 raise RuntimeError(f"DiffusionLoss: {name} must be an fp32 tensor on a ROCm device (there is no CPU path)")
@@ -141,6 +148,12 @@ class DiffusionLoss:
             if not sample_w.is_cuda or sample_w.dtype != torch.float32 or sample_w.numel() != B:
                 raise RuntimeError(f"DiffusionLoss: sample_w must be {B} fp32 values on the device")
             sample_w = sample_w.contiguous()
+        if valid is not None:
+            if pred.dim() != 4:
+                raise ValueError(f"DiffusionLoss: a mask needs pred as (B, C, H, W), got {tuple(pred.shape)}")
+            if not valid.is_cuda or valid.dtype != torch.uint8 or valid.numel() * pred.shape[1] != pred.numel():
+                raise RuntimeError(f"DiffusionLoss: valid must be {B} x {n // max(pred.shape[1], 1)} uint8 values on the device")
+            valid = valid.contiguous()
         npart = B * ((n + 3) // CHUNK + 1)
         if self._partials is None or self._partials.numel() < npart or self._partials.device != dev:
             self._partials = torch.empty(npart, dtype=torch.float64, device=dev)
@@ -150,6 +163,18 @@ class DiffusionLoss:
         self.per_image = torch.empty(B, dtype=torch.float64, device=dev)
         out = torch.empty(2, dtype=torch.float64, device=dev)  # the loss as double, and as fp32 in the first half of word 1
         bins = self.bins
+        self.valid_counts = None
+        if valid is not None:
+            self.valid_counts = torch.empty(B, dtype=torch.int64, device=dev)
+            with torch.cuda.device(dev):
+                st = _lib.load().drs_diffusion_loss_masked(
+                    _ptr(pred), _ptr(target), _ptr(valid), _ptr(t), B, pred.shape[1], n // pred.shape[1], _ptr(self.table), T,
+                    _ptr(sample_w), KINDS[self.kind], self.delta, _ptr(grad), _ptr(self.per_image), _ptr(self.valid_counts),
+                    _ptr(self._partials), _ptr(out), _ptr(bins.buf if bins else None), bins.nbins if bins else 0,
+                    bins.history if bins else 0, int(with_grad), _ptr(self._bad_t), _stream(dev))
+            _lib.check(st, "drs_diffusion_loss_masked")
+            self.loss_f64 = out[0]
+            return out.view(torch.float32)[2], grad
         with torch.cuda.device(dev):
             st = _lib.load().drs_diffusion_loss(
                 _ptr(pred), _ptr(target), _ptr(t), B, n, _ptr(self.table), T, _ptr(sample_w), KINDS[self.kind], self.delta,
@@ -159,18 +184,21 @@ class DiffusionLoss:
         self.loss_f64 = out[0]
         return out.view(torch.float32)[2], grad
 
-    def loss_and_grad(self, pred, target, t=None, sample_w=None):
+    def loss_and_grad(self, pred, target, t=None, sample_w=None, valid=None):
         """(loss, d loss / d pred) from the one launch: a 0-dim fp32 device tensor and a tensor of pred's shape, for
-        `pred.backward(grad)`.  Appends to the bins' ring."""
-        loss, grad = self._launch(pred, target, t, sample_w, True)
+        `pred.backward(grad)`.  Appends to the bins' ring.  `valid`: (B, 1, H, W) uint8, non-zero = data (what
+        `hip_ops.noise_target_nodata` returns): the loss over the valid pixels alone (include/drs_hip.h:
+        drs_diffusion_loss_masked), each image's mean over its own valid elements, the batch mean over the images that have
+        any; the gradient is +0.0 elsewhere and `valid_counts` holds the valid pixels per image.  None: the unmasked launch."""
+        loss, grad = self._launch(pred, target, t, sample_w, True, **_masked(valid))
         return loss, grad.view(pred.shape)
 
-    def __call__(self, pred, target, t=None, sample_w=None):
+    def __call__(self, pred, target, t=None, sample_w=None, valid=None):
         """The loss as a scalar that `.backward()` works on.  Under `torch.no_grad()`, or for a `pred` that needs no gradient, no
         gradient buffer is written and the ring is left alone."""
         if torch.is_grad_enabled() and pred.requires_grad:
-            return _LossFunction.apply(pred, self, target, t, sample_w)
-        return self._launch(pred, target, t, sample_w, False)[0]
+            return _LossFunction.apply(pred, self, target, t, sample_w, valid)
+        return self._launch(pred, target, t, sample_w, False, **_masked(valid))[0]
 
     def check_faults(self):
         """Raises if a call since the last check was handed a t outside [0, T).  Synchronises: for the end of an epoch."""
@@ -183,15 +211,15 @@ class DiffusionLoss:
 
 class _LossFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, loss_fn, target, t, sample_w):
-        loss, grad = loss_fn._launch(pred, target, t, sample_w, True)
+    def forward(ctx, pred, loss_fn, target, t, sample_w, valid=None):
+        loss, grad = loss_fn._launch(pred, target, t, sample_w, True, **_masked(valid))
         ctx.save_for_backward(grad.view(pred.shape))
         return loss.clone()
 
     @staticmethod
     def backward(ctx, grad_output):
         (grad,) = ctx.saved_tensors
-        return grad * grad_output, None, None, None, None
+        return grad * grad_output, None, None, None, None, None
 
 
 class LossAwareSampler:

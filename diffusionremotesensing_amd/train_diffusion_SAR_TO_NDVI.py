@@ -14,7 +14,8 @@ import torch.nn as nn
 
 from . import dist as drs_dist
 from .augment import add_augment_args
-from .cli import add_finetune_args, add_prediction_args, add_train_args, base_arg_parser, check_objective_args, check_train_args  # noqa: F401 - re-exported
+from .cli import (add_finetune_args, add_nodata_args, add_prediction_args, add_train_args, base_arg_parser,  # noqa: F401 - re-exported
+                  check_objective_args, check_train_args)
 from .launcher import launch_device, make_loaders, save_final_samples, train_model
 from .sampling import _repeat_members, asks_for_known_pixels, check_inpaint_args, check_sampling_args
 from .train_diffusion_superres import Diffusion as _SuperresDiffusion
@@ -79,15 +80,17 @@ class Diffusion(_SuperresDiffusion):
             known=known, known_mask=known_mask, resample=resample, jump=jump)
 
     def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None, known_mask_fn=None,
-                 resample=1, jump=1, ensemble=None, member_batch=None):
+                 resample=1, jump=1, ensemble=None, member_batch=None, nodata=None):
         """PSNR / SSIM (and the spectral angle when NDVI has several bands) of `sample`'s output against the NDVI truth over
         the (SAR, NDVI) batches of `loader`: the super-resolution `evaluate` without a magnification, hence without ERGAS, and
         without a bicubic baseline; `known_mask_fn` / `resample` / `jump` as there ("psnr_unknown").
         Returns {"model": {metric: mean}, "per_image": {"model": {metric: [...]}}, "n": N}; with `ensemble=N` (and
-        `member_batch`) also "member" and "ensemble", as the super-resolution `evaluate` does."""
+        `member_batch`) also "member" and "ensemble", as the super-resolution `evaluate` does.  `nodata` as there: the scores
+        are over the valid pixels of the NDVI truth, and "valid_fraction" is added."""
+        self._check_evaluate_nodata(nodata, ensemble, known_mask_fn)
         sample, members = self._evaluate_samplers(model, "NDVI_channels", sampling_steps, eta, noise_source, known_mask_fn,
                                                   resample, jump, ensemble, member_batch)
-        return self._evaluate(model, loader, n_images, {"model": sample}, None, members)
+        return self._evaluate(model, loader, n_images, {"model": sample}, None, members, nodata)
 
 
 class SyntheticSarNdviDataset(torch.utils.data.Dataset):
@@ -129,7 +132,8 @@ def folder_feed(args, device, split, rank=0, world_size=1, limit=None, fixed=Non
     if not os.path.isdir(os.path.join(root, "sar")) or not os.path.isdir(os.path.join(root, "opt")):
         raise FileNotFoundError(f"--dataset_path {args.dataset_path!r}: expected the folders train/sar, train/opt, test/sar and "
                                 f"test/opt (or synthetic[:N]); {root} lacks sar/ or opt/")
-    sar, ndvi = load_sar_ndvi_folder(root, getattr(args, "data_format", "torch"), rank, world_size, limit)
+    sar, ndvi = load_sar_ndvi_folder(root, getattr(args, "data_format", "torch"), rank, world_size, limit,
+                                     nodata=getattr(args, "nodata", None))
     for what, t, bands_flag, want in (("sar", sar, "--SAR_channels", args.SAR_channels),
                                       ("opt", ndvi, "--NDVI_channels", args.NDVI_channels)):
         if t.shape[1] != want:
@@ -156,7 +160,11 @@ def launch(args):
         train_dataset, val_dataset = synthetic_datasets(args)
         train_loader, val_loader = make_loaders(args, train_dataset, val_dataset)
     model = Residual_Attention_UNet_SAR_TO_NDVI(args.SAR_channels, args.NDVI_channels, device).to(device)
-    diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader)
+    # (--nodata: the folder loader has turned every no-data pixel into NaN, so the run masks by the NaN rule; the seeded pairs
+    #  are not rewritten: the rule is applied to the batches as it stands)
+    nodata = getattr(args, "nodata", None)
+    diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader,
+                            nodata=True if folder and nodata is not None else nodata)
     if folder:
         if r != 0:
             return  # one rank samples and writes the results, as in the super-resolution launch
@@ -194,7 +202,7 @@ def train_main_parser():
     flags (cli.add_train_args): what `main` parses."""
     p = train_arg_parser()
     add_augment_args(p)
-    return add_finetune_args(add_prediction_args(add_train_args(p), in_help=False))
+    return add_nodata_args(add_finetune_args(add_prediction_args(add_train_args(p), in_help=False)), in_help=False)
 
 
 def main(argv=None):

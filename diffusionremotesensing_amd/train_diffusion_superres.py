@@ -27,7 +27,7 @@ from . import dist as drs_dist
 from . import hip_ops
 from .augment import add_augment_args
 # (the names this module does not use itself are re-exported: they lived here before cli.py, launcher.py and superres_feeds.py)
-from .cli import (OBJECTIVE_DEFAULTS, OPTIM_DEFAULTS, add_bsr_args, add_finetune_args, add_objective_args, add_optim_args,  # noqa: F401
+from .cli import (OBJECTIVE_DEFAULTS, OPTIM_DEFAULTS, add_bsr_args, add_finetune_args, add_nodata_args, add_objective_args, add_optim_args,  # noqa: F401
                   add_prediction_args, add_sampling_args, add_solver_args, add_train_args, base_arg_parser, check_objective_args, check_optim_args,
                   check_train_args, cli_sampling_steps, objective_train_kwargs, optim_train_kwargs, str2bool)
 from .finetune import freeze_parameters, load_init_weights
@@ -45,7 +45,8 @@ from .UNet_model_superres import EMA, Residual_Attention_UNet_superres
 _DEGRADATIONS = ("downblur", "bsrgan", "downblurnoise")
 
 METRIC_FORMATS = {"psnr": ("PSNR", "{:.2f} dB"), "ssim": ("SSIM", "{:.4f}"), "sam": ("SAM", "{:.3f} deg"),
-                  "ergas": ("ERGAS", "{:.4g}"), "psnr_unknown": ("PSNR unknown", "{:.2f} dB")}
+                  "ergas": ("ERGAS", "{:.4g}"), "psnr_unknown": ("PSNR unknown", "{:.2f} dB"),
+                  "valid_fraction": ("valid", "{:.4f}")}
 
 
 def format_scores(scores):
@@ -94,6 +95,11 @@ class Diffusion:
         # with it (phi in [0, 1], a plain attribute; acts where a sampler guides with cfg_scale > 0).  DESIGN.md section 26.
         self.zero_terminal_snr = check_zero_terminal_snr(zero_terminal_snr, self.prediction)
         self.guidance_rescale = 0.0
+        # ... and the no-data marker of the clean images (None: every pixel is data; True: a pixel with a NaN band is no-data;
+        # a number: also a pixel whose bands all equal it).  A plain attribute, read by `_noised_target`, the train and validation
+        # steps and `train`'s --eval_metrics scores; `nodata_fill` is what the network sees under the mask, forward-noised.
+        # DESIGN.md section 27.
+        self.nodata, self.nodata_fill = None, 0.5
         self.noise_steps = noise_steps
         self.beta_start = beta_start
         self.beta_end = beta_end
@@ -154,12 +160,22 @@ class Diffusion:
     def _noised_target(self, x0, t):
         """(x_t, what the network is trained to return for it) of a clean batch at the levels t, for the training and the
         validation loop alike: `noise_images`' pair for "eps"; its x_t and the clean batch for "x0"; for "v" the same draw
-        of eps, x_t and v from one launch (`hip_ops.noise_v_target`: that x_t is `noise_images`')."""
+        of eps, x_t and v from one launch (`hip_ops.noise_v_target`: that x_t is `noise_images`').  With `self.nodata` set the
+        mask comes back as well, (x_t, target, valid) from one launch (`hip_ops.noise_target_nodata`): at valid pixels the same
+        bits, at no-data pixels the noised `nodata_fill` and a target of 0."""
+        if self.nodata is not None:
+            epsilon = torch.randn_like(x0, dtype=torch.float32)
+            return hip_ops.noise_target_nodata(x0, epsilon, t, self.alpha_hat, self.prediction, self.nodata, self.nodata_fill)
         if self.prediction == "v":
             epsilon = torch.randn_like(x0, dtype=torch.float32)
             return hip_ops.noise_v_target(x0, epsilon, t, self.alpha_hat)
         x_t, noise = self.noise_images(x0, t)
         return x_t, (x0 if self.prediction == "x0" else noise)
+
+    def _noised(self, x0, t):
+        """`_noised_target` as the two loops take it: always (x_t, target, valid), `valid` None for a run without `nodata`."""
+        out = self._noised_target(x0, t)
+        return out if len(out) == 3 else (*out, None)
 
     # -- reverse process (reference :207-255) ---------------------------------------------------
     def sample(self, n, model, lr_img, input_channels=3, generate_video=False, noise_source=None, sampling_steps=None,
@@ -266,7 +282,8 @@ class Diffusion:
 
     # -- image quality of the samples (metrics.py; not in the reference) ---------------------------
     def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None, baseline=True,
-                 known_mask_fn=None, resample=1, jump=1, ensemble=None, member_batch=None, color_fix=None, color_fix_levels=5):
+                 known_mask_fn=None, resample=1, jump=1, ensemble=None, member_batch=None, color_fix=None, color_fix_levels=5,
+                 nodata=None):
         """PSNR / SSIM / SAM / ERGAS (metrics.image_quality) of `sample`'s output against the ground truth over the (lr, hr)
         batches of `loader`, every batch sampled as one call with n = its size, until `n_images` images are scored (None: the
         whole loader).  `sampling_steps`, `eta` and `noise_source` are `sample`'s (the source is asked batch after batch).
@@ -281,7 +298,10 @@ class Diffusion:
         `color_fix` ("wavelet" with `color_fix_levels`, or "adain"; not with `ensemble` or `known_mask_fn`) adds a third
         estimate, "model_fixed": the very sample "model" scored - each batch is still sampled once - clamped to [0, 1] as
         the scores clamp it and corrected against the bicubic up-sampling of its lr batch (`colorfix.color_fix`).
-        The model keeps the train / eval mode it came with."""
+        `nodata` (True / "nan" or the no-data value; not with `ensemble` or `known_mask_fn`) scores every row - the sample, the
+        bicubic baseline, the corrected sample - over the valid pixels of the truth alone (`metrics.image_quality(nodata=)`)
+        and adds "valid_fraction".  The model keeps the train / eval mode it came with."""
+        self._check_evaluate_nodata(nodata, ensemble, known_mask_fn)
         fix = self._evaluate_color_fix(color_fix, color_fix_levels, ensemble, known_mask_fn)
         sample, members = self._evaluate_samplers(model, "input_channels", sampling_steps, eta, noise_source, known_mask_fn,
                                                   resample, jump, ensemble, member_batch)
@@ -296,7 +316,15 @@ class Diffusion:
                 return kept["x"]
             scorers["model"] = sample_kept
             scorers["model_fixed"] = lambda lr_img, hr_img: fix(kept["x"], lr_img)
-        return self._evaluate(model, loader, n_images, scorers, self.magnification_factor, members)
+        return self._evaluate(model, loader, n_images, scorers, self.magnification_factor, members, nodata)
+
+    @staticmethod
+    def _check_evaluate_nodata(nodata, ensemble, known_mask_fn):
+        if nodata is None:
+            return
+        hip_ops.nodata_rule(nodata)  # (ValueError for a value that is no rule)
+        if ensemble is not None or known_mask_fn is not None:
+            raise ValueError("evaluate: nodata cannot be combined with ensemble=N or known_mask_fn: their scores are not masked")
 
     def _evaluate_color_fix(self, method, levels, ensemble, known_mask_fn):
         """`evaluate`'s f(sample batch, lr batch) -> corrected batch, None without a method; ValueError for a request it does
@@ -350,12 +378,13 @@ class Diffusion:
         out = sample_known(truth, mask)
         return out, {"psnr_unknown": metrics.psnr_masked(out, truth, mask == 0)}
 
-    def _evaluate(self, model, loader, n_images, scorers, magnification_factor, members=None):
+    def _evaluate(self, model, loader, n_images, scorers, magnification_factor, members=None, nodata=None):
         """`evaluate` for the estimators `scorers` = {name: f(conditioning batch, truth batch) -> estimate}.  With `members` =
         f(conditioning batch, truth batch) -> (N, B, C, S, S) the "model" scorer is replaced by the mean of those members,
         "member" scores member 0 and "ensemble" collects `ensemble.ensemble_scores` of the batch."""
         from . import ensemble, metrics
         was_training = model.training
+        masked = {} if nodata is None else {"nodata": nodata}  # (None: the call it always was)
         ens = {}
         if members is not None:
             drawn = {}
@@ -379,7 +408,7 @@ class Diffusion:
             for name, estimate in scorers.items():
                 est = estimate(cond, truth)
                 est, more = est if isinstance(est, tuple) else (est, {})  # (`_score_known`: scores of its own)
-                for k, v in {**metrics.image_quality(est, truth, magnification_factor), **more}.items():
+                for k, v in {**metrics.image_quality(est, truth, magnification_factor, **masked), **more}.items():
                     per_image[name].setdefault(k, []).append(v)
             n += truth.shape[0]
             if n_images is not None and n >= n_images:
@@ -466,6 +495,8 @@ class Diffusion:
             ts["FREEZE_BN"], ts["FREEZE"] = run.freeze_bn, tuple(run.freeze)
         if self.zero_terminal_snr:  # (likewise)
             ts["ZERO_TERMINAL_SNR"] = True
+        if self.nodata is not None:  # (likewise)
+            ts["NODATA"] = self._nodata_key(self.nodata)
         torch.save(ts, self.train_state_path())
 
     def _load_train_state(self, run):
@@ -484,6 +515,9 @@ class Diffusion:
         if bool(ts.get("ZERO_TERMINAL_SNR", False)) != self.zero_terminal_snr:
             raise ValueError(f"{self.train_state_path()} was written with zero_terminal_snr="
                              f"{bool(ts.get('ZERO_TERMINAL_SNR', False))}: a resumed run must keep the schedule")
+        if ts.get("NODATA") != self._nodata_key(self.nodata):
+            raise ValueError(f"{self.train_state_path()} was written with nodata={ts.get('NODATA')!r}, this run has "
+                             f"nodata={self._nodata_key(self.nodata)!r}: a resumed run must mask the same pixels")
         if run.loss_bins is not None:
             run.loss_bins.load_state_dict(ts["LOSS_BINS"])  # (other T / bin count: ValueError)
         # (another parameter count or other shapes: ValueError from FusedAdamW.load_state_dict, the first thing loaded)
@@ -498,6 +532,14 @@ class Diffusion:
         torch.set_rng_state(ts["CPU_RNG_STATE"])
         torch.cuda.set_rng_state(ts["DEVICE_RNG_STATE"], self.device)
         print(f"Resuming the training state of {self.train_state_path()} at Epoch {self.epochs_run}")
+
+    @staticmethod
+    def _nodata_key(nodata):
+        """`nodata` as `train_state.pt` keeps and compares it: None, "nan" (the NaN rule alone) or the value as fp32 compares it."""
+        if nodata is None:
+            return None
+        value = hip_ops.nodata_rule(nodata)
+        return "nan" if value != value else float(torch.tensor(value, dtype=torch.float32))
 
     def early_stopping(self, patience, epochs_without_improving):
         if epochs_without_improving >= patience:
@@ -577,10 +619,16 @@ class Diffusion:
         else:
             t = self.sample_timesteps(hr_img.shape[0])
             t = (t.pin_memory() if not t.is_cuda else t).to(self.device, non_blocking=True)
-        x_t, noise = self._noised_target(hr_img, t)  # (`noise`: the target - eps, v or x0 - of `self.prediction`)
+        # (`noise`: the target - eps, v or x0 - of `self.prediction`; `valid`: the mask of a run with `nodata`, else None)
+        x_t, noise, valid = self._noised(hr_img, t)
         optimizer.zero_grad()
         predicted_noise = self._predict(model, x_t, t, self._train_cond(lr_img))
-        if isinstance(loss_function, DiffusionLoss):
+        if valid is not None:
+            if not isinstance(loss_function, DiffusionLoss):
+                raise ValueError("nodata needs a losses.DiffusionLoss as loss_function: torch's modules have no mask")
+            train_loss, grad = loss_function.loss_and_grad(predicted_noise, noise, t, sample_w, valid=valid)
+            predicted_noise.backward(grad)
+        elif isinstance(loss_function, DiffusionLoss):
             # loss and d loss / d prediction from one launch: no second pass for autograd's grad_output
             train_loss, grad = loss_function.loss_and_grad(predicted_noise, noise, t, sample_w)
             predicted_noise.backward(grad)
@@ -631,7 +679,12 @@ class Diffusion:
         Fine-tuning a snapshot (finetune.py; all off by default): `init_from=PATH` starts a run whose own
         snapshot does not exist yet from the MODEL_STATE of that file, at epoch 0; `freeze_bn=True` keeps every BatchNorm2d on
         its running statistics (`model.freeze_batchnorm()`: the frozen train plan, statistics never written);
-        `freeze=("downs.", "LR_encoder.")` takes the parameters under those state_dict-key prefixes out of training."""
+        `freeze=("downs.", "LR_encoder.")` takes the parameters under those state_dict-key prefixes out of training.
+        No-data pixels are not an argument but the attribute `self.nodata` (None: off): with it both loops
+        take the mask from `_noised_target` and run `losses.DiffusionLoss(valid=)` - a `DiffusionLoss(loss)` of their own where
+        the run would otherwise use torch's module -, `eval_metrics` scores under the truth's mask, `loss="MSE+Perceptual_noise"`
+        raises, and `save_train_state` stores the setting."""
+        self._check_nodata(loss)  # (before any weight is loaded or frozen)
         self._prepare_finetune(freeze_bn, freeze, init_from)
         run = self._begin_run(
             loss, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule,
@@ -676,14 +729,31 @@ class Diffusion:
         if self.ema_smoothing:
             ema = EMA(beta=0.995)
             ema_model = copy.deepcopy(model).eval().requires_grad_(False)
-        loss_function = objective.train if objective is not None else self._loss_function(loss, self.device)
+        if objective is not None:
+            loss_function, val_loss_function = objective.train, objective.val
+        elif self.nodata is not None:  # the masked launch is DiffusionLoss's: unit weights, no bins
+            loss_function, val_loss_function = DiffusionLoss(loss), DiffusionLoss(loss)
+        else:
+            loss_function, val_loss_function = self._loss_function(loss, self.device), None
         self.timestep_sampler = objective.sampler if objective is not None else None
         run = self.train_state = TrainRun(model, loss, optimizer, scheduler, ema, ema_model, objective, loss_function,
                                           clipping=max_grad_norm is not None, save_train_state=save_train_state)
         run.freeze_bn, run.freeze = bool(freeze_bn), tuple(freeze)
+        run.val_loss_function = val_loss_function  # (None: validation calls `loss_function`, torch's module)
         if save_train_state and os.path.exists(self.snapshot_path) and os.path.exists(self.train_state_path()):
             self._load_train_state(run)
         return run
+
+    def _check_nodata(self, loss):
+        """ValueError, before any device work of a run, for a `nodata` setting this trainer does not take."""
+        if self.nodata is None:
+            return
+        hip_ops.nodata_rule(self.nodata)
+        if loss == "MSE+Perceptual_noise":
+            raise ValueError("--loss MSE+Perceptual_noise cannot be combined with nodata: the VGG term has no mask")
+        if str(getattr(self, "Degradation_type", "DownBlur")).lower() == "bsrgan":
+            raise ValueError("nodata cannot be combined with --Degradation_type BSRGAN: its HR image is sharpened, so a "
+                             "no-data value does not survive into the training target")
 
     def _prepare_finetune(self, freeze_bn, freeze, init_from):
         """What `train`'s `init_from` / `freeze_bn` / `freeze` do to the network before the optimizer and the EMA copy are
@@ -760,9 +830,11 @@ class Diffusion:
             for batch in val_loader:
                 lr_img, hr_img = self._split_batch(batch)
                 t = self.sample_timesteps(hr_img.shape[0]).to(self.device)
-                x_t, noise = self._noised_target(hr_img, t)
+                x_t, noise, valid = self._noised(hr_img, t)
                 predicted_noise = self._predict(run.saved, x_t, t, self._train_cond(lr_img))
-                if run.objective is not None:  # the same table through the no-grad path; uniform t, bins of its own
+                if valid is not None:
+                    running_val_loss += run.val_loss_function(predicted_noise, noise, t, valid=valid)
+                elif run.objective is not None:  # the same table through the no-grad path; uniform t, bins of its own
                     running_val_loss += run.objective.val(predicted_noise, noise, t)
                 else:
                     running_val_loss += run.loss_function(predicted_noise, noise)
@@ -780,7 +852,7 @@ class Diffusion:
             print(f"Epoch {epoch}: Val loss by timestep bin (low noise first) "
                   + self._bins_line(run.objective.val_bins.read_and_reset()))
         if eval_args is not None:
-            scores = self.evaluate(run.saved, val_loader, **eval_args)
+            scores = self.evaluate(run.saved, val_loader, **eval_args, **({} if self.nodata is None else {"nodata": self.nodata}))
             print(f"Epoch {epoch}: Val metrics on {scores['n']} images | " + format_scores(scores))
 
     def _keep_if_best(self, run, epoch, val_loss):
@@ -805,6 +877,7 @@ def launch(args):
     if args.UNet_type.lower() != "residual attention unet":
         raise ValueError("The UNet type must be Residual Attention UNet or Residual MultiHead Attention UNet or "
                          "Residual Visual MultiHeadAttention UNet superres")
+    nodata = nodata_u8_value(getattr(args, "nodata", None), args.Degradation_type)
     print("Using multiple GPUs" if args.multiple_gpus else "Using single GPU")
     device = launch_device(args)
     train_loader, val_loader, final_lr = make_superres_feeds(args, device)
@@ -816,7 +889,7 @@ def launch(args):
     train_kwargs = {}
     if getattr(args, "eval_metrics", 0):
         train_kwargs = {"eval_metrics": args.eval_metrics, "sampling_steps": args.sampling_steps, "eta": args.eta}
-    diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader, train_kwargs,
+    diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader, train_kwargs, nodata=nodata,
                             magnification_factor=args.magnification_factor, Degradation_type=args.Degradation_type)
     if r != 0:
         return  # one rank samples and writes models_run/<name>/results/superres_results.pt (every rank holds the same weights)
@@ -824,6 +897,20 @@ def launch(args):
     def sample(lr_i, **ddim):
         return diffusion.sample(n=1, model=model, lr_img=lr_i, input_channels=ch, generate_video=args.generate_video, **ddim)
     save_final_samples(args, sample, final_lr, "superres_results.pt")
+
+
+def nodata_u8_value(k, degradation_type):
+    """The `nodata` of a super-resolution `Diffusion` for --nodata K (None: None): float32(K) / 255, the bits the uint8 feeds
+    give a stored K, so that the rule's fp32 compare finds the HR pixels whose bands all hold K.  DownBlur / DownBlurNoise only:
+    ValueError under BSRGAN, whose HR image is sharpened.  The LR image is still made from the stored pixels, K included."""
+    if k is None:
+        return None
+    if not 0 <= int(k) <= 255:
+        raise ValueError(f"--nodata {k} must be an integer in 0 .. 255")
+    if str(degradation_type).lower() == "bsrgan":
+        raise ValueError("--nodata cannot be combined with --Degradation_type BSRGAN: its HR image is sharpened, so the "
+                         "no-data value does not survive into the training target")
+    return float(torch.tensor(float(int(k)), dtype=torch.float32) / 255)
 
 
 def build_arg_parser():
@@ -848,6 +935,7 @@ def parse_train_args(argv=None):
     add_train_args(p)
     add_prediction_args(p, in_help=False)
     add_finetune_args(p)
+    add_nodata_args(p, in_help=False, u8=True)
     p.add_argument("--eval_metrics", type=int, default=0,
                    help="score the network on the first N validation images (PSNR / SSIM / SAM / ERGAS against the bicubic "
                         "baseline) at every epoch with epoch %% check_preds_epoch == 0; 0 = off")
@@ -856,6 +944,8 @@ def parse_train_args(argv=None):
         p.error("--eval_metrics must be >= 0")
     if args.eval_metrics and args.multiple_gpus:
         p.error("--eval_metrics runs in one process: it cannot be combined with --multiple_gpus")
+    if args.nodata is not None and args.Degradation_type.lower() == "bsrgan":
+        p.error("--nodata cannot be combined with --Degradation_type BSRGAN: its HR image is sharpened")
     return check_train_args(p, args)
 
 

@@ -484,6 +484,53 @@ DRS_API int drs_metrics_pointwise(const float* sr, const float* hr, double* out,
 DRS_API int drs_ssim(const float* sr, const float* hr, double* out, int B, int C, int H, int W, int clamp, void* workspace,
                      size_t workspace_bytes, drs_stream_t stream);
 
+/* Training and scoring on imagery with no-data pixels (csrc/nodata.hip; not in the reference).  One rule everywhere: a pixel of
+ * a clean / truth image (C, H, W) is NO-DATA when any of its bands is NaN, or when `nodata_value` is finite and all of its bands
+ * equal it (fp32 compare); nodata_value = NaN means "the NaN rule only".  The mask is per pixel, shared by the bands, and taken
+ * from the image as stored, before any clamp.  No-data elements are selected out, not multiplied by zero: a NaN or an infinity
+ * there reaches no output.  No atomics, no host synchronisation: two calls give the same bits.  Every refusal below is reported
+ * before anything is launched.
+ *
+ * drs_noise_target_nodata: x_t, the training target and the mask of a batch x0 (n, C, hw) from one pass.  valid: (n, hw) uint8,
+ * 1 = data.  At a valid pixel x_t has the bits of drs_noise_images and target those of eps (DRS_PRED_EPS), of drs_noise_v_target's
+ * v (DRS_PRED_V) or of x0 (DRS_PRED_X0); at a no-data pixel x_t = fl(a fill) + fl(b eps) and target = +0.0.  A t[i] outside
+ * [0, noise_steps) makes x_t and target of that image NaN and its valid 0, and reads no table entry.  16-byte accesses (and one
+ * 32-bit store of four mask decisions) need hw % 4 == 0, 16-byte aligned fp32 tensors and a 4-byte aligned mask; anything else
+ * runs element by element.  DRS_ERR_ARG: null pointer, x_t == target, unknown kind; DRS_ERR_SHAPE: C outside 1 .. 16, n < 0,
+ * hw < 0, noise_steps <= 0.  n == 0 or hw == 0: DRS_OK, nothing is done.
+ *
+ * drs_diffusion_loss_masked: drs_diffusion_loss over the valid elements of pred, target (B, C, hw) under valid (B, hw) uint8
+ * (non-zero = data).  With nv_b the valid pixels of image b (written to counts, B int64), n_b = C nv_b and Bv the images with
+ * nv_b > 0:
+ *   per_image[b] = (1/n_b) sum over valid elements of l(d)          0 when nv_b = 0
+ *   loss         = (1/Bv) sum over nv_b > 0 of w_b per_image[b]     0 when Bv = 0
+ *   grad[b,i]    = (float)(w_b c / (Bv n_b)) * l'(d[b,i])           +0.0 at no-data elements; Huber's outer branch likewise
+ * An image with nv_b = 0 enters neither bins nor ring.  Chunks, order and precision of the sums are drs_diffusion_loss's: when
+ * every pixel is valid every output has its bits.  `partials`: workspace of B * ((C hw + 3) / 4096 + 1) doubles.  Three
+ * launches on the stream: the count of the mask rows, the streaming pass, the finish.  Refusals as drs_diffusion_loss, and
+ * DRS_ERR_ARG for a null valid or counts, DRS_ERR_SHAPE for C outside 1 .. 16 or hw < 1.
+ *
+ * drs_metrics_pointwise_nodata: out is B x (2 C + 3) doubles: the 2 C + 2 sums of drs_metrics_pointwise over the valid pixels
+ * of hr, then out[b][2 C + 2] = nv_b.  drs_ssim_nodata: out is B x 2 doubles: out[b][0] = the mean SSIM over the bands and over
+ * the window positions whose 11 x 11 pixels are all valid (NaN when there is none), out[b][1] = the number of such positions
+ * (per band).  The per-tile pivot is the tile's middle pixel or, when that is no-data, the first valid pixel of the tile in row
+ * order.  drs_ssim_nodata first writes hr's mask into the workspace (one pass over hr, one byte per pixel), so that the blocks
+ * of a tile's C bands read a byte per pixel instead of every band.  With every pixel valid the shared outputs have the bits of
+ * drs_metrics_pointwise / drs_ssim.  One workspace of drs_metrics_nodata_workspace_bytes(B, C, H, W) bytes (the partial rows,
+ * then B H W mask bytes) serves either call.  Refusals as drs_metrics_pointwise / drs_ssim. */
+DRS_API int drs_noise_target_nodata(const float* x0, const float* eps, const int64_t* t, const float* alpha_hat, int noise_steps,
+                                    int kind, float nodata_value, float fill, float* x_t, float* target, uint8_t* valid, int n,
+                                    int C, int64_t hw, drs_stream_t stream);
+DRS_API int drs_diffusion_loss_masked(const float* pred, const float* target, const uint8_t* valid, const int64_t* t, int B,
+                                      int C, int64_t hw, const float* table, int T, const float* sample_w, int kind, double delta,
+                                      float* grad, double* per_image, int64_t* counts, double* partials, double* out,
+                                      double* bins, int nbins, int history, int update_ring, int64_t* bad_t, drs_stream_t stream);
+DRS_API size_t drs_metrics_nodata_workspace_bytes(int B, int C, int H, int W);
+DRS_API int drs_metrics_pointwise_nodata(const float* sr, const float* hr, float nodata_value, double* out, int B, int C, int H,
+                                         int W, int clamp, void* workspace, size_t workspace_bytes, drs_stream_t stream);
+DRS_API int drs_ssim_nodata(const float* sr, const float* hr, float nodata_value, double* out, int B, int C, int H, int W,
+                            int clamp, void* workspace, size_t workspace_bytes, drs_stream_t stream);
+
 /* Per-pixel statistics and scores of an ensemble of N samples of one conditional distribution (csrc/ensemble.hip; public
  * API in diffusionremotesensing_amd/ensemble.py).  The reference draws its n_generations samples and plots them.
  *   members: (N,B,C,H,W) fp32, member axis first, 2 <= N <= 32;  truth: (B,C,H,W) fp32;  clamp != 0: members and truth are

@@ -1,0 +1,112 @@
+"""The entry points of csrc/nodata.hip between guard bands at the three pointer phases of tests/guard.py, run through
+`test_gpu_guard.guarded_runs` - so that they count for that module's `test_every_entry_point_that_launches_is_guarded`, which
+walks `_lib.SIGNATURES` and runs after this file (files run in name order; on its own that test does not know these entries).
+
+Every mode must give the bits of the normal call.  The shifted and mixed modes take other paths than the aligned one (element
+by element instead of 16-byte groups; a loss row cut into head, groups and tail), whose partial sums cover other elements - so
+the sums' inputs are dyadic rationals here, every partial sum is exact, and the order cannot show: what is left to differ is a
+wrong element, a wrong mask byte or a write outside the payload.  (hw % 4 != 0 leaves the metrics launcher one path.)"""
+import math
+
+import pytest
+import torch
+
+import nodata_oracle as NO
+import test_gpu_guard as G
+import test_gpu_loss as GL
+import test_gpu_metrics as GM
+import test_gpu_nodata as N
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "gpu tests need a ROCm device"
+    from diffusionremotesensing_amd import _lib
+    _lib.load()
+    return torch.device("cuda:0")
+
+
+def _dyadic(shape, seed, lo=-16, hi=17, step=8.0):
+    return torch.randint(lo, hi, shape, generator=torch.Generator().manual_seed(seed)).float() / step
+
+
+@pytest.mark.parametrize("shape", [N.A, N.V2], ids=str)
+def test_noise_target_nodata_between_guards(monkeypatch, dev, shape):
+    from diffusionremotesensing_amd import hip_ops
+    x0 = N._marked(shape, "nan")
+    g = torch.Generator().manual_seed(2)
+    eps, ah = torch.randn(shape, generator=g), N._schedule()
+    t = torch.randint(1, N.T, (shape[0],), generator=g)
+
+    def fn(put):
+        x_t, target, valid = hip_ops.noise_target_nodata(put(x0.to(dev)), put(eps.to(dev)), put(t.to(dev)), put(ah.to(dev)), "v")
+        return {"x_t": x_t, "target": target, "valid": valid}
+
+    def oracle(res):
+        want_xt, want_target, want_valid = NO.noise_target(x0, eps, t, ah, "v")
+        assert torch.equal(res["valid"][:, 0].bool().cpu(), want_valid)
+        # test_gpu_nodata.test_noise_vs_oracle's bound, 2^-22 (|a x| + |b eps|), with |a x| + |b eps| < 8 (|eps| < 7)
+        assert float(eps.abs().max()) < 7
+        assert torch.allclose(res["x_t"].cpu().double(), want_xt, rtol=0, atol=2.0 ** -19)
+        assert torch.allclose(res["target"].cpu().double(), want_target, rtol=0, atol=2.0 ** -19)
+    G.guarded_runs(monkeypatch, dev, "drs_noise_target_nodata", fn, oracle, case=str(shape))
+
+
+@pytest.mark.parametrize("kind", ["MSE", "Huber"])
+@pytest.mark.parametrize("shape", [N.A, N.V1], ids=str)
+def test_diffusion_loss_masked_between_guards(monkeypatch, dev, shape, kind):
+    from diffusionremotesensing_amd.losses import DiffusionLoss, LossBins
+    pred, target = _dyadic(shape, 1), _dyadic(shape, 2)  # d a multiple of 1/8, |d| <= 4: every l(d) and every sum of them exact
+    nd = N._nodata(shape)
+    pred = torch.where(nd[:, None], torch.full_like(pred, math.nan), pred)
+    valid = (~nd).to(torch.uint8)[:, None].contiguous()
+    _, _, t, table, sample_w = GL._inputs(shape)
+    w = GL.O.image_weights(shape[0], t, table, sample_w)
+    per_image, loss, grad, counts, _ = NO.masked_loss(pred, target, ~nd, kind, GL.DELTA, w)
+
+    def fn(put):
+        bins = LossBins(N.T, 4, dev)
+        lf = DiffusionLoss(kind, put(table.to(dev)), bins, delta=GL.DELTA)
+        got_loss, got_grad = lf.loss_and_grad(put(pred.to(dev)), put(target.to(dev)), put(t.to(dev)), put(sample_w.to(dev)),
+                                              valid=put(valid.to(dev)))
+        return {"loss": got_loss.clone(), "grad": got_grad, "per_image": lf.per_image, "loss_f64": lf.loss_f64.clone(),
+                "counts": lf.valid_counts, "bins": bins.buf}
+
+    def oracle(res):
+        assert torch.equal(res["counts"].cpu(), counts)
+        assert torch.allclose(res["per_image"].cpu(), per_image, rtol=GL.SUM_RTOL, atol=0.0)
+        assert abs(res["loss_f64"].item() - loss.item()) <= GL.SUM_RTOL * abs(loss.item())
+        GL._assert_grad(res["grad"], grad, f"{shape} {kind} masked, guarded")
+    G.guarded_runs(monkeypatch, dev, "drs_diffusion_loss_masked", fn, oracle, case=f"{shape} {kind}")
+
+
+@pytest.mark.parametrize("shape", [N.A, N.V1, N.S], ids=str)
+def test_metrics_nodata_between_guards(monkeypatch, dev, shape):
+    """Both metric entries and their shared workspace (allocated inside the block).  (3, 3, 37, 41) and (5, 2, 11, 11) leave
+    the pointwise launcher its element-by-element instance whatever the pointers are; (2, 1, 16, 16) takes the 16-byte instance
+    when aligned - one band of powers of two in [1/4, 1] (sr: and zeros): squared errors and sums are exact in fp32 and every
+    normalised value is exactly 1, every angle exactly 0."""
+    from diffusionremotesensing_amd import hip_ops, metrics
+    one_band = shape[1] == 1
+    if one_band:
+        g = torch.Generator().manual_seed(3)
+        hr, sr = 2.0 ** -torch.randint(0, 3, shape, generator=g).float(), 2.0 ** -torch.randint(0, 3, shape, generator=g).float()
+        sr = torch.where(torch.rand(shape, generator=g) < 0.1, torch.zeros_like(sr), sr)
+        hr = torch.where(N._nodata(shape)[:, None], torch.full_like(hr, math.nan), hr)
+    else:
+        hr = N._marked(shape, "nan")
+        sr = torch.nan_to_num(hr, nan=0.5) + 0.05 * torch.randn(shape, generator=torch.Generator().manual_seed(6))
+    want = NO.image_quality(sr, hr, GM.MAG)
+
+    def fn(put):
+        s, h = put(sr.to(dev)), put(hr.to(dev))
+        out = dict(metrics.image_quality(s, h, GM.MAG, nodata=True))
+        out["sums"] = hip_ops.metrics_pointwise_nodata(s, h, True)
+        out["ssim_count"] = hip_ops.ssim_nodata(s, h, True)
+        return out
+
+    def oracle(res):
+        GM._assert_matches_oracle({k: res[k] for k in want}, want, shape)
+    G.guarded_runs(monkeypatch, dev, "drs_metrics_pointwise_nodata+drs_ssim_nodata", fn, oracle, case=str(shape))
