@@ -266,7 +266,7 @@ class split_aggregation_sampling:
         return x[0]
 
     def aggregation_sampling(self, noise_source=None, sampling_steps=None, eta=0.0, aggregation="final", color_fix=None,
-                             color_fix_levels=5, known=None, known_mask=None, resample=1, jump=1):
+                             color_fix_levels=5, known=None, known_mask=None, resample=1, jump=1, lr_consistency=None):
         """Reference :76-116 (`sampling_steps` / `eta`: every tile runs a DDIM chain).  `aggregation`: "final" (the
         reference: independent tile chains, blended once; `noise_source(tile, i, shape)`) or "per_step" (`sample_scene`:
         one joint chain, blended at every step; `noise_source(i, scene_shape)`), clamped to [0, 1] (the constructor's `clamp`).
@@ -275,10 +275,15 @@ class split_aggregation_sampling:
         (`colorfix.color_fix`) and clamped to [0, 1] again.
         `known` / `known_mask` of scene size (`sample_scene`), with `resample` / `jump`, keep those pixels in either mode: the
         tiles' chains (`sample_tiles`) or the joint chain keep them at every step, and the known pixels of the blended scene are
-        `known` under the clamp, exactly (in the final mode one `aggregate_tiles(..., known=, known_mask=)`)."""
+        `known` under the clamp, exactly (in the final mode one `aggregate_tiles(..., known=, known_mask=)`).
+        `lr_consistency` (a consistency.LRConsistency; super-resolution only) projects the finished scene once, as a whole, onto
+        the scenes the degradation maps to img_lr's first image (`consistency.project` with an operator of scene size, (H m, W m)
+        -> (H, W)): in either mode, after `color_fix` and before the last clamp.  It does not reach into the chains: in the final
+        mode the tiles' chains follow `diffusion_model.lr_consistency`, each against its own LR tile - a cropped LR image, whose
+        borders the operator treats as the image's edge - and the per-step chain takes none (`sample_chain` refuses the pair)."""
         if aggregation not in ("final", "per_step"):
             raise ValueError(f"aggregation={aggregation!r} must be 'final' or 'per_step'")
-        fix = self._color_fix(color_fix, color_fix_levels)
+        fix = self._lr_project(lr_consistency, self._color_fix(color_fix, color_fix_levels))
         self.check_known(sampling_steps, known, known_mask, resample, jump)
         batch_size, channels, height, width = self.img_lr.shape
         m = self.magnification_factor
@@ -299,6 +304,25 @@ class split_aggregation_sampling:
 
     def _clamp(self, scene):
         return scene if self.clamp is None else torch.clamp(scene, self.clamp[0], self.clamp[1])
+
+    def _lr_project(self, request, fix):
+        """`fix` followed by the scene's LR projection and the clamp; `fix` itself without a request.  The operator and its
+        projector are made here, before anything is sampled (ValueError for a request this scene does not take)."""
+        from .consistency import check_lr_consistency, project
+        if check_lr_consistency(request) is None:
+            return fix
+        Hs, Ws = self._scene_size()
+        batch_size, channels, height, width = self.img_lr.shape
+        if channels != self.out_channels:
+            raise ValueError(f"lr_consistency: the conditioning has {channels} bands, the scene {self.out_channels}: it is no "
+                             "degraded copy of the scene (super-resolution only)")
+        projector = request.operator_for(self.diffusion_model, (Hs, Ws), lr_hw=(height, width)).projector(request.damping, self.device)
+
+        def projected(scene):
+            scene = fix(scene)
+            lr = self.img_lr[:1].to(scene.device, torch.float32).contiguous()
+            return self._clamp(project(scene.unsqueeze(0).contiguous(), lr, projector, request.strength)[0])
+        return projected
 
     def _color_fix(self, method, levels):
         """f(clamped scene (C, Hs, Ws)) -> the scene `aggregation_sampling` returns: the identity without a method (checked
@@ -344,7 +368,7 @@ def launch(args):
     import os
 
     from .colorfix import cli_color_fix
-    from .cli import cli_prediction, cli_sampling_steps, cli_threshold, cli_ztsnr, set_guidance_rescale
+    from .cli import cli_consistency, cli_prediction, cli_sampling_steps, cli_threshold, cli_ztsnr, set_guidance_rescale
     device = args.device
     task = getattr(args, "task", "superres")
     if args.UNet_type.lower() != "residual attention unet":
@@ -376,6 +400,12 @@ def launch(args):
     else:
         raise ValueError(f"--task {task!r} must be 'superres' or 'sar_to_ndvi'")
     set_guidance_rescale(diffusion, args)
+    consistent = cli_consistency(args)
+    if consistent["lr_consistency"] is not None:
+        if task != "superres":
+            raise ValueError("--lr_consistency belongs to --task superres: only its conditioning is a degraded copy of the scene")
+        if getattr(args, "aggregation", "final") == "final":  # (the per-step chain takes none: the finished scene is projected)
+            diffusion.lr_consistency = consistent["lr_consistency"]
     print(f"You are using {args.UNet_type} model")
     img_lr = _load_tensor(args.img_lr_path).float()
     if img_lr.dim() == 3:
@@ -394,17 +424,18 @@ def launch(args):
     final_pred = tiler.aggregation_sampling(sampling_steps=cli_sampling_steps(args),
                                             eta=getattr(args, "eta", 0.0),
                                             aggregation=getattr(args, "aggregation", "final"),
-                                            **cli_color_fix(args), **kept)
+                                            **cli_color_fix(args), **kept,
+                                            **{k: v for k, v in consistent.items() if v is not None})
     torch.save(final_pred.squeeze(0).cpu(), args.destination_path)
 
 
 def build_arg_parser():
-    """The reference's flags, verbatim (:217-231), the DDIM flags, --aggregation, the colour-correction flags, the known-pixel
-    flags, --task / --clamp and --prediction / --x0_clip (the snapshot's prediction; the clip of the x0 implied at every step)."""
+    """The reference's flags, verbatim (:217-231), the DDIM flags, --aggregation, the colour-correction flags, the LR-consistency
+    flags (`cli.add_consistency_args`), the known-pixel flags, --task / --clamp and --prediction / --x0_clip (the snapshot's prediction; the clip of the x0 implied at every step)."""
     import argparse
 
     from .colorfix import add_color_fix_args
-    from .cli import add_prediction_args, add_sampling_args, add_solver_args
+    from .cli import add_consistency_args, add_prediction_args, add_sampling_args, add_solver_args
     p = argparse.ArgumentParser(description=" ")
     p.add_argument("--noise_schedule", type=str, default="cosine")
     p.add_argument("--snapshot_name", type=str, default="snapshot.pt")
@@ -427,6 +458,7 @@ def build_arg_parser():
                    help="final: independent tile chains blended once (the reference); per_step: one joint chain of the "
                         "whole scene, the tiles' noise predictions blended at every reverse step")
     add_color_fix_args(p)
+    add_consistency_args(p)
     p.add_argument("--known_path", type=str, default=None,
                    help=".pt / .npy scene (C_out,Hs,Ws) whose pixels under --known_mask_path are kept (RePaint)")
     p.add_argument("--known_mask_path", type=str, default=None,

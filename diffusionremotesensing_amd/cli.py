@@ -142,6 +142,62 @@ def cli_threshold(args):
     return {"x0_threshold": getattr(args, "x0_threshold", None)}
 
 
+def cli_nonnegative(text):
+    """The value of --lr_damping / --lr_blur_radius: a finite number >= 0, read while the command line is parsed."""
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} must be a number >= 0") from None
+    if not 0.0 <= v < float("inf"):
+        raise argparse.ArgumentTypeError(f"{text!r} must be a finite number >= 0")
+    return v
+
+
+def cli_finite(text):
+    """The value of --lr_strength: a finite number."""
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} must be a finite number") from None
+    if not abs(v) < float("inf"):
+        raise argparse.ArgumentTypeError(f"{text!r} must be a finite number")
+    return v
+
+
+def add_consistency_args(p):
+    """--lr_consistency and --lr_damping / --lr_strength / --lr_blur_radius of `evaluate` (superres) and the tiler
+    (`cli_consistency`; consistency.py).  Not in the reference, and not on the trainers."""
+    p.add_argument("--lr_consistency", type=str2bool, nargs="?", const=True, default=False,
+                   help="LR-consistent sampling: project the clean image every reverse step implies (the tiler: also the finished "
+                        "scene) onto the images the DownBlur degradation maps to the LR input; needs --Degradation_type DownBlur "
+                        "or DownBlurNoise")
+    p.add_argument("--lr_damping", type=cli_nonnegative, default=0.01, metavar="D",
+                   help="with --lr_consistency: the Tikhonov damping of the projection's gain (0: the exact pseudo-inverse, "
+                        "refused for an ill-conditioned blur); default 0.01")
+    p.add_argument("--lr_strength", type=cli_finite, default=1.0, metavar="S",
+                   help="with --lr_consistency: the share of the correction that is applied; default 1")
+    p.add_argument("--lr_blur_radius", type=cli_nonnegative, default=None, metavar="R",
+                   help="with --lr_consistency: the blur radius of the degradation the LR input was made with; default: the "
+                        "trainer's 0.5")
+    return p
+
+
+def cli_consistency(args):
+    """`add_consistency_args`' flags as the `lr_consistency` keyword of `Diffusion.evaluate` and the tiler's
+    `aggregation_sampling`: None without --lr_consistency (and for a namespace without the flags), else an `LRConsistency`.
+    ValueError for --lr_damping / --lr_strength / --lr_blur_radius without it."""
+    given = [name for name, default in (("lr_damping", 0.01), ("lr_strength", 1.0), ("lr_blur_radius", None))
+             if getattr(args, name, default) != default]
+    if not getattr(args, "lr_consistency", False):
+        if given:
+            raise ValueError("--" + " / --".join(given) + " belong to --lr_consistency")
+        return {"lr_consistency": None}
+    from .consistency import LRConsistency
+    return {"lr_consistency": LRConsistency(blur_radius=getattr(args, "lr_blur_radius", None),
+                                            damping=getattr(args, "lr_damping", 0.01),
+                                            strength=getattr(args, "lr_strength", 1.0))}
+
+
 def cli_prefixes(text):
     """The value of --freeze: 'PREFIX[,PREFIX...]' as a tuple of state_dict-key prefixes (empty pieces: an error)."""
     parts = tuple(s.strip() for s in text.split(","))

@@ -26,14 +26,18 @@ same samples, colour-corrected against the up-sampled LR image (colorfix.py).
 `--nodata V` (sar_to_ndvi: 'nan' or the files' no-data value; superres: the stored byte K in 0 .. 255, as on its trainer - the
 rule value is float32(K) / 255, the bits the uint8 feeds give it) scores every row over the valid pixels of the truth alone and adds the `valid` column, the share of valid pixels;
 for sar_to_ndvi the folder is also read with it (a no-data pixel becomes NaN).  Not with --ensemble or --known_fraction.
+
+`--lr_consistency [--lr_damping D --lr_strength S --lr_blur_radius R]` (superres, DownBlur / DownBlurNoise) samples LR-consistently
+(consistency.py): the `model` row is the projected chain, a `model_free` row the plain chain of the same noise, and every row
+gains `LR RMSE`, the root mean square of (degraded estimate - LR input).  Not with --ensemble or --known_fraction.
 """
 import json
 import os
 
 import torch
 
-from .cli import (add_bsr_args, add_nodata_args, add_prediction_args, add_solver_args, cli_prediction, cli_sampling_steps, cli_threshold,
-                  cli_ztsnr, set_guidance_rescale)
+from .cli import (add_bsr_args, add_consistency_args, add_nodata_args, add_prediction_args, add_solver_args, cli_consistency,
+                  cli_prediction, cli_sampling_steps, cli_threshold, cli_ztsnr, set_guidance_rescale)
 from .colorfix import add_color_fix_args, cli_color_fix
 from .launcher import launch_device
 from .sampling import plan_of
@@ -94,9 +98,9 @@ def format_table(scores):
     """The means of `Diffusion.evaluate` as a table: PSNR to 0.01 dB, SSIM to 4 decimals, SAM to 0.001 degrees, ERGAS to 4
     significant digits."""
     keys = list(scores["model"])
-    w = 12 if "model_fixed" in scores else 10
+    w = 12 if "model_fixed" in scores or "model_free" in scores else 10
     lines = [f"{'':{w}s}" + "".join(f"{METRIC_FORMATS[k][0]:>14s}" for k in keys)]
-    for name in ("model", "model_fixed", "member", "bicubic"):
+    for name in ("model", "model_fixed", "model_free", "member", "bicubic"):
         if name in scores:  # (a score only the model has, psnr_unknown, leaves the baseline's cell empty)
             lines.append(f"{name:{w}s}" + "".join(
                 f"{METRIC_FORMATS[k][1].format(scores[name][k]) if k in scores[name] else '-':>14s}" for k in keys))
@@ -175,7 +179,7 @@ def cli_arg_parser(task="superres"):
     --color_fix_levels and the BSRGAN feed's --bsr_kind / --bsr_seed."""
     p = add_nodata_args(add_prediction_args(add_solver_args(add_ensemble_args(add_known_args(evaluate_arg_parser(task))))),
                         u8=task == "superres")
-    return add_bsr_args(add_color_fix_args(p)) if task == "superres" else p
+    return add_consistency_args(add_bsr_args(add_color_fix_args(p))) if task == "superres" else p
 
 
 def main(argv=None):
@@ -210,6 +214,12 @@ def main(argv=None):
         p.error("--color_fix cannot be combined with --ensemble or --known_fraction")
     if fix and fix["color_fix"] == "adain" and fix["color_fix_levels"] != 5:
         p.error("--color_fix_levels belongs to --color_fix wavelet")
+    try:
+        consistent = cli_consistency(args)
+    except ValueError as e:
+        p.error(str(e))
+    if consistent["lr_consistency"] is not None and (args.ensemble is not None or args.known_fraction is not None):
+        p.error("--lr_consistency cannot be combined with --ensemble or --known_fraction")
     args.snapshot_folder_path = os.path.join(os.curdir, "models_run", args.model_name, "weights")
     snapshot = os.path.join(args.snapshot_folder_path, args.snapshot_name)
     if not os.path.exists(snapshot):
@@ -221,13 +231,16 @@ def main(argv=None):
     scores = diffusion.evaluate(model, unshuffled(val_loader), n_images=args.n_images, sampling_steps=cli_sampling_steps(args),
                                 eta=args.eta, known_mask_fn=known_mask_fn(args), resample=args.resample, jump=args.jump,
                                 **({"ensemble": args.ensemble, "member_batch": args.member_batch} if args.ensemble else {}),
-                                **({"nodata": _evaluate_nodata(args, task)} if args.nodata is not None else {}), **fix)
+                                **({"nodata": _evaluate_nodata(args, task)} if args.nodata is not None else {}), **fix,
+                                **({k: v for k, v in consistent.items() if v is not None}))
     print(f"{scores['n']} validation images, snapshot of epoch {diffusion.epochs_run}, "
           + (sampling_line(cli_sampling_steps(args), args.eta) if args.sampling_steps else f"{args.noise_steps - 1} ancestral steps")
           + (f", {args.known_fraction:.0%} of every image hidden, the rest known (resample {args.resample}, jump {args.jump})"
              if args.known_fraction is not None else "")
           + (f", ensembles of {args.ensemble} members" if args.ensemble else "")
-          + (f", model_fixed: {fix['color_fix']} colour correction against the up-sampled LR image" if fix else ""))
+          + (f", model_fixed: {fix['color_fix']} colour correction against the up-sampled LR image" if fix else "")
+          + (f", LR-consistent sampling ({consistent['lr_consistency']}), model_free: the plain chain of the same noise"
+             if consistent["lr_consistency"] is not None else ""))
     print(format_table(scores))
     if "ensemble" in scores:
         print(format_ensemble(scores["ensemble"]))

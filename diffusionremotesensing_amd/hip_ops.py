@@ -915,3 +915,102 @@ def colorfix_adain(sr, guide):
         st = lib.drs_colorfix_adain(_ptr(sr), _ptr(guide), _ptr(out), *sr.shape, _ptr(ws), ws.numel(), _stream(sr.device))
     _lib.check(st, "drs_colorfix_adain")
     return out
+
+
+_SEP_WS = {}  # device index -> uint8 workspace of drs_sep_apply / drs_sep_project / drs_sep_project_eps, grown as needed
+
+
+def _sep_workspace(lib, shape, device):
+    need = lib.drs_sep_workspace_bytes(*shape)
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    ws = _SEP_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _SEP_WS[key] = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _req_sep(op, x, name="x"):
+    x = _req(x, name)
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise RuntimeError(f"{op}: {name} must be a (B, C, H, W) tensor without an empty extent, got {tuple(x.shape)}")
+    return x
+
+
+def _req_matrix(op, m, name, shape):
+    m = _req(m, name)
+    if tuple(m.shape) != tuple(shape):
+        raise RuntimeError(f"{op}: {name} is {tuple(m.shape)}, expected {tuple(shape)}")
+    return m
+
+
+def sep_apply(x, d_y, d_x):
+    """d_y x d_x^T per plane of x (B, C, H, W) for matrices d_y (h, H) and d_x (w, W): (B, C, h, w), exact fp32 products in a
+    fixed order (include/drs_hip.h: drs_sep_apply)."""
+    lib = _lib.load()
+    x = _req_sep("sep_apply", x)
+    B, Cn, H, W = x.shape
+    d_y, d_x = _req(d_y, "d_y"), _req(d_x, "d_x")
+    if d_y.dim() != 2 or d_x.dim() != 2 or d_y.shape[1] != H or d_x.shape[1] != W:
+        raise RuntimeError(f"sep_apply: d_y {tuple(d_y.shape)} / d_x {tuple(d_x.shape)} do not take {H} x {W} planes")
+    h, w = d_y.shape[0], d_x.shape[0]
+    out = torch.empty((B, Cn, h, w), dtype=torch.float32, device=x.device)
+    ws = _sep_workspace(lib, (B, Cn, H, W, h, w), x.device)
+    with torch.cuda.device(x.device):
+        st = lib.drs_sep_apply(_ptr(x), _ptr(d_y), _ptr(d_x), _ptr(out), B, Cn, H, W, h, w, _ptr(ws), ws.numel(), _stream(x.device))
+    _lib.check(st, "drs_sep_apply")
+    return out
+
+
+def _sep_projector_args(op, projector, yt, B, Cn, H, W):
+    h, w = projector.D_y.shape[0], projector.D_x.shape[0]
+    mats = (_req_matrix(op, projector.D_y, "D_y", (h, H)), _req_matrix(op, projector.D_x, "D_x", (w, W)),
+            _req_matrix(op, projector.U_y, "U_y", (H, h)), _req_matrix(op, projector.U_x, "U_x", (W, w)),
+            _req_matrix(op, projector.G, "G", (h, w)))
+    yt = _req_matrix(op, yt, "yt", (B, Cn, h, w))
+    return yt, mats, h, w
+
+
+def sep_project(x, yt, projector, strength=1.0, out=None):
+    """x + strength U_y (G o (yt - D_y x D_x^T)) U_x^T per plane of x (B, C, H, W), with the tensors of `projector` (a
+    consistency.LRProjector) and yt = projector.prepare(y); into `out` (may be x; default: a new tensor).  include/drs_hip.h:
+    drs_sep_project."""
+    lib = _lib.load()
+    x = _req_sep("sep_project", x)
+    B, Cn, H, W = x.shape
+    yt, mats, h, w = _sep_projector_args("sep_project", projector, yt, B, Cn, H, W)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _req_state(out, "sep_project", "out")
+        _req_numel("sep_project", x, (("out", out),))
+    ws = _sep_workspace(lib, (B, Cn, H, W, h, w), x.device)
+    with torch.cuda.device(x.device):
+        st = lib.drs_sep_project(_ptr(x), _ptr(yt), *(_ptr(m) for m in mats), float(strength), _ptr(out), B, Cn, H, W, h, w,
+                                 _ptr(ws), ws.numel(), _stream(x.device))
+    _lib.check(st, "drs_sep_project")
+    return out
+
+
+def lr_consistent_eps_(eps, x, t, alpha_hat, yt, projector, strength=1.0):
+    """The in-chain projection, in place on `eps` (B, C, H, W): the noise prediction of the x0 that `eps` implies for the state
+    `x` at the levels `t` (B int64 values on the device), moved onto the images `projector`'s operator maps to the observation
+    behind yt = projector.prepare(y).  x0 is formed as it is loaded and never stored; strength 0 leaves eps its bits
+    (include/drs_hip.h: drs_sep_project_eps).  Returns eps."""
+    lib = _lib.load()
+    _req_state(eps, "lr_consistent_eps_", "eps")
+    if eps.dim() != 4 or min(eps.shape) < 1:
+        raise RuntimeError(f"lr_consistent_eps_: eps must be a (B, C, H, W) tensor without an empty extent, got {tuple(eps.shape)}")
+    x = _req(x, "x"); t = _req(t, "t", torch.int64); alpha_hat = _req(alpha_hat, "alpha_hat")
+    if tuple(x.shape) != tuple(eps.shape):
+        raise RuntimeError(f"lr_consistent_eps_: x is {tuple(x.shape)}, eps {tuple(eps.shape)}")
+    B, Cn, H, W = eps.shape
+    if t.numel() != B:
+        raise RuntimeError(f"lr_consistent_eps_: t has {t.numel()} elements, eps has {B} images")
+    yt, mats, h, w = _sep_projector_args("lr_consistent_eps_", projector, yt, B, Cn, H, W)
+    ws = _sep_workspace(lib, (B, Cn, H, W, h, w), eps.device)
+    with torch.cuda.device(eps.device):
+        st = lib.drs_sep_project_eps(_ptr(eps), _ptr(x), _ptr(t), _ptr(alpha_hat), alpha_hat.numel(), _ptr(yt),
+                                     *(_ptr(m) for m in mats), float(strength), B, Cn, H, W, h, w, _ptr(ws), ws.numel(),
+                                     _stream(eps.device))
+    _lib.check(st, "drs_sep_project_eps")
+    return eps

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib, hip_ops
+from .consistency import chain_projector, check_lr_consistency
 
 
 def ddim_timesteps(noise_steps, sampling_steps):
@@ -212,6 +213,24 @@ def check_solver_known(sampling_steps, known, known_mask):
                          "resampling invalidate the multistep history (use solver='ddim' or the ancestral chain)")
 
 
+def check_chain_consistency(schedule, update=None, lr_img=None, needs_lr=False):
+    """The `lr_consistency` of `schedule` (None when it has none) for `sample_chain`; ValueError for a value that is no
+    `consistency.LRConsistency`, for the per-step `update` hook of the tiler (its state is a scene, its LR images are tiles) and -
+    `needs_lr` - for a chain without an LR image: only the super-resolution sampler has an observation to be consistent with; and
+    for a degradation the request has no operator for (`LRConsistency.check_for`)."""
+    request = check_lr_consistency(getattr(schedule, "lr_consistency", None))
+    if request is None:
+        return None
+    if update is not None:
+        raise ValueError("lr_consistency cannot be combined with a per-step update hook (the tiler's aggregation='per_step'): "
+                         "the hook blends tiles into a scene state, and no tile's LR image describes it; use aggregation='final', "
+                         "or the tiler's own lr_consistency= for the finished scene")
+    if needs_lr and lr_img is None:
+        raise ValueError("lr_consistency belongs to the super-resolution sampler: this chain has no LR image to be consistent with")
+    request.check_for(schedule)
+    return request
+
+
 def check_terminal_chain(schedule, prediction, eta, update=None):
     """(the terminal level of `schedule` or None, its guidance_rescale) for `sample_chain`; ValueError for a chain on a
     zero-terminal-SNR schedule that cannot run: an eps network, eta > 1, or the per-step `update` hook of the tiler, whose
@@ -376,7 +395,7 @@ def chain_moves(noise_steps, sampling_steps=None, resample=1, jump=1, spacing="u
 
 
 def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=None, sampling_steps=None, eta=0.0,
-                 cfg_scale=0.0, update=None, known=None, known_mask=None, resample=1, jump=1, frames=None):
+                 cfg_scale=0.0, update=None, known=None, known_mask=None, resample=1, jump=1, frames=None, lr_img=None):
     """The reverse chain from x_T to the returned x_0 (arguments: `Diffusion._sample_chain`).  `schedule` holds noise_steps, the
     alpha / alpha_hat / beta tables and their device (a Diffusion); `frames`, when a list, gets a copy of x after every move.
     One `step` takes every move of `chain_moves`.  A forward jump to level t_to is one `renoise_` with the draw for t_to.  A
@@ -406,7 +425,14 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
     the ancestral chain that move is taken as eta = 1, the true posterior at beta = 1.  The `update` hook cannot take it
     (ValueError: `check_terminal_chain`).  `schedule.guidance_rescale` = phi in (0, 1] (0 when it has none) acts where `predict`
     returns a pair and cfg_scale > 0: one `hip_ops.cfg_rescale` forms the rescaled guided prediction first, and everything after
-    it sees a single prediction and cfg_scale 0."""
+    it sees a single prediction and cfg_scale 0.
+    `schedule.lr_consistency` (None when it has none; a `consistency.LRConsistency`, super-resolution only: it needs `lr_img`, the
+    (n | 1, C, h, w) observation of the chains) makes every reverse move below the terminal level LR-consistent: the conversion
+    above always runs, and right after it - before the move's draw and the update - one `hip_ops.lr_consistent_eps_` replaces eps
+    by that of the implied x0 projected onto the images the degradation maps to `lr_img`.  The projector
+    is cached per image size, magnification, radius, damping and device (`consistency.chain_projector`), the observation is
+    taken into its basis once per chain.  The terminal move is left as it is: its x0-form step has no eps to correct, and the
+    moves after it pull the sample onto the observation.  The `update` hook cannot be combined with it (ValueError)."""
     ddim = sampling_steps is not None
     solver, spacing = plan_of(sampling_steps)
     dpm = solver == "dpmpp_2m"
@@ -415,6 +441,8 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
     dynamic = {"x0_threshold": x0_threshold} if x0_threshold is not None else {}
     convert = (prediction != "eps" or x0_clip is not None) and not getattr(predict, "converts_prediction", False)
     terminal_level, phi = check_terminal_chain(schedule, prediction, eta, update)
+    consistency = check_chain_consistency(schedule, update, lr_img, needs_lr=True)
+    convert = convert or (consistency is not None and not getattr(predict, "converts_prediction", False))
     moves = chain_moves(schedule.noise_steps, sampling_steps, resample, jump, spacing, schedule.alpha_hat if ddim else None)
     with torch.no_grad():
         x = noise_source(schedule.noise_steps, shape) if noise_source is not None else torch.randn(shape)  # (CPU generator, :230)
@@ -425,6 +453,11 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
         state = {"first": True, "hist_level": None}  # (`first` is not set again after a roll-back)
         hist = torch.empty_like(x) if dpm else None
         level_before = {m.t: before.t for before, m in zip(moves, moves[1:])} if dpm else {}
+        projector = yt = None
+        if consistency is not None:
+            projector = chain_projector(schedule, consistency, shape[2:], x.device)
+            lr = lr_img.to(device=x.device, dtype=torch.float32)
+            yt = projector.prepare((lr if lr.dim() == 4 else lr.unsqueeze(0)).expand(shape[0], -1, -1, -1).contiguous())
 
         def draw(t):
             return noise_source(t, shape).to(x.device) if noise_source is not None else torch.randn_like(x)
@@ -458,6 +491,8 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
                     eps = hip_ops.pred_to_eps_(eps, x, t_rows[t][:shape[0]], schedule.alpha_hat, prediction, x0_clip,
                                                pred_uncond=eps_uncond, cfg_scale=cfg_scale, **dynamic)
                     eps_uncond, guide = None, 0.0
+                if projector is not None:
+                    hip_ops.lr_consistent_eps_(eps, x, t_rows[t][:shape[0]], schedule.alpha_hat, yt, projector, consistency.strength)
                 noise = draw(t) if t_to > 0 and (known is not None or not ddim or eta > 0) else None
                 if dpm:
                     second = t_to > 0 and state["hist_level"] is not None and state["hist_level"] == level_before.get(t)

@@ -36,7 +36,7 @@ from .losses import DiffusionLoss, LossAwareSampler, LossBins, min_snr_weights
 from .optim import FusedAdam, FusedAdamW, WarmupCosine
 from .sampling import (CHAIN_CHECK_EVERY, _is_int, _repeat_members, asks_for_known_pixels,  # noqa: F401 - re-exported
                        check_ensemble_args, check_inpaint_args, check_prediction, check_sampling_args, check_threshold, check_solver_known,
-                       check_terminal_chain, check_zero_terminal_snr, ddim_chain_noise,
+                       check_chain_consistency, check_terminal_chain, check_zero_terminal_snr, ddim_chain_noise,
                        rescale_zero_terminal_snr, ddim_timesteps, ensemble_chunks, inpaint_schedule, known_tensors, run_reverse_chain, sample_chain,
                        sampling_plan)
 from .superres_feeds import SyntheticSuperresDataset, make_superres_feeds  # noqa: F401
@@ -46,7 +46,7 @@ _DEGRADATIONS = ("downblur", "bsrgan", "downblurnoise")
 
 METRIC_FORMATS = {"psnr": ("PSNR", "{:.2f} dB"), "ssim": ("SSIM", "{:.4f}"), "sam": ("SAM", "{:.3f} deg"),
                   "ergas": ("ERGAS", "{:.4g}"), "psnr_unknown": ("PSNR unknown", "{:.2f} dB"),
-                  "valid_fraction": ("valid", "{:.4f}")}
+                  "valid_fraction": ("valid", "{:.4f}"), "lr_rmse": ("LR RMSE", "{:.4g}")}
 
 
 def format_scores(scores):
@@ -100,6 +100,11 @@ class Diffusion:
         # steps and `train`'s --eval_metrics scores; `nodata_fill` is what the network sees under the mask, forward-noised.
         # DESIGN.md section 27.
         self.nodata, self.nodata_fill = None, 0.5
+        # ... and LR-consistent sampling (None, or a consistency.LRConsistency: every reverse move of `sample` projects the x0 it
+        # implies onto the images the degradation maps to the LR image, with the DownBlur operator of `blur_radius` unless the
+        # request names another).  Plain attributes like x0_clip, read at the start of every chain, not written into snapshots;
+        # the super-resolution sampler only.  DESIGN.md section 28.
+        self.lr_consistency, self.blur_radius = None, 0.5
         self.noise_steps = noise_steps
         self.beta_start = beta_start
         self.beta_end = beta_end
@@ -246,10 +251,10 @@ class Diffusion:
             lambda engine, x, t, first: engine.forward(x, t, lr_img, self.magnification_factor, reuse_cond=not first,
                                                        check_weights=first),
             table_rows=n, generate_video=generate_video, noise_source=noise_source, sampling_steps=sampling_steps, eta=eta,
-            known=known, known_mask=known_mask, resample=resample, jump=jump)
+            known=known, known_mask=known_mask, resample=resample, jump=jump, lr_img=lr_img)
 
     def _sample_chain(self, model, shape, predict, *, table_rows, generate_video, noise_source, sampling_steps, eta,
-                      cfg_scale=0.0, update=None, known=None, known_mask=None, resample=1, jump=1):
+                      cfg_scale=0.0, update=None, known=None, known_mask=None, resample=1, jump=1, lr_img=None):
         """The reverse chain all three samplers share (reference :226-255), from x_T to the returned x_0.
         `predict(engine, x, t, first)` is the sampler's model call for one step: x in its current state, t one row of the
         (noise_steps, table_rows) timestep table, `first` True on the first call of the chain only (weights checked,
@@ -264,15 +269,18 @@ class Diffusion:
         plain sampler.  With an `update` hook as well (the tiler's scene with known pixels) the moves are the same and a
         reverse move calls `update(x, eps, noise, i, i_prev, known=, known_mask=)` with the converted tensors and that draw; a
         forward jump is the `renoise_` of the scene state.  With a `sampling_plan` of solver "dpmpp_2m" the moves are `dpm_step_`s and the `update` hook also gets
-        `hist=` and `t_q=`, as `sampling.sample_chain` says.  The chain is `sampling.sample_chain`; this method adds the eval
+        `hist=` and `t_q=`, as `sampling.sample_chain` says.  `lr_img` is the observation `self.lr_consistency` projects onto
+        (only `sample` and its relatives here pass one: with the attribute set, a chain without it, or with `update`, raises).
+        The chain is `sampling.sample_chain`; this method adds the eval
         mode around it and the video."""
         check_solver_known(sampling_steps, known, known_mask)
         check_terminal_chain(self, self.prediction, eta, update)
+        check_chain_consistency(self, update, lr_img, needs_lr=True)
         model.eval()
         frames = [] if generate_video else None
         x = sample_chain(self, self._engine_net(model).hip_engine(), shape, predict, table_rows=table_rows, noise_source=noise_source,
                          sampling_steps=sampling_steps, eta=eta, cfg_scale=cfg_scale, update=update, known=known,
-                         known_mask=known_mask, resample=resample, jump=jump, frames=frames)
+                         known_mask=known_mask, resample=resample, jump=jump, frames=frames, lr_img=lr_img)
         if generate_video:
             from .video import video_maker  # optional dependency (cv2), same call as reference :253
             video_maker(frames, os.path.join(os.getcwd(), "models_run", self.model_name, "results",
@@ -283,7 +291,7 @@ class Diffusion:
     # -- image quality of the samples (metrics.py; not in the reference) ---------------------------
     def evaluate(self, model, loader, n_images=None, sampling_steps=None, eta=0.0, noise_source=None, baseline=True,
                  known_mask_fn=None, resample=1, jump=1, ensemble=None, member_batch=None, color_fix=None, color_fix_levels=5,
-                 nodata=None):
+                 lr_consistency=None, nodata=None):
         """PSNR / SSIM / SAM / ERGAS (metrics.image_quality) of `sample`'s output against the ground truth over the (lr, hr)
         batches of `loader`, every batch sampled as one call with n = its size, until `n_images` images are scored (None: the
         whole loader).  `sampling_steps`, `eta` and `noise_source` are `sample`'s (the source is asked batch after batch).
@@ -300,23 +308,90 @@ class Diffusion:
         the scores clamp it and corrected against the bicubic up-sampling of its lr batch (`colorfix.color_fix`).
         `nodata` (True / "nan" or the no-data value; not with `ensemble` or `known_mask_fn`) scores every row - the sample, the
         bicubic baseline, the corrected sample - over the valid pixels of the truth alone (`metrics.image_quality(nodata=)`)
-        and adds "valid_fraction".  The model keeps the train / eval mode it came with."""
+        and adds "valid_fraction".  The model keeps the train / eval mode it came with.
+        `lr_consistency` (a consistency.LRConsistency; not with `ensemble` or `known_mask_fn`) samples every batch with that
+        request as `self.lr_consistency` - the "model" row - and a second time without it from the same noise (`noise_source`
+        asked again, or torch's generators put back where they were), the "model_free" row; "model", "model_free" and "bicubic"
+        gain "lr_rmse", `consistency.lr_rmse` of the estimate clamped to [0, 1] against the batch's LR images.  Without it the
+        result is what it was, key for key."""
         self._check_evaluate_nodata(nodata, ensemble, known_mask_fn)
         fix = self._evaluate_color_fix(color_fix, color_fix_levels, ensemble, known_mask_fn)
+        consistent = self._evaluate_consistency(lr_consistency, ensemble, known_mask_fn)
         sample, members = self._evaluate_samplers(model, "input_channels", sampling_steps, eta, noise_source, known_mask_fn,
                                                   resample, jump, ensemble, member_batch)
         scorers = {"model": sample}
+        if consistent is not None:
+            scorers.update(consistent(sample))
         if baseline:
             scorers["bicubic"] = lambda lr_img, hr_img: hip_ops.bicubic_upsample(lr_img, self.magnification_factor)
+            if consistent is not None:
+                scorers["bicubic"] = consistent.scored(scorers["bicubic"])
         if fix is not None:
             kept = {}  # the batch's sample, as `drawn` keeps the members of an ensemble: "model" runs before "model_fixed"
 
+            model_scorer = scorers["model"]  # (`sample`, or its LR-consistent form, which returns scores of its own as well)
+
             def sample_kept(lr_img, hr_img):
-                kept["x"] = sample(lr_img, hr_img)
-                return kept["x"]
+                out = model_scorer(lr_img, hr_img)
+                kept["x"] = out[0] if isinstance(out, tuple) else out
+                return out
             scorers["model"] = sample_kept
             scorers["model_fixed"] = lambda lr_img, hr_img: fix(kept["x"], lr_img)
         return self._evaluate(model, loader, n_images, scorers, self.magnification_factor, members, nodata)
+
+    def _evaluate_consistency(self, request, ensemble, known_mask_fn):
+        """`evaluate`'s LR-consistent scorers, None without a request: f(sample) -> {"model": the chain with `request` as
+        `self.lr_consistency`, "model_free": the plain chain of the same noise}, and `.scored(scorer)`, the scorer with "lr_rmse"
+        added; ValueError for a request `evaluate` does not take (checked before anything is sampled)."""
+        from .consistency import check_lr_consistency, lr_rmse
+        if check_lr_consistency(request) is None:
+            return None
+        if ensemble is not None or known_mask_fn is not None:
+            raise ValueError("evaluate: lr_consistency cannot be combined with ensemble=N or known_mask_fn")
+        ops = {}
+
+        def rmse(est, lr_img):
+            size = tuple(est.shape[-2:])
+            if size not in ops:
+                ops[size] = request.operator_for(self, size)
+            return {"lr_rmse": lr_rmse(torch.clamp(est, 0, 1), lr_img, ops[size])}
+        request.operator_for(self, (self.image_size, self.image_size))  # (ValueError for a degradation without an operator)
+
+        def scored(scorer):
+            def with_rmse(lr_img, hr_img):
+                est = scorer(lr_img, hr_img)
+                return est, rmse(est, lr_img)
+            return with_rmse
+        cuda = torch.cuda.is_available() and torch.device(self.device).type == "cuda"
+
+        def rng_state():
+            return torch.get_rng_state(), (torch.cuda.get_rng_state(self.device) if cuda else None)
+
+        def set_rng_state(state):
+            torch.set_rng_state(state[0])
+            if cuda:
+                torch.cuda.set_rng_state(state[1], self.device)
+
+        def scorers(sample):
+            kept = {}
+
+            def with_attribute(value, lr_img, hr_img):
+                before, self.lr_consistency = self.lr_consistency, value
+                try:
+                    return sample(lr_img, hr_img)
+                finally:
+                    self.lr_consistency = before
+
+            def projected(lr_img, hr_img):
+                kept["rng"] = rng_state()
+                return with_attribute(request, lr_img, hr_img)
+
+            def free(lr_img, hr_img):
+                set_rng_state(kept.pop("rng"))
+                return with_attribute(None, lr_img, hr_img)
+            return {"model": scored(projected), "model_free": scored(free)}
+        scorers.scored = scored
+        return scorers
 
     @staticmethod
     def _check_evaluate_nodata(nodata, ensemble, known_mask_fn):

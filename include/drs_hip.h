@@ -588,6 +588,36 @@ DRS_API size_t drs_colorfix_adain_workspace_bytes(int B, int C, int H, int W);
 DRS_API int drs_colorfix_adain(const float* sr, const float* guide, float* out, int B, int C, int H, int W, void* workspace,
                                size_t workspace_bytes, drs_stream_t stream);
 
+/* LR-consistent sampling (csrc/consistency.hip; not in the reference): the damped range-null-space
+ * projection of an image onto the images a separable linear degradation A_y . A_x^T maps to the observation.  All tensors are
+ * fp32 and row-major; x: (n,c,H,W); with the thin SVDs A = P diag(s) V^T per axis the caller holds
+ *   d_y (h,H) = diag(s_y) V_y^T,  d_x (w,W);  u_y (H,h) = V_y,  u_x (W,w);  gain (h,w);  yt (n,c,h,w) = P_y^T y P_x per plane.
+ * drs_sep_apply:        out (n,c,h,w) = d_y x d_x^T per plane, for any pair of matrices of those shapes (the degradation itself,
+ *                       the residual basis, or - with P_y^T (h,h) and P_x^T (w,w) on an (n,c,h,w) input - yt).
+ * drs_sep_project:      out = x + strength u_y (gain o (yt - d_y x d_x^T)) u_x^T per plane; out may be x.
+ * drs_sep_project_eps:  the same on the x0 that the noise prediction `eps` implies for the state `x` at the levels t (n int64
+ *                       on the device), x0 = (x - sqrt(1 - ah) eps) / sqrt(ah), formed as it is loaded and never stored; eps is
+ *                       replaced by the prediction of the projected x0, eps - sqrt(ah / (1 - ah)) strength (the correction).  The
+ *                       coefficients are formed in fp64 from the device table and rounded once (as drs_ddim_step's).  A level
+ *                       outside the table never indexes it: that image's eps comes out NaN (as drs_pred_to_eps; t lives on the
+ *                       device and is not read back).  No chain calls it at a level with ah == 0 or ah == 1.
+ * Every product is an exact fp32 multiply-add chain (v_mfma_f32_16x16x4_f32) in a fixed order, without atomics: two calls give
+ * the same bits, and so does a call whose pointers are not 16-byte aligned (4-byte loads of the same elements).  strength == 0
+ * launches nothing (drs_sep_project: one copy when out != x).  No host synchronisation.  workspace: 4-byte aligned,
+ * >= drs_sep_workspace_bytes(n, c, H, W, h, w) bytes (0 for a shape the calls do not take).
+ * DRS_ERR_ARG: null pointer, strength not finite, noise_steps < 1, eps == x; DRS_ERR_SHAPE: c > 16, any extent < 1, a plane or
+ * a matrix of 2^31 elements; DRS_ERR_WORKSPACE: workspace too small or misaligned.  All are reported before any launch. */
+DRS_API size_t drs_sep_workspace_bytes(int n, int c, int H, int W, int h, int w);
+DRS_API int drs_sep_apply(const float* x, const float* d_y, const float* d_x, float* out, int n, int c, int H, int W, int h,
+                          int w, void* workspace, size_t workspace_bytes, drs_stream_t stream);
+DRS_API int drs_sep_project(const float* x, const float* yt, const float* d_y, const float* d_x, const float* u_y,
+                            const float* u_x, const float* gain, float strength, float* out, int n, int c, int H, int W,
+                            int h, int w, void* workspace, size_t workspace_bytes, drs_stream_t stream);
+DRS_API int drs_sep_project_eps(float* eps, const float* x, const int64_t* t, const float* alpha_hat, int noise_steps,
+                                const float* yt, const float* d_y, const float* d_x, const float* u_y, const float* u_x,
+                                const float* gain, float strength, int n, int c, int H, int W, int h, int w, void* workspace,
+                                size_t workspace_bytes, drs_stream_t stream);
+
 /* "DownBlur" degradation of the super-resolution data feed on the device, bit-exact with the Pillow calls of the
  * reference's dataset item: x = ToTensor(GaussianBlur(radius)(resize(y, (out_w, out_h), BICUBIC))), y = ToTensor(hr).
  *   hr: (N,C,H,W) uint8;  x_lr: (N,C,out_h,out_w) float32 in [0,1];  y_hr: (N,C,H,W) float32 or NULL;
