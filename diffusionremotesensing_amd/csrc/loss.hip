@@ -6,8 +6,13 @@
 // 64 lanes are combined by a shuffle tree (offsets 32, 16, .. 1); the four wave sums are added in wave order through LDS; the
 // finish combines an image's chunk partials the same way (a lane adds chunks l, l + 64, ... in that order, then the shuffle
 // tree), then adds the images' weighted losses in batch order.  No atomics, no fences: the finish is a second launch.
+//
+// drs_diffusion_loss_masked is the MASKED instance of the same two kernels behind a count of every
+// image's valid pixels: a no-data element is SELECTED out - it adds nothing and its gradient is +0.0 - so a mask without a
+// no-data pixel gives the unmasked entry's bits.
 #include "drs_common.h"
 
+constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kChunk = 4096;         // elements per block of the streaming pass: 256 threads x 4 groups of 4
 constexpr int kGroups = 4;           // 16-byte groups per thread
 constexpr int kFinThreads = 1024;    // the finish: one block of 16 waves, one wave per image
@@ -47,12 +52,24 @@ __device__ __forceinline__ float loss_element(float p, float q, double delta, fl
 // Grid (chunks, B).  A row's elements are addressed on the 16-byte grid of its own start address (virtual index = element
 // index + the start's misalignment in floats), so every whole group is one aligned float4 whatever n is; the groups cut by the
 // row's two ends, and every group when the three tensors' rows are misaligned differently, go element by element.
-template <int KIND, bool GRAD>
+// MASKED: element i of a row belongs to pixel i % hw.  The four decisions of a group are one 32-bit load where the group lies
+// inside one band and its mask bytes are 4-byte aligned, four byte loads otherwise.  A no-data element's pred and target are
+// loaded but never used.  The coefficient needs Bv (the images with a valid pixel) and n_b = C nv_b instead of `scale`: every
+// block counts Bv from `counts` itself.
+struct LossMask {
+  const unsigned char* valid;  // [B][hw], non-zero = data
+  const long long* counts;     // [B]: valid_count_kernel's
+  long long hw;
+  int B, C;
+};
+
+template <int KIND, bool GRAD, bool MASKED>
 __global__ __launch_bounds__(256) void diffusion_loss_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                              const long long* __restrict__ t, long long n,
                                                              const float* __restrict__ table, int T,
                                                              const float* __restrict__ sample_w, double delta, double scale,
-                                                             float* __restrict__ grad, double* __restrict__ partials) {
+                                                             float* __restrict__ grad, double* __restrict__ partials,
+                                                             const LossMask mask) {
   const int b = blockIdx.y;
   const float* p = pred + (long long)b * n;
   const float* q = target + (long long)b * n;
@@ -62,12 +79,33 @@ __global__ __launch_bounds__(256) void diffusion_loss_kernel(const float* __rest
   const int mis = vec ? mp : 0;
   float coef = 0.f, coef_delta = 0.f;
   if (GRAD) {
+    double image_scale = scale;  // 1 / (B n); MASKED: 1 / (Bv n_b)
+    if constexpr (MASKED) {
+      __shared__ int wave_images[kWaves];
+      int images = 0;
+      for (int i = threadIdx.x; i < mask.B; i += kThreads) images += mask.counts[i] > 0;
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) images += __shfl_down(images, off, 64);
+      if ((threadIdx.x & 63) == 0) wave_images[threadIdx.x >> 6] = images;
+      __syncthreads();
+      const int Bv = wave_images[0] + wave_images[1] + wave_images[2] + wave_images[3];
+      // An image without a valid pixel (nv_b = 0) gets 1 / 0 here and a non-finite coef: every one of its elements is selected
+      // out below, so no element takes it.  (A guard around it costs nothing in time but moves the instance off the register
+      // budget - and the occupancy - DESIGN.md section 27 records for it.)
+      image_scale = 1.0 / ((double)Bv * (double)((long long)mask.C * mask.counts[b]));
+    }
     const double w = image_weight(table, T, table ? t[b] : 0, sample_w, b);
-    coef = (float)__dmul_rn(w, KIND == DRS_LOSS_MSE ? 2.0 * scale : scale);  // (2 * scale is exact)
-    coef_delta = (float)__dmul_rn(w, delta * scale);
+    coef = (float)__dmul_rn(w, KIND == DRS_LOSS_MSE ? 2.0 * image_scale : image_scale);  // (2 * scale is exact)
+    coef_delta = (float)__dmul_rn(w, delta * image_scale);
   }
   float pv[kGroups][4], qv[kGroups][4];
+  bool ok[kGroups][4];  // MASKED only
   long long first[kGroups];
+  long long pix = 0;  // MASKED only: the pixel of the group's first element
+  if constexpr (MASKED) {
+    pix = (4 * ((long long)blockIdx.x * (kChunk / 4) + threadIdx.x) - mis) % mask.hw;
+    if (pix < 0) pix += mask.hw;  // (of element -mis .. -1: counted back from the row's end)
+  }
 #pragma unroll
   for (int k = 0; k < kGroups; ++k) {
     const long long i = 4 * ((long long)blockIdx.x * (kChunk / 4) + threadIdx.x + 256 * k) - mis;  // the group's first element
@@ -84,6 +122,23 @@ __global__ __launch_bounds__(256) void diffusion_loss_kernel(const float* __rest
         qv[k][e] = in ? q[i + e] : 0.f;
       }
     }
+    if constexpr (MASKED) {
+      const unsigned char* m = mask.valid + (long long)b * mask.hw;
+      if (vec && i >= 0 && i + 4 <= n && pix + 4 <= mask.hw && (((uintptr_t)(m + pix)) & 3u) == 0) {
+        const unsigned four = *reinterpret_cast<const unsigned*>(m + pix);
+        ok[k][0] = (four & 0xffu) != 0, ok[k][1] = (four & 0xff00u) != 0;
+        ok[k][2] = (four & 0xff0000u) != 0, ok[k][3] = (four & 0xff000000u) != 0;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          long long at = pix + e;
+          if (at >= mask.hw) at %= mask.hw;
+          ok[k][e] = i + e >= 0 && i + e < n && m[at] != 0;  // (outside the row: nothing is read, added or stored)
+        }
+      }
+      pix += 4 * kThreads;
+      if (pix >= mask.hw) pix = mask.hw > 4 * kThreads ? pix - mask.hw : pix % mask.hw;
+    }
   }
   double s = 0.0;
 #pragma unroll
@@ -91,7 +146,13 @@ __global__ __launch_bounds__(256) void diffusion_loss_kernel(const float* __rest
     const long long i = first[k];
     float gv[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) gv[e] = loss_element<KIND>(pv[k][e], qv[k][e], delta, coef, coef_delta, s);
+    for (int e = 0; e < 4; ++e) {
+      if constexpr (MASKED) {
+        gv[e] = 0.f;
+        if (!ok[k][e]) continue;
+      }
+      gv[e] = loss_element<KIND>(pv[k][e], qv[k][e], delta, coef, coef_delta, s);
+    }
     if (!GRAD) continue;
     if (vec && i >= 0 && i + 4 <= n) {
       *reinterpret_cast<float4*>(g + i) = make_float4(gv[0], gv[1], gv[2], gv[3]);
@@ -111,18 +172,52 @@ __global__ __launch_bounds__(256) void diffusion_loss_kernel(const float* __rest
         __dadd_rn(__dadd_rn(__dadd_rn(wave_sum[0], wave_sum[1]), wave_sum[2]), wave_sum[3]);
 }
 
+// counts[b] = the valid pixels of image b: one block per image, 16 mask bytes per thread and trip where the row allows
+__global__ __launch_bounds__(kThreads) void valid_count_kernel(const unsigned char* __restrict__ valid, int64_t hw,
+                                                               long long* __restrict__ counts) {
+  __shared__ long long red[kWaves];
+  const unsigned char* row = valid + (int64_t)blockIdx.x * hw;
+  const int64_t lead = (16 - ((uintptr_t)row & 15u)) & 15u, head = lead < hw ? lead : hw, lines = (hw - head) / 16;
+  long long n = 0;
+  for (int64_t j = threadIdx.x; j < lines; j += kThreads) {
+    const uint4 v = *reinterpret_cast<const uint4*>(row + head + 16 * j);
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      n += ((w[k] & 0xffu) != 0) + ((w[k] & 0xff00u) != 0) + ((w[k] & 0xff0000u) != 0) + ((w[k] & 0xff000000u) != 0);
+  }
+  const int64_t rest = hw - 16 * lines;  // head and tail bytes: at most 30
+  for (int64_t r = threadIdx.x; r < rest; r += kThreads) n += row[r < head ? r : 16 * lines + r] != 0;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) n += __shfl_down(n, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) counts[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
 // One block of 16 waves.  Images are taken 1024 at a time: thread i forms image i's weight and bin; wave w adds the chunk
 // partials of images w, w + 16, ... - lane l those of chunks l, l + 64, ... in that order, then the shuffle tree of pass one -
 // with an image's loads issued together (the sum is a few additions; what it would wait for is one L2 round trip per load).
 // Then the batch is walked in order by nbins + 1 threads at once: thread k < nbins keeps bin k (sum, count and ring position in
 // registers), thread 64 - another wave - the weighted sum and the two counters.
+// MASKED: over the images that have a valid pixel.  per_image divides by n_b = C counts[b] instead of n, the loss by Bv instead
+// of B; an image without a valid pixel has per_image 0 and enters neither the loss, the bins nor the ring.
+template <bool MASKED>
+struct FinishMaskLds {};
+template <>
+struct FinishMaskLds<true> {
+  long long elements[kFinThreads];  // n_b; 0: no valid pixel
+};
+
+template <bool MASKED>
 __global__ __launch_bounds__(kFinThreads) void diffusion_loss_finish_kernel(
     const double* __restrict__ partials, int chunks, int B, long long n, const long long* __restrict__ t,
     const float* __restrict__ table, int T, const float* __restrict__ sample_w, double* __restrict__ per_image,
     double* __restrict__ out, double* __restrict__ bins, int nbins, int history, int update_ring,
-    long long* __restrict__ bad_t) {
+    long long* __restrict__ bad_t, const long long* __restrict__ counts, int C) {
   __shared__ double image_loss[kFinThreads], weight[kFinThreads];
   __shared__ int image_bin[kFinThreads];  // >= 0: the bin, -1: no bins, -2: t outside [0, T)
+  __shared__ FinishMaskLds<MASKED> ml;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool uses_t = table || bins;
   const bool bin_thread = bins && tid < nbins;
@@ -138,7 +233,7 @@ __global__ __launch_bounds__(kFinThreads) void diffusion_loss_finish_kernel(
     ring = bins + 3 * nbins + 1 + tid * history;
   }
   double S = 0.0;
-  long long bad = 0, nonfinite = 0;
+  long long bad = 0, nonfinite = 0, Bv = 0;
   for (int b0 = 0; b0 < B; b0 += kFinThreads) {
     const int nb = min(kFinThreads, B - b0);
     __syncthreads();  // (the previous tile's walk)
@@ -148,7 +243,9 @@ __global__ __launch_bounds__(kFinThreads) void diffusion_loss_finish_kernel(
       const bool in_range = tv >= 0 && tv < T;
       weight[tid] = image_weight(table, T, tv, sample_w, b);
       image_bin[tid] = !uses_t || in_range ? (bins ? (int)(tv * nbins / T) : -1) : -2;
+      if constexpr (MASKED) ml.elements[tid] = (long long)C * counts[b];
     }
+    if constexpr (MASKED) __syncthreads();  // (elements: read by the waves below)
     for (int i = wave; i < nb; i += kFinThreads / 64) {
       const double* row = partials + (long long)(b0 + i) * chunks;
       double s = 0.0;
@@ -165,7 +262,9 @@ __global__ __launch_bounds__(kFinThreads) void diffusion_loss_finish_kernel(
 #pragma unroll
       for (int off = 32; off >= 1; off >>= 1) s = __dadd_rn(s, __shfl_down(s, off, 64));
       if (lane == 0) {
-        const double v = s / (double)n;
+        double v;
+        if constexpr (MASKED) v = ml.elements[i] > 0 ? s / (double)ml.elements[i] : 0.0;
+        else v = s / (double)n;
         per_image[b0 + i] = v;
         image_loss[i] = v;
       }
@@ -175,6 +274,8 @@ __global__ __launch_bounds__(kFinThreads) void diffusion_loss_finish_kernel(
       for (int i = 0; i < nb; ++i) {
         const double v = image_loss[i];
         if (image_bin[i] != tid || !isfinite(v)) continue;
+        if constexpr (MASKED)
+          if (ml.elements[i] == 0) continue;
         bin_sum = __dadd_rn(bin_sum, v);
         ++bin_count;
         if (update_ring) {
@@ -186,8 +287,12 @@ __global__ __launch_bounds__(kFinThreads) void diffusion_loss_finish_kernel(
     } else if (tid == 64) {
       for (int i = 0; i < nb; ++i) {
         const double v = image_loss[i];
-        S = __dadd_rn(S, __dmul_rn(weight[i], v));
         bad += image_bin[i] == -2;
+        if constexpr (MASKED) {
+          if (ml.elements[i] == 0) continue;
+          ++Bv;
+        }
+        S = __dadd_rn(S, __dmul_rn(weight[i], v));
         nonfinite += image_bin[i] >= 0 && !isfinite(v);
       }
     }
@@ -198,7 +303,7 @@ __global__ __launch_bounds__(kFinThreads) void diffusion_loss_finish_kernel(
     bins[2 * nbins + tid] = __longlong_as_double(bin_appended);
   }
   if (tid == 64) {
-    const double loss = S / (double)B;
+    const double loss = !MASKED ? S / (double)B : Bv > 0 ? S / (double)Bv : 0.0;
     out[0] = loss;
     reinterpret_cast<float*>(out)[2] = (float)loss;
     if (nonfinite) bins[3 * nbins] = __longlong_as_double(__double_as_longlong(bins[3 * nbins]) + nonfinite);
@@ -214,16 +319,56 @@ static int check_bins(const char* what, const void* bins, int T, int nbins, int 
   return DRS_OK;
 }
 
-template <int KIND>
-static void launch_loss(dim3 grid, hipStream_t s, const float* pred, const float* target, const int64_t* t, int64_t n,
+template <int KIND, bool MASKED>
+static void launch_loss(dim3 grid, hipStream_t s, const float* pred, const float* target, const long long* t, long long n,
                         const float* table, int T, const float* sample_w, double delta, double scale, float* grad,
-                        double* partials) {
+                        double* partials, const LossMask& mask) {
   if (grad)
-    DRS_LAUNCH((diffusion_loss_kernel<KIND, true>), grid, dim3(256), 0, s, pred, target, (const long long*)t, (long long)n,
-               table, T, sample_w, delta, scale, grad, partials);
+    DRS_LAUNCH((diffusion_loss_kernel<KIND, true, MASKED>), grid, dim3(256), 0, s, pred, target, t, n, table, T, sample_w, delta,
+               scale, grad, partials, mask);
   else
-    DRS_LAUNCH((diffusion_loss_kernel<KIND, false>), grid, dim3(256), 0, s, pred, target, (const long long*)t, (long long)n,
-               table, T, sample_w, delta, scale, grad, partials);
+    DRS_LAUNCH((diffusion_loss_kernel<KIND, false, MASKED>), grid, dim3(256), 0, s, pred, target, t, n, table, T, sample_w, delta,
+               scale, grad, partials, mask);
+}
+
+// The checks of both entries, under the entry's name `what`, in the order the unmasked entry always had: pointers (the entry's
+// own), check_kind, the shape (the entry's own), then the rest in diffusion_loss.
+static int check_kind(const char* what, int kind, double delta) {
+  DRS_REQUIRE(kind == DRS_LOSS_MSE || kind == DRS_LOSS_MAE || kind == DRS_LOSS_HUBER, DRS_ERR_ARG, "%s: unknown kind %d", what,
+              kind);
+  DRS_REQUIRE(kind != DRS_LOSS_HUBER || delta > 0.0, DRS_ERR_ARG, "%s: Huber needs delta > 0, got %g", what, delta);
+  return DRS_OK;
+}
+
+// What the two entries share after those: the remaining checks, then the launches.  n = C hw for the masked entry, whose scale
+// is formed per image on the device.
+template <bool MASKED>
+static int diffusion_loss(const char* what, const float* pred, const float* target, const long long* t, int B, long long n,
+                          const float* table, int T, const float* sample_w, int kind, double delta, float* grad,
+                          double* per_image, double* partials, double* out, double* bins, int nbins, int history,
+                          int update_ring, long long* bad_t, const LossMask& mask, hipStream_t s) {
+  DRS_REQUIRE(n / kChunk + 1 < (1LL << 31) / 256, DRS_ERR_SHAPE, "%s: %s=%lld is too large", what, MASKED ? "C hw" : "n", n);
+  DRS_REQUIRE(!(table || bins) || (t && T >= 1), DRS_ERR_ARG, "%s: a table or bins need t and T >= 1, got T=%d", what, T);
+  if (int st = check_bins(what, bins, T, nbins, history)) return st;
+  const int chunks = (int)((n + 3) / kChunk + 1);  // covers the row on the grid of its start address (up to 3 floats in front)
+  const double scale = MASKED ? 0.0 : 1.0 / ((double)B * (double)n);
+  const dim3 grid(chunks, B);
+  if (MASKED) {
+    DRS_LAUNCH(valid_count_kernel, dim3(B), dim3(kThreads), 0, s, mask.valid, (int64_t)mask.hw,
+               const_cast<long long*>(mask.counts));
+    DRS_CHECK_HIP(hipGetLastError());
+  }
+  if (kind == DRS_LOSS_MSE)
+    launch_loss<DRS_LOSS_MSE, MASKED>(grid, s, pred, target, t, n, table, T, sample_w, delta, scale, grad, partials, mask);
+  if (kind == DRS_LOSS_MAE)
+    launch_loss<DRS_LOSS_MAE, MASKED>(grid, s, pred, target, t, n, table, T, sample_w, delta, scale, grad, partials, mask);
+  if (kind == DRS_LOSS_HUBER)
+    launch_loss<DRS_LOSS_HUBER, MASKED>(grid, s, pred, target, t, n, table, T, sample_w, delta, scale, grad, partials, mask);
+  DRS_CHECK_HIP(hipGetLastError());
+  DRS_LAUNCH(diffusion_loss_finish_kernel<MASKED>, dim3(1), dim3(kFinThreads), 0, s, partials, chunks, B, n, t, table, T,
+             sample_w, per_image, out, bins, nbins, history, update_ring, bad_t, mask.counts, mask.C);
+  DRS_CHECK_HIP(hipGetLastError());
+  return DRS_OK;
 }
 
 extern "C" int drs_diffusion_loss(const float* pred, const float* target, const int64_t* t, int B, int64_t n,
@@ -231,27 +376,29 @@ extern "C" int drs_diffusion_loss(const float* pred, const float* target, const 
                                   double* per_image, double* partials, double* out, double* bins, int nbins, int history,
                                   int update_ring, int64_t* bad_t, drs_stream_t stream) {
   DRS_REQUIRE(pred && target && per_image && partials && out, DRS_ERR_ARG, "diffusion_loss: null pointer");
-  DRS_REQUIRE(kind == DRS_LOSS_MSE || kind == DRS_LOSS_MAE || kind == DRS_LOSS_HUBER, DRS_ERR_ARG,
-              "diffusion_loss: unknown kind %d", kind);
-  DRS_REQUIRE(kind != DRS_LOSS_HUBER || delta > 0.0, DRS_ERR_ARG, "diffusion_loss: Huber needs delta > 0, got %g", delta);
+  if (int st = check_kind("diffusion_loss", kind, delta)) return st;
   DRS_REQUIRE(1 <= B && B <= 65535 && n >= 1, DRS_ERR_SHAPE, "diffusion_loss: need 1 <= B <= 65535 and n >= 1, got B=%d n=%lld",
               B, (long long)n);
-  DRS_REQUIRE(n / kChunk + 1 < (1LL << 31) / 256, DRS_ERR_SHAPE, "diffusion_loss: n=%lld is too large", (long long)n);
-  DRS_REQUIRE(!(table || bins) || (t && T >= 1), DRS_ERR_ARG, "diffusion_loss: a table or bins need t and T >= 1, got T=%d", T);
-  if (int st = check_bins("diffusion_loss", bins, T, nbins, history)) return st;
-  const int chunks = (int)((n + 3) / kChunk + 1);  // covers the row on the grid of its start address (up to 3 floats in front)
-  const double scale = 1.0 / ((double)B * (double)n);
-  const dim3 grid(chunks, B);
-  hipStream_t s = (hipStream_t)stream;
-  if (kind == DRS_LOSS_MSE) launch_loss<DRS_LOSS_MSE>(grid, s, pred, target, t, n, table, T, sample_w, delta, scale, grad, partials);
-  if (kind == DRS_LOSS_MAE) launch_loss<DRS_LOSS_MAE>(grid, s, pred, target, t, n, table, T, sample_w, delta, scale, grad, partials);
-  if (kind == DRS_LOSS_HUBER)
-    launch_loss<DRS_LOSS_HUBER>(grid, s, pred, target, t, n, table, T, sample_w, delta, scale, grad, partials);
-  DRS_CHECK_HIP(hipGetLastError());
-  DRS_LAUNCH(diffusion_loss_finish_kernel, dim3(1), dim3(kFinThreads), 0, s, partials, chunks, B, (long long)n, (const long long*)t,
-             table, T, sample_w, per_image, out, bins, nbins, history, update_ring, (long long*)bad_t);
-  DRS_CHECK_HIP(hipGetLastError());
-  return DRS_OK;
+  return diffusion_loss<false>("diffusion_loss", pred, target, (const long long*)t, B, n, table, T, sample_w, kind, delta, grad,
+                               per_image, partials, out, bins, nbins, history, update_ring, (long long*)bad_t, LossMask{},
+                               (hipStream_t)stream);
+}
+
+extern "C" int drs_diffusion_loss_masked(const float* pred, const float* target, const uint8_t* valid, const int64_t* t, int B,
+                                         int C, int64_t hw, const float* table, int T, const float* sample_w, int kind,
+                                         double delta, float* grad, double* per_image, int64_t* counts, double* partials,
+                                         double* out, double* bins, int nbins, int history, int update_ring, int64_t* bad_t,
+                                         drs_stream_t stream) {
+  DRS_REQUIRE(pred && target && valid && per_image && counts && partials && out, DRS_ERR_ARG,
+              "diffusion_loss_masked: null pointer");
+  if (int st = check_kind("diffusion_loss_masked", kind, delta)) return st;
+  DRS_REQUIRE(1 <= B && B <= 65535 && 1 <= C && C <= kMaxBands && hw >= 1, DRS_ERR_SHAPE,
+              "diffusion_loss_masked: need 1 <= B <= 65535, 1 <= C <= %d and hw >= 1, got B=%d C=%d hw=%lld", kMaxBands, B, C,
+              (long long)hw);
+  const LossMask mask{valid, (const long long*)counts, hw, B, C};
+  return diffusion_loss<true>("diffusion_loss_masked", pred, target, (const long long*)t, B, (long long)C * hw, table, T, sample_w,
+                              kind, delta, grad, per_image, partials, out, bins, nbins, history, update_ring, (long long*)bad_t,
+                              mask, (hipStream_t)stream);
 }
 
 // Every block forms the proposal from the ring on its own (nbins <= 64 terms, in double, in index order: all blocks hold the

@@ -743,71 +743,54 @@ def metrics_workspace(B, C, H, W, device):
     return torch.empty(max(_lib.load().drs_metrics_workspace_bytes(B, C, H, W), 8), dtype=torch.uint8, device=device)
 
 
-def metrics_pointwise(sr, hr, clamp=True, workspace=None):
-    """Per-image sums of one pass over sr and hr (B, C, H, W): a (B, 2 C + 2) float64 device tensor holding the per-band
-    squared error, the per-band sum of hr, the sum of the per-pixel spectral angles in radians and the number of pixels in
-    that sum (include/drs_hip.h: drs_metrics_pointwise)."""
-    lib = _lib.load()
-    sr, hr = _req_image_pair(sr, hr, "metrics_pointwise")
-    B, C_, H, W = sr.shape
-    ws = metrics_workspace(B, C_, H, W, sr.device) if workspace is None else _req(workspace, "workspace", torch.uint8)
-    out = torch.empty((B, 2 * C_ + 2), dtype=torch.float64, device=sr.device)
-    with torch.cuda.device(sr.device):
-        st = lib.drs_metrics_pointwise(_ptr(sr), _ptr(hr), _ptr(out), B, C_, H, W, int(bool(clamp)), _ptr(ws), ws.numel(),
-                                       _stream(sr.device))
-    _lib.check(st, "drs_metrics_pointwise")
-    return out
-
-
-def ssim_mean(sr, hr, clamp=True, workspace=None):
-    """Per-image mean SSIM over bands and valid window positions: a (B,) float64 device tensor (include/drs_hip.h: drs_ssim)."""
-    lib = _lib.load()
-    sr, hr = _req_image_pair(sr, hr, "ssim_mean")
-    B, C_, H, W = sr.shape
-    ws = metrics_workspace(B, C_, H, W, sr.device) if workspace is None else _req(workspace, "workspace", torch.uint8)
-    out = torch.empty((B,), dtype=torch.float64, device=sr.device)
-    with torch.cuda.device(sr.device):
-        st = lib.drs_ssim(_ptr(sr), _ptr(hr), _ptr(out), B, C_, H, W, int(bool(clamp)), _ptr(ws), ws.numel(),
-                          _stream(sr.device))
-    _lib.check(st, "drs_ssim")
-    return out
-
-
 def metrics_nodata_workspace(B, C, H, W, device):
     """The scratch buffer `metrics_pointwise_nodata` and `ssim_nodata` take (either call, stream-ordered)."""
     return torch.empty(max(_lib.load().drs_metrics_nodata_workspace_bytes(B, C, H, W), 8), dtype=torch.uint8, device=device)
 
 
+def _metrics_launch(entry, what, sr, hr, width, clamp, workspace, masked=False, nodata=None):
+    """One call of the C-ABI `entry` ("drs_metrics_pointwise" | "drs_ssim") into a fresh (B, *width(C)) float64 tensor, or -
+    `masked` - of its `_nodata` sibling, which takes the `nodata` rule's value after hr and the larger workspace."""
+    lib = _lib.load()
+    sr, hr = _req_image_pair(sr, hr, what)
+    rule = (nodata_rule(nodata),) if masked else ()
+    B, C_, H, W = sr.shape
+    if workspace is None:
+        ws = (metrics_nodata_workspace if masked else metrics_workspace)(B, C_, H, W, sr.device)
+    else:
+        ws = _req(workspace, "workspace", torch.uint8)
+    out = torch.empty((B, *width(C_)), dtype=torch.float64, device=sr.device)
+    entry += "_nodata" if masked else ""
+    with torch.cuda.device(sr.device):
+        st = getattr(lib, entry)(_ptr(sr), _ptr(hr), *rule, _ptr(out), B, C_, H, W, int(bool(clamp)), _ptr(ws), ws.numel(),
+                                 _stream(sr.device))
+    _lib.check(st, entry)
+    return out
+
+
+def metrics_pointwise(sr, hr, clamp=True, workspace=None):
+    """Per-image sums of one pass over sr and hr (B, C, H, W): a (B, 2 C + 2) float64 device tensor holding the per-band
+    squared error, the per-band sum of hr, the sum of the per-pixel spectral angles in radians and the number of pixels in
+    that sum (include/drs_hip.h: drs_metrics_pointwise)."""
+    return _metrics_launch("drs_metrics_pointwise", "metrics_pointwise", sr, hr, lambda C_: (2 * C_ + 2,), clamp, workspace)
+
+
+def ssim_mean(sr, hr, clamp=True, workspace=None):
+    """Per-image mean SSIM over bands and valid window positions: a (B,) float64 device tensor (include/drs_hip.h: drs_ssim)."""
+    return _metrics_launch("drs_ssim", "ssim_mean", sr, hr, lambda C_: (), clamp, workspace)
+
+
 def metrics_pointwise_nodata(sr, hr, nodata, clamp=True, workspace=None):
     """`metrics_pointwise` over the valid pixels of hr (`nodata`: True / "nan" or the no-data value): a (B, 2 C + 3) float64
     device tensor, the last column the number of valid pixels (include/drs_hip.h: drs_metrics_pointwise_nodata)."""
-    lib = _lib.load()
-    sr, hr = _req_image_pair(sr, hr, "metrics_pointwise_nodata")
-    value = nodata_rule(nodata)
-    B, C_, H, W = sr.shape
-    ws = metrics_nodata_workspace(B, C_, H, W, sr.device) if workspace is None else _req(workspace, "workspace", torch.uint8)
-    out = torch.empty((B, 2 * C_ + 3), dtype=torch.float64, device=sr.device)
-    with torch.cuda.device(sr.device):
-        st = lib.drs_metrics_pointwise_nodata(_ptr(sr), _ptr(hr), value, _ptr(out), B, C_, H, W, int(bool(clamp)), _ptr(ws),
-                                              ws.numel(), _stream(sr.device))
-    _lib.check(st, "drs_metrics_pointwise_nodata")
-    return out
+    return _metrics_launch("drs_metrics_pointwise", "metrics_pointwise_nodata", sr, hr, lambda C_: (2 * C_ + 3,), clamp, workspace,
+                           masked=True, nodata=nodata)
 
 
 def ssim_nodata(sr, hr, nodata, clamp=True, workspace=None):
     """Per image (mean SSIM over bands and over the window positions whose 11 x 11 pixels of hr are all valid - NaN when there
     is none -, number of such positions): a (B, 2) float64 device tensor (include/drs_hip.h: drs_ssim_nodata)."""
-    lib = _lib.load()
-    sr, hr = _req_image_pair(sr, hr, "ssim_nodata")
-    value = nodata_rule(nodata)
-    B, C_, H, W = sr.shape
-    ws = metrics_nodata_workspace(B, C_, H, W, sr.device) if workspace is None else _req(workspace, "workspace", torch.uint8)
-    out = torch.empty((B, 2), dtype=torch.float64, device=sr.device)
-    with torch.cuda.device(sr.device):
-        st = lib.drs_ssim_nodata(_ptr(sr), _ptr(hr), value, _ptr(out), B, C_, H, W, int(bool(clamp)), _ptr(ws), ws.numel(),
-                                 _stream(sr.device))
-    _lib.check(st, "drs_ssim_nodata")
-    return out
+    return _metrics_launch("drs_ssim", "ssim_nodata", sr, hr, lambda C_: (2,), clamp, workspace, masked=True, nodata=nodata)
 
 
 def _req_members(members, what, truth=None):

@@ -163,24 +163,22 @@ class DiffusionLoss:
         self.per_image = torch.empty(B, dtype=torch.float64, device=dev)
         out = torch.empty(2, dtype=torch.float64, device=dev)  # the loss as double, and as fp32 in the first half of word 1
         bins = self.bins
-        self.valid_counts = None
-        if valid is not None:
-            self.valid_counts = torch.empty(B, dtype=torch.int64, device=dev)
-            with torch.cuda.device(dev):
+        tail = (_ptr(out), _ptr(bins.buf if bins else None), bins.nbins if bins else 0, bins.history if bins else 0, int(with_grad),
+                _ptr(self._bad_t), _stream(dev))
+        self.valid_counts = None if valid is None else torch.empty(B, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            if valid is not None:
+                entry = "drs_diffusion_loss_masked"
                 st = _lib.load().drs_diffusion_loss_masked(
                     _ptr(pred), _ptr(target), _ptr(valid), _ptr(t), B, pred.shape[1], n // pred.shape[1], _ptr(self.table), T,
                     _ptr(sample_w), KINDS[self.kind], self.delta, _ptr(grad), _ptr(self.per_image), _ptr(self.valid_counts),
-                    _ptr(self._partials), _ptr(out), _ptr(bins.buf if bins else None), bins.nbins if bins else 0,
-                    bins.history if bins else 0, int(with_grad), _ptr(self._bad_t), _stream(dev))
-            _lib.check(st, "drs_diffusion_loss_masked")
-            self.loss_f64 = out[0]
-            return out.view(torch.float32)[2], grad
-        with torch.cuda.device(dev):
-            st = _lib.load().drs_diffusion_loss(
-                _ptr(pred), _ptr(target), _ptr(t), B, n, _ptr(self.table), T, _ptr(sample_w), KINDS[self.kind], self.delta,
-                _ptr(grad), _ptr(self.per_image), _ptr(self._partials), _ptr(out), _ptr(bins.buf if bins else None),
-                bins.nbins if bins else 0, bins.history if bins else 0, int(with_grad), _ptr(self._bad_t), _stream(dev))
-        _lib.check(st, "drs_diffusion_loss")
+                    _ptr(self._partials), *tail)
+            else:
+                entry = "drs_diffusion_loss"
+                st = _lib.load().drs_diffusion_loss(
+                    _ptr(pred), _ptr(target), _ptr(t), B, n, _ptr(self.table), T, _ptr(sample_w), KINDS[self.kind], self.delta,
+                    _ptr(grad), _ptr(self.per_image), _ptr(self._partials), *tail)
+        _lib.check(st, entry)
         self.loss_f64 = out[0]
         return out.view(torch.float32)[2], grad
 

@@ -1,4 +1,5 @@
-"""The entry points of csrc/nodata.hip between guard bands at the three pointer phases of tests/guard.py, run through
+"""The no-data entry points (csrc/nodata.hip, csrc/loss.hip, csrc/metrics.hip) between guard bands at the three pointer phases
+of tests/guard.py, run through
 `test_gpu_guard.guarded_runs` - so that they count for that module's `test_every_entry_point_that_launches_is_guarded`, which
 walks `_lib.SIGNATURES` and runs after this file (files run in name order; on its own that test does not know these entries).
 

@@ -1,6 +1,7 @@
-"""No-data pixels on the GPU (csrc/nodata.hip through hip_ops / losses / metrics / the SAR -> NDVI trainer) against the float64
-oracle of tests/nodata_oracle.py and against the unmasked siblings.  The guard-band runs of the four entry points are in
-tests/test_gpu_entry_guards_nodata.py, whose name puts them in front of tests/test_gpu_guard.py's census of the ABI."""
+"""No-data pixels on the GPU (csrc/nodata.hip and the MASKED kernels of csrc/loss.hip and csrc/metrics.hip, through hip_ops /
+losses / metrics / the SAR -> NDVI trainer) against the float64 oracle of tests/nodata_oracle.py and against the unmasked
+siblings.  The guard-band runs of the four entry points are in tests/test_gpu_entry_guards_nodata.py, whose name puts them in
+front of tests/test_gpu_guard.py's census of the ABI."""
 import functools
 import math
 import os

@@ -1,6 +1,6 @@
 """No-data pixels without a GPU: the float64 oracle of tests/nodata_oracle.py against hand-worked cases, the argument refusals
-of the four entry points of csrc/nodata.hip through the library, `feeds.load_sar_ndvi_folder(nodata=)`, the refusals of the
-trainers and the train state."""
+of the four no-data entry points (csrc/nodata.hip, csrc/loss.hip, csrc/metrics.hip) through the library,
+`feeds.load_sar_ndvi_folder(nodata=)`, the refusals of the trainers and the train state."""
 import ctypes as C
 import math
 import os

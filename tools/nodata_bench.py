@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""The no-data launches (csrc/nodata.hip) at B = 16, 256 x 256, C = 1, 3 and 13 with a quarter of the pixels marked, next to
-their unmasked siblings on tensors of the same size and next to a torch composition of the same result (`isnan` / `where` /
-`sum`), in one process.  HIP events around --iters calls after a warm-up, best of --reps windows; one JSON line per band count:
+"""The no-data launches (csrc/nodata.hip, csrc/loss.hip, csrc/metrics.hip) at B = 16, 256 x 256, C = 1, 3 and 13 with a quarter
+of the pixels marked, next to their unmasked siblings on tensors of the same size and next to a torch composition of the same
+result (`isnan` / `where` / `sum`), in one process.  HIP events around --iters calls after a warm-up, best of --reps windows;
+one JSON line per band count:
 
     noise    noise_target_nodata (x_t, v target, mask)   | noise_v_target                | where / isnan around it
     loss     DiffusionLoss.loss_and_grad(valid=)         | DiffusionLoss.loss_and_grad   | masked MSE and its gradient in torch
