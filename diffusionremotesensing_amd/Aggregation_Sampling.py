@@ -37,6 +37,9 @@ from . import hip_ops
 TILE_BATCH = 16
 
 
+_WEIGHT_TABLES = {}  # (tile width, tile height, device) -> the Gaussian tile weights on the device
+
+
 class split_aggregation_sampling:
     def __init__(self, img_lr, patch_size, stride, magnification_factor, diffusion_model, device, *, out_channels=None,
                  clamp=(0.0, 1.0)):
@@ -85,7 +88,11 @@ class split_aggregation_sampling:
         midpoint = tile_height / 2
         y_probs = [exp(-(y - midpoint) * (y - midpoint) / (tile_height * tile_height) / (2 * var)) / sqrt(2 * pi * var)
                    for y in range(tile_height)]
-        weights = torch.tensor(np.outer(y_probs, x_probs)).to(torch.float32).to(self.device)
+        # (uploaded once per tile size and device: an upload from pageable memory makes the host wait for the current stream)
+        key = (tile_width, tile_height, str(self.device))
+        weights = _WEIGHT_TABLES.get(key)
+        if weights is None:
+            weights = _WEIGHT_TABLES[key] = torch.tensor(np.outer(y_probs, x_probs)).to(torch.float32).to(self.device)
         return torch.tile(weights, (nbatches, 3, 1, 1))
 
     def _scene_size(self):

@@ -121,12 +121,25 @@ def inv_freq_table(channels=100):
     return (1.0 / (10000 ** (torch.arange(0, channels, 2).float() / channels))).contiguous()
 
 
+_INV_FREQ = {}  # (channels, device) -> the table on the device
+
+
+def _inv_freq_on(channels, device):
+    """`inv_freq_table(channels)` on `device`, uploaded once: an upload from pageable memory per call would make the host wait
+    for everything enqueued on the caller's stream."""
+    key = (int(channels), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    table = _INV_FREQ.get(key)
+    if table is None:
+        table = _INV_FREQ[key] = inv_freq_table(channels).to(device)
+    return table
+
+
 def time_mlp(t, W1, b1, W2, b2):
     lib = _lib.load()
     t = _req(t, "t", torch.int64)
     W1, b1, W2, b2 = (_req(a, n) for a, n in ((W1, "W1"), (b1, "b1"), (W2, "W2"), (b2, "b2")))
     dim_out, dim_in = W1.shape
-    inv = inv_freq_table(dim_in).to(t.device)
+    inv = _inv_freq_on(dim_in, t.device)
     out = torch.empty((t.shape[0], dim_out), dtype=torch.float32, device=t.device)
     with torch.cuda.device(t.device):
         st = lib.drs_time_mlp(_ptr(t), _ptr(inv), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(out), t.shape[0], dim_in,
@@ -583,6 +596,22 @@ def _req_known(op, known, mask, shape, state):
     return known, mask
 
 
+_ORIGIN_TABLES = {}  # (origins, device) -> (n, 2) int32 device table, kept for the life of the process (8 bytes per tile)
+
+
+def _origin_table(origins, device):
+    """[(y0, x0), ...] as an (n, 2) int32 table on `device`, uploaded once per layout and device: an upload from pageable
+    memory makes the host wait for everything enqueued on the caller's stream, and a tiler asks for the same table every chain.
+    The table is shared and READ-ONLY: kernels of any stream may be reading it, so it is never written, freed or evicted."""
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (tuple((int(y), int(x)) for y, x in origins), device)
+    table = _ORIGIN_TABLES.get(key)
+    if table is None:
+        table = _ORIGIN_TABLES[key] = torch.tensor(key[0], dtype=torch.int32).reshape(-1, 2).to(device)
+    return table
+
+
 def aggregate_tiles(tiles, origins, weight, height, width, clamp=(0.0, 1.0), known=None, known_mask=None):
     """Gaussian-weighted blend of (n,C,S,S) tiles placed at `origins` [(y0, x0), ...] into a (C,height,width) image,
     normalised by the summed weights and clamped to [0,1] (reference Aggregation_Sampling.py:90-116).
@@ -600,7 +629,7 @@ def aggregate_tiles(tiles, origins, weight, height, width, clamp=(0.0, 1.0), kno
     plain = known is None and known_mask is None and (flag, lo, hi) == (1, 0.0, 1.0)
     if known is not None or known_mask is not None:
         known, known_mask = _req_known("aggregate_tiles", known, known_mask, (C, int(height), int(width)), tiles)
-    org = torch.tensor([[int(y), int(x)] for y, x in origins], dtype=torch.int32).to(tiles.device)
+    org = _origin_table(origins, tiles.device)
     out = torch.empty((C, int(height), int(width)), dtype=torch.float32, device=tiles.device)
     uncovered = torch.zeros(1, dtype=torch.int32, device=tiles.device)
     with torch.cuda.device(tiles.device):
@@ -627,7 +656,7 @@ def tile_origins(origins, S, height, width, device):
         raise RuntimeError("tile_origins: no tiles")
     if int(org.min()) < 0 or int(org[:, 0].max()) + S > height or int(org[:, 1].max()) + S > width:
         raise RuntimeError(f"tile_origins: a {S}x{S} tile window leaves the {height}x{width} scene")
-    return org.to(device)
+    return _origin_table(origins, torch.device(device)).clone()  # (the caller's own: a device copy of the shared table)
 
 
 def _req_origins(origins, name):

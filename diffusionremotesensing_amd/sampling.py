@@ -156,9 +156,20 @@ def plan_of(sampling_steps):
     return solver, spacing if spacing is not None else ("logsnr" if solver == "dpmpp_2m" else "uniform")
 
 
+def host_alpha_hat(schedule):
+    """The float64 host copy of `schedule.alpha_hat`, kept on the schedule object next to the table it was read from and
+    read back again only when another tensor stands there: one read-back per schedule, not one per chain (a read-back makes
+    the host wait for everything enqueued on the current stream).  A schedule's table is replaced, never edited in place."""
+    ah = schedule.alpha_hat
+    held = getattr(schedule, "_alpha_hat_host", None)
+    if held is None or held[0] is not ah:
+        held = schedule._alpha_hat_host = (ah, torch.as_tensor(ah).detach().to("cpu", torch.float64))
+    return held[1]
+
+
 def logsnr_timesteps(alpha_hat, sampling_steps):
     """S levels, descending and distinct, in [1, T - 1], as uniform in lam_t = 0.5 ln(ah_t / (1 - ah_t)) as the table allows
-    (float64 arithmetic on the fp32 table, one read-back per chain): for each of linspace(lam_{T-1}, lam_1, S) the nearest t
+    (float64 arithmetic on the fp32 table; a device table is read back, so callers with a chain to run hand in a host copy): for each of linspace(lam_{T-1}, lam_1, S) the nearest t
     (ties: the larger t), then t_k = min(t_k, t_{k-1} - 1) going down the list and t_k = max(t_k, S - k) going back up, so
     that the last entry is at least 1.  The step after the last entry goes to level 0, as after `ddim_timesteps`.
     On a zero-terminal-SNR table (ah_{T-1} == 0: lam_{T-1} = -inf, which never enters the linspace) the list is T - 1 followed by
@@ -443,7 +454,7 @@ def sample_chain(schedule, engine, shape, predict, *, table_rows, noise_source=N
     terminal_level, phi = check_terminal_chain(schedule, prediction, eta, update)
     consistency = check_chain_consistency(schedule, update, lr_img, needs_lr=True)
     convert = convert or (consistency is not None and not getattr(predict, "converts_prediction", False))
-    moves = chain_moves(schedule.noise_steps, sampling_steps, resample, jump, spacing, schedule.alpha_hat if ddim else None)
+    moves = chain_moves(schedule.noise_steps, sampling_steps, resample, jump, spacing, host_alpha_hat(schedule) if ddim else None)
     with torch.no_grad():
         x = noise_source(schedule.noise_steps, shape) if noise_source is not None else torch.randn(shape)  # (CPU generator, :230)
         x = x.to(schedule.device).contiguous()

@@ -52,7 +52,9 @@ enum {
 };
 
 /* Threading: a drs_plan (and the buffers bound to it) is used by ONE host thread at a time - its launches, events and side
- * streams are not locked.  Different plans may be driven from different threads and on different devices; the plan-less
+ * streams are not locked.  Every entry orders all of its work, side streams included, after the work already enqueued on the
+ * `stream` it is given and before anything enqueued on that stream later.
+ * Different plans may be driven from different threads and on different devices; the plan-less
  * entry points (noise_images, sampler steps, adam / ema, downblur, the feed gathers, aggregate) are re-entrant.  The library's only
  * process-wide state is a mutex-guarded per-device cache of kernel attributes, plus kernel-family switches read ONCE per
  * process from the environment (A/B experiments and the variant tests; unset = the shipped defaults): DRS_SP,
