@@ -369,7 +369,8 @@ def cli_clamp(args):
 def launch(args):
     """Reference launch (:140-212): model + snapshot + Diffusion + tiler.  The image file I/O of the reference
     (PIL / torchvision.transforms) is outside the hot path: `--img_lr_path` takes a `.pt` / `.npy` tensor (C,H,W) or
-    (1,C,H,W) in [0,1], `--destination_path` receives a `.pt` tensor.  `--task sar_to_ndvi` builds the SAR -> NDVI model and
+    (1,C,H,W) in [0,1] - or a uint16 `.npy` of digital numbers, normalised with the snapshot's band ranges or `--data_range` -,
+    `--destination_path` receives a `.pt` tensor (`--out_u16`: a uint16 `.npy` of digital numbers).  `--task sar_to_ndvi` builds the SAR -> NDVI model and
     `Diffusion` instead (`--SAR_channels`, `--NDVI_channels`; `--img_lr_path` is then the SAR scene and
     `--magnification_factor` must be 1); `--known_path` / `--known_mask_path` hold the known scene (C_out,Hs,Ws) and its mask."""
     import os
@@ -414,7 +415,27 @@ def launch(args):
         if getattr(args, "aggregation", "final") == "final":  # (the per-step chain takes none: the finished scene is projected)
             diffusion.lr_consistency = consistent["lr_consistency"]
     print(f"You are using {args.UNet_type} model")
-    img_lr = _load_tensor(args.img_lr_path).float()
+    img_lr, data_range = _load_tensor(args.img_lr_path), None
+    if img_lr.dtype == torch.uint16 or getattr(args, "out_u16", False):
+        # 16-bit digital numbers (radiometry.py): normalised with --data_range, else with the band ranges in the snapshot
+        from . import radiometry
+        channels = img_lr.shape[-3] if img_lr.dim() >= 3 else 1
+        given = getattr(args, "data_range", None)
+        if given is not None:
+            kind, *rest = radiometry.parse_data_range(given)
+            if kind != "fixed":
+                raise ValueError("--data_range auto needs a training cache: the tiler takes LO,HI or LO,HI;LO,HI;...")
+            data_range = radiometry.range_table(rest[0], channels)
+        else:
+            data_range = getattr(diffusion, "snapshot_data_range", None)
+            if data_range is None:
+                raise ValueError(f"{snapshot_path} holds no DATA_RANGE (it was not trained with --bit_depth 16): give --data_range")
+            data_range = radiometry.check_table(data_range, channels)
+        if img_lr.dtype == torch.uint16:
+            img_lr = torch.from_numpy(radiometry.normalise_host(img_lr.numpy(), data_range, band_axis=img_lr.dim() - 3))
+    elif getattr(args, "data_range", None) is not None:
+        raise ValueError("--data_range belongs to a uint16 --img_lr_path or to --out_u16")
+    img_lr = img_lr.float()
     if img_lr.dim() == 3:
         img_lr = img_lr.unsqueeze(0)
     img_lr = img_lr.to(device)
@@ -433,6 +454,13 @@ def launch(args):
                                             aggregation=getattr(args, "aggregation", "final"),
                                             **cli_color_fix(args), **kept,
                                             **{k: v for k, v in consistent.items() if v is not None})
+    if getattr(args, "out_u16", False):  # the scene as digital numbers, a uint16 .npy (C, H, W)
+        from . import radiometry
+        final_pred = final_pred if final_pred.dim() == 4 else final_pred.unsqueeze(0)
+        dn = radiometry.quantize_u16(final_pred.float().contiguous(), radiometry.device_table(data_range, final_pred.device))
+        with open(args.destination_path, "wb") as f:  # (np.save would append .npy to another name)
+            np.save(f, dn.squeeze(0).cpu().numpy())
+        return
     torch.save(final_pred.squeeze(0).cpu(), args.destination_path)
 
 
@@ -478,6 +506,11 @@ def build_arg_parser():
                    help="sar_to_ndvi: --img_lr_path is a SAR scene, sampled to NDVI at --magnification_factor 1")
     p.add_argument("--SAR_channels", type=int, default=2)
     p.add_argument("--NDVI_channels", type=int, default=1)
+    p.add_argument("--data_range", type=str, default=None,
+                   help="LO,HI or LO,HI;LO,HI;... : the band ranges a uint16 --img_lr_path .npy (digital numbers) is normalised "
+                        "with and --out_u16 writes with; default: the DATA_RANGE of the snapshot (a --bit_depth 16 training run)")
+    p.add_argument("--out_u16", action="store_true",
+                   help="write --destination_path as a uint16 .npy of digital numbers (C,H,W) under the band ranges")
     p.add_argument("--clamp", type=str, default=None,
                    help="'none' or 'LO,HI' (--clamp=-1,1 for a negative bound): the range of the returned scene; default 0,1 for "
                         "superres, none for sar_to_ndvi")

@@ -61,6 +61,9 @@ SIGNATURES = {
     "drs_crop_d4_u8": (_I, [_P, _P, _I, _L] + [_I] * 4 + [_P, _P]),
     "drs_crop_d4_u8_f32": (_I, [_P, _P, _P, _I, _L] + [_I] * 4 + [_P, _P, _P]),
     "drs_crop_d4_pairs_f32": (_I, [_P, _P, _P, _I, _L] + [_I] * 5 + [_P, _P, _P]),
+    "drs_hist_u16": (_I, [_P, _L, _I, _I, _I, _I, _P, _P]),
+    "drs_crop_d4_u16_f32": (_I, [_P, _P, _I, _L] + [_I] * 4 + [_P, _I, _P, _P, _P]),
+    "drs_quantize_u16": (_I, [_P, _I, _I, _L, _P, _I, _P, _P]),
     "drs_aggregate_tiles": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "drs_aggregate_tiles_known": (_I, [_P] * 7 + [_I] * 7 + [_F, _F, _P]),
     "drs_gather_tiles": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -249,6 +249,26 @@ def cli_nodata_u8(text):
     return k
 
 
+def cli_nodata_u16(text):
+    """--nodata of a super-resolution command line that also has --bit_depth: an integer K in 0 .. 65535; `check_nodata_depth`
+    holds it to 0 .. 255 once the bit depth is known."""
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} must be an integer in 0 .. 255") from None
+    if not 0 <= k <= 65535:
+        raise argparse.ArgumentTypeError(f"{text!r} must lie in 0 .. 255" if k < 0 else f"{text!r} must lie in 0 .. 65535")
+    return k
+
+
+def check_nodata_depth(p, args):
+    """`p.error`, in `cli_nodata_u8`'s words, for a --nodata above 255 without --bit_depth 16."""
+    k = getattr(args, "nodata", None)
+    if k is not None and k > 255 and int(getattr(args, "bit_depth", 8) or 8) != 16:
+        p.error(f"argument --nodata: {str(k)!r} must lie in 0 .. 255")
+    return args
+
+
 def add_nodata_args(p, in_help=True, u8=False):
     """--nodata of the two conditional trainers and `evaluate`.  `u8`: the super-resolution form, an
     integer pixel value K (the rule value is float32(K) / 255, the bits the u8 feeds produce); otherwise 'nan' or a number.

@@ -24,19 +24,23 @@ line gives CRPS, spread, RMSE of the mean, the spread / skill ratio and the rank
 same samples, colour-corrected against the up-sampled LR image (colorfix.py).
 
 `--nodata V` (sar_to_ndvi: 'nan' or the files' no-data value; superres: the stored byte K in 0 .. 255, as on its trainer - the
-rule value is float32(K) / 255, the bits the uint8 feeds give it) scores every row over the valid pixels of the truth alone and adds the `valid` column, the share of valid pixels;
+rule value is float32(K) / 255, the bits the uint8 feeds give it; with --bit_depth 16 the stored value K in 0 .. 65535) scores every row over the valid pixels of the truth alone and adds the `valid` column, the share of valid pixels;
 for sar_to_ndvi the folder is also read with it (a no-data pixel becomes NaN).  Not with --ensemble or --known_fraction.
 
 `--lr_consistency [--lr_damping D --lr_strength S --lr_blur_radius R]` (superres, DownBlur / DownBlurNoise) samples LR-consistently
 (consistency.py): the `model` row is the projected chain, a `model_free` row the plain chain of the same noise, and every row
 gains `LR RMSE`, the root mean square of (degraded estimate - LR input).  Not with --ensemble or --known_fraction.
+
+`--bit_depth 16 [--data_range ...]` (superres, DownBlur) scores a model trained on 16-bit digital numbers (radiometry.py): the
+validation files are read into a uint16 cache and normalised with the snapshot's band ranges unless --data_range names others.
 """
 import json
 import os
 
 import torch
 
-from .cli import (add_bsr_args, add_consistency_args, add_nodata_args, add_prediction_args, add_solver_args, cli_consistency,
+from .cli import (add_bsr_args, add_consistency_args, add_nodata_args, add_prediction_args, add_solver_args, check_nodata_depth,
+                  cli_consistency, cli_nodata_u16,
                   cli_prediction, cli_sampling_steps, cli_threshold, cli_ztsnr, set_guidance_rescale)
 from .colorfix import add_color_fix_args, cli_color_fix
 from .launcher import launch_device
@@ -130,6 +134,10 @@ def unshuffled(loader):
 
 
 def _superres_setup(args, device, snapshot):
+    from . import radiometry
+    if radiometry.is_u16(radiometry.check_args(args)) and args.data_range is None:
+        # the band ranges the network was trained under (a snapshot without them: the default 0,65535)
+        args.data_range_table = torch.load(snapshot, map_location="cpu").get("DATA_RANGE")
     _, val_loader, _ = make_superres_feeds(args, device)
     ch = args.inp_out_channels
     model = Residual_Attention_UNet_superres(ch, ch, device).to(device)
@@ -159,7 +167,10 @@ def _evaluate_nodata(args, task):
     NaN (the synthetic pairs have none: the value rule stays), so the NaN rule scores it; superres takes the stored byte K and
     compares float32(K) / 255 (`nodata_u8_value`: ValueError under BSRGAN, whose HR image is sharpened)."""
     if task == "superres":
+        from . import radiometry
         from .train_diffusion_superres import nodata_u8_value
+        if radiometry.is_u16(args):  # the 16-bit feed has compared the stored integers with K and marked the truth with NaN
+            return True
         return nodata_u8_value(args.nodata, args.Degradation_type)
     folder = not str(args.dataset_path or "").startswith("synthetic")
     return True if folder else args.nodata
@@ -179,7 +190,11 @@ def cli_arg_parser(task="superres"):
     --color_fix_levels and the BSRGAN feed's --bsr_kind / --bsr_seed."""
     p = add_nodata_args(add_prediction_args(add_solver_args(add_ensemble_args(add_known_args(evaluate_arg_parser(task))))),
                         u8=task == "superres")
-    return add_consistency_args(add_bsr_args(add_color_fix_args(p))) if task == "superres" else p
+    if task != "superres":
+        return p
+    from . import radiometry
+    next(a for a in p._actions if a.dest == "nodata").type = cli_nodata_u16  # (0 .. 255 without --bit_depth 16: `main`)
+    return radiometry.add_radiometry_args(add_consistency_args(add_bsr_args(add_color_fix_args(p))))
 
 
 def main(argv=None):
@@ -209,6 +224,13 @@ def main(argv=None):
         p.error("--ensemble and --known_fraction cannot be combined")
     if args.nodata is not None and (args.ensemble is not None or args.known_fraction is not None):
         p.error("--nodata cannot be combined with --ensemble or --known_fraction")
+    if task == "superres":
+        from . import radiometry
+        check_nodata_depth(p, args)
+        try:
+            radiometry.check_args(args)
+        except ValueError as e:
+            p.error(str(e))
     fix = cli_color_fix(args)
     if fix and (args.ensemble is not None or args.known_fraction is not None):
         p.error("--color_fix cannot be combined with --ensemble or --known_fraction")

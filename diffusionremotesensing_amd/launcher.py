@@ -36,10 +36,10 @@ def make_loaders(args, train_dataset, val_dataset):
 
 
 def train_model(args, diffusion_class, model, device, train_loader, val_loader, train_kwargs=None, nodata=None,
-                **diffusion_kwargs):
+                data_range=None, **diffusion_kwargs):
     """Same weights on every rank, `diffusion_class(...)` from the flags (a snapshot, if there is one, is loaded here),
-    the training run, and the end of the process group.  `nodata`: the Diffusion's attribute of that name (None: left alone).
-    Returns the Diffusion."""
+    the training run, and the end of the process group.  `nodata`, `data_range`: the Diffusion's attributes of those names (None: left
+    alone).  Returns the Diffusion."""
     print("Num params: ", sum(p.numel() for p in model.parameters()))
     if args.multiple_gpus:
         drs_dist.broadcast_module(model)  # what the DDP constructor does in the reference (:658)
@@ -52,6 +52,8 @@ def train_model(args, diffusion_class, model, device, train_loader, val_loader, 
     cli.set_guidance_rescale(diffusion, args)
     if nodata is not None:
         diffusion.nodata = nodata
+    if data_range is not None:
+        diffusion.data_range = data_range
     diffusion.train(lr=args.lr, epochs=args.epochs, check_preds_epoch=args.check_preds_epoch,
                     train_loader=train_loader, val_loader=val_loader, patience=args.patience, loss=args.loss,
                     verbose=True, **cli.train_kwargs(args), **cli.cli_finetune(args), **(train_kwargs or {}))

@@ -123,11 +123,60 @@ def _synthetic_feeds(args, device, spec, makers, r, wsz):
     return train_loader, val_loader, final_lr
 
 
+def _u16_feeds(args, device, spec, r, wsz):
+    """--bit_depth 16 (radiometry.py): `<dataset_path>/train_original` and `/val_original` hold 16-bit files
+    at the cache's size, or `synthetic_u16[:N]` - the `synthetic` HR patches as round(hr * 10000) -, kept as uint16 caches on the
+    device and fed by `DeviceU16SuperresFeed`.  The band ranges are `args.data_range_table` (what `evaluate` read from the
+    snapshot), else --data_range: given, or the percentiles of the training cache, summed over the ranks under --multiple_gpus.
+    Both feeds carry the table as `data_range`."""
+    from . import radiometry as R
+    R.check_args(args)
+    cache_size, ch = scene_size(args), args.inp_out_channels
+    if spec.startswith("synthetic_u16"):
+        length = int(spec.split(":")[1]) if ":" in spec else 4 * args.batch_size
+        sets = [SyntheticSuperresDataset(n, ch, cache_size, args.magnification_factor, seed=s)
+                for n, s in ((length, 1), (max(length // 4, 1), 2))]
+        if min(len(ds) // wsz for ds in sets) == 0:
+            raise ValueError(f"datasets of {[len(ds) for ds in sets]} images cannot be sharded over {wsz} ranks")
+        train, val = (R.synthetic_u16(ds.hr[r::wsz][:len(ds) // wsz]) for ds in sets)
+        first = R.synthetic_u16(sets[0].hr[:5])
+    else:
+        if not os.path.isdir(os.path.join(spec, "train_original")) or not os.path.isdir(os.path.join(spec, "val_original")):
+            raise FileNotFoundError(f"--dataset_path {spec!r}: expected the folders train_original/ and val_original/ "
+                                    "(or synthetic_u16[:N])")
+        train = R.load_folder_u16(os.path.join(spec, "train_original"), cache_size, r, wsz)
+        val = R.load_folder_u16(os.path.join(spec, "val_original"), cache_size, r, wsz)
+        first = R.load_folder_u16(os.path.join(spec, "train_original"), cache_size, limit=5)
+    for what, cache in (("train_original", train), ("val_original", val)):
+        if cache.shape[1] != ch:
+            raise ValueError(f"the images of {what} have {cache.shape[1]} channels, --inp_out_channels is {ch}")
+    train, val, nodata = train.to(device), val.to(device), getattr(args, "nodata", None)
+    table = getattr(args, "data_range_table", None)
+    if table is None:
+        table = R.resolve_range(getattr(args, "data_range", None), train, nodata, all_ranks=bool(args.multiple_gpus))
+    table = R.check_table(table, ch)
+    print(f"16-bit radiometry: band ranges {R.format_table(table)}")
+    radius = args.Blur_radius if args.Blur_radius == "random" else float(args.Blur_radius)
+
+    def make_feed(cache, fixed=False):  # ("random": one draw per feed, as the 8-bit feeds)
+        return R.DeviceU16SuperresFeed(cache, args.magnification_factor, radius, args.batch_size, True, table, nodata,
+                                       **feed_kwargs(args, r, fixed))
+    train_loader, val_loader = make_feed(train), make_feed(val, fixed=True)
+    # the final sampling conditions on the first training images of the WHOLE list (centre windows), blurred as the train feed blurs
+    firsts = R.DeviceU16SuperresFeed(first.to(device), args.magnification_factor, train_loader.blur_radius, 1, False, table, nodata,
+                                     **feed_kwargs(args, fixed=True))
+    return train_loader, val_loader, [firsts.item(i)[0] for i in range(first.shape[0])]
+
+
 def make_superres_feeds(args, device):
     """(train feed, validation feed, the LR images the final sampling conditions on) of `--dataset_path`: the reference's
-    image folder or `synthetic[:N]` / `synthetic_u8[:N]` (see `train_diffusion_superres.launch`)."""
+    image folder or `synthetic[:N]` / `synthetic_u8[:N]` (see `train_diffusion_superres.launch`); with --bit_depth 16 the uint16
+    entrance (`_u16_feeds`)."""
     spec = str(args.dataset_path or "")
     r, wsz = (drs_dist.rank(), drs_dist.world_size()) if args.multiple_gpus else (0, 1)
+    if int(getattr(args, "bit_depth", 8) or 8) == 16 or getattr(args, "data_range", None) is not None or \
+            spec.startswith("synthetic_u16"):
+        return _u16_feeds(args, device, spec, r, wsz)
     makers = None
     if not spec.startswith("synthetic") or spec.startswith("synthetic_u8"):
         build = _bsrgan_feed_makers if args.Degradation_type.lower() == "bsrgan" else _downblur_feed_makers

@@ -25,9 +25,10 @@ import torch.nn as nn
 
 from . import dist as drs_dist
 from . import hip_ops
+from . import radiometry
 from .augment import add_augment_args
 # (the names this module does not use itself are re-exported: they lived here before cli.py, launcher.py and superres_feeds.py)
-from .cli import (OBJECTIVE_DEFAULTS, OPTIM_DEFAULTS, add_bsr_args, add_finetune_args, add_nodata_args, add_objective_args, add_optim_args,  # noqa: F401
+from .cli import (OBJECTIVE_DEFAULTS, OPTIM_DEFAULTS, add_bsr_args, add_finetune_args, add_nodata_args, add_objective_args, add_optim_args, check_nodata_depth, cli_nodata_u16,  # noqa: F401
                   add_prediction_args, add_sampling_args, add_solver_args, add_train_args, base_arg_parser, check_objective_args, check_optim_args,
                   check_train_args, cli_sampling_steps, objective_train_kwargs, optim_train_kwargs, str2bool)
 from .finetune import freeze_parameters, load_init_weights
@@ -105,6 +106,10 @@ class Diffusion:
         # request names another).  Plain attributes like x0_clip, read at the start of every chain, not written into snapshots;
         # the super-resolution sampler only.  DESIGN.md section 28.
         self.lr_consistency, self.blur_radius = None, 0.5
+        # ... and the band ranges of a 16-bit run (None, or the (C, 2) fp32 table (lo_c, hi_c) the uint16 feed normalises with:
+        # radiometry.py).  A plain attribute: written into snapshots and train_state.pt when set, and
+        # `snapshot_data_range` is what the loaded snapshot holds (None: an 8-bit run's file).
+        self.data_range, self.snapshot_data_range = None, None
         self.noise_steps = noise_steps
         self.beta_start = beta_start
         self.beta_end = beta_end
@@ -517,6 +522,8 @@ class Diffusion:
             snapshot["PREDICTION"] = self.prediction
         if self.zero_terminal_snr:  # (likewise: an off run writes what it always wrote)
             snapshot["ZERO_TERMINAL_SNR"] = True
+        if getattr(self, "data_range", None) is not None:  # (likewise: only a 16-bit run)
+            snapshot["DATA_RANGE"] = self._data_range_key(self.data_range)
         torch.save(snapshot, self.snapshot_path)
         print(f"Epoch {epoch} | Training snapshot saved at {self.snapshot_path}")
 
@@ -548,6 +555,22 @@ class Diffusion:
             raise ValueError(f"{self.snapshot_path} holds a network trained with zero_terminal_snr={saved}, this Diffusion was "
                              f"built with zero_terminal_snr={self.zero_terminal_snr}: the two schedules differ at every level "
                              f"({'pass' if saved else 'drop'} --zero_terminal_snr)")
+        self.snapshot_data_range = snapshot.get("DATA_RANGE")
+
+    @staticmethod
+    def _data_range_key(table):
+        """A band-range table as the files keep and compare it: None, or a (C, 2) fp32 host tensor."""
+        return None if table is None else torch.as_tensor(table, dtype=torch.float32).detach().cpu().reshape(-1, 2).clone()
+
+    def _check_data_range(self, saved, where):
+        """ValueError for a run that goes on from a file written under other band ranges than `self.data_range`: its network
+        was trained on other numbers for the same pixels."""
+        mine = self._data_range_key(getattr(self, "data_range", None))
+        if (saved is None) != (mine is None) or (mine is not None and not torch.equal(self._data_range_key(saved), mine)):
+            def text(t):
+                return "none (an 8-bit run)" if t is None else ";".join(f"{lo:g},{hi:g}" for lo, hi in self._data_range_key(t).tolist())
+            raise ValueError(f"{where} was written with --data_range {text(saved)}, this run has {text(mine)}: a resumed run "
+                             "must normalise with the same band ranges")
 
     # -- the rest of a run's state (not in the reference, which marks the gap: LR_SCHEDULER is commented out at :275) --------
     def train_state_path(self):
@@ -572,6 +595,8 @@ class Diffusion:
             ts["ZERO_TERMINAL_SNR"] = True
         if self.nodata is not None:  # (likewise)
             ts["NODATA"] = self._nodata_key(self.nodata)
+        if getattr(self, "data_range", None) is not None:  # (likewise)
+            ts["DATA_RANGE"] = self._data_range_key(self.data_range)
         torch.save(ts, self.train_state_path())
 
     def _load_train_state(self, run):
@@ -593,6 +618,7 @@ class Diffusion:
         if ts.get("NODATA") != self._nodata_key(self.nodata):
             raise ValueError(f"{self.train_state_path()} was written with nodata={ts.get('NODATA')!r}, this run has "
                              f"nodata={self._nodata_key(self.nodata)!r}: a resumed run must mask the same pixels")
+        self._check_data_range(ts.get("DATA_RANGE"), self.train_state_path())
         if run.loss_bins is not None:
             run.loss_bins.load_state_dict(ts["LOSS_BINS"])  # (other T / bin count: ValueError)
         # (another parameter count or other shapes: ValueError from FusedAdamW.load_state_dict, the first thing loaded)
@@ -760,6 +786,9 @@ class Diffusion:
         the run would otherwise use torch's module -, `eval_metrics` scores under the truth's mask, `loss="MSE+Perceptual_noise"`
         raises, and `save_train_state` stores the setting."""
         self._check_nodata(loss)  # (before any weight is loaded or frozen)
+        if os.path.exists(self.snapshot_path) and (getattr(self, "data_range", None) is not None or
+                                                 getattr(self, "snapshot_data_range", None) is not None):
+            self._check_data_range(self.snapshot_data_range, self.snapshot_path)  # (a run that goes on from a snapshot)
         self._prepare_finetune(freeze_bn, freeze, init_from)
         run = self._begin_run(
             loss, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule,
@@ -952,7 +981,10 @@ def launch(args):
     if args.UNet_type.lower() != "residual attention unet":
         raise ValueError("The UNet type must be Residual Attention UNet or Residual MultiHead Attention UNet or "
                          "Residual Visual MultiHeadAttention UNet superres")
-    nodata = nodata_u8_value(getattr(args, "nodata", None), args.Degradation_type)
+    u16 = radiometry.is_u16(radiometry.check_args(args))
+    # a 16-bit run: the feed compares the stored integers with --nodata K and marks the target with NaN (the NaN rule alone)
+    nodata = (None if getattr(args, "nodata", None) is None else True) if u16 else \
+        nodata_u8_value(getattr(args, "nodata", None), args.Degradation_type)
     print("Using multiple GPUs" if args.multiple_gpus else "Using single GPU")
     device = launch_device(args)
     train_loader, val_loader, final_lr = make_superres_feeds(args, device)
@@ -965,7 +997,7 @@ def launch(args):
     if getattr(args, "eval_metrics", 0):
         train_kwargs = {"eval_metrics": args.eval_metrics, "sampling_steps": args.sampling_steps, "eta": args.eta}
     diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader, train_kwargs, nodata=nodata,
-                            magnification_factor=args.magnification_factor, Degradation_type=args.Degradation_type)
+                            **({"data_range": train_loader.data_range} if u16 else {}), magnification_factor=args.magnification_factor, Degradation_type=args.Degradation_type)
     if r != 0:
         return  # one rank samples and writes models_run/<name>/results/superres_results.pt (every rank holds the same weights)
 
@@ -1011,6 +1043,8 @@ def parse_train_args(argv=None):
     add_prediction_args(p, in_help=False)
     add_finetune_args(p)
     add_nodata_args(p, in_help=False, u8=True)
+    radiometry.add_radiometry_args(p, in_help=False)
+    next(a for a in p._actions if a.dest == "nodata").type = cli_nodata_u16  # (0 .. 255 without --bit_depth 16: checked below)
     p.add_argument("--eval_metrics", type=int, default=0,
                    help="score the network on the first N validation images (PSNR / SSIM / SAM / ERGAS against the bicubic "
                         "baseline) at every epoch with epoch %% check_preds_epoch == 0; 0 = off")
@@ -1021,6 +1055,11 @@ def parse_train_args(argv=None):
         p.error("--eval_metrics runs in one process: it cannot be combined with --multiple_gpus")
     if args.nodata is not None and args.Degradation_type.lower() == "bsrgan":
         p.error("--nodata cannot be combined with --Degradation_type BSRGAN: its HR image is sharpened")
+    check_nodata_depth(p, args)
+    try:
+        radiometry.check_args(args)
+    except ValueError as e:
+        p.error(str(e))
     return check_train_args(p, args)
 
 

@@ -676,6 +676,32 @@ DRS_API int drs_crop_d4_u8_f32(const uint8_t* cache_u8, const int64_t* labels, c
 DRS_API int drs_crop_d4_pairs_f32(const float* sar_cache, const float* ndvi_cache, const int32_t* items, int n, int64_t L,
                                   int Cs, int Cn, int H, int W, int S, float* sar_out, float* ndvi_out, drs_stream_t stream);
 
+/* 16-bit radiometry (csrc/radiometry.hip, diffusionremotesensing_amd/radiometry.py): a uint16 scene cache
+ * (L, C, H, W) of digital numbers beside the uint8 one.  range: (C, 2) fp32 on the device, range[c] = (lo_c, hi_c), hi_c > lo_c,
+ * both in 0 .. 65535 (the caller checks); the span hi_c - lo_c is formed once in fp32.  Every step below is one correctly
+ * rounded fp32 operation (no contraction):
+ *   normalise:  x = min(max((float(v) - lo_c) / (hi_c - lo_c), 0), 1)
+ *   quantise:   v = clamp(rint(min(max(x, 0), 1) * (hi_c - lo_c) + lo_c), 0, 65535), rint to even; a NaN x gives `fill`
+ * so quantise(normalise(v)) == v for every v in [lo_c, hi_c].  nodata: -1 (none) or the stored value 0 .. 65535 that marks a
+ * no-data pixel when ALL C bands of the pixel hold it (compared on the integers).  1 <= C <= 16.
+ *   drs_hist_u16:        counts (C, 65536) uint64, zeroed by the entry on `stream`, then the exact number of pixels of band c
+ *                        that hold each value, over the whole cache, no-data pixels left out.  Integer atomics: the result is
+ *                        the same in every run.
+ *   drs_crop_d4_u16_f32: the batch launch of the 16-bit feed: items (n, 4) int32 and the dihedral rule as drs_crop_d4_u8 above;
+ *                        hr (n, C, S, S) fp32 = the normalised windows; hr_marked (NULL: not written) the same values with NaN
+ *                        in all bands of every no-data pixel.  An invalid item reads nothing: zeros in both.
+ *   drs_quantize_u16:    x (n, C, HW) fp32 -> out (n, C, HW) uint16.
+ * Vector accesses only where the address is aligned for them (a uint16 row starts on any 2-byte phase), element-wise otherwise,
+ * with the same bits.  No workspace, no host synchronisation.  DRS_ERR_ARG: null or misaligned pointer, nodata / fill out of range;
+ * DRS_ERR_SHAPE: an extent < 1, C > 16, S > H or W, more than 2^40 elements.  Replaces: none - not in the reference, whose
+ * datasets are 8-bit (`(y * 255).astype(np.uint8)`, utils.py:131-133). */
+DRS_API int drs_hist_u16(const uint16_t* cache_u16, int64_t L, int C, int H, int W, int nodata, uint64_t* counts,
+                         drs_stream_t stream);
+DRS_API int drs_crop_d4_u16_f32(const uint16_t* cache_u16, const int32_t* items, int n, int64_t L, int C, int H, int W, int S,
+                                const float* range, int nodata, float* hr, float* hr_marked, drs_stream_t stream);
+DRS_API int drs_quantize_u16(const float* x, int n, int C, int64_t HW, const float* range, int fill, uint16_t* out,
+                             drs_stream_t stream);
+
 /* The ops of the blind (BSRGAN-plus) degradation feed (csrc/bsr_degrade.hip; recipe and feed in diffusionremotesensing_amd/bsr.py,
  * definitions in DESIGN.md section 19).  Every op is one launch (sharpen and jpeg: two) over a dense (N,C,H,W) fp32 batch, 1 <= C
  * <= 16; per-image parameters are device arrays, so a batch's whole recipe is one upload.  Nothing draws random numbers.
