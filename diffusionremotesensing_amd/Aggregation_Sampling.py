@@ -398,11 +398,16 @@ def launch(args):
         from .train_diffusion_superres import Diffusion
         from .UNet_model_superres import Residual_Attention_UNet_superres
         model = Residual_Attention_UNet_superres(args.inp_out_channels, args.inp_out_channels, device).to(device)
+        # an MTF run (mtf.py): --mtf_nyquist, else the snapshot's MTF_NYQUIST; neither: whatever --Degradation_type says
+        from . import mtf
+        nyquist = mtf.resolve_nyquist(args, snapshot_path, args.inp_out_channels)
+        degradation = {"Degradation_type": args.Degradation_type} if nyquist is None else \
+            {"Degradation_type": "MTF", "mtf_nyquist": nyquist}
         diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot_path,
                               noise_steps=args.noise_steps, beta_start=1e-4, beta_end=0.02,
                               magnification_factor=args.magnification_factor, device=device,
                               image_size=args.model_input_size, model_name=args.model_name,
-                              Degradation_type=args.Degradation_type, multiple_gpus=False, ema_smoothing=False,
+                              multiple_gpus=False, ema_smoothing=False, **degradation,
                               **cli_prediction(args), **cli_threshold(args), **cli_ztsnr(args))
         out_channels = None
     else:
@@ -494,6 +499,8 @@ def build_arg_parser():
                         "whole scene, the tiles' noise predictions blended at every reverse step")
     add_color_fix_args(p)
     add_consistency_args(p)
+    from .mtf import add_mtf_args
+    add_mtf_args(p, noise=False)
     p.add_argument("--known_path", type=str, default=None,
                    help=".pt / .npy scene (C_out,Hs,Ws) whose pixels under --known_mask_path are kept (RePaint)")
     p.add_argument("--known_mask_path", type=str, default=None,

@@ -89,6 +89,10 @@ SIGNATURES = {
     "drs_sep_apply": (_I, [_P] * 4 + [_I] * 6 + [_P, _Z, _P]),
     "drs_sep_project": (_I, [_P] * 7 + [_F, _P] + [_I] * 6 + [_P, _Z, _P]),
     "drs_sep_project_eps": (_I, [_P] * 4 + [_I] + [_P] * 6 + [_F] + [_I] * 6 + [_P, _Z, _P]),
+    "drs_sep_apply_bands": (_I, [_P] * 4 + [_I] * 6 + [_P, _I, _P, _Z, _P]),
+    "drs_sep_project_bands": (_I, [_P] * 7 + [_F, _P] + [_I] * 6 + [_P, _I, _P, _Z, _P]),
+    "drs_sep_project_eps_bands": (_I, [_P] * 4 + [_I] + [_P] * 6 + [_F] + [_I] * 6 + [_P, _I, _P, _Z, _P]),
+    "drs_fir_decimate": (_I, [_P] * 4 + [_I] * 6 + [_P, _P, _I, _P] + [_I] * 6 + [_P]),
     "drs_bsr_blur": (_I, [_P, _P, _P, _P] + [_I] * 5 + [_P]),
     "drs_bsr_blur_sep": (_I, [_P, _P, C.POINTER(_F)] + [_I] * 5 + [_P]),
     "drs_bsr_sharpen": (_I, [_P, _P, _P, C.POINTER(_F), _I, _F, _F] + [_I] * 4 + [_P]),

@@ -169,8 +169,8 @@ def add_consistency_args(p):
     (`cli_consistency`; consistency.py).  Not in the reference, and not on the trainers."""
     p.add_argument("--lr_consistency", type=str2bool, nargs="?", const=True, default=False,
                    help="LR-consistent sampling: project the clean image every reverse step implies (the tiler: also the finished "
-                        "scene) onto the images the DownBlur degradation maps to the LR input; needs --Degradation_type DownBlur "
-                        "or DownBlurNoise")
+                        "scene) onto the images the degradation maps to the LR input; needs --Degradation_type DownBlur or "
+                        "DownBlurNoise, or an MTF run (--mtf_nyquist: each band's own operator)")
     p.add_argument("--lr_damping", type=cli_nonnegative, default=0.01, metavar="D",
                    help="with --lr_consistency: the Tikhonov damping of the projection's gain (0: the exact pseudo-inverse, "
                         "refused for an ill-conditioned blur); default 0.01")

@@ -4,7 +4,8 @@ degradation maps to the observation (DDNM, Wang et al. 2023; DESIGN.md section 2
 `SeparableOperator` holds the two float64 matrices of x -> A_y x A_x^T - `downblur` is the trainer's degradation without its
 roundings - and makes an `LRProjector`, whose fp32 device tensors the kernels of csrc/consistency.hip take (`degrade`, `project`,
 `lr_rmse` here; `hip_ops.lr_consistent_eps_` inside a chain).  `LRConsistency` is the request a `Diffusion`, the tiler and
-`evaluate` take; `chain_projector` resolves it for a chain."""
+`evaluate` take; `chain_projector` resolves it for a chain.  `BandOperator` is one `SeparableOperator` per band - the sensor-MTF
+degradation's (`SeparableOperator.mtf`, mtf.py) - with the same surface and stacked device tensors."""
 import math
 import numbers
 
@@ -119,6 +120,17 @@ class SeparableOperator:
             raise ValueError(f"box: {H}x{W} is no multiple of m={m}")
         return cls(np.kron(np.eye(H // m), np.full((1, m), 1.0 / m)), np.kron(np.eye(W // m), np.full((1, m), 1.0 / m)))
 
+    @classmethod
+    def mtf(cls, size_hw, m, g, lr_hw=None):
+        """The sensor-MTF degradation of an (H, W) band (mtf.py): the Gaussian of gain `g` at the LR Nyquist
+        frequency and decimation by m, replicated edges, as the dense matrices of its fp32 taps.  The LR size is (H // m, W // m),
+        not swapped, unless `lr_hw` names it."""
+        from . import mtf as _mtf
+        m = _mtf._check_factor(m, "m")
+        taps, left = _mtf.gaussian_taps(g, m)
+        h, w = _mtf.lr_shape(size_hw, m, lr_hw)
+        return cls(_mtf.dense_axis(size_hw[0], h, taps, left, m), _mtf.dense_axis(size_hw[1], w, taps, left, m))
+
     @property
     def hr_shape(self):
         return self.A_y.shape[1], self.A_x.shape[1]
@@ -166,19 +178,87 @@ class SeparableOperator:
         return self._projectors[key]
 
 
+MAX_OPERATORS = 16  # the band table of the kernels
+
+
+class BandOperator:
+    """One `SeparableOperator` per band: up to 16 operators of one shape and, for each of the C bands, the index of the one it
+    uses.  It has the surface of a `SeparableOperator` on (.., C, H, W) images; its device tensors carry a leading n_ops axis
+    and go to the *_bands entries with `band_op` (include/drs_hip.h)."""
+
+    def __init__(self, operators, band_op):
+        self.operators = list(operators)
+        if not 1 <= len(self.operators) <= MAX_OPERATORS or not all(isinstance(o, SeparableOperator) for o in self.operators):
+            raise ValueError(f"BandOperator needs 1 .. {MAX_OPERATORS} SeparableOperators")
+        if any(o.hr_shape != self.operators[0].hr_shape or o.lr_shape != self.operators[0].lr_shape for o in self.operators):
+            raise ValueError("BandOperator: the operators differ in shape")
+        try:
+            self.band_op = [int(b) for b in band_op]
+        except (TypeError, ValueError):
+            raise ValueError(f"BandOperator: band_op={band_op!r} must list one operator index per band") from None
+        if not len(self.operators) <= len(self.band_op) <= MAX_OPERATORS:
+            raise ValueError(f"BandOperator: {len(self.band_op)} bands for {len(self.operators)} operators (need n_ops <= bands <= "
+                             f"{MAX_OPERATORS})")
+        if min(self.band_op) < 0 or max(self.band_op) >= len(self.operators):
+            raise ValueError(f"BandOperator: band_op={self.band_op} names an operator outside 0 .. {len(self.operators) - 1}")
+        self._device, self._projectors = {}, {}
+
+    @classmethod
+    def mtf(cls, size_hw, m, gains, lr_hw=None):
+        """One MTF operator per distinct gain of `gains` (C values); bands with equal gains share it (and its SVD)."""
+        gains = [float(g) for g in gains]
+        distinct = sorted(set(gains), key=gains.index)  # (the order of mtf.band_taps: the FIR's rows and these operators pair up)
+        return cls([SeparableOperator.mtf(size_hw, m, g, lr_hw) for g in distinct], [distinct.index(g) for g in gains])
+
+    @property
+    def bands(self):
+        return len(self.band_op)
+
+    @property
+    def hr_shape(self):
+        return self.operators[0].hr_shape
+
+    @property
+    def lr_shape(self):
+        return self.operators[0].lr_shape
+
+    def apply(self, x):
+        """Band c of x (.., C, H, W) through its own operator, in float64 numpy."""
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim < 3 or x.shape[-3] != self.bands:
+            raise ValueError(f"BandOperator.apply: x {x.shape} does not have {self.bands} bands")
+        return np.stack([self.operators[o].apply(x[..., c, :, :]) for c, o in enumerate(self.band_op)], axis=-3)
+
+    def matrices(self, device):
+        """(A_y (n_ops, h, H), A_x (n_ops, w, W)) as fp32 tensors on `device`, made once."""
+        device = torch.device(device)
+        if device not in self._device:
+            self._device[device] = tuple(torch.from_numpy(np.stack([getattr(o, k) for o in self.operators])).to(torch.float32)
+                                         .to(device).contiguous() for k in ("A_y", "A_x"))
+        return self._device[device]
+
+    def factors(self, damping=0.01):
+        """`SeparableOperator.factors` of every operator, each key stacked along a leading n_ops axis."""
+        per = [o.factors(damping) for o in self.operators]
+        return {k: np.stack([f[k] for f in per]) for k in per[0]}
+
+    projector = SeparableOperator.projector
+
+
 class LRProjector:
     """The fp32 device tensors of the projection X' = X + strength U_y (G o (Yt - D_y X D_x^T)) U_x^T of `operator`, from its
     per-axis SVDs computed once in float64: D_y (h, H), D_x (w, W), U_y (H, h), U_x (W, w), G (h, w) and, for `prepare`,
-    P_y^T (h, h) and P_x^T (w, w)."""
+    P_y^T (h, h) and P_x^T (w, w).  Of a `BandOperator`: each with a leading n_ops axis, and `band_op`, the operator of each band."""
 
     def __init__(self, operator, damping=0.01, device="cuda"):
         f = operator.factors(damping)
         self.operator, self.damping, self.device = operator, float(damping), torch.device(device)
+        self.band_op = getattr(operator, "band_op", None)
 
         def dev(a):
             return torch.from_numpy(np.ascontiguousarray(a)).to(torch.float32).to(self.device).contiguous()
         self.D_y, self.D_x, self.U_y, self.U_x, self.G = (dev(f[k]) for k in ("D_y", "D_x", "U_y", "U_x", "G"))
-        self.Pt_y, self.Pt_x = dev(f["P_y"].T), dev(f["P_x"].T)
+        self.Pt_y, self.Pt_x = dev(np.swapaxes(f["P_y"], -1, -2)), dev(np.swapaxes(f["P_x"], -1, -2))
 
     @property
     def hr_shape(self):
@@ -192,7 +272,11 @@ class LRProjector:
         """Yt = P_y^T y P_x per plane of the observation y (B, C, h, w): made once per chain."""
         if tuple(y.shape[-2:]) != self.lr_shape:
             raise ValueError(f"the observation is {tuple(y.shape[-2:])}, the operator maps to {self.lr_shape}")
-        return hip_ops.sep_apply(y, self.Pt_y, self.Pt_x)
+        if self.band_op is None:
+            return hip_ops.sep_apply(y, self.Pt_y, self.Pt_x)
+        if y.shape[1] != len(self.band_op):
+            raise ValueError(f"the observation has {y.shape[1]} bands, the operator {len(self.band_op)}")
+        return hip_ops.sep_apply(y, self.Pt_y, self.Pt_x, band_op=self.band_op)
 
 
 class LRConsistency:
@@ -207,8 +291,8 @@ class LRConsistency:
             raise ValueError(f"blur_radius={blur_radius!r} must be None or a number >= 0")
         if isinstance(damping, bool) or not isinstance(damping, numbers.Real) or not (math.isfinite(damping) and damping >= 0):
             raise ValueError(f"damping={damping!r} must be a finite number >= 0")
-        if operator is not None and not isinstance(operator, SeparableOperator):
-            raise ValueError("operator must be a SeparableOperator")
+        if operator is not None and not isinstance(operator, (SeparableOperator, BandOperator)):
+            raise ValueError("operator must be a SeparableOperator or a BandOperator")
         self.blur_radius = None if blur_radius is None else float(blur_radius)
         self.damping, self.strength, self.operator = float(damping), _check_strength(strength), operator
 
@@ -231,21 +315,34 @@ class LRConsistency:
             if self.operator.hr_shape != tuple(size_hw):
                 raise ValueError(f"lr_consistency: the operator takes {self.operator.hr_shape} images, the chain's are {tuple(size_hw)}")
             return self.operator
-        return SeparableOperator.downblur(size_hw, diffusion.magnification_factor, self.check_for(diffusion), lr_hw)
+        what = self.check_for(diffusion)
+        if isinstance(what, tuple):  # an MTF diffusion: its per-band gains
+            return BandOperator.mtf(size_hw, diffusion.magnification_factor, what, lr_hw)
+        return SeparableOperator.downblur(size_hw, diffusion.magnification_factor, what, lr_hw)
 
     def check_for(self, diffusion):
-        """ValueError where `diffusion` gives the request no operator (BSRGAN, a "random" radius); the blur radius, or None
-        with an explicit operator.  Cheap: `sample_chain` asks before the engine is touched."""
+        """ValueError where `diffusion` gives the request no operator (BSRGAN, a "random" radius); the blur radius - for an MTF
+        diffusion the tuple of its per-band Nyquist gains -, or None with an explicit operator.  Cheap: `sample_chain` asks
+        before the engine is touched."""
         if self.operator is not None:
             return None
         kind = str(getattr(diffusion, "Degradation_type", "DownBlur")).lower()
+        if kind == "mtf":
+            if self.blur_radius is not None:
+                raise ValueError("lr_consistency: blur_radius belongs to the DownBlur operator; an MTF diffusion's operator comes from "
+                                 "its mtf_nyquist")
+            gains = getattr(diffusion, "mtf_nyquist", None)
+            if gains is None:
+                raise ValueError("lr_consistency: the MTF diffusion has no mtf_nyquist")
+            return tuple(float(g) for g in gains)
         if kind not in ("downblur", "downblurnoise"):
-            raise ValueError(f"lr_consistency needs Degradation_type DownBlur or DownBlurNoise (got {kind!r}: no linear operator "
+            raise ValueError(f"lr_consistency needs Degradation_type DownBlur, DownBlurNoise or MTF (got {kind!r}: no linear operator "
                              "describes it); pass LRConsistency(operator=...) to name one")
         return self.radius_for(diffusion)
 
 
-_OPERATORS = {}  # (H, W, m, radius) -> the DownBlur operator of the chains of that size (each keeps its projectors)
+# (H, W, m, radius | the tuple of MTF gains) -> the diffusion's own operator of the chains of that size (each keeps its projectors)
+_OPERATORS = {}
 
 
 def check_lr_consistency(request):
@@ -276,7 +373,12 @@ def degrade(x, op):
     _planes(x, "degrade: x")
     if tuple(x.shape[-2:]) != op.hr_shape:
         raise ValueError(f"degrade: x is {tuple(x.shape[-2:])}, the operator takes {op.hr_shape}")
-    return hip_ops.sep_apply(x, *op.matrices(x.device))
+    band_op = getattr(op, "band_op", None)
+    if band_op is None:
+        return hip_ops.sep_apply(x, *op.matrices(x.device))
+    if x.shape[1] != len(band_op):
+        raise ValueError(f"degrade: x has {x.shape[1]} bands, the operator {len(band_op)}")
+    return hip_ops.sep_apply(x, *op.matrices(x.device), band_op=band_op)
 
 
 def project(x0, y, projector, strength=1.0, out=None):

@@ -12,6 +12,9 @@
 // operands, so two calls give the same bits.  A lane's four consecutive k of an operand row are one 16-byte load when the
 // pointer, the row length and the plane stride allow it and four 4-byte loads otherwise: the same elements reach the same MFMA
 // in the same order, so an unaligned pointer changes no bit.  The intermediates live in the workspace (T1^T and T2^T share it).
+// Per-band operators: D, U and G may be stacks of n_ops operators; a plane takes the matrix operand and
+// the gain of slot op[plane % bands], a 16-byte table in the kernel arguments.  One operator is slot 0 for every band: the same
+// addresses, tiles and MFMA order as before the table existed, so the one-operator entries keep their bits.
 #include "drs_common.h"
 
 namespace {
@@ -23,18 +26,19 @@ enum { EPI_STORE = 0, EPI_RESID = 1, EPI_ADD = 2, EPI_EPS = 3 };
 constexpr int kTile = 64;  // a block's tile of C: 4 waves of 32 x 32, each 2 x 2 MFMA tiles
 
 struct SepArgs {
-  const float* A;   // M x K, row-major; a_plane floats between planes (0: one matrix for all)
+  const float* A;   // M x K, row-major; a_plane floats between planes (0: one matrix per operator slot, a_slot floats apart)
   const float* B;   // N x K
   const float* B2;  // LOAD_X0: eps beside the state B
   float* C;         // M x N
   const float* E1;  // EPI_RESID: Yt; EPI_ADD: X - laid out as C
-  const float* E2;  // EPI_RESID: the gain, one M x N matrix
+  const float* E2;  // EPI_RESID: the gain, one M x N matrix per operator slot
   const int64_t* t;
   const float* alpha_hat;
-  int64_t a_plane, b_plane, c_plane;
+  int64_t a_plane, a_slot, b_plane, c_plane;
   int M, N, K, planes, bands, noise_steps;
   float strength;
   bool a_vec, b_vec;
+  signed char op[kMaxBands];  // the operator slot of each band (all 0: one operator)
 };
 
 // elements k .. k + 3 of a row of K (zero past the end and for a row outside the matrix); `vec`: k % 4 == K % 4 == 0, 16-byte aligned
@@ -75,7 +79,8 @@ __global__ __launch_bounds__(256) void sep_gemm_kernel(const SepArgs p) {
         ce = (float)(a / s * (double)p.strength);
       }
     }
-    const float* A = p.A + (int64_t)pl * p.a_plane;
+    const int slot = p.op[pl % p.bands];
+    const float* A = p.A + (int64_t)pl * p.a_plane + (int64_t)slot * p.a_slot;
     const float* B = p.B + (int64_t)pl * p.b_plane;
     const float* B2 = LOAD == LOAD_X0 ? p.B2 + (int64_t)pl * p.b_plane : nullptr;
     const float* arow[2];
@@ -117,6 +122,7 @@ __global__ __launch_bounds__(256) void sep_gemm_kernel(const SepArgs p) {
     // lane (r, q) holds C[m0 + 16 i + 4 q + e][n0 + 16 j + r] in acc[i][j][e]
     float* Cp = p.C + (int64_t)pl * p.c_plane;
     const float* E1 = (EPI == EPI_RESID || EPI == EPI_ADD) ? p.E1 + (int64_t)pl * p.c_plane : nullptr;
+    const float* E2 = EPI == EPI_RESID ? p.E2 + (int64_t)slot * p.c_plane : nullptr;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -134,7 +140,7 @@ __global__ __launch_bounds__(256) void sep_gemm_kernel(const SepArgs p) {
               o = v;
             } else if (EPI == EPI_RESID) {
               const float d = E1[at] - v;
-              o = p.E2[at] * d;
+              o = E2[at] * d;
             } else if (EPI == EPI_ADD) {
               const float d = p.strength * v;
               o = E1[at] + d;
@@ -152,14 +158,31 @@ bool vec_ok(const float* ptr, int K, int64_t plane) { return aligned16(ptr) && K
 
 template <int LOAD, int EPI>
 void launch(SepArgs a, hipStream_t stream) {
-  a.a_vec = vec_ok(a.A, a.K, a.a_plane);
+  a.a_vec = vec_ok(a.A, a.K, a.a_plane) && a.a_slot % 4 == 0;
   a.b_vec = vec_ok(a.B, a.K, a.b_plane) && (LOAD != LOAD_X0 || vec_ok(a.B2, a.K, a.b_plane));
   const dim3 grid((unsigned)drs_cdiv(a.N, kTile), (unsigned)drs_cdiv(a.M, kTile), (unsigned)std::min(a.planes, 65535));
   DRS_LAUNCH((sep_gemm_kernel<LOAD, EPI>), grid, dim3(256), 0, stream, a);
 }
 
+// the operator slot of every band: band_op as the caller gave it (host memory), or band b -> min(b, n_ops - 1)
+struct BandSlots {
+  signed char op[kMaxBands];
+};
+
+int check_slots(const char* what, int c, const int32_t* band_op, int n_ops, BandSlots* slots) {
+  DRS_REQUIRE(n_ops >= 1 && n_ops <= c, DRS_ERR_SHAPE, "%s: n_ops=%d outside 1 .. c=%d", what, n_ops, c);
+  *slots = BandSlots{};
+  for (int b = 0; b < c; ++b) {
+    const int op = band_op ? band_op[b] : std::min(b, n_ops - 1);
+    DRS_REQUIRE(op >= 0 && op < n_ops, DRS_ERR_SHAPE, "%s: band_op[%d]=%d outside 0 .. n_ops-1=%d", what, b, op, n_ops - 1);
+    slots->op[b] = (signed char)op;
+  }
+  return DRS_OK;
+}
+
 struct SepShape {
   int n, c, H, W, h, w;
+  BandSlots slots;  // (all 0 until check_slots fills it)
   int planes() const { return n * c; }
   int64_t t_floats() const { return (int64_t)planes() * std::max((int64_t)w * H, (int64_t)W * h); }
   int64_t r_floats() const { return (int64_t)planes() * h * w; }
@@ -192,10 +215,11 @@ void run_down(const SepShape& s, const float* x, const float* eps, const int64_t
               const float* d_y, const float* d_x, const float* yt, const float* gain, float* t1, float* c2, hipStream_t stream) {
   SepArgs a = {};
   a.planes = s.planes(); a.bands = s.c; a.t = t; a.alpha_hat = alpha_hat; a.noise_steps = noise_steps; a.strength = 0.f;
-  a.A = d_x; a.a_plane = 0; a.B = x; a.B2 = eps; a.b_plane = (int64_t)s.H * s.W;
+  std::copy(s.slots.op, s.slots.op + kMaxBands, a.op);
+  a.A = d_x; a.a_plane = 0; a.a_slot = (int64_t)s.w * s.W; a.B = x; a.B2 = eps; a.b_plane = (int64_t)s.H * s.W;
   a.C = t1; a.c_plane = (int64_t)s.w * s.H; a.M = s.w; a.N = s.H; a.K = s.W;
   launch<LOAD, EPI_STORE>(a, stream);
-  a.A = d_y; a.B = t1; a.B2 = nullptr; a.b_plane = (int64_t)s.w * s.H;
+  a.A = d_y; a.a_slot = (int64_t)s.h * s.H; a.B = t1; a.B2 = nullptr; a.b_plane = (int64_t)s.w * s.H;
   a.C = c2; a.c_plane = (int64_t)s.h * s.w; a.M = s.h; a.N = s.w; a.K = s.H;
   a.E1 = yt; a.E2 = gain;
   launch<LOAD_PLAIN, EPI>(a, stream);
@@ -207,10 +231,11 @@ void run_up(const SepShape& s, const float* r, const float* u_y, const float* u_
             const int64_t* t, const float* alpha_hat, int noise_steps, float* t2, hipStream_t stream) {
   SepArgs a = {};
   a.planes = s.planes(); a.bands = s.c; a.t = t; a.alpha_hat = alpha_hat; a.noise_steps = noise_steps; a.strength = strength;
-  a.A = u_x; a.a_plane = 0; a.B = r; a.b_plane = (int64_t)s.h * s.w;
+  std::copy(s.slots.op, s.slots.op + kMaxBands, a.op);
+  a.A = u_x; a.a_plane = 0; a.a_slot = (int64_t)s.W * s.w; a.B = r; a.b_plane = (int64_t)s.h * s.w;
   a.C = t2; a.c_plane = (int64_t)s.W * s.h; a.M = s.W; a.N = s.h; a.K = s.w;
   launch<LOAD_PLAIN, EPI_STORE>(a, stream);
-  a.A = u_y; a.B = t2; a.b_plane = (int64_t)s.W * s.h;
+  a.A = u_y; a.a_slot = (int64_t)s.H * s.h; a.B = t2; a.b_plane = (int64_t)s.W * s.h;
   a.C = out; a.c_plane = (int64_t)s.H * s.W; a.M = s.H; a.N = s.W; a.K = s.h;
   a.E1 = x;
   launch<LOAD_PLAIN, EPI>(a, stream);
@@ -224,29 +249,33 @@ extern "C" size_t drs_sep_workspace_bytes(int n, int c, int H, int W, int h, int
   return (size_t)(s.t_floats() + s.r_floats()) * sizeof(float) + 16;
 }
 
-extern "C" int drs_sep_apply(const float* x, const float* d_y, const float* d_x, float* out, int n, int c, int H, int W, int h,
-                             int w, void* workspace, size_t workspace_bytes, drs_stream_t stream) {
-  const SepShape s{n, c, H, W, h, w};
-  DRS_REQUIRE(x && d_y && d_x && out, DRS_ERR_ARG, "sep_apply: null pointer");
-  if (int st = check_shape("sep_apply", s)) return st;
-  if (int st = check_workspace("sep_apply", s, workspace, workspace_bytes)) return st;
+
+namespace {
+
+int apply_bands(const char* what, const float* x, const float* d_y, const float* d_x, float* out, SepShape s,
+                const int32_t* band_op, int n_ops, void* workspace, size_t workspace_bytes, drs_stream_t stream) {
+  DRS_REQUIRE(x && d_y && d_x && out, DRS_ERR_ARG, "%s: null pointer", what);
+  if (int st = check_shape(what, s)) return st;
+  if (int st = check_slots(what, s.c, band_op, n_ops, &s.slots)) return st;
+  if (int st = check_workspace(what, s, workspace, workspace_bytes)) return st;
   run_down<LOAD_PLAIN, EPI_STORE>(s, x, nullptr, nullptr, nullptr, 0, d_y, d_x, nullptr, nullptr, ws_base(workspace), out,
                                   (hipStream_t)stream);
   DRS_CHECK_HIP(hipGetLastError());
   return DRS_OK;
 }
 
-extern "C" int drs_sep_project(const float* x, const float* yt, const float* d_y, const float* d_x, const float* u_y,
-                               const float* u_x, const float* gain, float strength, float* out, int n, int c, int H, int W,
-                               int h, int w, void* workspace, size_t workspace_bytes, drs_stream_t stream) {
-  const SepShape s{n, c, H, W, h, w};
-  DRS_REQUIRE(x && yt && d_y && d_x && u_y && u_x && gain && out, DRS_ERR_ARG, "sep_project: null pointer");
-  DRS_REQUIRE(std::isfinite(strength), DRS_ERR_ARG, "sep_project: strength=%g must be finite", (double)strength);
-  if (int st = check_shape("sep_project", s)) return st;
-  if (int st = check_workspace("sep_project", s, workspace, workspace_bytes)) return st;
+int project_bands(const char* what, const float* x, const float* yt, const float* d_y, const float* d_x, const float* u_y,
+                  const float* u_x, const float* gain, float strength, float* out, SepShape s, const int32_t* band_op, int n_ops,
+                  void* workspace, size_t workspace_bytes, drs_stream_t stream) {
+  DRS_REQUIRE(x && yt && d_y && d_x && u_y && u_x && gain && out, DRS_ERR_ARG, "%s: null pointer", what);
+  DRS_REQUIRE(std::isfinite(strength), DRS_ERR_ARG, "%s: strength=%g must be finite", what, (double)strength);
+  if (int st = check_shape(what, s)) return st;
+  if (int st = check_slots(what, s.c, band_op, n_ops, &s.slots)) return st;
+  if (int st = check_workspace(what, s, workspace, workspace_bytes)) return st;
   hipStream_t hs = (hipStream_t)stream;
   if (strength == 0.f) {  // the identity, bit for bit
-    if (out != x) DRS_CHECK_HIP(hipMemcpyAsync(out, x, (size_t)s.planes() * H * W * sizeof(float), hipMemcpyDeviceToDevice, hs));
+    if (out != x)
+      DRS_CHECK_HIP(hipMemcpyAsync(out, x, (size_t)s.planes() * s.H * s.W * sizeof(float), hipMemcpyDeviceToDevice, hs));
     return DRS_OK;
   }
   float* tbuf = ws_base(workspace);
@@ -257,17 +286,17 @@ extern "C" int drs_sep_project(const float* x, const float* yt, const float* d_y
   return DRS_OK;
 }
 
-extern "C" int drs_sep_project_eps(float* eps, const float* x, const int64_t* t, const float* alpha_hat, int noise_steps,
-                                   const float* yt, const float* d_y, const float* d_x, const float* u_y, const float* u_x,
-                                   const float* gain, float strength, int n, int c, int H, int W, int h, int w, void* workspace,
-                                   size_t workspace_bytes, drs_stream_t stream) {
-  const SepShape s{n, c, H, W, h, w};
-  DRS_REQUIRE(eps && x && t && alpha_hat && yt && d_y && d_x && u_y && u_x && gain, DRS_ERR_ARG, "sep_project_eps: null pointer");
-  DRS_REQUIRE(noise_steps >= 1, DRS_ERR_ARG, "sep_project_eps: noise_steps=%d", noise_steps);
-  DRS_REQUIRE(std::isfinite(strength), DRS_ERR_ARG, "sep_project_eps: strength=%g must be finite", (double)strength);
-  DRS_REQUIRE(eps != x, DRS_ERR_ARG, "sep_project_eps: eps and x are one buffer");
-  if (int st = check_shape("sep_project_eps", s)) return st;
-  if (int st = check_workspace("sep_project_eps", s, workspace, workspace_bytes)) return st;
+int project_eps_bands(const char* what, float* eps, const float* x, const int64_t* t, const float* alpha_hat, int noise_steps,
+                      const float* yt, const float* d_y, const float* d_x, const float* u_y, const float* u_x, const float* gain,
+                      float strength, SepShape s, const int32_t* band_op, int n_ops, void* workspace, size_t workspace_bytes,
+                      drs_stream_t stream) {
+  DRS_REQUIRE(eps && x && t && alpha_hat && yt && d_y && d_x && u_y && u_x && gain, DRS_ERR_ARG, "%s: null pointer", what);
+  DRS_REQUIRE(noise_steps >= 1, DRS_ERR_ARG, "%s: noise_steps=%d", what, noise_steps);
+  DRS_REQUIRE(std::isfinite(strength), DRS_ERR_ARG, "%s: strength=%g must be finite", what, (double)strength);
+  DRS_REQUIRE(eps != x, DRS_ERR_ARG, "%s: eps and x are one buffer", what);
+  if (int st = check_shape(what, s)) return st;
+  if (int st = check_slots(what, s.c, band_op, n_ops, &s.slots)) return st;
+  if (int st = check_workspace(what, s, workspace, workspace_bytes)) return st;
   if (strength == 0.f) return DRS_OK;  // eps keeps its bits
   hipStream_t hs = (hipStream_t)stream;
   float* tbuf = ws_base(workspace);
@@ -276,4 +305,51 @@ extern "C" int drs_sep_project_eps(float* eps, const float* x, const int64_t* t,
   run_up<EPI_EPS>(s, rbuf, u_y, u_x, strength, nullptr, eps, t, alpha_hat, noise_steps, tbuf, hs);
   DRS_CHECK_HIP(hipGetLastError());
   return DRS_OK;
+}
+
+}  // namespace
+
+extern "C" int drs_sep_apply_bands(const float* x, const float* d_y, const float* d_x, float* out, int n, int c, int H, int W,
+                                   int h, int w, const int32_t* band_op, int n_ops, void* workspace, size_t workspace_bytes,
+                                   drs_stream_t stream) {
+  return apply_bands("sep_apply_bands", x, d_y, d_x, out, SepShape{n, c, H, W, h, w}, band_op, n_ops, workspace, workspace_bytes,
+                     stream);
+}
+
+extern "C" int drs_sep_project_bands(const float* x, const float* yt, const float* d_y, const float* d_x, const float* u_y,
+                                     const float* u_x, const float* gain, float strength, float* out, int n, int c, int H, int W,
+                                     int h, int w, const int32_t* band_op, int n_ops, void* workspace, size_t workspace_bytes,
+                                     drs_stream_t stream) {
+  return project_bands("sep_project_bands", x, yt, d_y, d_x, u_y, u_x, gain, strength, out, SepShape{n, c, H, W, h, w}, band_op,
+                       n_ops, workspace, workspace_bytes, stream);
+}
+
+extern "C" int drs_sep_project_eps_bands(float* eps, const float* x, const int64_t* t, const float* alpha_hat, int noise_steps,
+                                         const float* yt, const float* d_y, const float* d_x, const float* u_y, const float* u_x,
+                                         const float* gain, float strength, int n, int c, int H, int W, int h, int w,
+                                         const int32_t* band_op, int n_ops, void* workspace, size_t workspace_bytes,
+                                         drs_stream_t stream) {
+  return project_eps_bands("sep_project_eps_bands", eps, x, t, alpha_hat, noise_steps, yt, d_y, d_x, u_y, u_x, gain, strength,
+                           SepShape{n, c, H, W, h, w}, band_op, n_ops, workspace, workspace_bytes, stream);
+}
+
+// one operator for all bands: the calls above with n_ops = 1
+extern "C" int drs_sep_apply(const float* x, const float* d_y, const float* d_x, float* out, int n, int c, int H, int W, int h,
+                             int w, void* workspace, size_t workspace_bytes, drs_stream_t stream) {
+  return apply_bands("sep_apply", x, d_y, d_x, out, SepShape{n, c, H, W, h, w}, nullptr, 1, workspace, workspace_bytes, stream);
+}
+
+extern "C" int drs_sep_project(const float* x, const float* yt, const float* d_y, const float* d_x, const float* u_y,
+                               const float* u_x, const float* gain, float strength, float* out, int n, int c, int H, int W,
+                               int h, int w, void* workspace, size_t workspace_bytes, drs_stream_t stream) {
+  return project_bands("sep_project", x, yt, d_y, d_x, u_y, u_x, gain, strength, out, SepShape{n, c, H, W, h, w}, nullptr, 1,
+                       workspace, workspace_bytes, stream);
+}
+
+extern "C" int drs_sep_project_eps(float* eps, const float* x, const int64_t* t, const float* alpha_hat, int noise_steps,
+                                   const float* yt, const float* d_y, const float* d_x, const float* u_y, const float* u_x,
+                                   const float* gain, float strength, int n, int c, int H, int W, int h, int w, void* workspace,
+                                   size_t workspace_bytes, drs_stream_t stream) {
+  return project_eps_bands("sep_project_eps", eps, x, t, alpha_hat, noise_steps, yt, d_y, d_x, u_y, u_x, gain, strength,
+                           SepShape{n, c, H, W, h, w}, nullptr, 1, workspace, workspace_bytes, stream);
 }

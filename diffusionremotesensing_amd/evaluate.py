@@ -138,13 +138,19 @@ def _superres_setup(args, device, snapshot):
     if radiometry.is_u16(radiometry.check_args(args)) and args.data_range is None:
         # the band ranges the network was trained under (a snapshot without them: the default 0,65535)
         args.data_range_table = torch.load(snapshot, map_location="cpu").get("DATA_RANGE")
-    _, val_loader, _ = make_superres_feeds(args, device)
     ch = args.inp_out_channels
+    # an MTF run (mtf.py): --mtf_nyquist, else the snapshot's MTF_NYQUIST; neither: whatever --Degradation_type says
+    from . import mtf
+    nyquist = mtf.resolve_nyquist(args, snapshot, ch)
+    if nyquist is not None:
+        args.Degradation_type, args.mtf_nyquist = "MTF", ",".join(repr(g) for g in nyquist)
+    mtf.check_args(args)
+    _, val_loader, _ = make_superres_feeds(args, device)
     model = Residual_Attention_UNet_superres(ch, ch, device).to(device)
     diffusion = Diffusion(noise_schedule=args.noise_schedule, model=model, snapshot_path=snapshot,
                           noise_steps=args.noise_steps, device=device, magnification_factor=args.magnification_factor,
                           image_size=args.image_size, model_name=args.model_name, Degradation_type=args.Degradation_type,
-                          **cli_prediction(args), **cli_threshold(args), **cli_ztsnr(args))
+                          **mtf.diffusion_kwargs(args), **cli_prediction(args), **cli_threshold(args), **cli_ztsnr(args))
     return model, set_guidance_rescale(diffusion, args), val_loader
 
 
@@ -192,9 +198,9 @@ def cli_arg_parser(task="superres"):
                         u8=task == "superres")
     if task != "superres":
         return p
-    from . import radiometry
+    from . import mtf, radiometry
     next(a for a in p._actions if a.dest == "nodata").type = cli_nodata_u16  # (0 .. 255 without --bit_depth 16: `main`)
-    return radiometry.add_radiometry_args(add_consistency_args(add_bsr_args(add_color_fix_args(p))))
+    return mtf.add_mtf_args(radiometry.add_radiometry_args(add_consistency_args(add_bsr_args(add_color_fix_args(p)))), noise=False)
 
 
 def main(argv=None):

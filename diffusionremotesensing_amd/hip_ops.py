@@ -955,41 +955,70 @@ def _req_matrix(op, m, name, shape):
     return m
 
 
-def sep_apply(x, d_y, d_x):
+
+
+def _band_table(op, band_op, n_ops, Cn):
+    """The host int32 table the *_bands entries take: `band_op` (Cn slots in 0 .. n_ops - 1), or None for the entries' default."""
+    if not 1 <= n_ops <= Cn:
+        raise RuntimeError(f"{op}: {n_ops} operators for {Cn} bands (need 1 .. the band count)")
+    if band_op is None:
+        return None
+    band_op = [int(b) for b in band_op]
+    if len(band_op) != Cn or min(band_op) < 0 or max(band_op) >= n_ops:
+        raise RuntimeError(f"{op}: band_op={band_op} must name one of the {n_ops} operators for each of the {Cn} bands")
+    return (C.c_int32 * Cn)(*band_op)
+
+
+def sep_apply(x, d_y, d_x, band_op=None):
     """d_y x d_x^T per plane of x (B, C, H, W) for matrices d_y (h, H) and d_x (w, W): (B, C, h, w), exact fp32 products in a
-    fixed order (include/drs_hip.h: drs_sep_apply)."""
+    fixed order (include/drs_hip.h: drs_sep_apply).  Stacked matrices (n_ops, h, H) / (n_ops, w, W): band b takes the pair
+    band_op[b] (None: min(b, n_ops - 1); drs_sep_apply_bands)."""
     lib = _lib.load()
     x = _req_sep("sep_apply", x)
     B, Cn, H, W = x.shape
     d_y, d_x = _req(d_y, "d_y"), _req(d_x, "d_x")
-    if d_y.dim() != 2 or d_x.dim() != 2 or d_y.shape[1] != H or d_x.shape[1] != W:
+    if d_y.dim() != d_x.dim() or d_y.dim() not in (2, 3) or d_y.shape[-1] != H or d_x.shape[-1] != W or (
+            d_y.dim() == 3 and d_y.shape[0] != d_x.shape[0]):
         raise RuntimeError(f"sep_apply: d_y {tuple(d_y.shape)} / d_x {tuple(d_x.shape)} do not take {H} x {W} planes")
-    h, w = d_y.shape[0], d_x.shape[0]
+    if d_y.dim() == 2 and band_op is not None:
+        raise RuntimeError("sep_apply: band_op goes with stacked (n_ops, ., .) matrices")
+    h, w = d_y.shape[-2], d_x.shape[-2]
+    table = _band_table("sep_apply", band_op, d_y.shape[0], Cn) if d_y.dim() == 3 else None
     out = torch.empty((B, Cn, h, w), dtype=torch.float32, device=x.device)
     ws = _sep_workspace(lib, (B, Cn, H, W, h, w), x.device)
     with torch.cuda.device(x.device):
-        st = lib.drs_sep_apply(_ptr(x), _ptr(d_y), _ptr(d_x), _ptr(out), B, Cn, H, W, h, w, _ptr(ws), ws.numel(), _stream(x.device))
-    _lib.check(st, "drs_sep_apply")
+        if d_y.dim() == 2:
+            st = lib.drs_sep_apply(_ptr(x), _ptr(d_y), _ptr(d_x), _ptr(out), B, Cn, H, W, h, w, _ptr(ws), ws.numel(),
+                                   _stream(x.device))
+        else:
+            st = lib.drs_sep_apply_bands(_ptr(x), _ptr(d_y), _ptr(d_x), _ptr(out), B, Cn, H, W, h, w, table, d_y.shape[0],
+                                         _ptr(ws), ws.numel(), _stream(x.device))
+    _lib.check(st, "drs_sep_apply" if d_y.dim() == 2 else "drs_sep_apply_bands")
     return out
 
 
 def _sep_projector_args(op, projector, yt, B, Cn, H, W):
-    h, w = projector.D_y.shape[0], projector.D_x.shape[0]
-    mats = (_req_matrix(op, projector.D_y, "D_y", (h, H)), _req_matrix(op, projector.D_x, "D_x", (w, W)),
-            _req_matrix(op, projector.U_y, "U_y", (H, h)), _req_matrix(op, projector.U_x, "U_x", (W, w)),
-            _req_matrix(op, projector.G, "G", (h, w)))
+    """(yt, the five matrices, h, w, bands): `bands` None for a one-operator projector (2-D matrices: the plain entries), else
+    (the host table or None, n_ops) of a stacked one."""
+    stacked = projector.D_y.dim() == 3
+    lead = (projector.D_y.shape[0],) if stacked else ()
+    h, w = projector.D_y.shape[-2], projector.D_x.shape[-2]
+    mats = (_req_matrix(op, projector.D_y, "D_y", lead + (h, H)), _req_matrix(op, projector.D_x, "D_x", lead + (w, W)),
+            _req_matrix(op, projector.U_y, "U_y", lead + (H, h)), _req_matrix(op, projector.U_x, "U_x", lead + (W, w)),
+            _req_matrix(op, projector.G, "G", lead + (h, w)))
     yt = _req_matrix(op, yt, "yt", (B, Cn, h, w))
-    return yt, mats, h, w
+    bands = (_band_table(op, getattr(projector, "band_op", None), lead[0], Cn), lead[0]) if stacked else None
+    return yt, mats, h, w, bands
 
 
 def sep_project(x, yt, projector, strength=1.0, out=None):
     """x + strength U_y (G o (yt - D_y x D_x^T)) U_x^T per plane of x (B, C, H, W), with the tensors of `projector` (a
     consistency.LRProjector) and yt = projector.prepare(y); into `out` (may be x; default: a new tensor).  include/drs_hip.h:
-    drs_sep_project."""
+    drs_sep_project, or drs_sep_project_bands for the stacked tensors of a per-band projector."""
     lib = _lib.load()
     x = _req_sep("sep_project", x)
     B, Cn, H, W = x.shape
-    yt, mats, h, w = _sep_projector_args("sep_project", projector, yt, B, Cn, H, W)
+    yt, mats, h, w, bands = _sep_projector_args("sep_project", projector, yt, B, Cn, H, W)
     if out is None:
         out = torch.empty_like(x)
     else:
@@ -997,9 +1026,13 @@ def sep_project(x, yt, projector, strength=1.0, out=None):
         _req_numel("sep_project", x, (("out", out),))
     ws = _sep_workspace(lib, (B, Cn, H, W, h, w), x.device)
     with torch.cuda.device(x.device):
-        st = lib.drs_sep_project(_ptr(x), _ptr(yt), *(_ptr(m) for m in mats), float(strength), _ptr(out), B, Cn, H, W, h, w,
-                                 _ptr(ws), ws.numel(), _stream(x.device))
-    _lib.check(st, "drs_sep_project")
+        if bands is None:
+            st = lib.drs_sep_project(_ptr(x), _ptr(yt), *(_ptr(m) for m in mats), float(strength), _ptr(out), B, Cn, H, W, h, w,
+                                     _ptr(ws), ws.numel(), _stream(x.device))
+        else:
+            st = lib.drs_sep_project_bands(_ptr(x), _ptr(yt), *(_ptr(m) for m in mats), float(strength), _ptr(out), B, Cn, H, W,
+                                           h, w, *bands, _ptr(ws), ws.numel(), _stream(x.device))
+    _lib.check(st, "drs_sep_project" if bands is None else "drs_sep_project_bands")
     return out
 
 
@@ -1007,7 +1040,7 @@ def lr_consistent_eps_(eps, x, t, alpha_hat, yt, projector, strength=1.0):
     """The in-chain projection, in place on `eps` (B, C, H, W): the noise prediction of the x0 that `eps` implies for the state
     `x` at the levels `t` (B int64 values on the device), moved onto the images `projector`'s operator maps to the observation
     behind yt = projector.prepare(y).  x0 is formed as it is loaded and never stored; strength 0 leaves eps its bits
-    (include/drs_hip.h: drs_sep_project_eps).  Returns eps."""
+    (include/drs_hip.h: drs_sep_project_eps, or drs_sep_project_eps_bands for a per-band projector).  Returns eps."""
     lib = _lib.load()
     _req_state(eps, "lr_consistent_eps_", "eps")
     if eps.dim() != 4 or min(eps.shape) < 1:
@@ -1018,11 +1051,48 @@ def lr_consistent_eps_(eps, x, t, alpha_hat, yt, projector, strength=1.0):
     B, Cn, H, W = eps.shape
     if t.numel() != B:
         raise RuntimeError(f"lr_consistent_eps_: t has {t.numel()} elements, eps has {B} images")
-    yt, mats, h, w = _sep_projector_args("lr_consistent_eps_", projector, yt, B, Cn, H, W)
+    yt, mats, h, w, bands = _sep_projector_args("lr_consistent_eps_", projector, yt, B, Cn, H, W)
     ws = _sep_workspace(lib, (B, Cn, H, W, h, w), eps.device)
     with torch.cuda.device(eps.device):
-        st = lib.drs_sep_project_eps(_ptr(eps), _ptr(x), _ptr(t), _ptr(alpha_hat), alpha_hat.numel(), _ptr(yt),
-                                     *(_ptr(m) for m in mats), float(strength), B, Cn, H, W, h, w, _ptr(ws), ws.numel(),
-                                     _stream(eps.device))
-    _lib.check(st, "drs_sep_project_eps")
+        if bands is None:
+            st = lib.drs_sep_project_eps(_ptr(eps), _ptr(x), _ptr(t), _ptr(alpha_hat), alpha_hat.numel(), _ptr(yt),
+                                         *(_ptr(m) for m in mats), float(strength), B, Cn, H, W, h, w, _ptr(ws), ws.numel(),
+                                         _stream(eps.device))
+        else:
+            st = lib.drs_sep_project_eps_bands(_ptr(eps), _ptr(x), _ptr(t), _ptr(alpha_hat), alpha_hat.numel(), _ptr(yt),
+                                               *(_ptr(m) for m in mats), float(strength), B, Cn, H, W, h, w, *bands, _ptr(ws),
+                                               ws.numel(), _stream(eps.device))
+    _lib.check(st, "drs_sep_project_eps" if bands is None else "drs_sep_project_eps_bands")
     return eps
+
+
+def fir_decimate(x, taps_y, taps_x, left, m, band_op=None, noise=None, sigma=None, clamp=False):
+    """The separable FIR blur and decimation by m of x (B, C, H, W) -> (B, C, H // m, W // m): LR pixel (i, j) of band b sums
+    taps_y[op][u] taps_x[op][v] x[clamp(i m + u - Ly)][clamp(j m + v - Lx)], op = band_op[b] (None: min(b, n_ops - 1)), over the
+    rows of taps_y (n_ops, ntaps_y) / taps_x (n_ops, ntaps_x) (1-D: one operator); `left` = L or (Ly, Lx).  noise (B, C, h, w)
+    standard normals with sigma (C,): + sigma[b] z; clamp: into [0, 1] last.  One launch (include/drs_hip.h: drs_fir_decimate)."""
+    lib = _lib.load()
+    x = _req_sep("fir_decimate", x)
+    B, Cn, H, W = x.shape
+    taps_y, taps_x = _req(taps_y, "taps_y"), _req(taps_x, "taps_x")
+    if taps_y.dim() == 1 and taps_x.dim() == 1:
+        taps_y, taps_x = taps_y[None], taps_x[None]
+    if taps_y.dim() != 2 or taps_x.dim() != 2 or taps_y.shape[0] != taps_x.shape[0] or min(taps_y.shape + taps_x.shape) < 1:
+        raise RuntimeError(f"fir_decimate: taps_y {tuple(taps_y.shape)} / taps_x {tuple(taps_x.shape)} must be (n_ops, ntaps) each")
+    Ly, Lx = (int(left), int(left)) if not isinstance(left, (tuple, list)) else (int(left[0]), int(left[1]))
+    m = int(m)
+    if m < 1 or H // m < 1 or W // m < 1:
+        raise RuntimeError(f"fir_decimate: m={m} leaves no pixel of {H} x {W} planes")
+    h, w = H // m, W // m
+    table = _band_table("fir_decimate", band_op, taps_y.shape[0], Cn)
+    if (noise is None) != (sigma is None):
+        raise RuntimeError("fir_decimate: noise and sigma go together")
+    if noise is not None:
+        noise, sigma = _req_matrix("fir_decimate", noise, "noise", (B, Cn, h, w)), _req_matrix("fir_decimate", sigma, "sigma", (Cn,))
+    out = torch.empty((B, Cn, h, w), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        st = lib.drs_fir_decimate(_ptr(x), _ptr(taps_y), _ptr(taps_x), table, taps_y.shape[0], taps_y.shape[1], taps_x.shape[1],
+                                  Ly, Lx, m, _ptr(noise), _ptr(sigma), int(bool(clamp)), _ptr(out), B, Cn, H, W, h, w,
+                                  _stream(x.device))
+    _lib.check(st, "drs_fir_decimate")
+    return out

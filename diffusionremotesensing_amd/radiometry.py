@@ -451,8 +451,8 @@ def check_args(args):
     if kind == "bsrgan":
         raise ValueError("--bit_depth 16 cannot be combined with --Degradation_type BSRGAN: the blind degradation is defined on "
                          "8-bit images")
-    if kind != "downblur":
-        raise ValueError("--bit_depth 16 needs --Degradation_type DownBlur")
+    if kind not in ("downblur", "mtf"):
+        raise ValueError("--bit_depth 16 needs --Degradation_type DownBlur or MTF")
     if spec.startswith("synthetic") and not spec.startswith("synthetic_u16"):
         raise ValueError(f"--bit_depth 16 reads a folder of 16-bit files or synthetic_u16[:N], not {spec!r}")
     return args

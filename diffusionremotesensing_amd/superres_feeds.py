@@ -74,6 +74,22 @@ def _downblur_feed_makers(args, device, r):
     return make_feed, first_items
 
 
+def _mtf_feed_makers(args, device, r):
+    """The sensor-MTF degradation (mtf.py): blur with each band's own Gaussian, decimate, optional noise, per batch on the device;
+    rank r draws its own noise; the validation feed repeats its noise at every epoch."""
+    from .mtf import DeviceMTFFeed
+
+    def make_feed(u8, fixed=False):
+        return DeviceMTFFeed(u8.to(device), args.magnification_factor, args.mtf_nyquist, getattr(args, "mtf_noise", None),
+                             args.batch_size, shuffle=True, seed=1 if fixed else 2, fixed=fixed, **feed_kwargs(args, r, fixed))
+
+    def first_items(u8, train_feed):  # the first training images' centre windows through the same operator, without noise
+        feed = DeviceMTFFeed(u8.to(device), args.magnification_factor, args.mtf_nyquist, None, 1, shuffle=False, fixed=True,
+                             **feed_kwargs(args, fixed=True))
+        return [feed.item(i)[0] for i in range(u8.shape[0])]
+    return make_feed, first_items
+
+
 def _folder_feeds(args, device, spec, make_feed, first_items, r, wsz):
     """An image folder, laid out as the reference expects it (:597-598): <dataset_path>/train_original, /val_original.
     Decoded once with Pillow into the uint8 cache (this rank's shard only: rank r owns every world-th image like
@@ -117,7 +133,7 @@ def _synthetic_feeds(args, device, spec, makers, r, wsz):
             raise ValueError(f"dataset of {len(ds)} images cannot be sharded over {wsz} ranks")
         return make_feed(to_u8(ds.hr[r::wsz][:per_rank]), fixed)
     train_loader, val_loader = feed(train_dataset), feed(val_dataset, fixed=True)
-    if args.Degradation_type.lower() == "bsrgan" or size != args.image_size:
+    if args.Degradation_type.lower() in ("bsrgan", "mtf") or size != args.image_size:
         # (a DownBlur run without windows conditions on the dataset's own seeded LR patches, like the float path)
         final_lr = first_items(to_u8(train_dataset.hr[:5]), train_loader)
     return train_loader, val_loader, final_lr
@@ -156,6 +172,15 @@ def _u16_feeds(args, device, spec, r, wsz):
         table = R.resolve_range(getattr(args, "data_range", None), train, nodata, all_ranks=bool(args.multiple_gpus))
     table = R.check_table(table, ch)
     print(f"16-bit radiometry: band ranges {R.format_table(table)}")
+    if args.Degradation_type.lower() == "mtf":  # the same caches under the sensor-MTF degradation (mtf.py)
+        from .mtf import DeviceMTFFeed
+
+        def make_mtf(cache, fixed=False, noise=getattr(args, "mtf_noise", None), batch=args.batch_size, rank=r):
+            return DeviceMTFFeed(cache, args.magnification_factor, args.mtf_nyquist, noise, batch, shuffle=not fixed or batch > 1,
+                                 data_range=table, nodata=nodata, seed=1 if fixed else 2, fixed=fixed,
+                                 **feed_kwargs(args, rank, fixed))
+        firsts = make_mtf(first.to(device), fixed=True, noise=None, batch=1, rank=0)
+        return make_mtf(train), make_mtf(val, fixed=True), [firsts.item(i)[0] for i in range(first.shape[0])]
     radius = args.Blur_radius if args.Blur_radius == "random" else float(args.Blur_radius)
 
     def make_feed(cache, fixed=False):  # ("random": one draw per feed, as the 8-bit feeds)
@@ -179,7 +204,8 @@ def make_superres_feeds(args, device):
         return _u16_feeds(args, device, spec, r, wsz)
     makers = None
     if not spec.startswith("synthetic") or spec.startswith("synthetic_u8"):
-        build = _bsrgan_feed_makers if args.Degradation_type.lower() == "bsrgan" else _downblur_feed_makers
+        kind = args.Degradation_type.lower()
+        build = _bsrgan_feed_makers if kind == "bsrgan" else _mtf_feed_makers if kind == "mtf" else _downblur_feed_makers
         makers = build(args, device, r)
     if spec.startswith("synthetic"):
         return _synthetic_feeds(args, device, spec, makers, r, wsz)

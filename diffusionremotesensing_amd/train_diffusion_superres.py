@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from . import dist as drs_dist
 from . import hip_ops
+from . import mtf
 from . import radiometry
 from .augment import add_augment_args
 # (the names this module does not use itself are re-exported: they lived here before cli.py, launcher.py and superres_feeds.py)
@@ -43,7 +44,7 @@ from .sampling import (CHAIN_CHECK_EVERY, _is_int, _repeat_members, asks_for_kno
 from .superres_feeds import SyntheticSuperresDataset, make_superres_feeds  # noqa: F401
 from .UNet_model_superres import EMA, Residual_Attention_UNet_superres
 
-_DEGRADATIONS = ("downblur", "bsrgan", "downblurnoise")
+_DEGRADATIONS = ("downblur", "bsrgan", "downblurnoise", "mtf")
 
 METRIC_FORMATS = {"psnr": ("PSNR", "{:.2f} dB"), "ssim": ("SSIM", "{:.4f}"), "sam": ("SAM", "{:.3f} deg"),
                   "ergas": ("ERGAS", "{:.4g}"), "psnr_unknown": ("PSNR unknown", "{:.2f} dB"),
@@ -82,7 +83,7 @@ class Diffusion:
     def __init__(self, noise_schedule: str, model: nn.Module, snapshot_path: str, noise_steps=1000, beta_start=1e-4,
                  beta_end=0.02, device="cuda", magnification_factor=4, image_size=224, model_name="superres",
                  Degradation_type="BSRGAN", multiple_gpus=False, ema_smoothing=False, prediction="eps", x0_clip=None,
-                 x0_threshold=None, zero_terminal_snr=False):
+                 x0_threshold=None, zero_terminal_snr=False, mtf_nyquist=None, mtf_noise=None):
         # not in the reference, whose networks predict the noise: what this one predicts ("eps", "v" or "x0": the training
         # target, and what sampling converts to eps before every update) and the range the x0 implied at every reverse step
         # is clamped to (None or (lo, hi); a plain attribute, read at the start of every chain).  DESIGN.md section 23.
@@ -119,6 +120,11 @@ class Diffusion:
         self.device = device
         self.snapshot_path = snapshot_path
         self.Degradation_type = Degradation_type
+        # ... and the sensor-MTF degradation (Degradation_type "MTF": mtf.py): per band, the gain of the
+        # Gaussian blur at the LR Nyquist frequency and the standard deviation of the sensor noise, tuples of C floats (a number
+        # or "G1,..,GC" is spread / parsed; both None for every other degradation).  `mtf_nyquist` is written into snapshots and
+        # train_state.pt of an MTF run - no other run writes the key - and a file written under other gains is refused.
+        self.mtf_nyquist, self.mtf_noise = self._check_mtf(Degradation_type, mtf_nyquist, mtf_noise, model, magnification_factor)
         self.multiple_gpus = multiple_gpus
         self.ema_smoothing = ema_smoothing
         self.model = model.to(self.device)
@@ -524,6 +530,8 @@ class Diffusion:
             snapshot["ZERO_TERMINAL_SNR"] = True
         if getattr(self, "data_range", None) is not None:  # (likewise: only a 16-bit run)
             snapshot["DATA_RANGE"] = self._data_range_key(self.data_range)
+        if getattr(self, "mtf_nyquist", None) is not None:  # (likewise: only an MTF run)
+            snapshot["MTF_NYQUIST"] = [float(g) for g in self.mtf_nyquist]
         torch.save(snapshot, self.snapshot_path)
         print(f"Epoch {epoch} | Training snapshot saved at {self.snapshot_path}")
 
@@ -556,6 +564,36 @@ class Diffusion:
                              f"built with zero_terminal_snr={self.zero_terminal_snr}: the two schedules differ at every level "
                              f"({'pass' if saved else 'drop'} --zero_terminal_snr)")
         self.snapshot_data_range = snapshot.get("DATA_RANGE")
+        self._check_mtf_key(snapshot.get("MTF_NYQUIST"), self.snapshot_path)
+
+    @staticmethod
+    def _check_mtf(kind, nyquist, noise, model, magnification_factor):
+        """(mtf_nyquist, mtf_noise) of the constructor: (None, None) unless `kind` is "MTF", else per-band tuples, checked
+        against the network's band count (a model that does not tell it: the length of the list)."""
+        from . import mtf
+        if str(kind).lower() != "mtf":
+            if nyquist is not None or noise is not None:
+                raise ValueError(f"mtf_nyquist / mtf_noise belong to Degradation_type='MTF' (got {kind!r})")
+            return None, None
+        if nyquist is None:
+            raise ValueError("Degradation_type='MTF' needs mtf_nyquist: the gain at the LR Nyquist frequency, one number or one per "
+                             "band (--mtf_nyquist)")
+        mtf._check_factor(magnification_factor)
+        bands = getattr(model, "image_channels", None)
+        if bands is None:
+            bands = 1 if isinstance(nyquist, (int, float)) else len(nyquist.split(",") if isinstance(nyquist, str) else list(nyquist))
+        nyquist = mtf.parse_mtf_nyquist(nyquist, bands)
+        return nyquist, (None if noise is None else mtf.parse_mtf_noise(noise, len(nyquist)))
+
+    def _check_mtf_key(self, saved, where):
+        """ValueError for a file written under other per-band MTF gains than `self.mtf_nyquist` (None: not an MTF run)."""
+        mine = getattr(self, "mtf_nyquist", None)
+        saved = None if saved is None else tuple(float(g) for g in saved)
+        if saved != (None if mine is None else tuple(float(g) for g in mine)):
+            def text(t):
+                return "none (not an MTF run)" if t is None else ",".join(f"{g:g}" for g in t)
+            raise ValueError(f"{where} was written with --mtf_nyquist {text(saved)}, this run has {text(mine)}: a network goes on "
+                             "under the degradation it was trained for")
 
     @staticmethod
     def _data_range_key(table):
@@ -597,6 +635,8 @@ class Diffusion:
             ts["NODATA"] = self._nodata_key(self.nodata)
         if getattr(self, "data_range", None) is not None:  # (likewise)
             ts["DATA_RANGE"] = self._data_range_key(self.data_range)
+        if getattr(self, "mtf_nyquist", None) is not None:  # (likewise)
+            ts["MTF_NYQUIST"] = [float(g) for g in self.mtf_nyquist]
         torch.save(ts, self.train_state_path())
 
     def _load_train_state(self, run):
@@ -619,6 +659,7 @@ class Diffusion:
             raise ValueError(f"{self.train_state_path()} was written with nodata={ts.get('NODATA')!r}, this run has "
                              f"nodata={self._nodata_key(self.nodata)!r}: a resumed run must mask the same pixels")
         self._check_data_range(ts.get("DATA_RANGE"), self.train_state_path())
+        self._check_mtf_key(ts.get("MTF_NYQUIST"), self.train_state_path())
         if run.loss_bins is not None:
             run.loss_bins.load_state_dict(ts["LOSS_BINS"])  # (other T / bin count: ValueError)
         # (another parameter count or other shapes: ValueError from FusedAdamW.load_state_dict, the first thing loaded)
@@ -975,13 +1016,14 @@ def launch(args):
     cache on the device, DownBlur / DownBlurNoise per batch on the device) or `synthetic[:N]` / `synthetic_u8[:N]` (seeded
     patches; float pairs / the same device feed)."""
     if args.Degradation_type.lower() not in _DEGRADATIONS:
-        raise ValueError("The degradation type must be either BSRGAN or DownBlur or DownBlurNoise")
+        raise ValueError("The degradation type must be either BSRGAN or DownBlur or DownBlurNoise or MTF")
     if args.Degradation_type.lower() == "downblur" and args.image_size % args.magnification_factor != 0:
         raise ValueError("The image size must be a multiple of the magnification factor")
     if args.UNet_type.lower() != "residual attention unet":
         raise ValueError("The UNet type must be Residual Attention UNet or Residual MultiHead Attention UNet or "
                          "Residual Visual MultiHeadAttention UNet superres")
     u16 = radiometry.is_u16(radiometry.check_args(args))
+    mtf.check_args(args)
     # a 16-bit run: the feed compares the stored integers with --nodata K and marks the target with NaN (the NaN rule alone)
     nodata = (None if getattr(args, "nodata", None) is None else True) if u16 else \
         nodata_u8_value(getattr(args, "nodata", None), args.Degradation_type)
@@ -997,7 +1039,8 @@ def launch(args):
     if getattr(args, "eval_metrics", 0):
         train_kwargs = {"eval_metrics": args.eval_metrics, "sampling_steps": args.sampling_steps, "eta": args.eta}
     diffusion = train_model(args, Diffusion, model, device, train_loader, val_loader, train_kwargs, nodata=nodata,
-                            **({"data_range": train_loader.data_range} if u16 else {}), magnification_factor=args.magnification_factor, Degradation_type=args.Degradation_type)
+                            **({"data_range": train_loader.data_range} if u16 else {}), magnification_factor=args.magnification_factor, Degradation_type=args.Degradation_type,
+                            **mtf.diffusion_kwargs(args))
     if r != 0:
         return  # one rank samples and writes models_run/<name>/results/superres_results.pt (every rank holds the same weights)
 
@@ -1044,6 +1087,7 @@ def parse_train_args(argv=None):
     add_finetune_args(p)
     add_nodata_args(p, in_help=False, u8=True)
     radiometry.add_radiometry_args(p, in_help=False)
+    mtf.add_mtf_args(p, in_help=False)
     next(a for a in p._actions if a.dest == "nodata").type = cli_nodata_u16  # (0 .. 255 without --bit_depth 16: checked below)
     p.add_argument("--eval_metrics", type=int, default=0,
                    help="score the network on the first N validation images (PSNR / SSIM / SAM / ERGAS against the bicubic "
@@ -1058,6 +1102,7 @@ def parse_train_args(argv=None):
     check_nodata_depth(p, args)
     try:
         radiometry.check_args(args)
+        mtf.check_args(args)
     except ValueError as e:
         p.error(str(e))
     return check_train_args(p, args)

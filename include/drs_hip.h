@@ -620,6 +620,42 @@ DRS_API int drs_sep_project_eps(float* eps, const float* x, const int64_t* t, co
                                 const float* gain, float strength, int n, int c, int H, int W, int h, int w, void* workspace,
                                 size_t workspace_bytes, drs_stream_t stream);
 
+/* Per-band operators (not in the reference): the three calls above with one operator per band.  d_y, d_x,
+ * u_y, u_x and gain carry a leading n_ops axis - d_y (n_ops,h,H), d_x (n_ops,w,W), u_y (n_ops,H,h), u_x (n_ops,W,w), gain
+ * (n_ops,h,w) - and band b of every image uses slot band_op[b].  band_op: c int32 values in 0 .. n_ops-1 in HOST memory, copied
+ * into the kernel arguments before the call returns; NULL: band b uses slot min(b, n_ops-1).  yt stays per plane.  Same tiles,
+ * same MFMA order, same workspace and same contract as the calls above, which are these with n_ops = 1 and keep their bits.
+ * DRS_ERR_SHAPE besides theirs: n_ops outside 1 .. c, a band_op entry outside 0 .. n_ops-1. */
+DRS_API int drs_sep_apply_bands(const float* x, const float* d_y, const float* d_x, float* out, int n, int c, int H, int W, int h,
+                                int w, const int32_t* band_op, int n_ops, void* workspace, size_t workspace_bytes,
+                                drs_stream_t stream);
+DRS_API int drs_sep_project_bands(const float* x, const float* yt, const float* d_y, const float* d_x, const float* u_y,
+                                  const float* u_x, const float* gain, float strength, float* out, int n, int c, int H, int W,
+                                  int h, int w, const int32_t* band_op, int n_ops, void* workspace, size_t workspace_bytes,
+                                  drs_stream_t stream);
+DRS_API int drs_sep_project_eps_bands(float* eps, const float* x, const int64_t* t, const float* alpha_hat, int noise_steps,
+                                      const float* yt, const float* d_y, const float* d_x, const float* u_y, const float* u_x,
+                                      const float* gain, float strength, int n, int c, int H, int W, int h, int w,
+                                      const int32_t* band_op, int n_ops, void* workspace, size_t workspace_bytes,
+                                      drs_stream_t stream);
+
+/* Sensor-MTF degradation (csrc/mtf.hip, diffusionremotesensing_amd/mtf.py; not in the reference): a
+ * separable FIR blur and decimation by m in one launch, with one pair of tap rows per operator slot:
+ *   out[i][j] = sum_u ky[op][u] * sum_v kx[op][v] * x[clamp(i m + u - Ly, 0, H-1)][clamp(j m + v - Lx, 0, W-1)],  op = band_op[band]
+ * x: (n,c,H,W) fp32; taps_y (n_ops,ntaps_y), taps_x (n_ops,ntaps_x) fp32 on the device; band_op as in the *_bands calls above
+ * (host, c int32, may be NULL); out: (n,c,h,w) with h m <= H and w m <= W (rows and columns past h m, w m are only ever taps).
+ * noise (n,c,h,w) standard normals with sigma (c fp32 on the device), both or neither: v = fmaf(sigma[band], z, v); clamp01 != 0:
+ * v = min(max(v, 0), 1) last.  A workgroup stages the clamped input window of its LR tile in LDS, runs the row-direction pass
+ * (kx, along W) and then the column-direction pass (ky) from there, each an fmaf chain from 0 in ascending tap order: the sum
+ * depends on nothing but the output pixel, so two calls, any pointer phase (16-byte loads where pointer, W and plane stride allow
+ * them, 4-byte loads of the same elements otherwise) and any tile position give the same bits.  No atomics, no workspace, no host
+ * synchronisation.  DRS_ERR_ARG: null pointer, noise without sigma or the reverse, x and out overlapping; DRS_ERR_SHAPE: c > 16,
+ * n_ops outside 1 .. c, a band_op entry outside 0 .. n_ops-1, m outside 1 .. 8, ntaps outside 1 .. 64, L outside 0 .. ntaps-1,
+ * h m > H or w m > W, an extent < 1, a plane of 2^31 elements.  All are reported before the launch. */
+DRS_API int drs_fir_decimate(const float* x, const float* taps_y, const float* taps_x, const int32_t* band_op, int n_ops,
+                             int ntaps_y, int ntaps_x, int Ly, int Lx, int m, const float* noise, const float* sigma,
+                             int clamp01, float* out, int n, int c, int H, int W, int h, int w, drs_stream_t stream);
+
 /* "DownBlur" degradation of the super-resolution data feed on the device, bit-exact with the Pillow calls of the
  * reference's dataset item: x = ToTensor(GaussianBlur(radius)(resize(y, (out_w, out_h), BICUBIC))), y = ToTensor(hr).
  *   hr: (N,C,H,W) uint8;  x_lr: (N,C,out_h,out_w) float32 in [0,1];  y_hr: (N,C,H,W) float32 or NULL;
